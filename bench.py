@@ -10,7 +10,11 @@ BASELINE.json configs[1] - 64 synthetic 5 s utterances at 22.05 kHz, config_varB
 bits/frame) - PER GPU (weak scaling: utterances are independent, each rank runs its own batch with no
 data-path collective; one RCCL all-gather of the decoded waveforms per step is the "final gather" of the
 north star).  Inputs are resident in HBM before the timed region; the K steps are issued back to back on
-one stream.  Rank 0 prints ONE JSON line: metric/value (audio-seconds coded per wall-second, whole job), plus
+one stream.  Rank 0 prints ONE JSON line: metric/value (audio-seconds coded per wall-second, whole job), ms_per_step.
+
+A plain run does only that: set up, W warm-up steps, the K timed steps, the result line.  ``--dump-outputs DIR``
+writes what the last timed step returned (codes.npy, and wav.npy in codec mode; float32) for output-for-output
+comparisons of two builds; the inputs are seeded, so the same arguments give the same inputs.  ``--full`` adds
 
   roofline      - the dominant kernel (the persistent BVRNN recurrence, two launches per step) timed with HIP
                   event pairs on its launch stream inside the real schedule (bvc_probe_*), algorithmic FLOPs per
@@ -30,6 +34,7 @@ one stream.  Rank 0 prints ONE JSON line: metric/value (audio-seconds coded per 
   cpu_baseline  - the CPU oracle (oracle/, PyTorch-CPU port of the reference op sequence) timed on the host
                   cores on a bounded sample of the same workload (rank 0, N=1 only): the benchmark's batch of 64, one
                   second per utterance, 3 warm-ups, median of 5, at 8 threads and at all usable cores.
+The --no-* switches, --multi-streams and --legs pick among these within a --full run.
 
 Other workloads of BASELINE.json: ``--seconds 10`` (the north-star target's utterance length, and with
 ``--bitrate 1500|3000|6000`` one GPU's shard of configs[3]), ``--mode encode`` (configs[2]: front-end + coder only).
@@ -41,6 +46,8 @@ import os
 import sys
 import tempfile
 import time
+
+import numpy as np
 
 # The multi-stream schedule relies on the runtime's default of 4 hardware queues per process (one per stream): 3, 5 or 6
 # queues cost 20-60 % of its throughput on this pool.  Pin the default unless the caller chose otherwise; it must be in the
@@ -294,6 +301,26 @@ def time_steps(fn, n, device):
     return time.perf_counter() - t0, last
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6 - 4096         # 64 MB in all, .npy headers included
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: write {name: tensor, utterances along dim 0} as DIR/<name>.npy in float32.  Whole arrays when they fit
+    DUMP_LIMIT_BYTES together; otherwise the same fixed, seeded sample of utterances from each, with its indices in rows.npy."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in arrays.items() if v is not None}
+    B = next(iter(arrays.values())).shape[0]
+    per_row = sum(v.nbytes for v in arrays.values()) // B
+    if per_row * B > DUMP_LIMIT_BYTES:
+        k = max(1, (DUMP_LIMIT_BYTES - 8 * B) // per_row)
+        rows = np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+        arrays = {n: v[rows] for n, v in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    for n, v in arrays.items():
+        np.save(os.path.join(directory, n + ".npy"), v)
+    return {n: list(v.shape) for n, v in arrays.items()}
+
+
 def leg_target_workload(conf, model, device, B, bitrate, with_parity, steps=5, world=1, use_pg=False, rank=0, sweep=(1500.0, 6000.0)):
     """The workload the north-star target and its scaling are quoted on: BASELINE configs[3], 512 x 10 s sharded over 8 GPUs = 64 x 10 s
     per GPU, bitrates {1.5, 3, 6} kbit/s.  With a process group EVERY rank runs its shard and the per-step RCCL all-gather of the
@@ -475,6 +502,10 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the target_workload / encode_only / streaming / large_batch legs")
     ap.add_argument("--legs", default="target,encode,fused,streaming,large", help="which of the extra legs run (comma separated)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: multi_stream, roofline, the extra legs, parity against the oracle and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the codes (and waveforms) of the last timed step to DIR/<name>.npy, float32, at most 64 MB in all")
     a = ap.parse_args()
 
     # RCCL prints a version banner on STDOUT when its communicator is created; this program's stdout is one JSON line, so
@@ -584,6 +615,7 @@ def main():
         elapsed = max(float(t.item()) for t in tall)             # the job is as slow as its slowest rank
     assert codes.shape[2] == conf["z_dim"] and (wav is None or torch.isfinite(wav).all())
     model.check_status()                                          # no recurrence kernel may have given up waiting
+    dumped = dump_outputs(a.dump_outputs, {"codes": codes, "wav": wav}) if (a.dump_outputs and rank == 0) else None
 
     T = codes.shape[1]
     names = {"codec": "full encode -> BigVGAN decode", "encode": "encode only (STFT/mel + BVRNN.encode, no vocoder)"}
@@ -608,8 +640,10 @@ def main():
         "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms), "per_rank": rank_ms},
         "gather_ms": round(gather_ms, 3),          # rank 0's mean all-gather time per step (0: no process group, nothing to gather)
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
 
-    if a.multi_streams > 1 and len(streams) == 1:
+    if a.full and a.multi_streams > 1 and len(streams) == 1:
         # the same K steps with several independent batches in flight (throughput-oriented; results are bit-identical to the
         # serial schedule: tests/test_gpu_concurrency.py).  Timed like the headline (barrier + synchronize, max over ranks).
         def multi():
@@ -631,7 +665,7 @@ def main():
             local_step()
         torch.cuda.synchronize(device)
 
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         lib = _abi.load()
         fam = flops_per_step(conf, B, T, a.mode, fold=bool(model.engine().get_option("decode_fold")))
         rows = {}
@@ -679,9 +713,9 @@ def main():
                                          "gflop_per_audio_second": round(step_flops / (B * a.seconds) / 1e9, 3)}
         out["kernel_families"] = rows
     default_workload = full and a.seconds == SECONDS and B == BATCH
-    if rank == 0:
+    if rank == 0 and a.full:
         note("headline, multi_stream and roofline legs done")
-    legs = set() if a.no_extra else set(a.legs.split(","))
+    legs = set() if (a.no_extra or not a.full) else set(a.legs.split(","))
     if default_workload and "target" in legs and (use_pg or rank == 0):
         # with a process group every rank runs its shard of configs[3] (the gather is a collective); rank 0 reports
         tw = leg_target_workload(conf, model, device, B, a.bitrate, not a.no_parity, world=world, use_pg=use_pg and not a.no_gather, rank=rank)
@@ -702,7 +736,7 @@ def main():
         if "large" in legs:
             out["large_batch"] = leg_large_batch(conf, model, device, a.bitrate, with_par)
             note("large_batch done")
-    if rank == 0 and not (a.no_parity and (a.no_cpu_baseline or world > 1)):
+    if a.full and rank == 0 and not (a.no_parity and (a.no_cpu_baseline or world > 1)):
         leg = oracle_leg(conf, model, x, codes, wav, L, a.bitrate, a.mode, with_baseline=(world == 1 and not a.no_cpu_baseline))
         if not a.no_parity:
             out["parity"] = leg["parity"]

@@ -68,7 +68,7 @@ def test_bench_target_workload_leg_runs_under_a_process_group():
     import json
     env = dict(os.environ, BVC_FORCE_PG="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(29900 + os.getpid() % 90), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--multi-streams", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--multi-streams", "0",
                         "--no-cpu-baseline", "--no-roofline", "--legs", "target"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-4000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
