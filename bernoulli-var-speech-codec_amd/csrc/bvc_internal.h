@@ -215,8 +215,22 @@ struct FrontendTables {          // device pointers
     int num_mels;
     int kmax;                    // highest bin with non-zero weight (+1)
 };
+// lens (B) or nullptr: row b holds lens[b] valid samples of its L (mixed-length batch: ragged_frames below)
 int launch_stft_logmel(const FrontendTables &t, const float *wav, int B, long long L, long long T,
-                       int pad_left, float scale, float *mel, hipStream_t s);
+                       int pad_left, float scale, float *mel, hipStream_t s, const long long *lens = nullptr);
+// Frames of an utterance of `len` valid samples in a row of L: bvc_num_frames of len clamped into [0, L] (n_fft = 1024 and hop = 256,
+// which check_config enforces), 0 where the reflect padding does not fit.  The per-row lengths of a mixed-length batch live on the
+// device, so the kernels that read them clamp instead of validating.
+__host__ __device__ inline long long ragged_frames(long long len, long long L, int pad_left) {
+    len = len < 0 ? 0 : (len > L ? L : len);
+    const long long pr = 1024 - 256 - pad_left;
+    if (len <= pad_left || len <= pr) return 0;
+    return (len + pad_left + pr - 1024) / 256 + 1;
+}
+// mixed-length batch: bits (B, T) = d_bits[b] (or dflt) on row b's live frames, 0 behind them; codes (B, T, z) = 0.5 behind them
+int launch_ragged_bits(float *bits, const float *d_bits, float dflt, const long long *lens, int B, long long L, long long T,
+                       int pad_left, hipStream_t s);
+int launch_ragged_mask(float *codes, const long long *lens, int B, long long L, long long T, int z, int pad_left, hipStream_t s);
 
 int launch_resample_poly(const float *x, int B, long long Lin, const double *h, int ntaps, int up, int down,
                          long long n_pre_remove, float *y, long long n_out, hipStream_t s);
@@ -254,15 +268,21 @@ int conv_kernels_init();
 enum : unsigned { AMPK_C8 = 1u, AMPK_C16 = 2u, AMPK_ALL = 3u };
 unsigned amp_kernels_default();
 int launch_snakebeta_test(const float *x, long long n, float a, float ib, float *y, hipStream_t s);
+// row_lim (B) or nullptr: input rows of item b from row_lim[b] on read as zeros (a mixed-length batch; row_lim[b] <= Lin)
 int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *out, long long Lout,
                      int B, int epi, const float *res, const float *acc, float divisor, hipStream_t s,
-                     const ConvWindow *win = nullptr);
+                     const ConvWindow *win = nullptr, const long long *row_lim = nullptr);
 // one fused AMPBlock1 iteration: out = x + conv2(S2(conv1_dil(S1(x)))) (+acc, /divisor per epi); c2.dil == 1
 int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, long long L, float *out, int B, int epi,
                     const float *acc, float divisor, hipStream_t s, const ConvWindow *win = nullptr, unsigned kernels = AMPK_ALL);
 // SnakeBeta -> causal conv C->1 (k taps) -> tanh -> / div -> first n_out samples
+// n_rows (B) or nullptr: item b keeps its first n_rows[b] samples, the rest of its n_out are 0
 int launch_conv_post(const float *in, long long Lin, int C, int ks, const float *w, const float *bias,
                      const float *act_a, const float *act_ib, float div, float *wav, long long n_out,
-                     int B, hipStream_t s, const ConvWindow *win = nullptr);
+                     int B, hipStream_t s, const ConvWindow *win = nullptr, const long long *n_rows = nullptr);
+// mixed-length decode: lim ((n_up + 1) x B) = per-item input rows of the upsamplers, L_0 = frames[b] (clamped into [0, T]),
+// L_i = (L_{i-1} + 1) * up_rates[i-1], then the samples kept, min(lengths[b], L_{n_up}) clamped into [0, n_max] (0 without frames)
+int launch_ragged_limits(long long *lim, const long long *frames, const long long *lengths, int B, long long T, long long n_max,
+                         int n_up, const int *up_rates, hipStream_t s);
 
 }  // namespace bvc

@@ -1517,9 +1517,11 @@ int run_forward(const bvc_model *m, const Workspace &w, const float *d_mel, cons
 }
 
 // Runs the generator; stop_after: -1 = everything, otherwise the tap index of bvc_test_vocoder_tap.
+// lim: nullptr, or the (n_up + 1) x B bounds of a mixed-length batch (launch_ragged_limits): the upsamplers' input rows per item, then
+// the samples each item keeps of `length`.
 int run_vocoder(const bvc_model *m, const Workspace &w, const float *d_mel, int B, int64_t T, int64_t length,
                 float div, float *d_wav, int stop_after, const float **tap, int64_t *tap_len, int *tap_ch,
-                hipStream_t s) {
+                hipStream_t s, const long long *lim = nullptr) {
     const bvc_config &c = m->cfg;
     int rc;
     // pad[6,0] + conv_pre (models.py:212-213); input is already time-major (B,T,80)
@@ -1531,7 +1533,8 @@ int run_vocoder(const bvc_model *m, const Workspace &w, const float *d_mel, int 
         const int C = m->stage_ch[i];
         const int64_t L = (Lin + 1) * c.up_rates[i];
         // ConvTranspose1d as a 2-tap conv with u*C columns over Lin+1 rows (models.py:216-217)
-        if ((rc = launch_conv_mfma(m->ups[i], cur_in, Lin, w.X, Lin + 1, B, CE_STORE, nullptr, nullptr, 1.0f, s))) return rc;
+        if ((rc = launch_conv_mfma(m->ups[i], cur_in, Lin, w.X, Lin + 1, B, CE_STORE, nullptr, nullptr, 1.0f, s, nullptr,
+                                   lim ? lim + (size_t)i * B : nullptr))) return rc;
         if (stop_after == 1 + 2 * i) { *tap = w.X; *tap_len = L; *tap_ch = C; return BVC_OK; }
         for (int j = 0; j < c.n_resk; ++j) {                            // three parallel AMP blocks
             const float *cur = w.X;
@@ -1558,7 +1561,7 @@ int run_vocoder(const bvc_model *m, const Workspace &w, const float *d_mel, int 
     }
     const int64_t n_out = length < Lin ? length : Lin;
     return launch_conv_post(cur_in, Lin, m->post_c, m->post_ks, m->post_w, m->post_b, m->post_a, m->post_ib, div,
-                            d_wav, n_out, B, s);
+                            d_wav, n_out, B, s, nullptr, lim ? lim + (size_t)c.n_up * B : nullptr);
 }
 
 
@@ -1958,6 +1961,53 @@ int bvc_decode(const bvc_model *m, const float *d_codes, int32_t B, int64_t T, i
     hipStream_t s = (hipStream_t)stream;
     if ((rc = run_decode(m, w, d_ws, d_codes, nullptr, B, T, w.mel, nullptr, s))) return rc;
     return run_vocoder(m, w, w.mel, B, T, length, out_scale_div, d_wav, -1, nullptr, nullptr, nullptr, s);
+}
+
+int bvc_encode_ragged(const bvc_model *m, const float *d_wav, const int64_t *d_lengths, int32_t B, int64_t L, float scale,
+                      const float *d_bits, float bits_per_frame, float *d_codes, void *d_ws, size_t ws_bytes, void *stream) {
+    if (int st_ = sticky_status(m)) return st_;
+    if (!m) { set_error("null model"); return BVC_EINVAL; }
+    const int64_t T = bvc_num_frames(m, L);
+    if (T <= 0) { set_error("input too short for reflect padding (L=%lld)", (long long)L); return BVC_EINVAL; }
+    Workspace w;
+    int rc = check_ws(m, B, T, d_ws, ws_bytes, &w);
+    if (rc) return rc;
+    if (!d_wav || !d_lengths || !d_codes) { set_error("null argument"); return BVC_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    const long long *lens = reinterpret_cast<const long long *>(d_lengths);
+    const int pl = m->cfg.pad_left;
+    // every row runs all T frames through the coder; its frames behind T_b see the log floor and no bits, and are discarded
+    if ((rc = launch_stft_logmel(m->fe, d_wav, B, L, T, pl, scale, w.mel, s, lens))) return rc;
+    if ((rc = launch_ragged_bits(w.bits, d_bits, bits_per_frame, lens, B, L, T, pl, s))) return rc;
+    if ((rc = run_encode(m, w, d_ws, w.mel, w.bits, nullptr, B, T, d_codes, nullptr, nullptr, nullptr, s))) return rc;
+    if (!m->cfg.var_bit) return launch_ragged_mask(d_codes, lens, B, L, T, m->cfg.z_dim, pl, s);     // (var_bit: 0 bits did it)
+    return BVC_OK;
+}
+
+int bvc_decode_ragged(const bvc_model *m, const float *d_codes, const int64_t *d_frames, int32_t B, int64_t T,
+                      const int64_t *d_lengths, int64_t n_max, float out_scale_div, float *d_wav, void *d_ws, size_t ws_bytes,
+                      void *stream) {
+    if (int st_ = sticky_status(m)) return st_;
+    Workspace w;
+    int rc = check_ws(m, B, T, d_ws, ws_bytes, &w);
+    if (rc) return rc;
+    if (!d_codes || !d_frames || !d_lengths || !d_wav || n_max <= 0) {
+        set_error("null argument or non-positive n_max");
+        return BVC_EINVAL;
+    }
+    if (n_max > bvc_vocoder_length(m, T)) {
+        set_error("n_max %lld exceeds the generator's %lld samples for T=%lld", (long long)n_max,
+                  (long long)bvc_vocoder_length(m, T), (long long)T);
+        return BVC_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = run_decode(m, w, d_ws, d_codes, nullptr, B, T, w.mel, nullptr, s))) return rc;
+    // the bounds table goes to the normalised-mel buffer, which only encode uses: (n_up + 1) * B int64 <= B * T * num_mels floats
+    long long *lim = reinterpret_cast<long long *>(w.yn);
+    if ((size_t)(m->cfg.n_up + 1) * 2 > (size_t)T * m->cfg.num_mels) { set_error("ragged decode: no room for the bounds"); return BVC_EINVAL; }
+    if ((rc = launch_ragged_limits(lim, reinterpret_cast<const long long *>(d_frames), reinterpret_cast<const long long *>(d_lengths),
+                                   B, T, n_max, m->cfg.n_up, m->cfg.up_rates, s))) return rc;
+    return run_vocoder(m, w, w.mel, B, T, n_max, out_scale_div, d_wav, -1, nullptr, nullptr, nullptr, s, lim);
 }
 
 static int vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_per_push, bool slide, bvc_vocoder_stream **out);

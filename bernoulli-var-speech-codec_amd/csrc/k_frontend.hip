@@ -51,9 +51,13 @@ constexpr int SB = 65;                 // n0 stride of exchange buffer B
 constexpr int WAVE_LDS = 8 * SA + 8 * SB + 512;      // complex elements per wave
 constexpr int MAG_LDS = 520;                         // floats per wave
 
+// RAGGED: row b holds lens[b] valid samples (clamped into [0, L]) and reflects at ITS end; its frames from ragged_frames(lens[b]) on
+// read nothing and hold the log floor.  The equal-length instantiation is the kernel as it always was.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void stft_logmel_kernel(FrontendTables t, const float *__restrict__ wav,
                                                           long long L, long long T, long long nframes,
-                                                          int pad_left, float scale, float *__restrict__ mel) {
+                                                          int pad_left, float scale, float *__restrict__ mel,
+                                                          const long long *__restrict__ lens) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -85,6 +89,12 @@ __global__ __launch_bounds__(256) void stft_logmel_kernel(FrontendTables t, cons
         if (!live) f = nframes - 1;
         const long long b = f / T, tt = f - b * T;
         const float *src = wav + b * L;
+        long long Lr = L;                          // where this row reflects
+        bool dead = false;                         // a frame behind the row's own end: no load, the log floor
+        if (RAGGED) {
+            Lr = lens[b] < 0 ? 0 : (lens[b] > L ? L : lens[b]);
+            dead = tt >= ragged_frames(Lr, L, pad_left);
+        }
 
         // ---- load + window: lane holds z[64*n2 + lane], n2 = 0..7
         cplx v[8];
@@ -92,10 +102,15 @@ __global__ __launch_bounds__(256) void stft_logmel_kernel(FrontendTables t, cons
         for (int n2 = 0; n2 < 8; ++n2) {
             const int m = 64 * n2 + lane;
             long long i0 = tt * 256 + 2 * m - pad_left, i1 = i0 + 1;
-            i0 = i0 < 0 ? -i0 : (i0 >= L ? 2 * (L - 1) - i0 : i0);          // reflect, no edge repeat
-            i1 = i1 < 0 ? -i1 : (i1 >= L ? 2 * (L - 1) - i1 : i1);
-            v[n2].re = __fmul_rn(__fmul_rn(src[i0], scale), win0[n2]);
-            v[n2].im = __fmul_rn(__fmul_rn(src[i1], scale), win1[n2]);
+            i0 = i0 < 0 ? -i0 : (i0 >= Lr ? 2 * (Lr - 1) - i0 : i0);        // reflect, no edge repeat
+            i1 = i1 < 0 ? -i1 : (i1 >= Lr ? 2 * (Lr - 1) - i1 : i1);
+            if (RAGGED && dead) {
+                v[n2].re = 0.0f;
+                v[n2].im = 0.0f;
+            } else {
+                v[n2].re = __fmul_rn(__fmul_rn(src[i0], scale), win0[n2]);
+                v[n2].im = __fmul_rn(__fmul_rn(src[i1], scale), win1[n2]);
+            }
         }
         // ---- pass 1: DFT over n2, twiddle W_512^(lane*k0), scatter to [k0][lane]
         dft8(v);
@@ -143,6 +158,7 @@ __global__ __launch_bounds__(256) void stft_logmel_kernel(FrontendTables t, cons
             // torch.clamp(min=1e-5) keeps a NaN (fmaxf would not).  The logarithm goes through double precision and is rounded once: ocml's
             // logf is good to about two units in the last place - it gave -11.512927 for the floor itself, where the reference's
             // torch.log gives the correctly rounded -11.512925 (meldataset.py:38-39) - and 80 logarithms per frame cost nothing
+            if (RAGGED && dead) acc = 1e-5f;
             if (live) mel[f * t.num_mels + j] = (float)log((double)(acc < 1e-5f ? 1e-5f : acc));
         }
         // next iteration's first LDS write (bufA) is ordered after this iteration's last read of
@@ -194,6 +210,45 @@ int launch_unpack_codes(const unsigned char *in, long long frames, int z, int nb
     if (total <= 0) return BVC_OK;
     const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
     hipLaunchKernelGGL(unpack_codes_kernel, dim3(grid), dim3(256), 0, s, in, frames, z, nbits, nbytes, codes);
+    BVC_HIP_TRY(hipGetLastError());
+    return BVC_OK;
+}
+
+// ---- mixed-length batches (bvc_encode_ragged): row b's own frame count T_b = ragged_frames(lens[b]) decides which of its frames are live.
+// bits (B, T): the row's bits per frame (d_bits[b], or `dflt` for every row) on live frames, 0 behind them - a var_bit coder then emits
+// 0.5 there by itself.
+__global__ void ragged_bits_kernel(float *__restrict__ bits, const float *__restrict__ d_bits, float dflt,
+                                   const long long *__restrict__ lens, long long L, long long T, int pad_left, long long total) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long b = i / T, t = i - b * T;
+        bits[i] = t < ragged_frames(lens[b], L, pad_left) ? (d_bits ? d_bits[b] : dflt) : 0.0f;
+    }
+}
+
+// codes (B, T, z): 0.5 in every frame behind the row's end (the fixed-rate coders ignore the bits)
+__global__ void ragged_mask_kernel(float *__restrict__ codes, const long long *__restrict__ lens, long long L, long long T, int z,
+                                   int pad_left, long long total) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long f = i / z, b = f / T, t = f - b * T;
+        if (t >= ragged_frames(lens[b], L, pad_left)) codes[i] = 0.5f;
+    }
+}
+
+int launch_ragged_bits(float *bits, const float *d_bits, float dflt, const long long *lens, int B, long long L, long long T,
+                       int pad_left, hipStream_t s) {
+    const long long total = (long long)B * T;
+    if (total <= 0) return BVC_OK;
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(ragged_bits_kernel, dim3(grid), dim3(256), 0, s, bits, d_bits, dflt, lens, L, T, pad_left, total);
+    BVC_HIP_TRY(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_ragged_mask(float *codes, const long long *lens, int B, long long L, long long T, int z, int pad_left, hipStream_t s) {
+    const long long total = (long long)B * T * z;
+    if (total <= 0) return BVC_OK;
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(ragged_mask_kernel, dim3(grid), dim3(256), 0, s, codes, lens, L, T, z, pad_left, total);
     BVC_HIP_TRY(hipGetLastError());
     return BVC_OK;
 }
@@ -250,15 +305,19 @@ int launch_peak_normalize(float *x, int B, long long L, hipStream_t s) {
 }
 
 int launch_stft_logmel(const FrontendTables &t, const float *wav, int B, long long L, long long T,
-                       int pad_left, float scale, float *mel, hipStream_t s) {
+                       int pad_left, float scale, float *mel, hipStream_t s, const long long *lens) {
     const long long nframes = (long long)B * T;
     if (nframes <= 0) return BVC_OK;
     const long long nblocks = (nframes + 3) / 4;
     const int grid = (int)(nblocks > 2048 ? 2048 : nblocks);
     const size_t lds = (size_t)(4 * WAVE_LDS * 2 + 4 * MAG_LDS) * sizeof(float);
     ProbeScope probe(PK_STFT, s);
-    hipLaunchKernelGGL(stft_logmel_kernel, dim3(grid), dim3(256), lds, s, t, wav, L, T, nframes, pad_left,
-                       scale, mel);
+    if (lens)
+        hipLaunchKernelGGL(stft_logmel_kernel<true>, dim3(grid), dim3(256), lds, s, t, wav, L, T, nframes, pad_left,
+                           scale, mel, lens);
+    else
+        hipLaunchKernelGGL(stft_logmel_kernel<false>, dim3(grid), dim3(256), lds, s, t, wav, L, T, nframes, pad_left,
+                           scale, mel, lens);
     BVC_HIP_TRY(hipGetLastError());
     return BVC_OK;
 }

@@ -67,6 +67,7 @@ struct ConvArgs {
     const float *act_a; const float *act_ib;
     float divisor;
     int epi, ks, dil, cout, ntiles, tiles_per_batch;
+    const long long *row_lim;     // (B) input rows of each batch item (mixed-length batches), or nullptr: Lin for all
 };
 
 // sin(x)^2 with |error| < 2.5e-7 (checked against float64 up to |x| = 8060: tests/test_gpu_numerics.py; the reduction
@@ -148,6 +149,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
     const int ntile0 = NSPLIT ? (blockIdx.y * 4 + wave) * NTW : blockIdx.y * NTW;
     const int halo = (a.ks - 1) * a.dil;
     const int rows = TT + halo;
+    const long long lin = a.row_lim ? a.row_lim[b] : a.Lin;       // (uniform: one scalar load per workgroup at most)
 
     // ---- stage the activated input span [t0-halo, t0+TT) in LDS
     const float *inb = a.in + (long long)b * a.in_bs;
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
         const int row = idx / C4, c4 = idx - row * C4;
         const long long tg = t0 - halo + row;
         f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (tg >= 0 && tg < a.Lin) {
+        if (tg >= 0 && tg < lin) {
             v = *reinterpret_cast<const f32x4 *>(inb + tg * CIN + c4 * 4);
             if (a.act_a) {
                 const f32x4 aa = *reinterpret_cast<const f32x4 *>(a.act_a + c4 * 4);
@@ -1218,7 +1220,8 @@ int conv_kernels_init() {
 }
 
 int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *out, long long Lout, int B,
-                     int epi, const float *res, const float *acc, float divisor, hipStream_t s, const ConvWindow *win) {
+                     int epi, const float *res, const float *acc, float divisor, hipStream_t s, const ConvWindow *win,
+                     const long long *row_lim) {
     if (B <= 0 || Lout <= 0) return BVC_OK;
     if (c.cout % 4) { set_error("conv_mfma: %d output columns (the epilogue stores 16-byte granules)", c.cout); return BVC_EINVAL; }
     ConvArgs a;
@@ -1229,6 +1232,7 @@ int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *
     a.wp = c.wp; a.bias = c.bias; a.act_a = c.act_a; a.act_ib = c.act_ib;
     a.divisor = divisor; a.epi = epi; a.ks = c.ks; a.dil = c.dil; a.cout = c.cout; a.ntiles = c.ntiles;
     a.tiles_per_batch = 0;
+    a.row_lim = row_lim;
     // streaming hops: one or two new frames = at most 16 rows in front of the first two upsamplers; the row-split tiles (64 rows
     // and more per workgroup) would compute mostly rows nobody reads, so the waves split the columns instead
     if (win && Lout - a.row_begin <= 16) {
@@ -1261,7 +1265,8 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float *__restrict_
                                                         const float *__restrict__ act_a,
                                                         const float *__restrict__ act_ib, float div,
                                                         float *__restrict__ wav, long long n_out,
-                                                        int tiles_per_batch, long long in_bs, long long row_begin) {
+                                                        int tiles_per_batch, long long in_bs, long long row_begin,
+                                                        const long long *__restrict__ n_rows) {
     extern __shared__ __attribute__((aligned(16))) float tile[];     // [(256 + ks-1)][C]
     const int tid = threadIdx.x;
     const int b = blockIdx.x / tiles_per_batch;
@@ -1278,6 +1283,7 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float *__restrict_
     __syncthreads();
     const long long t = t0 + tid - row_begin;                        // output sample index
     if (t >= n_out) return;
+    if (n_rows && t >= n_rows[b]) { wav[(long long)b * n_out + t] = 0.0f; return; }       // behind a mixed-length batch item's end
     float acc = 0.0f;
     for (int j = 0; j < ks; ++j)
 #pragma unroll
@@ -1287,14 +1293,45 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float *__restrict_
 
 int launch_conv_post(const float *in, long long Lin, int C, int ks, const float *w, const float *bias,
                      const float *act_a, const float *act_ib, float div, float *wav, long long n_out, int B,
-                     hipStream_t s, const ConvWindow *win) {
+                     hipStream_t s, const ConvWindow *win, const long long *n_rows) {
     if (B <= 0 || n_out <= 0) return BVC_OK;
     if (C != 8) { set_error("conv_post: unsupported channel count %d", C); return BVC_EINVAL; }
     const int tiles = (int)((n_out + 255) / 256);
     const size_t lds = (size_t)(256 + ks - 1) * C * sizeof(float);
     ProbeScope probe(PK_POST, s);
     hipLaunchKernelGGL(conv_post_kernel<8>, dim3((unsigned)(tiles * (long long)B)), dim3(256), lds, s, in, Lin, ks,
-                       w, bias, act_a, act_ib, div, wav, n_out, tiles, win ? win->in_bs : Lin * C, win ? win->row_begin : 0);
+                       w, bias, act_a, act_ib, div, wav, n_out, tiles, win ? win->in_bs : Lin * C, win ? win->row_begin : 0, n_rows);
+    BVC_HIP_TRY(hipGetLastError());
+    return BVC_OK;
+}
+
+// Per-item bounds of a mixed-length decode (one thread per item).  Item b alone would run the generator on frames[b] frames: its
+// upsampler i reads L_i rows, L_0 = frames[b], L_{i+1} = (L_i + 1) * u_i, and row L_i (one past its end, which the equal-length
+// batch holds another frame in) must read as zero.  Everything else in the generator is causal, so those rows below the bound are
+// already the item's own.
+struct UpRates { int u[8]; };
+__global__ void ragged_limits_kernel(long long *__restrict__ lim, const long long *__restrict__ frames,
+                                     const long long *__restrict__ lengths, int B, long long T, long long n_max, int n_up, UpRates r) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const long long f = frames[b] < 0 ? 0 : (frames[b] > T ? T : frames[b]);
+    long long L = f;
+    for (int i = 0; i < n_up; ++i) {
+        lim[(long long)i * B + b] = L;
+        L = (L + 1) * r.u[i];
+    }
+    long long n = lengths[b] < L ? lengths[b] : L;
+    n = f == 0 ? 0 : (n < 0 ? 0 : (n > n_max ? n_max : n));
+    lim[(long long)n_up * B + b] = n;
+}
+
+int launch_ragged_limits(long long *lim, const long long *frames, const long long *lengths, int B, long long T, long long n_max,
+                         int n_up, const int *up_rates, hipStream_t s) {
+    if (B <= 0) return BVC_OK;
+    if (n_up > 8) { set_error("ragged limits: %d upsamplers", n_up); return BVC_EINVAL; }
+    UpRates r;
+    for (int i = 0; i < 8; ++i) r.u[i] = i < n_up ? up_rates[i] : 0;
+    hipLaunchKernelGGL(ragged_limits_kernel, dim3((B + 255) / 256), dim3(256), 0, s, lim, frames, lengths, B, T, n_max, n_up, r);
     BVC_HIP_TRY(hipGetLastError());
     return BVC_OK;
 }

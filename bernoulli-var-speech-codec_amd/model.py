@@ -16,7 +16,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _abi, weights
+from . import _abi, ragged, weights
 from .config import DEFAULT_CONFIG, load_config
 
 _ROOT = os.path.abspath(os.path.dirname(__file__))
@@ -374,10 +374,16 @@ class BVRNNCodecModel(_OnDevice):
         return mel.to(out_dev)
 
     @torch.no_grad()
-    def encode(self, x, bitrate):
+    def encode(self, x, bitrate, lengths=None):
         """Waveforms ``x`` (batch, samples), expected in [-1, 1], to codes (batch, samples // hop, z_dim) with values in
         {0, 1} and 0.5 at masked positions.  ``bitrate`` [bit/s] selects round(bitrate * hop / fs) leading bits per frame
-        (saturating at z_dim; ignored by fixed-rate configs) - bvrnn_codec_model.py:44-62."""
+        (saturating at z_dim; ignored by fixed-rate configs) - bvrnn_codec_model.py:44-62.
+
+        Mixed-length batch: ``lengths`` (batch,) gives the valid samples of each row (the rest of the row is never read), and
+        ``bitrate`` may be one value per row.  Row b then equals ``encode(x[b:b+1, :lengths[b]], bitrate[b])`` bit for bit in
+        its first num_frames(lengths[b]) frames and is 0.5 after them."""
+        if lengths is not None or ragged.per_row(bitrate, x.shape[0], "bitrate") is not None:
+            return self._encode_ragged(x, bitrate, lengths)
         eng = self.engine(x)
         out_dev = x.device
         x = _prep(x, eng.device)
@@ -396,9 +402,45 @@ class BVRNNCodecModel(_OnDevice):
         return eng.deliver(codes, out_dev)
 
     @torch.no_grad()
-    def decode(self, codes, length):
+    def _encode_ragged(self, x, bitrate, lengths):
+        eng = self.engine(x)
+        out_dev = x.device
+        x = _prep(x, eng.device)
+        if x.dim() != 2:
+            raise RuntimeError("expected a (batch, length) waveform")
+        B, L = x.shape
+        lens = ragged.per_row_ints(L if lengths is None else lengths, B, "lengths")
+        if (lens > L).any():
+            raise RuntimeError(f"lengths must not exceed the row length {L} (got {int(lens.max())})")
+        for n in [L] + sorted(set(lens.tolist())):            # the equal-length path's check, for the row and for every utterance
+            if eng.num_frames(int(n)) <= 0:
+                raise RuntimeError(f"Argument #4: Padding size should be less than the corresponding input dimension "
+                                   f"(length {int(n)} is too short for the reflect padding of the STFT front-end)")
+        T = eng.num_frames(L)
+        rates = ragged.per_row(bitrate, B, "bitrate")
+        bits = None
+        if rates is not None:                                  # bits_per_frame per row, the reference's rounding in float64
+            bits = torch.from_numpy(np.round(rates * self.conf['hopsize'] / self.conf['fs']).astype(np.float32)).to(eng.device)
+        d_lens = torch.from_numpy(lens).to(eng.device)
+        codes = torch.empty(B, T, self.conf["z_dim"], device=eng.device)
+        ws, nws = eng.workspace(B, T)
+        with torch.cuda.device(eng.device):
+            _abi.check(eng.lib.bvc_encode_ragged(eng.handle, _abi.ptr(x), ctypes.c_void_p(d_lens.data_ptr()), B, L, float(SCALING),
+                                                 _abi.ptr(bits), self.bits_per_frame(bitrate) if rates is None else 0.0,
+                                                 _abi.ptr(codes), ws, nws, eng.stream()))
+        return eng.deliver(codes, out_dev)
+
+    @torch.no_grad()
+    def decode(self, codes, length, frames=None):
         """Codes (batch, frames, z_dim) back to waveforms (batch, min(length, 256 * frames + 294)): coder decode from a
-        zero state, vocoder, output gain undone - bvrnn_codec_model.py:64-71."""
+        zero state, vocoder, output gain undone - bvrnn_codec_model.py:64-71.
+
+        Mixed-length batch: ``length`` (batch,) per row, and optionally ``frames`` (batch,) valid code frames per row (default
+        min(frames, num_frames(length[b])), the frame count encode gives for that length).  Returns (batch, max n_b): row b equals
+        ``decode(codes[b:b+1, :frames[b]], length[b])`` in its first n_b = min(length[b], 256 * frames[b] + 294) samples and is 0
+        after them (n_b = 0 for a row without frames)."""
+        if frames is not None or ragged.per_row(length, codes.shape[0], "length") is not None:
+            return self._decode_ragged(codes, length, frames)
         eng = self.engine(codes)
         out_dev = codes.device
         codes = _prep(codes, eng.device)
@@ -414,11 +456,85 @@ class BVRNNCodecModel(_OnDevice):
                                               _abi.ptr(wav), ws, nws, eng.stream()))
         return eng.deliver(wav, out_dev)
 
-    def forward(self, x, bitrate):
-        """decode(encode(x, bitrate)) trimmed to the input length (bvrnn_codec_model.py:73-76)."""
+    @torch.no_grad()
+    def _decode_ragged(self, codes, length, frames):
+        eng = self.engine(codes)
+        out_dev = codes.device
+        codes = _prep(codes, eng.device)
+        B, T, Z = codes.shape
+        if Z != self.conf["z_dim"]:
+            raise RuntimeError(f"codes must have {self.conf['z_dim']} values per frame, got {Z}")
+        lens = ragged.per_row_ints(length, B, "length")
+        if (lens < 0).any():
+            raise RuntimeError("per-row lengths must not be negative")
+        if frames is None:
+            fr = np.array([min(T, max(eng.num_frames(int(n)), 0)) for n in lens], dtype=np.int64)
+        else:
+            fr = ragged.per_row_ints(frames, B, "frames")
+            if (fr < 0).any() or (fr > T).any():
+                raise RuntimeError(f"frames must lie in [0, {T}]")
+        n = [min(int(l), eng.vocoder_length(int(f))) if f > 0 else 0 for l, f in zip(lens, fr)]
+        n_max = max(n) if n else 0
+        wav = torch.empty(B, n_max, device=eng.device)
+        if n_max:
+            d_fr = torch.from_numpy(fr).to(eng.device)
+            d_lens = torch.from_numpy(lens).to(eng.device)
+            ws, nws = eng.workspace(B, T)
+            with torch.cuda.device(eng.device):
+                _abi.check(eng.lib.bvc_decode_ragged(eng.handle, _abi.ptr(codes), ctypes.c_void_p(d_fr.data_ptr()), B, T,
+                                                     ctypes.c_void_p(d_lens.data_ptr()), n_max, float(SCALING), _abi.ptr(wav),
+                                                     ws, nws, eng.stream()))
+        return eng.deliver(wav, out_dev)
+
+    def forward(self, x, bitrate, lengths=None):
+        """decode(encode(x, bitrate)) trimmed to the input length (bvrnn_codec_model.py:73-76); with ``lengths`` (batch,),
+        decode(encode(x, bitrate, lengths), lengths): row b is forward(x[b:b+1, :lengths[b]]) followed by zeros."""
         length = x.shape[1]
-        codes = self.encode(x, bitrate)
-        return self.decode(codes, length)
+        codes = self.encode(x, bitrate, lengths)
+        return self.decode(codes, length if lengths is None else lengths)
+
+    # ---- corpora: lists of utterances of any lengths, coded in mixed-length batches
+    @torch.no_grad()
+    def encode_many(self, waves, bitrate, max_batch=64):
+        """1-D waveforms of any lengths -> their codes, a list of (num_frames(len_i), z_dim) tensors in input order.
+        ``bitrate``: one value, or one per item.  The items are sorted by length and coded in mixed-length calls of at most
+        ``max_batch`` rows (ragged.batch_plan); item i equals ``encode(waves[i][None], bitrate_i)[0]`` bit for bit."""
+        waves = list(waves)
+        if not waves:
+            return []
+        rates = ragged.per_row(bitrate, len(waves), "bitrate")
+        lens = [int(w.shape[-1]) for w in waves]
+        eng = self.engine(waves[0])
+        out_dev = waves[0].device
+        perm, bounds, inv = ragged.batch_plan(lens, max_batch)
+        done = []
+        for a, e in bounds:
+            idx = perm[a:e]
+            x = nn.utils.rnn.pad_sequence([_prep(waves[i].reshape(-1), eng.device) for i in idx], batch_first=True)
+            br = bitrate if rates is None else rates[idx]
+            codes = self.encode(x, br, lengths=[lens[i] for i in idx]).to(out_dev)
+            done += [codes[r, :eng.num_frames(lens[i])] for r, i in enumerate(idx)]
+        return [done[k] for k in inv]
+
+    @torch.no_grad()
+    def decode_many(self, codes_list, lengths, max_batch=64):
+        """(frames_i, z_dim) codes of any frame counts -> waveforms, a list of (min(len_i, 256 * frames_i + 294),) tensors in
+        input order.  ``lengths``: one value, or one per item.  Item i equals ``decode(codes_list[i][None], lengths_i)[0]``."""
+        codes_list = list(codes_list)
+        if not codes_list:
+            return []
+        lens = ragged.per_row_ints(lengths, len(codes_list), "lengths")
+        frames = [int(c.shape[0]) for c in codes_list]
+        eng = self.engine(codes_list[0])
+        out_dev = codes_list[0].device
+        perm, bounds, inv = ragged.batch_plan(frames, max_batch)
+        done = []
+        for a, e in bounds:
+            idx = perm[a:e]
+            c = nn.utils.rnn.pad_sequence([_prep(codes_list[i], eng.device) for i in idx], batch_first=True, padding_value=0.5)
+            wav = self.decode(c, lens[idx], frames=[frames[i] for i in idx]).to(out_dev)
+            done += [wav[r, :(min(int(lens[i]), eng.vocoder_length(frames[i])) if frames[i] > 0 else 0)] for r, i in enumerate(idx)]
+        return [done[k] for k in inv]
 
     @torch.no_grad()
     def forward_fused(self, x, bitrate, return_codes=False):

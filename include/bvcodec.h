@@ -12,7 +12,7 @@
  *  - every pointer named d_* is DEVICE memory owned by the caller, contiguous float32;
  *    every pointer named h_* is HOST memory;
  *  - the compute entry points (bvc_stft_logmel, bvc_bvrnn_*, bvc_bigvgan, bvc_encode, bvc_decode,
- *    bvc_vocoder_stream_push, bvc_pack/unpack_codes, bvc_resample_poly, bvc_peak_normalize) are
+ *    bvc_encode_ragged, bvc_decode_ragged, bvc_vocoder_stream_push, bvc_pack/unpack_codes, bvc_resample_poly, bvc_peak_normalize) are
  *    asynchronous on `stream` and use only the caller-provided workspace.  They do not allocate or
  *    synchronise, with these exceptions: the first calls per process create a handful of HIP events (the
  *    persistent launches' ticket, the end-of-call mark of the "auto" schedule, one per bvc_flow_fence slot in
@@ -140,7 +140,7 @@ int bvc_model_get_option(const bvc_model *m, const char *name, int32_t *value);
 /* The persistent recurrence kernel's workgroups hand activations to each other, so all of them must be resident together;
  * every wait in it is bounded.  If a wait ever times out (a workgroup that never became resident: another process on the
  * device, a CU mask), the kernel still ends, with invalid results, and stores a code (frame << 4 | layer, top bit set) in a
- * status word in host-mapped memory.  EVERY compute entry point (bvc_encode, bvc_decode, bvc_bvrnn_*, bvc_bigvgan,
+ * status word in host-mapped memory.  EVERY compute entry point (bvc_encode, bvc_decode, bvc_*_ragged, bvc_bvrnn_*, bvc_bigvgan,
  * bvc_stft_logmel) reads that word first, without synchronising, and returns BVC_ETIMEOUT - once, clearing it - if an
  * earlier call of this model timed out.  bvc_model_status synchronises the device first, so it also sees calls still in
  * flight; it returns BVC_ETIMEOUT and the code, and clears it; BVC_OK and 0 otherwise. */
@@ -250,6 +250,25 @@ int bvc_encode(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, flo
 /* BVRNNCodecModel.decode (bvrnn_codec_model.py:64-71): zero state, BVRNN.decode, vocoder, /scale. */
 int bvc_decode(const bvc_model *m, const float *d_codes, int32_t B, int64_t T, int64_t length,
                float out_scale_div, float *d_wav, void *d_ws, size_t ws_bytes, void *stream);
+
+/* Mixed-length batches: utterances of their own lengths (and bitrates) in ONE call, each coded exactly as it would be alone.
+ * d_lengths / d_frames are DEVICE int64 arrays (B).  The library cannot look at them without synchronising, so validating them is
+ * the CALLER's job; the kernels only clamp (lengths into [0, L], frames into [0, T]), and a row too short for the reflect padding
+ * (bvc_num_frames(length) <= 0) yields all-0.5 codes / an all-zero waveform without touching memory out of bounds.  Workspace:
+ * bvc_workspace_bytes(m, B, T) as for bvc_encode / bvc_decode.  Asynchronous, no allocation, capturable, like every compute entry point.
+ *
+ * Encode: row b of d_wav (B, L) holds d_lengths[b] <= L valid samples (the rest of the row is never read); d_bits (B) bits per frame
+ * per utterance, or NULL for bits_per_frame everywhere.  d_codes (B, T, z_dim), T = bvc_num_frames(L); frames t >= T_b =
+ * bvc_num_frames(d_lengths[b]) of row b are 0.5.  Row b == bvc_encode of that utterance alone (its T_b frames), bit for bit. */
+int bvc_encode_ragged(const bvc_model *m, const float *d_wav, const int64_t *d_lengths, int32_t B, int64_t L, float scale,
+                      const float *d_bits, float bits_per_frame, float *d_codes, void *d_ws, size_t ws_bytes, void *stream);
+/* Decode: d_frames (B) valid frames per row (<= T), d_lengths (B) samples wanted per row; d_wav (B, n_max),
+ * 0 < n_max <= bvc_vocoder_length(m, T).  Row b == bvc_decode(codes[b, :frames_b], length_b) in its first
+ * min(length_b, bvc_vocoder_length(frames_b)) samples (clamped to n_max) and 0 after them; code frames behind frames_b are never
+ * read into those samples. */
+int bvc_decode_ragged(const bvc_model *m, const float *d_codes, const int64_t *d_frames, int32_t B, int64_t T,
+                      const int64_t *d_lengths, int64_t n_max, float out_scale_div, float *d_wav, void *d_ws, size_t ws_bytes,
+                      void *stream);
 
 /* BVRNNCodecModel.forward (bvrnn_codec_model.py:73-76: decode(encode(x, bitrate), x.shape[1])) WITHOUT the second recurrence.  The
  * encoder's frame loop already runs the decoder on every frame (bvrnn.py:198-204) from exactly the states BVRNN.decode would visit
