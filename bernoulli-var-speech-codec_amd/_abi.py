@@ -62,6 +62,10 @@ SIGNATURES = {
     "bvc_stream_codec_destroy": (None, [_vp]),
     "bvc_stream_codec_buffers": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i32)]),
     "bvc_stream_codec_tick": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), _vp]),
+    "bvc_stream_codec_open": (ctypes.c_int, [_vp, _i32, _f, ctypes.POINTER(_i32)]),
+    "bvc_stream_codec_close": (ctypes.c_int, [_vp, _i32]),
+    "bvc_stream_codec_set_bits": (ctypes.c_int, [_vp, _i32, _f]),
+    "bvc_stream_codec_slot_frames": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
     "bvc_encode": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _f, _vp, _vp, _sz, _vp]),
     "bvc_decode": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i64, _f, _vp, _vp, _sz, _vp]),
     "bvc_forward": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _f, _i64, _f, _vp, _vp, _vp, _sz, _vp]),

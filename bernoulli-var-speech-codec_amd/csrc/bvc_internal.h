@@ -259,7 +259,12 @@ enum ConvEpi { CE_STORE = 0, CE_RES = 1, CE_RES_ACC = 2, CE_RES_ACC_DIV = 3 };
 #ifdef BVC_PHASE_PROBE
 int phase_probe_read(unsigned long long *out, int reset);   // debugging builds only (tools/phase_probe.py)
 #endif
-struct ConvWindow { long long in_bs, out_bs, row_begin, t_origin; };
+struct ConvWindow {
+    long long in_bs, out_bs, row_begin, t_origin;
+    // AMP pairs of a session whose rows start at different times: row b's t_origin is t_origin + age_rate * row_age[b] (device memory)
+    const int *row_age = nullptr;
+    int age_rate = 0;
+};
 // in (B, Lin, cin) channels-last; out (B, Lout, cout).  Output row r reads input rows
 // r - (ks-1)*dil ... r  (rows outside [0,Lin) are zero).  res/acc have the layout of out.
 int conv_kernels_init();

@@ -1605,6 +1605,9 @@ struct bvc_vocoder_stream {
     size_t pool_floats = 0;
     RotEntry *d_tab = nullptr;
     int n_ten = 0, max_hc4 = 0;
+    // rows that start at different times (bvc_stream_codec's slots): frames since each row's own start, capped at STREAM_WARM_FRAMES,
+    // in device memory owned by the session (nullptr: every row started with the state, `frames` decides)
+    const int *d_age = nullptr;
     StreamTensor mel, y0;
     std::vector<StreamTensor> X, XS;                  // per stage
     std::vector<StreamTensor> P, Q;                   // per (stage, AMP block): each block's intermediates keep their own history
@@ -1656,6 +1659,7 @@ int stream_push(bvc_vocoder_stream *st, const float *d_mel, int k, float div, fl
         // does, so the value is frozen there (a hop captured into a hipGraph then replays with identical arguments)
         const long long fr = st->frames < STREAM_WARM_FRAMES ? st->frames : STREAM_WARM_FRAMES;
         ConvWindow w{bs(X), bs(X), X.H, (long long)X.rate * fr - X.H};
+        if (st->d_age) { w.t_origin = -(long long)X.H; w.row_age = st->d_age; w.age_rate = X.rate; }    // per row, read by the kernel
         for (int j = 0; j < c.n_resk; ++j) {
             const StreamTensor &P = st->P[i * c.n_resk + j], &Q = st->Q[i * c.n_resk + j];
             const float *cur = at(X);
@@ -1713,12 +1717,18 @@ namespace {
 
 struct StreamDev { int fill; int pad_[3]; };             // samples buffered: sbuf[:, 0] is sample 256*F - 256, F = frames emitted
 
+// row_off[b]: the row's delay in samples (its hop lands that far behind the session's fill level), < 0 for an idle row, whose hop is
+// zeros whatever the caller's d_in holds
 __global__ __launch_bounds__(256) void sc_append_kernel(const StreamDev *__restrict__ st, const float *__restrict__ xin, int hop,
-                                                        float *__restrict__ sbuf, int cap) {
+                                                        float *__restrict__ sbuf, int cap, const int *__restrict__ row_off) {
     const int fill = st->fill;
-    float *d = sbuf + (long long)blockIdx.y * cap + fill;
+    const int off = row_off[blockIdx.y];
+    const int at = fill + (off < 0 ? 0 : off);
+    float *d = sbuf + (long long)blockIdx.y * cap + at;
     const float *x = xin + (long long)blockIdx.y * hop;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < hop; i += gridDim.x * 256) d[i] = x[i];
+    const int n = hop < cap - at ? hop : cap - at;
+    if (off < 0) { for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d[i] = 0.0f; }
+    else         { for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d[i] = x[i]; }
 }
 // first tick only: samples -256..-1 of the reflect padding (meldataset.py:72-81): x[-i] = x[i]
 __global__ __launch_bounds__(256) void sc_reflect_left_kernel(float *__restrict__ sbuf, int cap, int pad) {
@@ -1731,7 +1741,70 @@ __global__ __launch_bounds__(256) void sc_shift_kernel(const float *__restrict__
     float *d = dst + (long long)blockIdx.y * dstride;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d[i] = a[i];
 }
-__global__ void sc_advance_kernel(StreamDev *st, int delta) { if (threadIdx.x == 0) st->fill += delta; }
+// end of a tick: the fill level, and every row's age (frames since its own start, capped at `warm`: see bvc_vocoder_stream::d_age)
+__global__ void sc_advance_kernel(StreamDev *st, int delta, int *__restrict__ age, int B, int k, int warm) {
+    if (threadIdx.x == 0) st->fill += delta;
+    if (k > 0)
+        for (int b = threadIdx.x; b < B; b += blockDim.x) { const int a = age[b] + k; age[b] = a < warm ? a : warm; }
+}
+
+// ---- slots: rows of a session that are opened, closed and re-rated while the others keep running ----
+// The host keeps the book; what changed since the last tick travels as a kernel argument (up to SC_LIST rows per launch).
+const int SC_LIST = 64;
+enum { SC_SET_OFF = 1, SC_ZERO_TAIL = 2, SC_SET_BITS = 4 };
+struct SlotUpdate { int row, off, flags; float bits; };
+struct SlotUpdateList { int n; int pad_[3]; SlotUpdate e[SC_LIST]; };
+struct SlotRowList { int n; int pad_[3]; int row[SC_LIST]; };
+
+// before the append of a tick: new delay / idle mark, the closed stream's tail out of the sample buffer, bits per frame in every
+// (B, k) layout (bits_base: the layouts k = 1 .. kmax one behind the other)
+__global__ __launch_bounds__(256) void sc_slot_update_kernel(SlotUpdateList l, const StreamDev *__restrict__ st, int *__restrict__ row_off,
+                                                             float *__restrict__ sbuf, int cap, float *__restrict__ bits_base, int B, int kmax) {
+    const SlotUpdate u = l.e[blockIdx.x];
+    if ((u.flags & SC_SET_OFF) && threadIdx.x == 0) row_off[u.row] = u.off;
+    if (u.flags & SC_ZERO_TAIL) {
+        float *d = sbuf + (long long)u.row * cap;
+        for (int i = st->fill + threadIdx.x; i < cap; i += 256) d[i] = 0.0f;
+    }
+    if (u.flags & SC_SET_BITS) {
+        const int tri = kmax * (kmax + 1) / 2;             // layout k starts B * k (k - 1) / 2 floats in; entry i of the triangle is (k, j)
+        for (int i = threadIdx.x; i < tri; i += 256) {
+            int k = 1, j = i;
+            while (j >= k) { j -= k; ++k; }
+            bits_base[(long long)B * (k * (k - 1) / 2) + (long long)u.row * k + j] = u.bits;
+        }
+    }
+}
+
+// the tick that emits frame 0 of the rows in `l`, after the append: what a new session has at tick 0, for those rows only.
+// blockIdx.y < n_ten: that tensor's history rows of the generator (both copies, where the windows stand); blockIdx.y == n_ten: the left
+// reflect padding x[-i] = x[i] (the row's sample 0 sits `pad` samples into the buffer: its frame 0 is the first of this tick), both GRU
+// states, the row's age
+__global__ __launch_bounds__(256) void sc_slot_start_kernel(SlotRowList l, const RotEntry *__restrict__ tab, int n_ten, int cursor,
+                                                            float *__restrict__ sbuf, int cap, int pad, float *__restrict__ h_enc,
+                                                            float *__restrict__ h_dec, int Hd, int *__restrict__ age) {
+    const int row = l.row[blockIdx.z];
+    if ((int)blockIdx.y < n_ten) {
+        const RotEntry e = tab[blockIdx.y];
+        const long long n4 = (long long)e.H * e.C / 4;
+        const long long at = (long long)row * e.bs + (long long)cursor * e.rate * e.C;
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = 0; q < (e.buf[1] == e.buf[0] ? 1 : 2); ++q) {
+            float4 *d = reinterpret_cast<float4 *>(e.buf[q] + at);
+            for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) d[i] = z;
+        }
+        return;
+    }
+    if (blockIdx.x == 0) {
+        float *d = sbuf + (long long)row * cap;
+        for (int i = 1 + threadIdx.x; i <= pad; i += 256) d[pad - i] = d[pad + i];
+        if (threadIdx.x == 0) age[row] = 0;
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < Hd; i += gridDim.x * 256) {
+        h_enc[(long long)row * Hd + i] = 0.0f;
+        h_dec[(long long)row * Hd + i] = 0.0f;
+    }
+}
 
 }  // namespace
 
@@ -1749,6 +1822,22 @@ struct bvc_stream_codec {
           *wav = nullptr, *h_enc = nullptr, *h_dec = nullptr;
     void *ws = nullptr; size_t ws_bytes = 0;
     bvc_vocoder_stream *voc = nullptr;
+    // slots: each row is a stream of its own (see include/bvcodec.h).  Device side: row_off (delay in samples, < 0 idle), age (frames
+    // since the row's start, capped), bitsbuf = the bits per (row, frame) in every (B, k) layout, k = 1 .. kmax, one behind the other
+    // (bits_of(k)): a tick - and a graph captured for its k - reads the layout of its own frame count.
+    struct Slot {
+        bool open = true, started = true;
+        int delay = 0, pending = 0;     // pending: SC_* flags that the next tick sends to the device
+        int64_t frame0 = 0;             // session frame that is the stream's frame 0
+        float bits = 0.0f;
+        int last_count = 0;             // frames of the last tick that belong to the stream, and the stream's index of the first
+        int64_t last_frame0 = 0;
+    };
+    std::vector<Slot> slots;
+    int *row_off = nullptr, *age = nullptr;
+    int max_delay = 0;
+    int n_pending = 0, n_waiting = 0;   // slots with pending flags / open slots whose frame 0 is still to come
+    float *bits_of(int k) const { return bitsbuf + (size_t)B * (k * (k - 1) / 2); }
     hipGraphExec_t graph[8][2] = {};    // [k][vocoder parity]
     bool use_graph = true;
     bool tick_flow = true;      // the ticks' recurrences on the persistent kernel where it is available (BVC_STREAM_FLOW=0: never)
@@ -1760,6 +1849,75 @@ struct bvc_stream_codec {
 };
 
 namespace {
+
+// Where a stream that joins a running session starts.  `samples` = samples per row the session has taken so far (ticks * hop_samples).
+// Frame f reads samples [hop f - pad, hop f - pad + n_fft), so the tick that completes it is the first whose samples reach
+// hop f - pad + n_fft.  The stream's sample 0 must be a session frame boundary hop * f0 not before its arrival; f0 is made the FIRST frame
+// of its tick, so that the row's reset lies between two ticks: the smallest such f0 >= ceil(samples / hop).  delay = hop * f0 - samples.
+// (bvcodec.streaming.join_plan is the same arithmetic; tests/test_stream_slots_cpu.py checks it against a simulation of the schedule.)
+int64_t tick_of_frame(int64_t f, int hop_samples, const bvc_config &c) {
+    const int64_t need = c.hop * f - c.pad_left + c.n_fft;
+    return (need + hop_samples - 1) / hop_samples - 1;
+}
+void join_plan(int64_t samples, int hop_samples, const bvc_config &c, int *delay, int64_t *frame0, int64_t *tick0) {
+    int64_t f = (samples + c.hop - 1) / c.hop;
+    while (f > 0 && tick_of_frame(f - 1, hop_samples, c) == tick_of_frame(f, hop_samples, c)) ++f;
+    *delay = (int)(c.hop * f - samples);
+    *frame0 = f;
+    if (tick0) *tick0 = tick_of_frame(f, hop_samples, c);
+}
+
+// pending slot changes -> device, in one launch per SC_LIST slots (before the tick's append)
+int stream_send_pending(bvc_stream_codec *st, hipStream_t s) {
+    SlotUpdateList l;
+    l.n = 0;
+    auto flush = [&]() -> int {
+        if (l.n == 0) return BVC_OK;
+        sc_slot_update_kernel<<<dim3(l.n), 256, 0, s>>>(l, st->d_state, st->row_off, st->sbuf, st->cap, st->bitsbuf, st->B, st->kmax);
+        BVC_HIP_TRY(hipGetLastError());
+        l.n = 0;
+        return BVC_OK;
+    };
+    int rc;
+    for (int b = 0; b < st->B && st->n_pending > 0; ++b) {
+        bvc_stream_codec::Slot &sl = st->slots[b];
+        if (!sl.pending) continue;
+        l.e[l.n++] = SlotUpdate{b, sl.open ? sl.delay : -1, sl.pending, sl.bits};
+        sl.pending = 0;
+        --st->n_pending;
+        if (l.n == SC_LIST && (rc = flush())) return rc;
+    }
+    st->n_pending = 0;
+    return flush();
+}
+
+// the rows whose frame 0 is the first frame of this tick (frames [f_begin, f_begin + k)): per-row reset, after the append
+int stream_start_rows(bvc_stream_codec *st, int64_t f_begin, int k, hipStream_t s) {
+    const bvc_config &c = st->m->cfg;
+    const bvc_vocoder_stream *v = st->voc;
+    SlotRowList l;
+    l.n = 0;
+    auto flush = [&]() -> int {
+        if (l.n == 0) return BVC_OK;
+        const unsigned gx = (unsigned)std::max(1, std::min(16, (v->max_hc4 + 255) / 256));
+        sc_slot_start_kernel<<<dim3(gx, (unsigned)v->n_ten + 1, (unsigned)l.n), 256, 0, s>>>(
+            l, v->d_tab, v->n_ten, v->slide ? v->cursor : 0, st->sbuf, st->cap, c.pad_left, st->h_enc, st->h_dec, c.h_dim, st->age);
+        BVC_HIP_TRY(hipGetLastError());
+        l.n = 0;
+        return BVC_OK;
+    };
+    int rc;
+    for (int b = 0; b < st->B && st->n_waiting > 0; ++b) {
+        bvc_stream_codec::Slot &sl = st->slots[b];
+        if (!sl.open || sl.started || sl.frame0 >= f_begin + k) continue;
+        if (sl.frame0 != f_begin) { set_error("bvc_stream_codec_tick: slot %d starts inside a tick (frame %lld of %lld+%d)", b, (long long)sl.frame0, (long long)f_begin, k); return BVC_EINVAL; }
+        sl.started = true;
+        --st->n_waiting;
+        l.row[l.n++] = b;
+        if (l.n == SC_LIST && (rc = flush())) return rc;
+    }
+    return flush();
+}
 
 // the launches of one tick with k new frames (k > 0), in stream order
 int stream_tick_body(bvc_stream_codec *st, int k, hipStream_t s) {
@@ -1775,7 +1933,7 @@ int stream_tick_body(bvc_stream_codec *st, int k, hipStream_t s) {
     sc_shift_kernel<<<dim3((unsigned)((keep + 255) / 256), B), 256, 0, s>>>(st->sbuf, st->cap, 256 * k, st->stmp, st->cap, keep);
     sc_shift_kernel<<<dim3((unsigned)((keep + 255) / 256), B), 256, 0, s>>>(st->stmp, st->cap, 0, st->sbuf, st->cap, keep);
     BVC_HIP_TRY(hipGetLastError());
-    if ((rc = run_encode(m, w, st->ws, st->mel, m->cfg.var_bit ? st->bitsbuf : nullptr, st->h_enc, B, k, st->codes, nullptr, st->h_enc,
+    if ((rc = run_encode(m, w, st->ws, st->mel, m->cfg.var_bit ? st->bits_of(k) : nullptr, st->h_enc, B, k, st->codes, nullptr, st->h_enc,
                          nullptr, s))) return rc;
     if ((rc = run_decode(m, w, st->ws, st->codes, st->h_dec, B, k, st->melhat, st->h_dec, s))) return rc;
     return bvc_vocoder_stream_push(st->voc, st->melhat, k, st->out_div, st->wav, s);
@@ -2116,7 +2274,13 @@ int bvc_stream_codec_create(const bvc_model *m, int32_t B, int32_t hop_samples, 
     st->m = m; st->B = B; st->hop = hop_samples; st->bits = bits_per_frame; st->scale = scale; st->out_div = out_scale_div;
     st->kmax = (hop_samples + c.hop - 1) / c.hop + 1;
     if (st->kmax > 7) { set_error("bvc_stream_codec_create: hop too long (%d frames per tick)", st->kmax); return BVC_EINVAL; }
-    st->cap = c.n_fft + c.hop * st->kmax + hop_samples;
+    // the longest delay a joining stream can get (join_plan): the pattern of frames per tick repeats after hop / gcd(hop, hop_samples) ticks
+    for (int64_t t = 0; t <= c.hop; ++t) {
+        int d; int64_t f0;
+        join_plan(t * hop_samples, hop_samples, c, &d, &f0, nullptr);
+        st->max_delay = std::max(st->max_delay, d);
+    }
+    st->cap = c.n_fft + c.hop * st->kmax + hop_samples + st->max_delay;
     st->ws_bytes = bvc_workspace_bytes(m, B, st->kmax);
     int spf = 1;                                             // samples per frame
     for (int i = 0; i < c.n_up; ++i) spf *= c.up_rates[i];
@@ -2124,7 +2288,7 @@ int bvc_stream_codec_create(const bvc_model *m, int32_t B, int32_t hop_samples, 
     auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_state = take(sizeof(StreamDev)), o_in = take((size_t)B * hop_samples * 4), o_sbuf = take((size_t)B * st->cap * 4),
                  o_stmp = take((size_t)B * st->cap * 4), o_mel = take((size_t)B * st->kmax * c.num_mels * 4),
-                 o_bits = take((size_t)B * st->kmax * 4), o_codes = take((size_t)B * st->kmax * c.z_dim * 4),
+                 o_bits = take((size_t)B * (st->kmax * (st->kmax + 1) / 2) * 4), o_rowoff = take((size_t)B * 4), o_age = take((size_t)B * 4), o_codes = take((size_t)B * st->kmax * c.z_dim * 4),
                  o_melhat = take((size_t)B * st->kmax * c.num_mels * 4), o_wav = take((size_t)B * st->kmax * spf * 4),
                  o_he = take((size_t)B * c.h_dim * 4), o_hd = take((size_t)B * c.h_dim * 4), o_ws = take(st->ws_bytes);
     if (hipMalloc(reinterpret_cast<void **>(&st->pool), off) != hipSuccess) {
@@ -2139,8 +2303,11 @@ int bvc_stream_codec_create(const bvc_model *m, int32_t B, int32_t hop_samples, 
     st->mel = reinterpret_cast<float *>(p + o_mel); st->bitsbuf = reinterpret_cast<float *>(p + o_bits); st->codes = reinterpret_cast<float *>(p + o_codes);
     st->melhat = reinterpret_cast<float *>(p + o_melhat); st->wav = reinterpret_cast<float *>(p + o_wav);
     st->h_enc = reinterpret_cast<float *>(p + o_he); st->h_dec = reinterpret_cast<float *>(p + o_hd); st->ws = p + o_ws;
+    st->row_off = reinterpret_cast<int *>(p + o_rowoff); st->age = reinterpret_cast<int *>(p + o_age);      // zero: every slot open, delay 0, age 0
+    st->slots.assign(B, bvc_stream_codec::Slot());
+    for (auto &sl : st->slots) sl.bits = bits_per_frame;
     int rc;
-    if ((rc = launch_fill(st->bitsbuf, bits_per_frame, (long long)B * st->kmax, nullptr))) return rc;
+    if ((rc = launch_fill(st->bitsbuf, bits_per_frame, (long long)B * (st->kmax * (st->kmax + 1) / 2), nullptr))) return rc;
     st->fill = c.pad_left;                                   // room for the left reflect padding of frame 0
     StreamDev init{st->fill, {0, 0, 0}};
     BVC_HIP_TRY(hipMemcpy(st->d_state, &init, sizeof(init), hipMemcpyHostToDevice));
@@ -2151,6 +2318,7 @@ int bvc_stream_codec_create(const bvc_model *m, int32_t B, int32_t hop_samples, 
     const char *sl = getenv("BVC_STREAM_SLIDE");
     const bool slide = st->tick_flow && flow_chains_static(m, B) != 0 && !(sl && sl[0] == '0');
     if ((rc = vocoder_stream_create(m, B, st->kmax, slide, &st->voc))) return rc;
+    st->voc->d_age = st->age;
     BVC_HIP_TRY(hipDeviceSynchronize());
     *out = st.release();
     return BVC_OK;
@@ -2167,6 +2335,61 @@ int bvc_stream_codec_buffers(bvc_stream_codec *st, float **d_in, float **d_codes
     return BVC_OK;
 }
 
+static int slot_arg(bvc_stream_codec *st, int32_t slot, const char *fn) {
+    if (!st) { set_error("%s: null stream codec", fn); return BVC_EINVAL; }
+    if (slot < 0 || slot >= st->B) { set_error("%s: slot %d outside 0..%d", fn, (int)slot, st->B - 1); return BVC_EINVAL; }
+    return BVC_OK;
+}
+static void slot_mark(bvc_stream_codec *st, bvc_stream_codec::Slot &sl, int flags) {
+    if (!sl.pending) ++st->n_pending;
+    sl.pending |= flags;
+}
+
+int bvc_stream_codec_open(bvc_stream_codec *st, int32_t slot, float bits_per_frame, int32_t *delay_samples) {
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_open")) return rc;
+    bvc_stream_codec::Slot &sl = st->slots[slot];
+    if (sl.open) { set_error("bvc_stream_codec_open: slot %d is open", (int)slot); return BVC_EINVAL; }
+    if (!(bits_per_frame >= 0.0f)) { set_error("bvc_stream_codec_open: bits per frame must not be negative"); return BVC_EINVAL; }
+    join_plan(st->ticks * st->hop, st->hop, st->m->cfg, &sl.delay, &sl.frame0, nullptr);
+    sl.open = true; sl.started = false; sl.bits = bits_per_frame;
+    sl.last_count = 0; sl.last_frame0 = 0;
+    ++st->n_waiting;
+    slot_mark(st, sl, SC_SET_OFF | SC_SET_BITS);
+    if (delay_samples) *delay_samples = sl.delay;
+    return BVC_OK;
+}
+
+int bvc_stream_codec_close(bvc_stream_codec *st, int32_t slot) {
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_close")) return rc;
+    bvc_stream_codec::Slot &sl = st->slots[slot];
+    if (!sl.open) { set_error("bvc_stream_codec_close: slot %d is idle", (int)slot); return BVC_EINVAL; }
+    if (!sl.started) --st->n_waiting;
+    sl.open = false; sl.started = false; sl.delay = 0;
+    sl.last_count = 0; sl.last_frame0 = 0;
+    slot_mark(st, sl, SC_SET_OFF | SC_ZERO_TAIL);
+    return BVC_OK;
+}
+
+int bvc_stream_codec_set_bits(bvc_stream_codec *st, int32_t slot, float bits_per_frame) {
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_set_bits")) return rc;
+    if (!st->m->cfg.var_bit) { set_error("bvc_stream_codec_set_bits: the model has a fixed bitrate (var_bit = 0)"); return BVC_EINVAL; }
+    bvc_stream_codec::Slot &sl = st->slots[slot];
+    if (!sl.open) { set_error("bvc_stream_codec_set_bits: slot %d is idle", (int)slot); return BVC_EINVAL; }
+    if (!(bits_per_frame >= 0.0f)) { set_error("bvc_stream_codec_set_bits: bits per frame must not be negative"); return BVC_EINVAL; }
+    sl.bits = bits_per_frame;
+    slot_mark(st, sl, SC_SET_BITS);
+    return BVC_OK;
+}
+
+int bvc_stream_codec_slot_frames(bvc_stream_codec *st, int32_t slot, int32_t *first, int32_t *count, int64_t *stream_frame0) {
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_slot_frames")) return rc;
+    const bvc_stream_codec::Slot &sl = st->slots[slot];
+    if (first) *first = 0;                                   // a stream's frame 0 is the first frame of its tick
+    if (count) *count = sl.last_count;
+    if (stream_frame0) *stream_frame0 = sl.last_frame0;
+    return BVC_OK;
+}
+
 int bvc_stream_codec_tick(bvc_stream_codec *st, int32_t *n_frames, void *stream) {
     if (!st) { set_error("null stream codec"); return BVC_EINVAL; }
     if (int st_ = sticky_status(st->m)) return st_;
@@ -2174,7 +2397,8 @@ int bvc_stream_codec_tick(bvc_stream_codec *st, int32_t *n_frames, void *stream)
     hipStream_t s = (hipStream_t)stream;
     const int B = st->B;
     // the hop joins the sample buffer (device-side fill level), frame 0's left reflect padding once the first samples are there
-    sc_append_kernel<<<dim3((unsigned)((st->hop + 255) / 256), B), 256, 0, s>>>(st->d_state, st->d_in, st->hop, st->sbuf, st->cap);
+    if (st->n_pending > 0) { if (int rc_ = stream_send_pending(st, s)) return rc_; }
+    sc_append_kernel<<<dim3((unsigned)((st->hop + 255) / 256), B), 256, 0, s>>>(st->d_state, st->d_in, st->hop, st->sbuf, st->cap, st->row_off);
     if (st->first) {
         sc_reflect_left_kernel<<<dim3(B), 256, 0, s>>>(st->sbuf, st->cap, c.pad_left);
         st->first = false;
@@ -2184,6 +2408,7 @@ int bvc_stream_codec_tick(bvc_stream_codec *st, int32_t *n_frames, void *stream)
     const int k = fill >= c.n_fft ? (fill - c.n_fft) / c.hop + 1 : 0;
     if (k > st->kmax) { set_error("bvc_stream_codec_tick: internal frame count %d", k); return BVC_EINVAL; }
     int rc = BVC_OK;
+    if (k > 0 && st->n_waiting > 0 && (rc = stream_start_rows(st, st->frames, k, s))) return rc;
     if (k > 0) {
         const int parity = st->voc->parity;
         // Which schedule?  Where the persistent recurrence kernel is available (flow_chains_static: the model's option, the
@@ -2219,8 +2444,13 @@ int bvc_stream_codec_tick(bvc_stream_codec *st, int32_t *n_frames, void *stream)
         g_stream_tick = false; g_tick_flow = false;
         if (rc) return rc;
     }
-    sc_advance_kernel<<<1, 64, 0, s>>>(st->d_state, st->hop - c.hop * k);
+    sc_advance_kernel<<<1, 64, 0, s>>>(st->d_state, st->hop - c.hop * k, st->age, B, k, (int)STREAM_WARM_FRAMES);
     BVC_HIP_TRY(hipGetLastError());
+    for (auto &sl : st->slots) {
+        const bool live = sl.open && sl.started && k > 0;
+        sl.last_count = live ? k : 0;
+        sl.last_frame0 = live ? st->frames - sl.frame0 : 0;
+    }
     st->fill = fill - c.hop * k;
     st->frames += k;
     st->ticks += 1;

@@ -255,7 +255,12 @@ struct AmpArgs {
     long long bs;                 // floats between batch items of x / out / acc
     long long row_begin;          // first output row (streaming: rows before it are history)
     long long t_origin;           // global time of buffer row 0 (streaming); 0 offline
+    const int *row_age;           // streaming sessions whose rows start at different times: frames since row b's own start (capped where
+    int age_rate;                 // no row of a window lies before it any more); row b's t_origin is t_origin + age_rate * row_age[b]
 };
+__device__ __forceinline__ long long amp_t_origin(const AmpArgs &a, int b) {
+    return a.row_age ? a.t_origin + (long long)a.age_rate * a.row_age[b] : a.t_origin;
+}
 
 #ifndef BVC_AMP_PINGPONG
 #define BVC_AMP_PINGPONG 1
@@ -474,7 +479,7 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
     if (ALIAS) __syncthreads();                            // every wave is done with S1(x): its LDS becomes t2
     for (int idx = tid; idx < (ks - 1) * S; idx += 256) t2[TR * S + idx] = 0.0f;    // spare rows read by discarded outputs
     // local rows before `zrow` lie before the start of the signal: zero there (the reference pads AFTER the activation)
-    const long long zr64 = -(tbase + a.t_origin);
+    const long long zr64 = -(tbase + amp_t_origin(a, b));
     const int zrow = zr64 <= 0 ? 0 : (zr64 > TR ? TR : (int)zr64);
     if constexpr (C == 8) {
         // Only 8 of the tile's 16 columns exist: lanes r >= 8 hold padding.  They take over rows g*4+2, g*4+3 of
@@ -722,7 +727,7 @@ __global__ __launch_bounds__(256, OCC) void amp_pair8_kernel(AmpArgs a) {
         conv(std::integral_constant<int, D>(), H1, w1reg);
         __syncthreads();                                   // every wave is done with S1(x)
         {
-            const long long zr64 = -(tbase + a.t_origin);  // local rows before zrow lie before the start of the signal: zero
+            const long long zr64 = -(tbase + amp_t_origin(a, b));  // local rows before zrow lie before the start of the signal: zero
             const int zrow = zr64 <= 0 ? 0 : (zr64 > TR ? TR : (int)zr64);      // (the reference pads AFTER the activation)
             auto s2_tile = [&](auto edge_c) {                  // (only a signal's first tile has rows to zero: the test is uniform)
                 constexpr bool EDGE = decltype(edge_c)::value;
@@ -969,7 +974,7 @@ __global__ __launch_bounds__(256, OCC) void amp_pair16_kernel(AmpArgs a) {
         // ---- phase 2: u = conv1(S1(x)); S2(u + b1) into its own tile, zero before the start of the signal
         conv(std::integral_constant<int, D>(), t1, w1reg);
         {
-            const long long zr64 = -(tbase + a.t_origin);  // local rows before zrow lie before the start of the signal
+            const long long zr64 = -(tbase + amp_t_origin(a, b));  // local rows before zrow lie before the start of the signal
             const int zrow = zr64 <= 0 ? 0 : (zr64 > TR ? TR : (int)zr64);      // (the reference pads AFTER the activation)
             auto s2_tile = [&](auto edge_c) {                  // (only a signal's first tile has rows to zero: the test is uniform)
                 constexpr bool EDGE = decltype(edge_c)::value;
@@ -1119,6 +1124,8 @@ int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, lo
     a.bs = win ? win->in_bs : L * c1.cin;
     a.row_begin = win ? win->row_begin : 0;
     a.t_origin = win ? win->t_origin : 0;
+    a.row_age = win ? win->row_age : nullptr;
+    a.age_rate = win ? win->age_rate : 0;
     // streaming hops compute a few new rows behind a 64-row history: the 128 / 256-row tiles of the offline sweep would spend
     // most of their MFMAs on rows nobody reads, so short windows take the smallest tile (4 waves x 16 rows)
     const long long new_rows = L - a.row_begin;

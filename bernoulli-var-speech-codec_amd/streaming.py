@@ -177,6 +177,23 @@ class _DeviceView:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (int(ptr), False), "version": 2}
 
 
+def join_plan(samples_so_far, hop, frame=256, pad_left=256, n_fft=1024):
+    """Where a stream that joins a running ``StreamingCodec`` session starts: ``(delay, start_frame, start_tick)``.
+
+    The session has taken ``samples_so_far`` samples per row (ticks so far * hop).  Session frame f reads the samples
+    [frame f - pad_left, frame f - pad_left + n_fft), so it is emitted by the first tick whose samples reach that far (ticks count
+    from 0).  A stream's frame grid is fixed by its sample 0, the session's by tick 0: the library delays the row by ``delay`` samples
+    so that the stream's sample 0 becomes session sample frame * start_frame, where start_frame is the first frame at or behind the
+    stream's arrival that is the FIRST frame of its tick (the row's reset then lies between two ticks).  Pure host arithmetic, the
+    same as the library's (csrc/bvcodec_abi.hip: join_plan)."""
+    def tick_of(f):
+        return -(-(frame * f - pad_left + n_fft) // hop) - 1
+    f = -(-samples_so_far // frame)
+    while f > 0 and tick_of(f - 1) == tick_of(f):
+        f += 1
+    return frame * f - samples_so_far, f, tick_of(f)
+
+
 class StreamingCodec:
     """BASELINE configs[4]: `batch` parallel streams, a fixed hop of new samples per tick, encode + decode of the frames
     each hop completes in ONE library call (``bvc_stream_codec_tick``: one persistent launch per recurrence where that
@@ -184,9 +201,18 @@ class StreamingCodec:
 
     ``push(x)`` with x (batch, hop) returns (codes (batch, k, z_dim), wav (batch, 256 k)) for the k frames completed;
     they equal the offline ``encode`` / ``decode`` of the whole signal on those frames (tests/test_gpu_streaming.py).
-    The returned tensors are views of the state's output buffers: valid until the next push."""
+    The returned tensors are views of the state's output buffers: valid until the next push.
 
-    def __init__(self, model, batch, bitrate, hop=441, device=None):
+    Every row is a *slot* with a life of its own.  Between two pushes ``open(slot, bitrate)`` starts a new stream in an idle row
+    (the samples pushed into that row from then on are its samples 0, 1, 2, ...; the returned delay says how many samples the
+    library holds the row back so that the stream's frames fall on the session's), ``close(slot)`` ends it, ``set_bitrate(slot,
+    bitrate)`` changes its bits per frame from the next push on, and ``slot_frames(slot)`` tells which frames of the last push
+    belong to the slot's stream.  Those frames are bit for bit the offline ``encode`` / ``decode`` of that stream's own signal alone.
+    There is no end-of-stream flush: a stream gets the frames its samples complete (``(n - delay - 768) // 256 + 1`` after n
+    samples); the last two frames of the offline call need the right reflect padding (``StreamingEncoder.flush``).  Idle rows of
+    ``x`` are never read.  ``open_all=False`` starts with every slot idle."""
+
+    def __init__(self, model, batch, bitrate, hop=441, device=None, open_all=True):
         eng = model.engine(None if device is None else torch.empty(0, device=device))
         self.eng, self.B, self.hop = eng, batch, hop
         self.dev = eng.device
@@ -204,6 +230,10 @@ class StreamingCodec:
         self._in = torch.as_tensor(_DeviceView(pin.value, (batch, hop)), device=self.dev)
         self._codes_ptr, self._wav_ptr = pc.value, pw.value
         self.frames = 0
+        self._model = model
+        if not open_all:
+            for b in range(batch):
+                self.close(b)
 
     def __del__(self):
         try:
@@ -212,6 +242,35 @@ class StreamingCodec:
                 self.handle = None
         except Exception:
             pass
+
+    def _slot_call(self, rc):
+        if rc == -1:                                           # BVC_EINVAL: a misuse of the slot calls, the session is untouched
+            msg = self.eng.lib.bvc_last_error()
+            raise ValueError(msg.decode() if msg else "bvcodec: invalid argument")
+        _abi.check(rc)
+
+    def open(self, slot, bitrate):
+        """Start a new stream in idle row `slot` from the next push on; returns its delay in samples."""
+        d = ctypes.c_int32()
+        self._slot_call(self.eng.lib.bvc_stream_codec_open(self.handle, int(slot), float(self._model.bits_per_frame(bitrate)),
+                                                           ctypes.byref(d)))
+        return d.value
+
+    def close(self, slot):
+        """The row is idle from the next push on (ask ``slot_frames`` first)."""
+        self._slot_call(self.eng.lib.bvc_stream_codec_close(self.handle, int(slot)))
+
+    def set_bitrate(self, slot, bitrate):
+        """Bits per frame of an open slot from the next push on (variable-bitrate models only)."""
+        self._slot_call(self.eng.lib.bvc_stream_codec_set_bits(self.handle, int(slot), float(self._model.bits_per_frame(bitrate))))
+
+    def slot_frames(self, slot):
+        """(first, count, stream_frame0): frames [first, first + count) of the last push are the slot's stream's frames
+        stream_frame0, stream_frame0 + 1, ...; count is 0 for an idle slot and before the stream's frame 0."""
+        f, n, s0 = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        self._slot_call(self.eng.lib.bvc_stream_codec_slot_frames(self.handle, int(slot), ctypes.byref(f), ctypes.byref(n),
+                                                                  ctypes.byref(s0)))
+        return f.value, n.value, s0.value
 
     @torch.no_grad()
     def push(self, x):

@@ -47,7 +47,9 @@ extern "C" {
 #endif
 
 #define BVC_ABI_VERSION 3   /* 2: + bvc_model_get_option, bvc_flow_fence, bvc_kprobe_read_span; recurrence option takes 2 (auto); status word reported by every compute entry
-                             * 3: + bvc_model_poll_status, bvc_forward */
+                             * 3: + bvc_model_poll_status, bvc_forward
+                             *    still 3 (new symbols only, nothing existing changed): + bvc_encode_ragged, bvc_decode_ragged;
+                             *    + bvc_stream_codec_open / close / set_bits / slot_frames */
 
 enum {
     BVC_OK = 0,
@@ -241,6 +243,38 @@ int  bvc_stream_codec_create(const bvc_model *m, int32_t B, int32_t hop_samples,
 void bvc_stream_codec_destroy(bvc_stream_codec *st);
 int  bvc_stream_codec_buffers(bvc_stream_codec *st, float **d_in, float **d_codes, float **d_wav, int32_t *max_frames_per_tick);
 int  bvc_stream_codec_tick(bvc_stream_codec *st, int32_t *n_frames, void *stream);
+
+/* Slots: every row of a session is a stream of its own that can be opened, closed, re-used and re-rated while the other rows
+ * keep running.  The session still advances in lock step (every tick takes hop_samples for every row and emits the same
+ * n_frames for every row); whatever a slot emits is bit for bit what the offline bvc_encode / bvc_decode give for that
+ * stream's own signal alone.  bvc_stream_codec_create opens every slot at tick 0 (delay 0); a session on which none of the
+ * calls below is made behaves as before.  All four are called BETWEEN two ticks; they are host-side bookkeeping only: they
+ * neither launch, allocate nor synchronise, and the next bvc_stream_codec_tick sends what they changed to the device on its own
+ * stream, ahead of its own work (one small launch for all changed slots, one more in the tick in which streams start; a
+ * tick without changes launches exactly what it launched before).
+ *  - open: the samples the caller writes into row `slot` of d_in from the next tick on are samples 0, 1, 2, ... of a new
+ *    stream coded with bits_per_frame.  A stream's frame grid is fixed by its sample 0 and the session's by tick 0, so the
+ *    library delays the row by a constant *delay_samples (0 <= delay < 256 * max_frames_per_tick; at most 370 for 441-sample
+ *    hops), chosen so that the stream's frame 0 is the FIRST frame of a tick.  In that tick, before anything else and for
+ *    that row only, the library writes the stream's left reflect padding and zeroes both GRU states and the row's history
+ *    in every buffer of the incremental generator.  Frames the session emits for the row before that ("pre-start") belong
+ *    to no stream.  After n samples a stream has got (n - delay - 768) / 256 + 1 frames (none while that is negative: the
+ *    last `delay` samples are still inside the library).
+ *  - close: the row is idle from the next tick on and what the library still holds of the stream (its delayed tail) is
+ *    dropped.  There is no end-of-stream flush: a stream gets the frames its samples complete, as in a session without
+ *    slots; the last two frames of the offline call, which need the right reflect padding, are the business of a
+ *    stateful encoder with a flush (bvcodec.streaming.StreamingEncoder.flush).  Idle rows ride along in every launch, but
+ *    the library never reads d_in for them (it appends zeros): whatever an idle row of d_in holds - uninitialised memory,
+ *    Inf, NaN - reaches nothing.  Outputs of idle and pre-start rows are unspecified but finite.
+ *  - set_bits: every frame of the row emitted from the next tick on is coded with bits_per_frame; the result equals
+ *    bvc_bvrnn_encode with the corresponding per-frame d_bits.  BVC_EINVAL for a model with var_bit = 0.
+ *  - slot_frames: which of the last tick's n_frames belong to the slot's stream: [*first, *first + *count), count 0 for an
+ *    idle or pre-start slot, and the stream's own index of the first of them.  (Ask before closing the slot.)
+ * BVC_EINVAL, with the session untouched: slot out of range, open on an open slot, close / set_bits on an idle one. */
+int  bvc_stream_codec_open(bvc_stream_codec *st, int32_t slot, float bits_per_frame, int32_t *delay_samples);
+int  bvc_stream_codec_close(bvc_stream_codec *st, int32_t slot);
+int  bvc_stream_codec_set_bits(bvc_stream_codec *st, int32_t slot, float bits_per_frame);
+int  bvc_stream_codec_slot_frames(bvc_stream_codec *st, int32_t slot, int32_t *first, int32_t *count, int64_t *stream_frame0);
 
 /* BVRNNCodecModel.encode (bvrnn_codec_model.py:44-62): scale, log-mel, bits/frame =
  * bits_per_frame for every (b,t), zero initial state, BVRNN.encode.  d_wav (B,L) -> d_codes. */

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """BASELINE.json configs[4]: 256 concurrent streams, 20 ms (441-sample) hops, config_varBitRate @ 3 kbit/s,
-per-hop encode+decode on one MI355X.  Prints one JSON line with p50 / p99 per-hop latency."""
+per-hop encode+decode on one MI355X.  Prints one JSON line with p50 / p99 per-hop latency.
+
+--churn [--ticks N]: the same session with streams that come and go: every 10th tick (5 times per second of audio) one slot is
+closed and another opened at a bitrate of its own, and every 250th tick 32 slots are closed and re-opened at once.  Reports the
+ticks in which nothing changes ("steady"), the ticks that carry a close / open to the device ("update") and the ticks in which
+streams start ("join": per-row reset of the GRU states, the generator histories and the reflect padding) separately."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -10,6 +15,59 @@ from bvcodec import synth
 from bvcodec.streaming import StreamingCodec, StreamingDecoder, StreamingEncoder
 
 B, hop, hops = 256, 441, 300
+
+
+def churn():
+    import random
+    from bvcodec.streaming import join_plan
+    ticks = int(sys.argv[sys.argv.index("--ticks") + 1]) if "--ticks" in sys.argv else 1500
+    model = make_model()[0]
+    x = synth.synthetic_speech(B, hop * 300, seed=3, kind="noise").to("cuda:0")
+    sc = StreamingCodec(model, B, 3000, hop=hop)
+    rng = random.Random(1)
+    idle = set(range(200, B))
+    for b in idle:
+        sc.close(b)
+    kind, lat, joins_at = {}, [], {}
+    for t in range(ticks):
+        n = 32 if t % 250 == 125 else (1 if t % 10 == 0 else 0)
+        if t >= 60 and n:
+            kind[t] = "update"
+            for _ in range(n):
+                b = rng.choice(sorted(set(range(B)) - idle))
+                sc.close(b)
+                o = rng.choice(sorted(idle))
+                sc.open(o, rng.choice((1500, 3000, 6000)))
+                idle.discard(o); idle.add(b)
+            jt = join_plan(t * hop, hop)[2]
+            joins_at[jt] = joins_at.get(jt, 0) + n
+        i = t % 300
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        c, w = sc.push(x[:, i * hop:(i + 1) * hop])
+        torch.cuda.synchronize(); lat.append((time.perf_counter() - t0) * 1e3)
+    model.check_status()
+    lat = np.array(lat)
+    rows = {"steady": [], "update": [], "join_1": [], "join_32": []}
+    for t in range(60, ticks):
+        if t in joins_at:
+            rows["join_32" if joins_at[t] >= 32 else "join_1"].append(lat[t])      # (a join tick that also carries an update counts as a join)
+        elif t in kind:
+            rows["update"].append(lat[t])
+        else:
+            rows["steady"].append(lat[t])
+    out = {"config": f"configs[4] with churn: {B} slots ({B - len(idle)} open) x 20 ms hops, {ticks} ticks; one close + open every 10th tick, 32 at once every 250th",
+           "hop_budget_ms": 20.0}
+    for k, v in rows.items():
+        if v:
+            v = np.array(v)
+            out[k] = {"ticks": int(v.size), "p50_ms": round(float(np.percentile(v, 50)), 3), "p99_ms": round(float(np.percentile(v, 99)), 3),
+                      "max_ms": round(float(v.max()), 3)}
+    print(json.dumps(out))
+
+
+if "--churn" in sys.argv:
+    churn()
+    sys.exit(0)
 incremental = "--context" not in sys.argv      # --context: stateless vocoder that re-runs a 26-frame context per hop
 python_path = "--python" in sys.argv or not incremental     # --python: the round-1 per-hop schedule driven from Python
 model = make_model()[0]
