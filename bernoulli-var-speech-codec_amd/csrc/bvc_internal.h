@@ -132,6 +132,40 @@ int skinny_kernels_init();
 int launch_step_advance(CallDesc *d, int by, hipStream_t s);
 int launch_set_desc(CallDesc *d, const CallDesc &v, hipStream_t s);
 
+// ------------------------------------------------------------------ how a launch is cut into tiles (host only, no HIP calls)
+// The MFMA-bound kernels run fixed-height tiles on a fixed number of workgroup slots, every tile takes the same time, and a
+// grid that ends in a partly filled round pays for a whole one.  tile_plan() picks, among the compiled tile heights, the one
+// that minimises rounds x (height + fixed): tiles = column_blocks x ceil(rows / (height - overlap)), rounds = ceil(tiles / slots).
+// `fixed` (rows) stands for what a tile costs whatever its height - prologue, halo, epilogue - and is fitted per kernel from
+// two measured heights (profiles/tile_rounds.md).  overlap: rows of a tile that produce no output (the causal halo ks - 1 of
+// the AMP pair; 0 for the GEMM).  Ties go to the taller tile.  No candidate or no rows: height 0.
+struct TilePlan { int height; long long tiles, rounds, cost; };
+inline TilePlan tile_plan(long long rows, long long column_blocks, const int *heights, const int *slots_for_height, int n,
+                          int fixed, int overlap = 0) {
+    TilePlan best = {0, 0, 0, 0};
+    if (rows <= 0 || column_blocks <= 0) return best;
+    for (int i = 0; i < n; ++i) {
+        const int h = heights[i], out_rows = h - overlap, slots = slots_for_height[i];
+        if (out_rows <= 0 || slots <= 0) continue;
+        const long long tiles = column_blocks * ((rows + out_rows - 1) / out_rows);
+        const long long rounds = (tiles + slots - 1) / slots;
+        const long long cost = rounds * (h + fixed);
+        if (best.height == 0 || cost < best.cost || (cost == best.cost && h > best.height)) best = {h, tiles, rounds, cost};
+    }
+    return best;
+}
+// The batched GEMM's cut: one launch of `height`-row tiles (tail_height 0), or full_blocks row blocks of 128 followed by a second
+// launch of tail_height-row tiles for the rows of the last, partly filled round.  cost100: the model's cost in hundredths of a row.
+struct GemmCut { int height; int full_blocks; int tail_height; long long tiles, rounds, cost100; };
+GemmCut gemm_batched_cut(int M, int N, int force_height = 0, bool legacy = false);
+// The offline C = 64 AMP pair's cut: rows per workgroup tile (a compiled TR) for L output rows x B items
+TilePlan amp_pair_cut(long long L, int B, int ks, int force_height = 0, bool legacy = false);
+// what the last launch_gemm_batched / offline C = 64 launch_amp_pair of this process chose (tests)
+bool tile_cut_legacy();
+void tile_trace(const char *what, long long rows, long long cols, int height, int tail_height, long long tiles, int slots, long long rounds);
+extern GemmCut g_last_gemm_cut;
+extern TilePlan g_last_amp_cut;
+
 // batched GEMM over all frames: y = act(x @ w^T + bias), M large.  out_mode (GemmOut) says where the rows go:
 // see out_index() in k_gemm.hip.  frames_T = frames per utterance, mt16 = utterances rounded up to 16.
 enum GemmOut { GO_NATURAL = 0, GO_FRAME_MAJOR_ROWS = 1, GO_PACKED_FRAMES = 2, GO_PACKED_FROM_UTT = 3 };

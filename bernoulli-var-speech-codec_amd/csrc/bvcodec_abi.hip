@@ -2714,6 +2714,21 @@ int bvc_test_linear_batched(const float *d_x, const float *d_w, const float *d_b
     return launch_gemm_batched(d_x, K, d_w, K, d_bias, M, N, K, act, d_y, N, (hipStream_t)stream);
 }
 
+int bvc_test_tile_plan(int32_t kind, int64_t rows, int32_t column_blocks, int32_t ks, int32_t mode, int64_t *out) {
+    if (!out || kind < 0 || kind > 1) { set_error("bvc_test_tile_plan: bad arguments"); return BVC_EINVAL; }
+    const bool last = mode == -1, legacy = mode == 1;
+    const int force = mode >= 16 ? mode : 0;
+    if (kind == 0) {
+        const GemmCut c = last ? g_last_gemm_cut : gemm_batched_cut((int)rows, column_blocks * 128, force, legacy);
+        out[0] = c.height; out[1] = c.full_blocks; out[2] = c.tail_height; out[3] = c.tiles; out[4] = c.rounds; out[5] = c.cost100;
+        return BVC_OK;
+    }
+    const TilePlan c = last ? g_last_amp_cut : amp_pair_cut(rows, column_blocks, ks, force, legacy);
+    out[0] = c.height; out[1] = c.height ? c.tiles / (column_blocks > 0 && !last ? column_blocks : 1) : 0; out[2] = 0;
+    out[3] = c.tiles; out[4] = c.rounds; out[5] = c.cost * 100;
+    return BVC_OK;
+}
+
 int bvc_test_snakebeta(const float *d_x, int64_t n, float alpha, float beta, float *d_y, void *stream) {
     if (!d_x || !d_y || n <= 0) { set_error("bvc_test_snakebeta: bad arguments"); return BVC_EINVAL; }
     const float a = (float)std::exp((double)alpha);                                  // as make_conv() derives them

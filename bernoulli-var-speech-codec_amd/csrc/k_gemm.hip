@@ -12,7 +12,10 @@
 //                        XCD so each weight row crosses the fabric once per step.
 //  gemm_batched_kernel - phi_x over all frames (bvrnn.py:178): M = B*T rows, 128x128 workgroup
 //                        tile, 64x64 per wave (4x4 MFMA tiles), operands loaded as k-contiguous
-//                        float4 fragments.
+//                        float4 fragments.  The K = 1024 layers go through LDS: gemm_batched_cols_kernel (four waves
+//                        along the columns, tile height picked per launch by gemm_batched_cut so that the grid fills
+//                        whole rounds of the workgroup slots) and gemm_batched_lds_kernel (2 x 2 waves; the quarter /
+//                        half tiles of the two-launch cut).
 //
 // ONE order of summation per output, whichever kernel computes a layer (the persistent recurrence kernel of k_flow.hip, the
 // launch-per-layer kernel below, the batched kernels): the K/16 k-blocks of a segment are cut into NCHUNK = 8 chunks - chunk c =
@@ -24,6 +27,7 @@
 //
 // Reference semantics: nn.Linear / nn.ELU / nn.Sigmoid / torch.round / nn.GRU as used at
 // bvrnn.py:44-83,163-229.
+#include <cstdio>
 #include <cstdlib>
 
 #include <cstdint>
@@ -741,6 +745,265 @@ __global__ __launch_bounds__(256, 2) void gemm_batched_lds_kernel(const float *_
     }
 }
 
+// The row part of out_index(), computed once per output row: out_at(out_row(row), col) == out_index(row, col).
+struct OutRow { long long base; int bb; };
+__device__ __forceinline__ OutRow out_row(int row, int N, long long ldy, long long T, int mt16, int mode) {
+    if (mode == GO_NATURAL) return {(long long)row * ldy, 0};
+    if (mode == GO_PACKED_FRAMES) {
+        const int tt = row / mt16;
+        return {(long long)tt * mt16 * N, row - tt * mt16};
+    }
+    const int Ti = (int)T;                               // (T divides M: it fits an int, and the division stays a 32-bit one)
+    const int bb = row / Ti;
+    const long long tt = row - bb * Ti;
+    if (mode == GO_FRAME_MAJOR_ROWS) return {(tt * mt16 + bb) * ldy, 0};
+    return {tt * (long long)mt16 * N, bb};
+}
+__device__ __forceinline__ long long out_at(const OutRow &o, int col, int N, int mode) {
+    return mode <= GO_FRAME_MAJOR_ROWS ? o.base + col : o.base + packed_off(o.bb, col, N);
+}
+
+// The same tile with the four waves side by side along the COLUMNS (each BM x 32: BM / 16 row tiles x 2 column tiles), so that
+// BM is any multiple of 16 - 144 rows put the layers of the benchmark shapes on whole rounds of the 512 workgroup slots
+// (launch_gemm_batched) - and with the LDS reads run as a pipeline: a 32-deep stage is 2 * BM / 16 steps of eight MFMAs (one A
+// fragment against the two B fragments of its half), the A fragment of step s + D and the B fragments of the next half are
+// requested before step s is multiplied (a few steps ahead: D below), and the stage's barrier stands D steps before its end - every read of the
+// current buffer has been issued by then - so that the first fragments of the next stage travel under the last MFMAs of this
+// one.  The barrier is a bare s_barrier behind lgkmcnt(0): the global loads of stage kt + 2 stay in flight across it.
+// Same products in the same order per accumulator as gemm_batched_lds_kernel: the same bits.
+template <int ACT, int BM, bool ROWVEC = false>
+__global__ __launch_bounds__(256, 2) void gemm_batched_cols_kernel(const float *__restrict__ x, long long ldx,
+                                                                   const float *__restrict__ w, long long ldw,
+                                                                   const float *__restrict__ bias, int M, int N,
+                                                                   int K, float *__restrict__ y, long long ldy,
+                                                                   long long frames_T, int mt16, int out_mode, int m_off) {
+    constexpr int BK = 32, LDT = BK + 4;                 // floats per LDS row
+    static_assert(BM % 16 == 0 && BM >= 48 && BM <= 144, "tile heights: 2 x 2 x (BM + 128) x 36 floats of LDS per CU");
+    constexpr int MI = BM / 16;                          // 16-row MFMA tiles per wave
+    constexpr int PA = (BM + 31) / 32;                   // staging passes of 32 rows for the A operand (the last one may be half used)
+    constexpr int NS = 2 * MI;                           // steps per stage
+    constexpr int RING = NS % 4 == 0 ? 4 : NS % 6 == 0 ? 6 : NS % 5 == 0 ? 5 : 7;      // A fragments in flight: step s lives in slot
+    constexpr int D = RING - 1;                          // s % RING in every stage, so RING divides the steps of a stage
+    static_assert(NS % RING == 0 && MI >= D && NS - D >= MI, "fragment ring");
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // [2][A BMxLDT | B 128xLDT]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, g = lane >> 4;
+    const int mblk = m_off + blockIdx.y * BM, nblk = blockIdx.x * 128;
+    const int wn = wave * 32;
+
+    // global staging through buffer loads: 32-bit lane offsets, the stage (and the weights' pass) go into the scalar offset - half
+    // the address registers of nine 64-bit pointers
+    const int srow = tid >> 3, spc = (tid & 7) * 4;
+    const int xrows = M - mblk < PA * 32 ? M - mblk : PA * 32;
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x + (long long)mblk * ldx), 0, (int)(xrows * ldx * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(w + (long long)nblk * ldw), 0, (int)(128 * ldw * 4), 0x00020000);
+    int xvo[PA];                                         // rows past M re-read the last one (never stored)
+#pragma unroll
+    for (int p = 0; p < PA; ++p) xvo[p] = ((srow + 32 * p < xrows ? srow + 32 * p : xrows - 1) * (int)ldx + spc) * 4;
+    const int wvo = (srow * (int)ldw + spc) * 4;
+    f32x4 acc[MI][2], tot[MI][2];                        // the running chunk | the sum of the finished chunks (head of this file)
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; tot[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+
+    constexpr int STAGE = (BM + 128) * LDT;              // floats per LDS buffer
+    const int nk = K / BK;
+    const int cst = nk >> 3;                             // stages per chunk (K is a multiple of 256: launch_gemm_batched)
+    f32x4 ga[PA], gb[4];
+    auto gload = [&](int kt) {                           // unconditional: past the end the last stage is read again
+        const int ko = (kt < nk ? kt : nk - 1) * BK;
+#pragma unroll
+        for (int p = 0; p < PA; ++p) ga[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, xvo[p], ko * 4, 0));
+#pragma unroll
+        for (int p = 0; p < 4; ++p) gb[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, wvo, (32 * p * (int)ldw + ko) * 4, 0));
+    };
+    auto park = [&](float *A) {
+        float *B = A + BM * LDT;
+#pragma unroll
+        for (int p = 0; p < PA; ++p)
+            if (32 * (p + 1) <= BM || srow + 32 * p < BM) *reinterpret_cast<f32x4 *>(A + (srow + 32 * p) * LDT + spc) = ga[p];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4 *>(B + (srow + 32 * p) * LDT + spc) = gb[p];
+    };
+    auto lds_barrier = [&]() {                           // LDS visibility only: no vmcnt(0)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
+    const int fo = r * LDT + g * 4;                      // this lane's fragment piece inside a 16-row tile
+    auto lda = [&](const float *buf, int s) {            // A fragment of step s: row tile s % MI, half s / MI
+        return *reinterpret_cast<const f32x4 *>(buf + fo + (s % MI) * 16 * LDT + (s / MI) * 16);
+    };
+    auto ldb = [&](const float *buf, int h, int j) {
+        return *reinterpret_cast<const f32x4 *>(buf + fo + (BM + wn + j * 16) * LDT + h * 16);
+    };
+    f32x4 ring[RING], bq[2][2];
+    gload(0);
+    park(smem);
+    gload(1);
+    lds_barrier();
+#pragma unroll
+    for (int s = 0; s < D; ++s) ring[s] = lda(smem, s);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bq[0][j] = ldb(smem, 0, j);
+
+    // one 32-deep stage
+    auto stage = [&](int kt) {
+        const float *cur = smem + (kt & 1) * STAGE;
+        float *nxt = smem + ((kt + 1) & 1) * STAGE;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int h = s / MI, i = s % MI;
+            if (s == NS - D) {                           // every read of `cur` has been issued: stage kt + 1 may land in `nxt`
+                park(nxt);
+                __builtin_amdgcn_sched_barrier(0);       // (the staging registers are free again only behind the writes)
+                gload(kt + 2);
+                lds_barrier();
+#pragma unroll
+                for (int j = 0; j < 2; ++j) bq[0][j] = ldb(nxt, 0, j);
+            }
+            if (s == MI - D) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) bq[1][j] = ldb(cur, 1, j);
+            }
+            ring[(s + D) % RING] = s + D < NS ? lda(cur, s + D) : lda(nxt, s + D - NS);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    acc[i][j] = ROWVEC ? mfma16(bq[h][j][e], ring[s % RING][e], acc[i][j]) : mfma16(ring[s % RING][e], bq[h][j][e], acc[i][j]);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    // A chunk's chain starts from a cleared accumulator and the sum of the chunks from zero: a chain that starts from +0 never
+    // ends in -0, so 0 + chunk 0 has the bits of the copy the other kernels make.
+    int in_chunk = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+        stage(kt);
+        if (++in_chunk == cst) {                         // (uniform) the chunk is complete: add it to the sum
+            in_chunk = 0;
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) { tot[i][j] += acc[i][j]; acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+        }
+    }
+
+    const int n0 = nblk + wn;
+    if (ROWVEC) {           // operands swapped (tile of y^T): tot[i][j][e] = y[mblk + 16 i + r][n0 + 16 j + 4 g + e], one 16-byte granule in every
+        f32x4 b4[2];        // output layout (see gemm_batched_kernel)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) b4[j] = bias ? *reinterpret_cast<const f32x4 *>(bias + n0 + j * 16 + g * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+            const int row = mblk + i * 16 + r;
+            if (row >= M) continue;
+            const OutRow o = out_row(row, N, ldy, frames_T, mt16, out_mode);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                f32x4 v = tot[i][j] + b4[j];
+                if (ACT == 1) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = elu1(v[e]);
+                }
+                *reinterpret_cast<f32x4 *>(y + out_at(o, n0 + j * 16 + g * 4, N, out_mode)) = v;
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int row = mblk + i * 16 + g * 4 + e;
+            if (row >= M) continue;
+            const OutRow o = out_row(row, N, ldy, frames_T, mt16, out_mode);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int col = n0 + j * 16 + r;
+                float v = tot[i][j][e] + (bias ? bias[col] : 0.0f);
+                if (ACT == 1) v = elu1(v);
+                y[out_at(o, col, N, out_mode)] = v;
+            }
+        }
+}
+
+// ---- how launch_gemm_batched cuts the rows (host only; tile_plan in bvc_internal.h)
+// BVC_TILE_CUT=legacy restores the cuts of before the plan (128-row tiles of gemm_batched_lds_kernel plus a tail launch; one
+// AMP tile shape per channel count) for A/B runs.
+bool tile_cut_legacy() {                                  // (read per call, like the forced heights: tests compare both in one process)
+    const char *v = getenv("BVC_TILE_CUT");
+    return v != nullptr && v[0] == 'l';
+}
+// BVC_TILE_TRACE=1: one line per distinct launch shape on stderr (profiles/tile_rounds.md)
+void tile_trace(const char *what, long long rows, long long cols, int height, int tail_height, long long tiles, int slots, long long rounds) {
+    static const bool on = getenv("BVC_TILE_TRACE") != nullptr;
+    if (!on) return;
+    static long long seen[64][4];
+    static int nseen = 0;
+    const long long key[4] = {(long long)what[0] * 256 + what[1], rows, cols, height * 1000 + tail_height};
+    for (int i = 0; i < nseen; ++i)
+        if (seen[i][0] == key[0] && seen[i][1] == key[1] && seen[i][2] == key[2] && seen[i][3] == key[3]) return;
+    if (nseen < 64) { for (int q = 0; q < 4; ++q) seen[nseen][q] = key[q]; ++nseen; }
+    fprintf(stderr, "tile_trace %s rows=%lld cols=%lld height=%d tail_height=%d tiles=%lld slots=%d rounds=%lld (%.2f needed)\n", what, rows, cols,
+            height, tail_height, tiles, slots, rounds, (double)tiles / slots);
+}
+
+GemmCut g_last_gemm_cut = {0, 0, 0, 0, 0, 0};
+// fixed: rows' worth of time a tile costs whatever its height (prologue fill, epilogue), fitted from the 144- and 112-row tiles
+// (3 rounds in 465.0 us against 4 rounds in 483.5 us: 1.4 rows; profiles/tile_rounds.md).  The tail launch of the two-launch cut runs at a lower rate than the main one (the same 128-column
+// weight stage for a quarter / half of the products): a quarter tile costs 0.46, a half tile 0.55 of a full one (measured).
+static constexpr int GEMM_FIXED_ROWS = 1;
+static constexpr int GEMM_SLOTS = 512;                    // two workgroups per CU
+GemmCut gemm_batched_cut(int M, int N, int force_height, bool legacy) {
+    GemmCut c = {0, 0, 0, 0, 0, 0};
+    if (M <= 0 || N < 128) return c;
+    const int ncol = N / 128, rows_blk = (M + 127) / 128;
+    // the two-launch cut: 128-row tiles for the full rounds, the rows of a partly filled last round as quarter / half tiles
+    static const bool no_tail = getenv("BVC_NO_GEMM_TAIL") != nullptr;
+    static const bool no_q = getenv("BVC_NO_GEMM_QUARTER") != nullptr;
+    const int per_round = GEMM_SLOTS / ncol > 0 ? GEMM_SLOTS / ncol : 1;     // row blocks per full round
+    int full_blk = rows_blk;
+    if (!no_tail && rows_blk > per_round && rows_blk % per_round != 0 && (rows_blk % per_round) * 2 <= per_round)   // the half tiles fit ONE round
+        full_blk = (rows_blk / per_round) * per_round;
+    GemmCut two = {128, full_blk, 0, 0, 0, 0};
+    two.tiles = (long long)ncol * full_blk;
+    two.rounds = (two.tiles + GEMM_SLOTS - 1) / GEMM_SLOTS;
+    two.cost100 = two.rounds * 100 * (128 + GEMM_FIXED_ROWS);
+    if (full_blk < rows_blk) {
+        const int m_off = full_blk * 128;
+        const long long q_tiles = (long long)ncol * ((M - m_off + 31) / 32), h_tiles = (long long)ncol * ((M - m_off + 63) / 64);
+        const bool quarter = !no_q && q_tiles <= 768;     // three quarter-height workgroups fit a CU
+        two.tail_height = quarter ? 32 : 64;
+        const long long t_tiles = quarter ? q_tiles : h_tiles, t_slots = quarter ? 768 : GEMM_SLOTS;
+        const long long t_rounds = (t_tiles + t_slots - 1) / t_slots;
+        two.tiles += t_tiles; two.rounds += t_rounds;
+        two.cost100 += t_rounds * (quarter ? 46 : 55) * (128 + GEMM_FIXED_ROWS);
+    }
+    if (legacy && force_height == 0) return two;
+    static const int heights[3] = {144, 128, 112}, slots[3] = {GEMM_SLOTS, GEMM_SLOTS, GEMM_SLOTS};
+    TilePlan p;
+    if (force_height) {
+        int one = 0;
+        for (int h : heights) if (h == force_height) one = h;
+        if (!one) return c;
+        p = tile_plan(M, ncol, &one, slots, 1, GEMM_FIXED_ROWS);
+    } else {
+        p = tile_plan(M, ncol, heights, slots, 3, GEMM_FIXED_ROWS);
+    }
+    if (!force_height && two.tail_height != 0 && two.cost100 < p.cost * 100) return two;
+    c.height = p.height; c.full_blocks = (M + p.height - 1) / p.height; c.tail_height = 0;
+    c.tiles = p.tiles; c.rounds = p.rounds; c.cost100 = p.cost * 100;
+    return c;
+}
+
+#define BVC_COLS_KERNELS(BM) (const void *)gemm_batched_cols_kernel<0, BM, false>, (const void *)gemm_batched_cols_kernel<1, BM, false>, \
+                             (const void *)gemm_batched_cols_kernel<0, BM, true>,  (const void *)gemm_batched_cols_kernel<1, BM, true>
+
 int launch_gemm_batched(const float *x, long long ldx, const float *w, long long ldw, const float *bias,
                         int M, int N, int K, int act, float *y, long long ldy, hipStream_t s, int out_mode,
                         long long frames_T, int mt16) {
@@ -781,28 +1044,49 @@ int launch_gemm_batched(const float *x, long long ldx, const float *w, long long
             if (rv) hipLaunchKernelGGL((gemm_batched_lds_kernel<A_, BM_, true>), grid_, dim3(256), lds_, s, x, ldx, w, ldw, bias, M, N, K, y, ldy, frames_T, mt16, out_mode, m_off_);
             else    hipLaunchKernelGGL((gemm_batched_lds_kernel<A_, BM_, false>), grid_, dim3(256), lds_, s, x, ldx, w, ldw, bias, M, N, K, y, ldy, frames_T, mt16, out_mode, m_off_);
         };
-        // Tail: 2 workgroups fit a CU, so the chip takes 512 tiles per round; a grid that ends with a partly filled round
-        // (configs[1]: 215 x 8 = 1,720 tiles = 3.36 rounds) pays a whole round for it.  The rows of that last round are
-        // computed with half-height tiles instead (a second launch; the same k order per accumulator, so the same bits) - or with
-        // quarter-height tiles (three workgroups of 45 KiB LDS per CU: 768 slots) when those still fit one round: a quarter tile
-        // has a quarter of the products but the same 128-column weight stage, so it is about 0.4 of a full tile's time against the
-        // half tile's 0.55 (the balance a stream-K split would buy, without a fix-up pass and with the summation order untouched).
-        static const bool no_tail = getenv("BVC_NO_GEMM_TAIL") != nullptr;
-        static const bool no_q = getenv("BVC_NO_GEMM_QUARTER") != nullptr;
-        const int ncol = N / 128, rows_blk = (M + 127) / 128;
-        const int slots = 512, per_round = slots / ncol > 0 ? slots / ncol : 1;     // row blocks per full round
-        int full_blk = rows_blk;
-        if (!no_tail && rows_blk > per_round && rows_blk % per_round != 0 && (rows_blk % per_round) * 2 <= per_round)   // the half tiles fit ONE round
-            full_blk = (rows_blk / per_round) * per_round;
-        if (full_blk > 0) {
+        // How the rows are cut (gemm_batched_cut above): one launch of the column-layout kernel at the height that fills whole
+        // rounds, or 128-row tiles plus a second launch of quarter / half tiles for the last round.
+        const char *force = getenv("BVC_GEMM_BM");         // read per call: tests force every compiled height in one process
+        const bool legacy = tile_cut_legacy();
+        const GemmCut cut = gemm_batched_cut(M, N, force ? atoi(force) : 0, legacy);
+        if (force && cut.height != atoi(force)) { set_error("gemm_batched: BVC_GEMM_BM=%s is not a compiled tile height", force); return BVC_EINVAL; }
+        g_last_gemm_cut = cut;
+        tile_trace("gemm_batched", M, N, cut.height, cut.tail_height, cut.tiles, 512, cut.rounds);
+        const int ncol = N / 128;
+        if (!legacy) {                                      // (the two-launch cut keeps its tail kernels, its 128-row tiles run on the new one)
+            static bool attr2 = false;
+            if (!attr2) {
+                const void *ks[] = {BVC_COLS_KERNELS(144), BVC_COLS_KERNELS(128), BVC_COLS_KERNELS(112)};
+                for (const void *k : ks) BVC_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (144 + 128) * 36 * (int)sizeof(float)));
+                attr2 = true;
+            }
+            auto launch_cols = [&](auto bm_c) {
+                constexpr int BM_ = decltype(bm_c)::value;
+                const dim3 grid_(ncol, cut.full_blocks);
+                const size_t lds_ = (size_t)2 * (BM_ + 128) * 36 * sizeof(float);
+                auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid_, dim3(256), lds_, s, x, ldx, w, ldw, bias, M, N, K, y, ldy, frames_T, mt16, out_mode, 0); };
+                if (act == 1) { if (rv) go(gemm_batched_cols_kernel<1, BM_, true>); else go(gemm_batched_cols_kernel<1, BM_, false>); }
+                else          { if (rv) go(gemm_batched_cols_kernel<0, BM_, true>); else go(gemm_batched_cols_kernel<0, BM_, false>); }
+            };
+            switch (cut.height) {
+                case 144: launch_cols(std::integral_constant<int, 144>()); break;
+                case 128: launch_cols(std::integral_constant<int, 128>()); break;
+                default:  launch_cols(std::integral_constant<int, 112>()); break;
+            }
+            if (cut.tail_height == 0) {
+                BVC_HIP_TRY(hipGetLastError());
+                return BVC_OK;
+            }
+        }
+        const int rows_blk = (M + 127) / 128, full_blk = cut.full_blocks;
+        if (full_blk > 0 && legacy) {
             dim3 g1(ncol, full_blk);
             if (act == 1) launch(std::integral_constant<int, 1>(), std::integral_constant<int, 128>(), g1, 0);
             else          launch(std::integral_constant<int, 0>(), std::integral_constant<int, 128>(), g1, 0);
         }
         if (full_blk < rows_blk) {
             const int m_off = full_blk * 128;
-            const int q_tiles = ncol * ((M - m_off + 31) / 32);
-            if (!no_q && q_tiles <= 768) {
+            if (cut.tail_height == 32) {
                 dim3 g2(ncol, (M - m_off + 31) / 32);
                 if (act == 1) launch(std::integral_constant<int, 1>(), std::integral_constant<int, 32>(), g2, m_off);
                 else          launch(std::integral_constant<int, 0>(), std::integral_constant<int, 32>(), g2, m_off);

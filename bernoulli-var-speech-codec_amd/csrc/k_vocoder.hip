@@ -1105,6 +1105,21 @@ static int launch_amp_t(AmpArgs a, int B, hipStream_t s) {
     return BVC_OK;
 }
 
+// ---- how the offline AMP pair of the C = 64 stage is cut into tiles (host only; tile_plan in bvc_internal.h).
+// A tile of TR rows yields TR - (ks - 1) output rows of one batch item; 512 slots (two workgroups per CU).  fixed: the rows'
+// worth of time a tile costs whatever its height, fitted from two measured heights on nearly whole rounds (ks = 7: 96 rows, 5 rounds,
+// 224.3 us against 80 rows, 6 rounds, 223.6 us: 1.5 rows; profiles/tile_rounds.md).
+TilePlan g_last_amp_cut = {0, 0, 0, 0};
+static constexpr int AMP64_FIXED_ROWS = 1;
+TilePlan amp_pair_cut(long long L, int B, int ks, int force_height, bool legacy) {
+    static const int heights[4] = {128, 112, 96, 80}, slots[4] = {512, 512, 512, 512};
+    if (!force_height && !legacy) return tile_plan(L, B, heights, slots, 4, AMP64_FIXED_ROWS, ks - 1);
+    int one = force_height ? 0 : heights[0];               // the shape of before the plan: the tallest
+    for (int h : heights) if (h == force_height) one = h;
+    if (!one) return {0, 0, 0, 0};
+    return tile_plan(L, B, &one, slots, 1, AMP64_FIXED_ROWS, ks - 1);
+}
+
 int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, long long L, float *out, int B, int epi,
                     const float *acc, float divisor, hipStream_t s, const ConvWindow *win, unsigned kernels) {
     if (B <= 0 || L <= 0) return BVC_OK;
@@ -1148,9 +1163,26 @@ int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, lo
         case 64: {
             static const bool rows = getenv("BVC_AMP64") && atoi(getenv("BVC_AMP64")) == 0;       // A/B: the waves along the rows (2.63 ms per step for the stage)
             if (rows) return launch_amp_t<64, 2, 2, true>(a, B, s);
-            return launch_amp_t<64, 8, 2, true, 4>(a, B, s);       // waves along the columns: 2.33 (two column groups x two row groups: 2.60)
+            // waves along the columns: 2.33 with eight row tiles per wave (two column groups x two row groups: 2.60); offline, the
+            // plan picks the tile height per launch (whole rounds of the 512 slots: amp_pair_cut)
+            int tr = 128;
+            if (!win) {
+                const char *force = getenv("BVC_AMP64_TR");       // read per call: tests force every compiled height in one process
+                const TilePlan cut = amp_pair_cut(new_rows, B, c1.ks, force ? atoi(force) : 0, tile_cut_legacy());
+                if (cut.height == 0) { set_error("amp_pair: BVC_AMP64_TR=%s is not a compiled tile height", force ? force : ""); return BVC_EINVAL; }
+                g_last_amp_cut = cut;
+                tile_trace("amp_pair64", new_rows, (long long)B * 100 + c1.ks, cut.height, 0, cut.tiles, 512, cut.rounds);
+                tr = cut.height;
+            }
+            switch (tr) {
+                case 80:  return launch_amp_t<64, 5, 2, true, 4>(a, B, s);
+                case 96:  return launch_amp_t<64, 6, 2, true, 4>(a, B, s);
+                case 112: return launch_amp_t<64, 7, 2, true, 4>(a, B, s);
+                default:  return launch_amp_t<64, 8, 2, true, 4>(a, B, s);
+            }
         }
-        case 32: return launch_amp_t<32, 4, 3, true>(a, B, s);     // (waves along the columns, CS = 2 with 4 or 8 row tiles: 4.64 / 4.41 against 4.48)
+        case 32: return launch_amp_t<32, 4, 3, true>(a, B, s);     // (waves along the columns, CS = 2 with 4 or 8 row tiles: 4.64 / 4.41 against 4.48;
+                                                                   // three row tiles per wave, 192 rows: slower at every ks, profiles/tile_rounds.md)
         case 16: {
             if ((kernels & AMPK_C16) && !win) {                  // offline sweep: the persistent C = 16 kernel
                 // four row tiles per wave (256 rows per workgroup): 2.82 (generic kernel) -> 2.62 ms per step for the stage; two tiles 2.82,

@@ -337,6 +337,12 @@ int bvc_test_linear(const float *d_x, const float *d_w, const float *d_bias, int
 /* same contract through the batched (all-frames) GEMM kernel */
 int bvc_test_linear_batched(const float *d_x, const float *d_w, const float *d_bias, int32_t M,
                             int32_t N, int32_t K, int32_t act, float *d_y, void *stream);
+/* How a launch is cut into tiles (host arithmetic only: needs no GPU).  kind 0: the batched GEMM over rows x (column_blocks *
+ * 128) outputs; 1: the offline AMP pair of the C = 64 stage over rows output rows x column_blocks batch items with ks taps.  mode 0: the planned cut, 1: the cut of before the plan (BVC_TILE_CUT=legacy), >= 16: that tile height forced (height 0
+ * comes back if it is not compiled), -1: what the last launch of that kind in this process used (other arguments ignored).
+ * out[6] = tile height, row blocks of that height (GEMM: of the first launch; AMP: tiles per batch item), height of the tail
+ * launch's tiles (0: one launch), tiles, rounds, model cost in hundredths of a row. */
+int bvc_test_tile_plan(int32_t kind, int64_t rows, int32_t column_blocks, int32_t ks, int32_t mode, int64_t *out);
 /* dump of one vocoder intermediate, channels-last: which = 0 conv_pre, 1+2i up_i, 2+2i stage_i.
  * Runs the vocoder up to that point.  d_out (B, len, C); returns len*C via *out_numel_per_batch. */
 int bvc_test_vocoder_tap(const bvc_model *m, const float *d_mel, int32_t B, int64_t T, int32_t which,
