@@ -66,6 +66,11 @@ SIGNATURES = {
     "bvc_stream_codec_close": (ctypes.c_int, [_vp, _i32]),
     "bvc_stream_codec_set_bits": (ctypes.c_int, [_vp, _i32, _f]),
     "bvc_stream_codec_slot_frames": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
+    "bvc_stream_codec_create_dir": (ctypes.c_int, [_vp, _i32, _i32, _f, _f, _f, _i32, ctypes.POINTER(_vp)]),
+    "bvc_stream_codec_packets": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i32)]),
+    "bvc_stream_codec_tick_recv": (ctypes.c_int, [_vp, _i32, _vp]),
+    "bvc_stream_codec_finish": (ctypes.c_int, [_vp, _i32, _i32]),
+    "bvc_stream_codec_slot_state": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i32)]),
     "bvc_encode": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _f, _vp, _vp, _sz, _vp]),
     "bvc_decode": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i64, _f, _vp, _vp, _sz, _vp]),
     "bvc_forward": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _f, _i64, _f, _vp, _vp, _vp, _sz, _vp]),

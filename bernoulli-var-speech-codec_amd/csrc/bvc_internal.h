@@ -271,6 +271,11 @@ int launch_resample_poly(const float *x, int B, long long Lin, const double *h, 
 int launch_peak_normalize(float *x, int B, long long L, hipStream_t s);
 int launch_pack_codes(const float *codes, long long frames, int z, int nbits, unsigned char *out, hipStream_t s);
 int launch_unpack_codes(const unsigned char *in, long long frames, int z, int nbits, float *codes, hipStream_t s);
+// the same wire format with every row's own bit count (directed streaming sessions): packets (B, kstride, nbytes) with nbytes = ceil(z / 8)
+// for every row, codes (B, k, z); bits (B, k) = bits per (row, frame) (nullptr: z everywhere), row_off[b] < 0 = idle row
+int launch_pack_rows(const float *codes, const float *bits, int B, int k, int z, int kstride, unsigned char *out, hipStream_t s);
+int launch_unpack_rows(const unsigned char *in, const unsigned char *present, const float *bits, const int *row_off, int B, int k,
+                       int z, int kstride, float *codes, hipStream_t s);
 
 // ------------------------------------------------------------------ vocoder (k_vocoder.hip)
 struct ConvLayer {               // one causal conv as implicit GEMM on fp32 MFMA

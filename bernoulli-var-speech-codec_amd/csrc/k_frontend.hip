@@ -214,6 +214,89 @@ int launch_unpack_codes(const unsigned char *in, long long frames, int z, int nb
     return BVC_OK;
 }
 
+// ---- the wire format inside a streaming tick (bvc_stream_codec_create_dir): every frame has ceil(z / 8) bytes whatever its row's bit
+// count, so a tick's addresses are fixed; row b's frame holds its nbits leading bits in the layout above and zeros behind them.
+__device__ inline int row_nbits(const float *__restrict__ bits, long long i, int z) {
+    if (!bits) return z;
+    const float v = bits[i];
+    return v >= (float)z ? z : (v > 0.0f ? (int)v : 0);
+}
+
+// one lane per (row, frame): the frame's z floats in 16-byte loads; z == 64: the whole frame is ONE 8-byte store
+__global__ __launch_bounds__(256) void sc_pack_rows_kernel(const float *__restrict__ codes, const float *__restrict__ bits, int B, int k,
+                                                           int z, int nbytes, int kstride, unsigned char *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * k) return;
+    const int b = (int)(i / k), j = (int)(i - (long long)b * k);
+    const int nbits = row_nbits(bits, i, z);
+    const float *c = codes + i * z;
+    unsigned char *o = out + ((long long)b * kstride + j) * nbytes;
+    if (z == 64) {
+        unsigned long long v = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const float4 f = reinterpret_cast<const float4 *>(c)[q];
+            const unsigned n = (f.x > 0.75f ? 1u : 0u) | (f.y > 0.75f ? 2u : 0u) | (f.z > 0.75f ? 4u : 0u) | (f.w > 0.75f ? 8u : 0u);
+            v |= (unsigned long long)n << (4 * q);
+        }
+        if (nbits < 64) v &= (1ull << nbits) - 1ull;
+        *reinterpret_cast<unsigned long long *>(o) = v;
+        return;
+    }
+    for (int y = 0; y < nbytes; ++y) {
+        unsigned v = 0;
+        for (int t = 0; t < 8; ++t) {
+            const int bit = y * 8 + t;
+            if (bit < nbits && c[bit] > 0.75f) v |= 1u << t;
+        }
+        o[y] = (unsigned char)v;
+    }
+}
+
+// one lane per four codes of a (row, frame): ONE 16-byte store.  A frame that did not arrive (present == 0) and every frame of an idle
+// row is all 0.5 - a frame of no bits - whatever its bytes hold; so are the positions behind the row's bit count.
+__global__ __launch_bounds__(256) void sc_unpack_rows_kernel(const unsigned char *__restrict__ in, const unsigned char *__restrict__ present,
+                                                             const float *__restrict__ bits, const int *__restrict__ row_off, int B, int k,
+                                                             int z, int nbytes, int kstride, float *__restrict__ codes) {
+    const int zq = (z + 3) / 4;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * k * zq) return;
+    const long long fr = i / zq;                            // (row, frame)
+    const int q = (int)(i - fr * zq);
+    const int b = (int)(fr / k), j = (int)(fr - (long long)b * k);
+    const long long pf = (long long)b * kstride + j;
+    int nbits = row_nbits(bits, fr, z);
+    if (row_off[b] < 0 || present[pf] == 0) nbits = 0;
+    float v[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int bit = 4 * q + t;
+        v[t] = 0.5f;
+        if (bit < nbits) v[t] = (float)((in[pf * nbytes + (bit >> 3)] >> (bit & 7)) & 1u);
+    }
+    float *o = codes + fr * z + 4 * q;
+    if ((z & 3) == 0) *reinterpret_cast<float4 *>(o) = make_float4(v[0], v[1], v[2], v[3]);
+    else for (int t = 0; t < 4 && 4 * q + t < z; ++t) o[t] = v[t];
+}
+
+int launch_pack_rows(const float *codes, const float *bits, int B, int k, int z, int kstride, unsigned char *out, hipStream_t s) {
+    const long long total = (long long)B * k;
+    if (total <= 0) return BVC_OK;
+    hipLaunchKernelGGL(sc_pack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, codes, bits, B, k, z, (z + 7) / 8, kstride, out);
+    BVC_HIP_TRY(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_unpack_rows(const unsigned char *in, const unsigned char *present, const float *bits, const int *row_off, int B, int k,
+                       int z, int kstride, float *codes, hipStream_t s) {
+    const long long total = (long long)B * k * ((z + 3) / 4);
+    if (total <= 0) return BVC_OK;
+    hipLaunchKernelGGL(sc_unpack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, present, bits, row_off, B, k, z,
+                       (z + 7) / 8, kstride, codes);
+    BVC_HIP_TRY(hipGetLastError());
+    return BVC_OK;
+}
+
 // ---- mixed-length batches (bvc_encode_ragged): row b's own frame count T_b = ragged_frames(lens[b]) decides which of its frames are live.
 // bits (B, T): the row's bits per frame (d_bits[b], or `dflt` for every row) on live frames, 0 behind them - a var_bit coder then emits
 // 0.5 there by itself.

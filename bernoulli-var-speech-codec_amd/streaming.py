@@ -173,8 +173,8 @@ class StreamingDecoder:
 class _DeviceView:
     """Raw device memory owned by the library, exposed to torch through the CUDA array interface."""
 
-    def __init__(self, ptr, shape):
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (int(ptr), False), "version": 2}
+    def __init__(self, ptr, shape, typestr="<f4"):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
 
 
 def join_plan(samples_so_far, hop, frame=256, pad_left=256, n_fft=1024):
@@ -194,6 +194,32 @@ def join_plan(samples_so_far, hop, frame=256, pad_left=256, n_fft=1024):
     return frame * f - samples_so_far, f, tick_of(f)
 
 
+def finish_plan(open_tick, finish_tick, n_last, hop, frame=256, pad_left=256, n_fft=1024):
+    """What a stream that is finished (``StreamingCodec.finish``) still gets: ``(n, total_frames, [(tick, count), ...])``.
+
+    The stream's first hop went into tick ``open_tick`` (``open`` was called before that push), ``finish(slot, n_last)`` is called
+    before the push of tick ``finish_tick``, whose hop holds the stream's last ``n_last`` samples: n = (finish_tick - open_tick) * hop
+    + n_last samples in all, total_frames = n // frame = the frames of the offline ``encode``.  The list says for tick finish_tick
+    and every later one up to the tick that emits the last frame how many of that tick's frames are the stream's (``slot_frames``'s
+    count); after the last entry the slot is idle.  Frames the stream got before tick finish_tick: total_frames minus the counts.
+    Pure host arithmetic, the same as the library's (csrc/bvcodec_abi.hip: stream_finish_rows and the end of bvc_stream_codec_tick)."""
+    def emitted_before(t):                                  # session frames emitted by the ticks before tick t
+        have = pad_left + t * hop
+        return (have - n_fft) // frame + 1 if have >= n_fft else 0
+    n = (finish_tick - open_tick) * hop + n_last
+    if not 0 <= n_last <= hop or n <= n_fft - frame - pad_left:
+        raise ValueError("finish_plan: n_last out of range or the stream is too short for the right reflect padding")
+    _, f0, _ = join_plan(open_tick * hop, hop, frame, pad_left, n_fft)
+    end = f0 + n // frame
+    out, t = [], finish_tick
+    while True:
+        lo, hi = emitted_before(t), emitted_before(t + 1)
+        out.append((t, max(0, min(hi, end) - max(lo, f0))))
+        if hi >= end:
+            return n, n // frame, out
+        t += 1
+
+
 class StreamingCodec:
     """BASELINE configs[4]: `batch` parallel streams, a fixed hop of new samples per tick, encode + decode of the frames
     each hop completes in ONE library call (``bvc_stream_codec_tick``: one persistent launch per recurrence where that
@@ -208,12 +234,31 @@ class StreamingCodec:
     library holds the row back so that the stream's frames fall on the session's), ``close(slot)`` ends it, ``set_bitrate(slot,
     bitrate)`` changes its bits per frame from the next push on, and ``slot_frames(slot)`` tells which frames of the last push
     belong to the slot's stream.  Those frames are bit for bit the offline ``encode`` / ``decode`` of that stream's own signal alone.
-    There is no end-of-stream flush: a stream gets the frames its samples complete (``(n - delay - 768) // 256 + 1`` after n
-    samples); the last two frames of the offline call need the right reflect padding (``StreamingEncoder.flush``).  Idle rows of
-    ``x`` are never read.  ``open_all=False`` starts with every slot idle."""
+    A stream that is closed has got the frames its samples complete (``(n - delay - 768) // 256 + 1`` after n samples); the last
+    two frames of the offline call need the right reflect padding: end the stream with ``finish`` instead to get them.  Idle rows of
+    ``x`` are never read.  ``open_all=False`` starts with every slot idle.
 
-    def __init__(self, model, batch, bitrate, hop=441, device=None, open_all=True):
+    ``finish(slot, n_last)`` ends a stream completely where ``close`` cuts it off: the next push's row holds the stream's last
+    ``n_last`` samples, the library writes the right reflect padding behind them and the slot *drains* - this and the next pushes
+    emit its remaining frames (``slot_frames`` says which, ``finish_plan`` predicts them), ALL ``num_frames(n)`` frames of the offline
+    ``encode``, and then the slot is idle (``slot_state``).
+
+    ``direction`` splits the loopback into the two halves a deployment runs in different places.  ``"send"``: ``push(x)`` returns
+    ``(packets (batch, k, bytes_per_frame) uint8, codes)``: the front-end and the encoder only; row b's frames hold its own
+    ``active_bits`` leading bits in the layout of ``model.pack`` and zeros behind them.  ``"recv"``: ``push_packets(packets,
+    present=None)`` with packets ``(batch, k, bytes_per_frame)``, 1 <= k <= ``kmax``, returns wav ``(batch, 256 k)``: the decoder and
+    the generator only.  ``present (batch, k)``: 0 marks a frame that did not arrive; it is decoded as a frame of no bits (codes all
+    0.5) and the state moves on.  ``hop`` means nothing to a receive session, ``open`` always returns 0 there."""
+
+    DIRECTIONS = {"duplex": 0, "send": 1, "recv": 2}
+
+    def __init__(self, model, batch, bitrate, hop=441, device=None, open_all=True, direction="duplex"):
+        if direction not in self.DIRECTIONS:
+            raise ValueError(f"direction must be one of {sorted(self.DIRECTIONS)}")
+        self.direction = direction
         eng = model.engine(None if device is None else torch.empty(0, device=device))
+        if direction == "recv":
+            hop = 0
         self.eng, self.B, self.hop = eng, batch, hop
         self.dev = eng.device
         self.z = model.conf["z_dim"]
@@ -221,14 +266,25 @@ class StreamingCodec:
         self.stream = torch.cuda.Stream(self.dev)          # a tick may be captured into a hipGraph: not possible on the default stream
         h = ctypes.c_void_p()
         with torch.cuda.device(self.dev):
-            _abi.check(eng.lib.bvc_stream_codec_create(eng.handle, batch, hop, float(model.bits_per_frame(bitrate)), float(SCALING),
-                                                       float(SCALING), ctypes.byref(h)))
+            if direction == "duplex":
+                _abi.check(eng.lib.bvc_stream_codec_create(eng.handle, batch, hop, float(model.bits_per_frame(bitrate)), float(SCALING),
+                                                           float(SCALING), ctypes.byref(h)))
+            else:
+                _abi.check(eng.lib.bvc_stream_codec_create_dir(eng.handle, batch, hop, float(model.bits_per_frame(bitrate)),
+                                                               float(SCALING), float(SCALING), self.DIRECTIONS[direction], ctypes.byref(h)))
         self.handle = h
         pin, pc, pw, kmax = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int32()
         _abi.check(eng.lib.bvc_stream_codec_buffers(h, ctypes.byref(pin), ctypes.byref(pc), ctypes.byref(pw), ctypes.byref(kmax)))
         self.kmax = kmax.value
-        self._in = torch.as_tensor(_DeviceView(pin.value, (batch, hop)), device=self.dev)
+        self._in = torch.as_tensor(_DeviceView(pin.value, (batch, hop)), device=self.dev) if pin.value else None
         self._codes_ptr, self._wav_ptr = pc.value, pw.value
+        pp, pr, bpf = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int32()
+        _abi.check(eng.lib.bvc_stream_codec_packets(h, ctypes.byref(pp), ctypes.byref(pr), ctypes.byref(bpf)))
+        self.bytes_per_frame = bpf.value
+        self._packets = self._present = None
+        if pp.value:                                           # (batch, kmax, bytes_per_frame) / (batch, kmax) whatever a tick's frame count
+            self._packets = torch.as_tensor(_DeviceView(pp.value, (batch, self.kmax, bpf.value), "|u1"), device=self.dev)
+            self._present = torch.as_tensor(_DeviceView(pr.value, (batch, self.kmax), "|u1"), device=self.dev)
         self.frames = 0
         self._model = model
         if not open_all:
@@ -272,8 +328,45 @@ class StreamingCodec:
                                                                   ctypes.byref(s0)))
         return f.value, n.value, s0.value
 
+    def finish(self, slot, n_last=None):
+        """The stream in `slot` ends with the first `n_last` samples of the next push's row (None: the whole hop; 0: it ended with
+        the last push).  The slot drains from that push on and is idle once its last frame is out."""
+        self._slot_call(self.eng.lib.bvc_stream_codec_finish(self.handle, int(slot), int(self.hop if n_last is None else n_last)))
+
+    def slot_state(self, slot):
+        """"idle", "waiting" (open, frame 0 still to come), "running" or "draining" (finished, frames still to come)."""
+        v = ctypes.c_int32()
+        self._slot_call(self.eng.lib.bvc_stream_codec_slot_state(self.handle, int(slot), ctypes.byref(v)))
+        return ("idle", "waiting", "running", "draining")[v.value]
+
+    @torch.no_grad()
+    def push_packets(self, packets, present=None):
+        """Receive session: packets (batch, k, bytes_per_frame) uint8 (fewer bytes per frame are taken as the leading ones),
+        present (batch, k) (None: everything arrived) -> wav (batch, 256 k), a view of the session's buffer, valid until the next push."""
+        if packets.dim() != 3 or packets.shape[0] != self.B or packets.shape[2] > self.bytes_per_frame or packets.dtype != torch.uint8:
+            raise ValueError(f"push_packets: expected uint8 packets ({self.B}, k, <= {self.bytes_per_frame})")
+        k = packets.shape[1]
+        if self.direction != "recv" or not 1 <= k <= self.kmax:    # the library's refusal (BVC_EINVAL), session untouched
+            self._slot_call(self.eng.lib.bvc_stream_codec_tick_recv(self.handle, k, ctypes.c_void_p(self.stream.cuda_stream)))
+            raise ValueError("push_packets: refused")
+        cur = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream), torch.cuda.device(self.dev):
+            self._packets[:, :k, :packets.shape[2]].copy_(packets.to(self.dev), non_blocking=True)
+            if present is None:
+                self._present[:, :k].fill_(1)
+            else:
+                self._present[:, :k].copy_(present.to(self.dev).ne(0).to(torch.uint8).reshape(self.B, k), non_blocking=True)
+            self._slot_call(self.eng.lib.bvc_stream_codec_tick_recv(self.handle, k, ctypes.c_void_p(self.stream.cuda_stream)))
+        cur.wait_stream(self.stream)
+        self.frames += k
+        return torch.as_tensor(_DeviceView(self._wav_ptr, (self.B, k * self.spf)), device=self.dev)
+
     @torch.no_grad()
     def push(self, x):
+        if self.direction == "recv":                           # the library's refusal (BVC_EINVAL), session untouched
+            self._slot_call(self.eng.lib.bvc_stream_codec_tick(self.handle, None, ctypes.c_void_p(self.stream.cuda_stream)))
+            raise ValueError("push: a receive session takes packets (push_packets)")
         assert tuple(x.shape) == (self.B, self.hop)
         cur = torch.cuda.current_stream(self.dev)
         self.stream.wait_stream(cur)
@@ -284,8 +377,13 @@ class StreamingCodec:
         cur.wait_stream(self.stream)
         k = k.value
         self.frames += k
+        send = self.direction == "send"
         if k == 0:
-            return torch.empty(self.B, 0, self.z, device=self.dev), torch.empty(self.B, 0, device=self.dev)
+            first = torch.empty(self.B, 0, self.bytes_per_frame, dtype=torch.uint8, device=self.dev) if send else \
+                torch.empty(self.B, 0, self.z, device=self.dev)
+            return first, (torch.empty(self.B, 0, self.z, device=self.dev) if send else torch.empty(self.B, 0, device=self.dev))
         codes = torch.as_tensor(_DeviceView(self._codes_ptr, (self.B, k, self.z)), device=self.dev)
+        if send:
+            return self._packets[:, :k], codes
         wav = torch.as_tensor(_DeviceView(self._wav_ptr, (self.B, k * self.spf)), device=self.dev)
         return codes, wav

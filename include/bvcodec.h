@@ -49,7 +49,8 @@ extern "C" {
 #define BVC_ABI_VERSION 3   /* 2: + bvc_model_get_option, bvc_flow_fence, bvc_kprobe_read_span; recurrence option takes 2 (auto); status word reported by every compute entry
                              * 3: + bvc_model_poll_status, bvc_forward
                              *    still 3 (new symbols only, nothing existing changed): + bvc_encode_ragged, bvc_decode_ragged;
-                             *    + bvc_stream_codec_open / close / set_bits / slot_frames */
+                             *    + bvc_stream_codec_open / close / set_bits / slot_frames;
+                             *    + bvc_stream_codec_create_dir / packets / tick_recv / finish / slot_state */
 
 enum {
     BVC_OK = 0,
@@ -261,9 +262,8 @@ int  bvc_stream_codec_tick(bvc_stream_codec *st, int32_t *n_frames, void *stream
  *    to no stream.  After n samples a stream has got (n - delay - 768) / 256 + 1 frames (none while that is negative: the
  *    last `delay` samples are still inside the library).
  *  - close: the row is idle from the next tick on and what the library still holds of the stream (its delayed tail) is
- *    dropped.  There is no end-of-stream flush: a stream gets the frames its samples complete, as in a session without
- *    slots; the last two frames of the offline call, which need the right reflect padding, are the business of a
- *    stateful encoder with a flush (bvcodec.streaming.StreamingEncoder.flush).  Idle rows ride along in every launch, but
+ *    dropped: the stream has got the frames its samples complete, as in a session without slots; the last two frames of
+ *    the offline call need the right reflect padding, which bvc_stream_codec_finish (below) writes.  Idle rows ride along in every launch, but
  *    the library never reads d_in for them (it appends zeros): whatever an idle row of d_in holds - uninitialised memory,
  *    Inf, NaN - reaches nothing.  Outputs of idle and pre-start rows are unspecified but finite.
  *  - set_bits: every frame of the row emitted from the next tick on is coded with bits_per_frame; the result equals
@@ -275,6 +275,55 @@ int  bvc_stream_codec_open(bvc_stream_codec *st, int32_t slot, float bits_per_fr
 int  bvc_stream_codec_close(bvc_stream_codec *st, int32_t slot);
 int  bvc_stream_codec_set_bits(bvc_stream_codec *st, int32_t slot, float bits_per_frame);
 int  bvc_stream_codec_slot_frames(bvc_stream_codec *st, int32_t slot, int32_t *first, int32_t *count, int64_t *stream_frame0);
+
+/* Sessions by direction: a tick above is a loopback (encode a row's samples, decode those codes); a deployment runs the two halves
+ * in different places with bytes on a wire between them.  bvc_stream_codec_create_dir makes a session that runs ONE half;
+ * BVC_STREAM_DUPLEX is bvc_stream_codec_create, launch for launch.  All slot calls work as above in every direction.
+ *  - Packets: bvc_stream_codec_packets gives d_packets (B, max_frames_per_tick, bytes_per_frame) uint8 and d_present
+ *    (B, max_frames_per_tick) uint8, owned by the session at fixed addresses (both NULL for a duplex session), with
+ *    bytes_per_frame = ceil(z_dim / 8) for EVERY row.  Row b's frame holds its nbits_b = min(z_dim, the slot's bits per frame)
+ *    leading bits (z_dim for a model with var_bit = 0), bit i in byte i / 8 at position i % 8: the layout of bvc_pack_codes, so
+ *    the first ceil(nbits_b / 8) bytes of each frame are what bvc_pack_codes gives for that row.  Frame j of row b of a tick is
+ *    at (b * max_frames_per_tick + j) * bytes_per_frame whatever the tick's n_frames.
+ *  - BVC_STREAM_SEND: bvc_stream_codec_tick as above on d_in: front-end, BVRNN.encode with the carried state, and the codes
+ *    packed into d_packets with each row's own bit count (bytes and bits behind nbits_b are written as 0).  d_codes is filled as
+ *    in a duplex session.  No decoder, no generator and no memory for them: bvc_stream_codec_buffers gives NULL for d_wav.
+ *    open / close / set_bits / slot_frames: same delays, same frames as a duplex session.
+ *  - BVC_STREAM_RECV (hop_samples is ignored; no sample buffer: bvc_stream_codec_buffers gives NULL for d_in): the caller writes
+ *    n_frames frames per row into d_packets, marks in d_present which of them arrived (1) and calls bvc_stream_codec_tick_recv
+ *    with 1 <= n_frames <= max_frames_per_tick (7: whatever one tick of a send session emits).  The tick unpacks with each row's
+ *    bit count, runs BVRNN.decode with the carried state and the incremental vocoder, and leaves d_wav (B, 256 n_frames) (and the
+ *    unpacked d_codes).  Bytes and bits behind nbits_b are ignored.  A frame whose d_present byte is 0 is a LOST frame: it is
+ *    decoded as a frame of no bits - codes all 0.5, what a variable-rate coder writes and reads at masked positions - whatever
+ *    its bytes hold, and the GRU state moves on through it; the result equals bvc_decode of the same code tensor with those frames
+ *    set to 0.5.  (A late packet is a lost packet; there is no reordering, no concealment from the model's prior.)  Idle rows
+ *    are all 0.5 whatever their bytes and d_present hold.  Slots: a receive tick is frame-aligned, so open reports delay 0 and the
+ *    stream's frame 0 is the first frame of the next tick, in which - ahead of its own work, for those rows only, in one launch -
+ *    h_dec, the row's age and its history in every buffer of the generator are reset.  set_bits changes nbits_b from the next
+ *    tick on, close idles the row, slot_frames reports [0, n_frames) for an open row and count 0 for an idle one.
+ *    bvc_stream_codec_tick on a receive session and bvc_stream_codec_tick_recv on any other are BVC_EINVAL.
+ *  - finish (DUPLEX and SEND; BVC_EINVAL on RECV): the end of a stream, called between two ticks on a running slot in place of
+ *    close.  Of the hop the caller writes into the row for the NEXT tick only the first n_last samples (0 <= n_last <=
+ *    hop_samples; 0: the stream ended with the previous hop) are the stream's, and they are its last.  With n the stream's
+ *    sample count, that tick writes the right reflect padding of the front-end (512 samples x[n - 2 - i], i = 0 .. 511) directly
+ *    behind sample n - 1 - nothing of the hop behind n_last is ever used - and from then on the slot is DRAINING: d_in is not
+ *    read for it, it rides along in lock step, and this and the following ticks emit its remaining frames up to and including
+ *    frame n / 256 - 1; then the slot is idle of its own accord and can be opened again.  slot_frames reports only frames below
+ *    that bound (count may be smaller than the tick's n_frames).  The stream has then got ALL bvc_num_frames(n) frames of the
+ *    offline bvc_encode (a close leaves it two short); in a duplex session they are decoded like any others.  The up to 294
+ *    samples bvc_decode adds behind sample 256 * frames are not part of this.  BVC_EINVAL, session untouched: finish on an idle,
+ *    waiting or draining slot, n_last out of range, n <= 512 (too short for the padding); open on a draining slot.  close on
+ *    a draining slot drops the rest.
+ *  - slot_state: 0 idle, 1 waiting for its frame 0, 2 running, 3 draining.
+ * Like the slot calls, finish and slot_state are host bookkeeping between two ticks; the tick that carries a finish out makes one
+ * more small launch.  A duplex session on which finish is never called launches exactly what it launched before. */
+enum { BVC_STREAM_DUPLEX = 0, BVC_STREAM_SEND = 1, BVC_STREAM_RECV = 2 };
+int  bvc_stream_codec_create_dir(const bvc_model *m, int32_t B, int32_t hop_samples, float bits_per_frame, float scale,
+                                 float out_scale_div, int32_t direction, bvc_stream_codec **out);
+int  bvc_stream_codec_packets(bvc_stream_codec *st, uint8_t **d_packets, uint8_t **d_present, int32_t *bytes_per_frame);
+int  bvc_stream_codec_tick_recv(bvc_stream_codec *st, int32_t n_frames, void *stream);
+int  bvc_stream_codec_finish(bvc_stream_codec *st, int32_t slot, int32_t n_last);
+int  bvc_stream_codec_slot_state(bvc_stream_codec *st, int32_t slot, int32_t *state);
 
 /* BVRNNCodecModel.encode (bvrnn_codec_model.py:44-62): scale, log-mel, bits/frame =
  * bits_per_frame for every (b,t), zero initial state, BVRNN.encode.  d_wav (B,L) -> d_codes. */

@@ -5,7 +5,11 @@ per-hop encode+decode on one MI355X.  Prints one JSON line with p50 / p99 per-ho
 --churn [--ticks N]: the same session with streams that come and go: every 10th tick (5 times per second of audio) one slot is
 closed and another opened at a bitrate of its own, and every 250th tick 32 slots are closed and re-opened at once.  Reports the
 ticks in which nothing changes ("steady"), the ticks that carry a close / open to the device ("update") and the ticks in which
-streams start ("join": per-row reset of the GRU states, the generator histories and the reflect padding) separately."""
+streams start ("join": per-row reset of the GRU states, the generator histories and the reflect padding) separately.
+
+--direction send|recv|duplex [--loss P]: the same 256 streams and inputs through a session that runs one half (send: samples ->
+packets; recv: packets -> samples) or both (duplex, the default run's loopback tick).  recv replays the packets of a send run
+(not timed) in ticks of the frame counts that run emitted; --loss P marks a seeded share P of the frames as not arrived."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -65,8 +69,50 @@ def churn():
     print(json.dumps(out))
 
 
+def direction(which):
+    loss = float(sys.argv[sys.argv.index("--loss") + 1]) if "--loss" in sys.argv else 0.0
+    model = make_model()[0]
+    x = synth.synthetic_speech(B, hop * hops, seed=3, kind="noise").to("cuda:0")
+    lat, frames = [], 0
+    if which == "recv":
+        tx = StreamingCodec(model, B, 3000, hop=hop, direction="send")
+        sent = [tx.push(x[:, i * hop:(i + 1) * hop])[0].clone() for i in range(hops)]
+        sent = [p for p in sent if p.shape[1]]
+        del tx
+        g = torch.Generator().manual_seed(11)
+        present = [(torch.rand(B, p.shape[1], generator=g) >= loss).to(torch.uint8).to("cuda:0") for p in sent]
+        sc = StreamingCodec(model, B, 3000, direction="recv")
+        for p, pr in zip(sent, present):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            sc.push_packets(p, pr)
+            torch.cuda.synchronize(); lat.append(time.perf_counter() - t0)
+            frames += p.shape[1]
+        lost = 1.0 - float(torch.cat([pr.float().flatten() for pr in present]).mean())
+    else:
+        sc = StreamingCodec(model, B, 3000, hop=hop, direction=which)
+        for i in range(hops):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            a, _ = sc.push(x[:, i * hop:(i + 1) * hop])
+            torch.cuda.synchronize(); lat.append(time.perf_counter() - t0)
+            frames += a.shape[1]
+        lost = 0.0
+    model.check_status()
+    n = len(lat)
+    lat = np.array(lat[50:]) * 1e3
+    print(json.dumps({"config": f"BASELINE configs[4]: {B} streams x 20 ms hops @ 3 kbit/s, {which} session",
+                      "direction": which, "ticks": n, "timed_ticks": int(lat.size), "frames_lost": round(lost, 4),
+                      "p50_ms": round(float(np.percentile(lat, 50)), 3), "p99_ms": round(float(np.percentile(lat, 99)), 3),
+                      "mean_ms": round(float(lat.mean()), 3), "hop_budget_ms": 20.0, "frames_per_tick": round(frames / n, 3)}))
+
+
 if "--churn" in sys.argv:
     churn()
+    sys.exit(0)
+if "--direction" in sys.argv:
+    which = sys.argv[sys.argv.index("--direction") + 1]
+    if which not in ("send", "recv", "duplex"):
+        sys.exit("--direction send|recv|duplex")
+    direction(which)
     sys.exit(0)
 incremental = "--context" not in sys.argv      # --context: stateless vocoder that re-runs a 26-frame context per hop
 python_path = "--python" in sys.argv or not incremental     # --python: the round-1 per-hop schedule driven from Python
