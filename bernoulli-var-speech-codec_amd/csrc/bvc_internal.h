@@ -311,6 +311,11 @@ int conv_kernels_init();
 // kernel with swapped operands; without the bit the generic amp_pair_kernel runs (same bits)
 enum : unsigned { AMPK_C8 = 1u, AMPK_C16 = 2u, AMPK_ALL = 3u };
 unsigned amp_kernels_default();
+// what the last launch_amp_pair of this process launched (tests): tiles that have work, workgroups in the grid (the generic kernel: the
+// tiles padded to a multiple of 8, one tile each; the persistent C = 8 / C = 16 kernels: at most the device's slots, each walking over
+// tiles), valid output rows per tile.  A launch that had nothing to do leaves the record alone.
+struct AmpLaunch { long long tiles, workgroups; int tile_rows; };
+extern AmpLaunch g_last_amp_launch;
 int launch_snakebeta_test(const float *x, long long n, float a, float ib, float *y, hipStream_t s);
 // row_lim (B) or nullptr: input rows of item b from row_lim[b] on read as zeros (a mixed-length batch; row_lim[b] <= Lin)
 int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *out, long long Lout,

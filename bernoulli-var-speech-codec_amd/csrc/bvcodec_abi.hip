@@ -2958,4 +2958,55 @@ int bvc_test_vocoder_tap(const bvc_model *m, const float *d_mel, int32_t B, int6
     return BVC_OK;
 }
 
+int bvc_test_vocoder_layer(const bvc_model *m, int32_t kind, int32_t stage, int32_t block, int32_t iteration, const float *d_x,
+                           int32_t B, int64_t L, float *d_out, int32_t epi, const float *d_acc, int32_t window, int64_t row_begin,
+                           int64_t t_origin, int64_t length, float div, int64_t *out_info, void *stream) {
+    // test helper (synchronises): ONE launch of the generator on the caller's input, through the launchers and the packed weights of the path
+    if (!m || !d_x || !d_out || B <= 0 || L <= 0) { set_error("bvc_test_vocoder_layer: bad arguments"); return BVC_EINVAL; }
+    const bvc_config &c = m->cfg;
+    hipStream_t s = (hipStream_t)stream;
+    int64_t rows = 0, ch = 0;
+    int rc = BVC_OK;
+    g_last_amp_launch = {0, 0, 0};
+    switch (kind) {
+        case 0:                                                              // conv_pre (as run_vocoder launches it)
+            rows = L; ch = c.upsample_initial_channel;
+            rc = launch_conv_mfma(m->conv_pre, d_x, L, d_out, L, B, CE_STORE, nullptr, nullptr, 1.0f, s);
+            break;
+        case 1:                                                              // upsampler `stage`: 2-tap conv with u * C columns over L + 1 rows
+            if (stage < 0 || stage >= c.n_up) { set_error("bvc_test_vocoder_layer: no upsampler %d", stage); return BVC_EINVAL; }
+            rows = (L + 1) * c.up_rates[stage]; ch = m->stage_ch[stage];
+            rc = launch_conv_mfma(m->ups[stage], d_x, L, d_out, L + 1, B, CE_STORE, nullptr, nullptr, 1.0f, s);
+            break;
+        case 2: {                                                            // AMP pair (stage, block, iteration)
+            if (stage < 0 || stage >= c.n_up || block < 0 || block >= c.n_resk || iteration < 0 || iteration >= 3) {
+                set_error("bvc_test_vocoder_layer: no AMP pair (%d, %d, %d)", stage, block, iteration); return BVC_EINVAL; }
+            if (epi < CE_RES || epi > CE_RES_ACC_DIV || (epi >= CE_RES_ACC && !d_acc)) {
+                set_error("bvc_test_vocoder_layer: epilogue %d (1 residual, 2 + running sum, 3 + running sum, / kernels; 2 and 3 need d_acc)", epi);
+                return BVC_EINVAL; }
+            if (!m->fused_amp) { set_error("bvc_test_vocoder_layer: the model runs its AMP pairs unfused"); return BVC_EINVAL; }
+            if (window && (row_begin < 0 || row_begin >= L)) { set_error("bvc_test_vocoder_layer: row_begin outside the buffer"); return BVC_EINVAL; }
+            const AmpPair &ap = m->amp[stage][block][iteration];
+            rows = L; ch = m->stage_ch[stage];
+            const long long bs = (long long)L * ch;
+            ConvWindow w{bs, bs, row_begin, t_origin};
+            rc = launch_amp_pair(ap.c1, ap.c2, d_x, L, d_out, B, epi, d_acc, (float)c.n_resk, s, window ? &w : nullptr, m->amp_kernels);
+            break;
+        }
+        case 3:                                                              // activation_post -> conv_post -> tanh -> / div, first `length` samples
+            rows = length < L ? length : L; ch = 1;
+            if (rows <= 0) { set_error("bvc_test_vocoder_layer: length %lld", (long long)length); return BVC_EINVAL; }
+            rc = launch_conv_post(d_x, L, m->post_c, m->post_ks, m->post_w, m->post_b, m->post_a, m->post_ib, div, d_out, rows, B, s);
+            break;
+        default: set_error("bvc_test_vocoder_layer: kind %d", kind); return BVC_EINVAL;
+    }
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) { set_error("bvc_test_vocoder_layer: %s", hipGetErrorString(e)); rc = BVC_EHIP; }
+    if (out_info) {
+        out_info[0] = rows; out_info[1] = ch;
+        out_info[2] = g_last_amp_launch.tiles; out_info[3] = g_last_amp_launch.workgroups; out_info[4] = g_last_amp_launch.tile_rows;
+    }
+    return rc;
+}
+
 }  // extern "C"

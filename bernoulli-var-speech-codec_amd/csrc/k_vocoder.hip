@@ -823,6 +823,8 @@ static bool amp8_slots_all() {
            amp8_slots<11, 1, MT2, OCC>() > 0 && amp8_slots<11, 3, MT2, OCC>() > 0 && amp8_slots<11, 5, MT2, OCC>() > 0;
 }
 
+AmpLaunch g_last_amp_launch = {0, 0, 0};
+
 template <int KS, int D, int MT2, int OCC>
 static int launch_amp8_t(AmpArgs a, int B, hipStream_t s) {
     using G = Amp8Geom<KS, D, MT2>;
@@ -836,6 +838,7 @@ static int launch_amp8_t(AmpArgs a, int B, hipStream_t s) {
     const unsigned ntile = (unsigned)(a.tiles_per_batch * (long long)B);
     a.ntile = ntile;
     const unsigned grid = ntile < (unsigned)slots ? ((ntile + 7u) & ~7u) : ((unsigned)slots & ~7u);
+    g_last_amp_launch = {(long long)ntile, (long long)grid, G::TT};
     hipLaunchKernelGGL((amp_pair8_kernel<KS, D, MT2, OCC>), dim3(grid), dim3(256), G::LDS_BYTES, s, a);
     BVC_HIP_TRY(hipGetLastError());
     return BVC_OK;
@@ -1053,6 +1056,7 @@ static int launch_amp16_t(AmpArgs a, int B, hipStream_t s) {
     const unsigned ntile = (unsigned)(a.tiles_per_batch * (long long)B);
     a.ntile = ntile;
     const unsigned grid = ntile < (unsigned)slots ? ((ntile + 7u) & ~7u) : ((unsigned)slots & ~7u);
+    g_last_amp_launch = {(long long)ntile, (long long)grid, G::TT};
     hipLaunchKernelGGL((amp_pair16_kernel<KS, D, MT, OCC>), dim3(grid), dim3(256), G::LDS_BYTES, s, a);
     BVC_HIP_TRY(hipGetLastError());
     return BVC_OK;
@@ -1100,6 +1104,7 @@ static int launch_amp_t(AmpArgs a, int B, hipStream_t s) {
         static bool attr = false;
         if (!attr) { BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(amp_pair_kernel<C, MT, OCC, ALIAS, CS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; }
     }
+    g_last_amp_launch = {(long long)ntile, (long long)((ntile + 7u) & ~7u), TT};
     hipLaunchKernelGGL((amp_pair_kernel<C, MT, OCC, ALIAS, CS>), dim3((ntile + 7u) & ~7u), dim3(256), lds, s, a);
     BVC_HIP_TRY(hipGetLastError());
     return BVC_OK;

@@ -398,6 +398,23 @@ int bvc_test_vocoder_tap(const bvc_model *m, const float *d_mel, int32_t B, int6
                          float *d_out, int64_t *out_numel_per_batch, void *d_ws, size_t ws_bytes,
                          void *stream);
 
+/* ONE layer of the generator on a caller-supplied input, through the launchers and the packed weights the path uses (no arithmetic of
+ * its own).  d_x (B, L, Cin) channels-last in device memory; d_out channels-last; L >= 1.  kind:
+ *   0 conv_pre: (B, L, num_mels) -> (B, L, upsample_initial_channel);
+ *   1 upsampler `stage`: (B, L, Cin) -> (B, (L + 1) * rate, C);
+ *   2 AMP pair (stage, block, iteration): out = x + conv2(S2(conv1_dil(S1(x)))), (B, L, C) -> (B, L, C).  epi 1: that; 2: d_acc + that;
+ *     3: (d_acc + that) / number of AMP blocks.  d_acc (B, L, C) is the running sum and may be d_out itself, as in the path.
+ *     window != 0: the buffer is a streaming window - row 0 is global time t_origin, rows before row_begin are history and only rows
+ *     [row_begin, L) of d_out are written; S2 rows before global time 0 are zero.  window == 0: the offline sweep.
+ *   3 activation_post -> conv_post -> tanh -> / div: (B, L, C) -> (B, min(length, L)).
+ * Arguments a kind does not use are ignored.  out_info[5] (may be NULL) = output rows per item, output channels, and for kind 2 what
+ * the launch was cut into: tiles, workgroups launched (fewer than tiles: a persistent kernel walks over several tiles per workgroup),
+ * output rows per tile. */
+int bvc_test_vocoder_layer(const bvc_model *m, int32_t kind, int32_t stage, int32_t block, int32_t iteration,
+                           const float *d_x, int32_t B, int64_t L, float *d_out, int32_t epi, const float *d_acc,
+                           int32_t window, int64_t row_begin, int64_t t_origin, int64_t length, float div,
+                           int64_t *out_info, void *stream);
+
 /* y[i] = SnakeBeta(x[i]) = x + sin(x*exp(alpha))^2 / (exp(beta) + 1e-9)  (activations.py:107-120), through the
  * device routines of the generator kernels (their sin^2 is a hand-written range reduction, not ocml's sinf). */
 int bvc_test_snakebeta(const float *d_x, int64_t n, float alpha, float beta, float *d_y, void *stream);
