@@ -51,6 +51,8 @@ SIGNATURES = {
     "bvc_stft_logmel": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _vp, _vp]),
     "bvc_bvrnn_encode": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "bvc_bvrnn_decode": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "bvc_bvrnn_decode_conceal": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "bvc_decode_conceal": (ctypes.c_int, [_vp, _vp, _vp, _f, _i32, _i64, _i64, _f, _vp, _vp, _vp, _sz, _vp]),
     "bvc_bvrnn_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _sz, _vp]),
     "bvc_bigvgan": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i64, _f, _vp, _vp, _sz, _vp]),
@@ -71,6 +73,7 @@ SIGNATURES = {
     "bvc_stream_codec_tick_recv": (ctypes.c_int, [_vp, _i32, _vp]),
     "bvc_stream_codec_finish": (ctypes.c_int, [_vp, _i32, _i32]),
     "bvc_stream_codec_slot_state": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i32)]),
+    "bvc_stream_codec_set_conceal": (ctypes.c_int, [_vp, _i32]),
     "bvc_encode": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _f, _vp, _vp, _sz, _vp]),
     "bvc_decode": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i64, _f, _vp, _vp, _sz, _vp]),
     "bvc_forward": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _f, _i64, _f, _vp, _vp, _vp, _sz, _vp]),

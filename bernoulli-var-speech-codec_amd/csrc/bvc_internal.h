@@ -97,7 +97,9 @@ enum GemmEpi {
 enum CodeSample {
     CS_ENCODE = 0,       // z = round(p)                              BVRNN.encode (bvrnn.py:191)
     CS_GREEDY = 1,       // z = (round(p) - p) + p                    BVRNN.forward greedy (bvrnn.py:124), straight-through value
-    CS_SAMPLE = 2        // z = (round((u - 0.5) + p) - p) + p        Bernoulli sampler (bvrnn.py:126), u from y2
+    CS_SAMPLE = 2,       // z = (round((u - 0.5) + p) - p) + p        Bernoulli sampler (bvrnn.py:126), u from y2
+    CS_SELECT = 3        // z = selector < 0 ? received code (y2) : round(p) masked to `selector` bits: the concealing decoder; p is the
+                         // prior's.  aux = the selector per row (launch_conceal_select), whatever var_bit says
 };
 
 // The first 16 dwords (M .. seg[0].x) hold everything a layer needs to map its tile and issue the operand
@@ -115,7 +117,7 @@ struct GemmParams {
     int     gate_il;           // weights are gate-interleaved [n/16][k/16][gate][lane][4] (GRU launches)
     const float *bias0;        // group 0 bias [gates*N] (may be null)
     const float *bias1;        // group 1 bias (GRU only)
-    DynPtr  y, y2, y3;         // outputs (y2/y3 optional); EPI_CODE with CS_SAMPLE: y2 = uniform noise INPUT
+    DynPtr  y, y2, y3;         // outputs (y2/y3 optional); EPI_CODE with CS_SAMPLE: y2 = uniform noise INPUT, with CS_SELECT: the received codes (INPUT)
     DynPtr  aux;               // CODE: bits per frame (one per row); GRU: previous h; LINEAR/ELU: optional addend (natural [M][N])
                                // GRU: y3 (if valid) = pre-computed part of the input gates gi, natural [M][3*gate_rows]
     const float *part_i; const float *part_h; long long ldpart;   // GRU_PART: side-branch partial sums [M][3H]
@@ -189,7 +191,8 @@ int launch_repack_rows(const float *src, float *dst, long long ld_natural, int r
 // flow + (id * 2 + parity) * slot_bytes, each a fragment-packed [MT16][dim] matrix.
 constexpr unsigned FLOW_POISON = 0xFFFFDEADu;      // a NaN bit pattern no layer may publish as data
 constexpr int FLOW_STAMPS = 6;                     // stamp kinds per layer and frame (k_flow.hip: flow_stamp)
-enum FlowEpi { FE_ELU = 0, FE_CODE = 1, FE_MEL = 2, FE_GRU = 3, FE_ELU_KEEP = 4 };   // FE_ELU_KEEP: ELU, and the result also goes to FlowArgs::keep
+enum FlowEpi { FE_ELU = 0, FE_CODE = 1, FE_MEL = 2, FE_GRU = 3, FE_ELU_KEEP = 4, FE_CODE_SEL = 5 };   // FE_ELU_KEEP: ELU, and the result also goes to FlowArgs::keep
+                                                                                     // FE_CODE_SEL: FE_CODE of the concealing decoder (CS_SELECT)
 enum FlowBuf { FB_H = 0, FB_E1, FB_E2, FB_ZC, FB_Q1, FB_Q2, FB_Q3, FB_D1, FB_D2, FB_D3, FB_DN, FB_G1, FB_G2, FB_G3, FB_COUNT };
 struct FlowLin {         // one K-segment of a layer as the persistent kernel sees it (32-/64-bit fields: scalar loads)
     const float *w;      // packed weights [n/16][k/16][lane][4], offset to the segment's first k-block
@@ -226,10 +229,15 @@ struct FlowArgs {
     // all frames in `keep` (B,T,H), and dec.6 itself - the decoder's output - is one batched GEMM over `keep` behind the launch.
     FlowLin pxc;                            // w == null: the layers as the reference lists them
     float *keep;
+    // the concealing decoder (the third program, CONCEAL): the encode program with prior.{0,2,4} in enc0h / enc1 / enc2 (enc0h with its own
+    // bias, no part0), `bits` = the selector per (utterance, frame) (launch_conceal_select) and the received codes; `codes` takes the
+    // filled codes (may be codes_in itself), `prob` the prior's probabilities
+    const float *codes_in;
 };
 int flow_kernels_init();
 int flow_perh(int h_dim);
-int launch_flow(const FlowArgs &a, FlowArgs *d_args, int perh, bool encode, bool fill, hipStream_t s, bool args_resident = false);
+int launch_flow(const FlowArgs &a, FlowArgs *d_args, int perh, bool encode, bool fill, hipStream_t s, bool args_resident = false,
+                bool conceal = false);
 // sentinel fill of the flow region + initial state into its first buffer + the device copy of the arguments, in one kernel
 int launch_flow_prepare(const FlowArgs &a, FlowArgs *d_args, unsigned *flow, long long n_flow, long long n_h0, const float *d_h0, int B, int H,
                         hipStream_t s);
@@ -276,6 +284,10 @@ int launch_unpack_codes(const unsigned char *in, long long frames, int z, int nb
 int launch_pack_rows(const float *codes, const float *bits, int B, int k, int z, int kstride, unsigned char *out, hipStream_t s);
 int launch_unpack_rows(const unsigned char *in, const unsigned char *present, const float *bits, const int *row_off, int B, int k,
                        int z, int kstride, float *codes, hipStream_t s);
+// the concealing decoder's selector, one float per (row, frame): -1 where the frame arrived (present (B, k) bytes, row stride kstride) or the
+// row is idle (row_off[b] < 0; row_off may be null), else the bits a generated frame gets: bits[b * k + t] (or dflt if bits is null), not below 0
+int launch_conceal_select(const unsigned char *present, long long kstride, const float *bits, float dflt, const int *row_off, int B,
+                          long long k, float *sel, hipStream_t s);
 
 // ------------------------------------------------------------------ vocoder (k_vocoder.hip)
 struct ConvLayer {               // one causal conv as implicit GEMM on fp32 MFMA

@@ -616,7 +616,8 @@ GemmParams lin2_params(const Linear &l, DynPtr x1, int K1, DynPtr x2, int K2, in
 enum { OP_KERNEL = 0, OP_RECORD = 1, OP_WAIT = 2 };
 enum { BR_MAIN = 0, BR_SIDE = 1 };
 struct StepNode { int op; int branch; int event; GemmParams p; int epi; };
-enum { STEP_ENCODE = 0, STEP_DECODE = 1, STEP_DECODE_PRE = 2 };   // _PRE: phi_z halves of dec.0 / GRU arrive pre-computed
+enum { STEP_ENCODE = 0, STEP_DECODE = 1, STEP_DECODE_PRE = 2, STEP_CONCEAL = 3 };   // _PRE: phi_z halves of dec.0 / GRU arrive pre-computed
+                                                                  // _CONCEAL: the concealing decoder - the encode step with the prior net in the encoder's place
 enum { STEP_KIND_MASK = 0xF, STEP_FOLD = 0x10 };                  // | STEP_FOLD: the folded hop (step_fold below)
 constexpr int64_t SMALL_T_FRAMES = 4;          // up to this many frames per call the all-frame MLPs run frame by frame on the recurrent-layer kernel
 enum { EV_START = 0, EV_DEC0H = 1, EV_PZ = 2, EV_GATES = 3, EV_COUNT = 4 };
@@ -627,12 +628,14 @@ enum { EV_START = 0, EV_DEC0H = 1, EV_PZ = 2, EV_GATES = 3, EV_COUNT = 4 };
 // order (packed=1) so every operand load is a coalesced 1 KiB read.
 //   encode (bvrnn.py:187-206): enc -> sigmoid/round/mask -> phi_z -> dec -> phi_x(norm) -> GRU
 //   decode (bvrnn.py:222-227): [phi_z batched over all frames beforehand] dec -> phi_x(norm) -> GRU
+//   conceal (bvc_bvrnn_decode_conceal): prior -> sigmoid/round/mask, SELECTED against the received codes -> phi_z -> ... as encode
 // Side branch: the halves of the split dot products that do not depend on the current frame's chain -
 // dec.0[:, H:] h, W_hh h + b_hh, W_ih[:, H:] phi_z + b_ih - run concurrently with the chain (which is
 // latency-bound), so the GRU kernel on the critical path only streams W_ih[:, :H].
 std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, int kind_and_fold) {
     const int kind = kind_and_fold & STEP_KIND_MASK;
     const bool fold = (kind_and_fold & STEP_FOLD) != 0;       // dec.6 -> norm -> phi_x.0 as one layer (bvc_model::px0_dec3)
+    const bool enc_like = kind == STEP_ENCODE || kind == STEP_CONCEAL;    // phi_z is computed inside the step
     const int H = m->cfg.h_dim, Z = m->cfg.z_dim, X = m->cfg.num_mels;
     std::vector<StepNode> plan;
     const long long MH = (long long)((B + 15) / 16) * 16 * H;
@@ -679,7 +682,19 @@ std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, 
         K(BR_SIDE, p, EPI_LINEAR);
     };
 
-    DynPtr pz_final = (kind == STEP_ENCODE) ? S(pz3, H) : dp_frame(DS_PZ, H, 0, 1);
+    DynPtr pz_final = enc_like ? S(pz3, H) : dp_frame(DS_PZ, H, 0, 1);
+    if (kind == STEP_CONCEAL) {
+        // p_t = prior(h_t) (bvrnn.py:68-73): no pre-computed half, the first layer's bias is its own; the code epilogue SELECTS between the
+        // received codes (DS_NOISE carries them) and the generated bits, by the selector in DS_BITS; p_t goes to DS_PROB
+        K(BR_MAIN, lin_params(m->prior[0], h_cur, B, S(e1, H)), EPI_ELU);
+        K(BR_MAIN, lin_params(m->prior[1], S(e1, H), B, S(e2, H)), EPI_ELU);
+        GemmParams p = lin_params(m->prior[2], S(e2, H), B, dp_frame(DS_CODES, Z));
+        p.sample = CS_SELECT;
+        p.aux = dp_frame(DS_BITS, 1);
+        p.y2 = dp_frame(DS_NOISE, Z);
+        p.y3 = dp_frame(DS_PROB, Z);
+        K(BR_MAIN, p, EPI_CODE);
+    }
     if (kind == STEP_ENCODE) {
         {   // enc.0([phi_x, h]) = (enc.0[:, :H] phi_x + b) [all frames beforehand: encode_prologue] + enc.0[:, H:] h, as in the persistent kernel
             GemmParams p = lin_params(m->enc[0], h_cur, B, S(e1, H));
@@ -696,6 +711,8 @@ std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, 
             p.y3 = dp_frame(DS_PROB, Z);
             K(BR_MAIN, p, EPI_CODE);
         }
+    }
+    if (enc_like) {
         K(BR_MAIN, lin_params(m->phi_z[0], dp_frame(DS_CODES, Z), B, S(pz1, H)), EPI_ELU);
         K(BR_MAIN, lin_params(m->phi_z[1], S(pz1, H), B, S(pz2, H)), EPI_ELU);
         K(BR_MAIN, lin_params(m->phi_z[2], S(pz2, H), B, S(pz3, H)), EPI_ELU);
@@ -730,7 +747,7 @@ std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, 
         // one launch less per frame: u = ELU(dec.4) (decode: also kept for all frames - dec.6(u), the decoder's output, is one batched
         // GEMM behind the recurrence), then phi_x.0(norm(dec.6(u))) as the one folded layer
         GemmParams p = lin_params(m->dec[2], S(d2, H), B, S(d3, H));
-        p.y2 = dp_frame(kind != STEP_ENCODE ? DS_KEEP : DS_KEEP_ENC, H);       // (encode: a null slot unless the fused forward wants mel^)
+        p.y2 = dp_frame(!enc_like ? DS_KEEP : DS_KEEP_ENC, H);       // (encode: a null slot unless the fused forward wants mel^)
         K(BR_MAIN, p, EPI_ELU);
         K(BR_MAIN, lin_params(m->px0_dec3, S(d3, H), B, S(g1, H)), EPI_ELU);
     } else {
@@ -784,7 +801,7 @@ std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, 
         side_dec0h();
         REC(BR_SIDE, EV_DEC0H);
         side_hh();
-        if (kind == STEP_DECODE) { side_ihz(pz_final); REC(BR_SIDE, EV_GATES); }
+        if (kind == STEP_DECODE) { side_ihz(pz_final); REC(BR_SIDE, EV_GATES); }      // (enc_like: behind EV_PZ, below)
         for (const StepNode &n : main_ops) {
             plan.push_back(n);
             if (n.op == OP_RECORD && n.event == EV_PZ) {        // encode: phi_z ready
@@ -989,11 +1006,16 @@ inline FlowLin flin(const Linear &l, size_t kb_offset = 0, bool with_bias = true
 // The layers of one frame (encode: bvrnn.py:187-206, decode: bvrnn.py:222-227).  Halves of a concatenated input that do
 // not depend on the frame's own chain - phi_x(y_t) in enc.0, phi_z(z_t) in dec.0 and in the GRU's input gates when the
 // codes are known - are batched over all frames beforehand and enter as addends (part0 / part_gru).
-void flow_layers(const bvc_model *m, bool encode, FlowArgs *a) {
+void flow_layers(const bvc_model *m, bool encode, FlowArgs *a, bool conceal = false) {
     const int hb = m->cfg.h_dim / 16;
     a->enc0h = flin(m->enc[0], hb, false);            // enc.0[:, H:] h  (+ part0 = enc.0[:, :H] phi_x + b)
     a->enc1 = flin(m->enc[1]);
     a->enc2 = flin(m->enc[2]);
+    if (conceal) {                                    // the concealing decoder: the prior net in the encoder's place, its first bias its own
+        a->enc0h = flin(m->prior[0]);
+        a->enc1 = flin(m->prior[1]);
+        a->enc2 = flin(m->prior[2]);
+    }
     a->pz0 = flin(m->phi_z[0]);
     a->pz1 = flin(m->phi_z[1]);
     a->pz2 = flin(m->phi_z[2]);
@@ -1005,7 +1027,7 @@ void flow_layers(const bvc_model *m, bool encode, FlowArgs *a) {
     a->px0 = flin(m->phi_x[0]);
     a->px1 = flin(m->phi_x[1]);
     a->px2 = flin(m->phi_x[2]);
-    if ((encode ? m->encode_fold : m->decode_fold) && m->px0_dec3.wp) a->pxc = flin(m->px0_dec3);
+    if (((encode && !conceal) ? m->encode_fold : m->decode_fold) && m->px0_dec3.wp) a->pxc = flin(m->px0_dec3);      // (a concealing decoder is a decoder)
     a->w_hh = m->w_hh_il;
     a->w_ihx = m->w_ih_il;
     a->w_ihz = m->w_ih_il + (size_t)hb * 3 * 256;
@@ -1148,9 +1170,10 @@ int decode_epilogue(const bvc_model *m, const float *keep, int B, int64_t T, flo
 // All T frames of BVRNN.encode (encode = true) or BVRNN.decode in one launch.  w.part_dec0 (and w.part_gru for decode)
 // must hold the pre-computed halves; h0 may be null (zero state).
 int run_flow(const bvc_model *m, const Workspace &w, bool encode, int chains, const float *d_h0, int B, int64_t T, const float *d_bits,
-             float *d_codes, float *d_prob, float *d_all_h, float *d_mel, float *d_hT, hipStream_t s) {
+             float *d_codes, float *d_prob, float *d_all_h, float *d_mel, float *d_hT, hipStream_t s, const float *d_codes_in = nullptr) {
     const int H = m->cfg.h_dim, Z = m->cfg.z_dim, X = m->cfg.num_mels;
     const int mt16 = ((B + 15) / 16) * 16;
+    const bool conceal = d_codes_in != nullptr;        // the concealing decoder (encode = true: its program is encode's; d_bits = the selector)
     int rc;
     {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1160,7 +1183,8 @@ int run_flow(const bvc_model *m, const Workspace &w, bool encode, int chains, co
     float *h0p = flow_buf(w, FB_H, 0);
     FlowArgs a;
     memset(&a, 0, sizeof(a));
-    flow_layers(m, encode, &a);
+    flow_layers(m, encode, &a, conceal);
+    a.codes_in = d_codes_in;
     a.flow = w.flow;
     a.slot_bytes = (unsigned)(w.flow_slot * sizeof(float));
     a.B = B; a.MT = mt16 / 16; a.T = T;
@@ -1212,7 +1236,7 @@ int run_flow(const bvc_model *m, const Workspace &w, bool encode, int chains, co
             if (f.pending) { BVC_HIP_TRY(hipStreamWaitEvent(s, f.ev, 0)); f.pending = false; }
         ProbeScope probe(PK_LINEAR, s);
         static const bool fill = !(getenv("BVC_FLOW_FILL") && getenv("BVC_FLOW_FILL")[0] == '0');
-        if ((rc = launch_flow(a, w.flow_args, m->flow_perh, encode, fill && !m->flow_debug_nofill && a.MG == 1, s, fused_prepare))) return rc;
+        if ((rc = launch_flow(a, w.flow_args, m->flow_perh, encode, fill && !m->flow_debug_nofill && a.MG == 1, s, fused_prepare, conceal))) return rc;
         BVC_HIP_TRY(hipEventRecord(ev, s));
         ++g_flow_n[dev];
     }
@@ -1398,6 +1422,47 @@ int run_decode(const bvc_model *m, const Workspace &w, void *ws_base, const floa
     const int rc = run_decode_body(m, w, ws_base, d_codes, d_h0, B, T, d_mel, d_hT, s);
     const int rc2 = mark_call_end(s);
     return rc ? rc : rc2;
+}
+
+// ---- the concealing decoder (bvc_bvrnn_decode_conceal) -------------------------------------------------
+// BVRNN.decode in which a frame that did not arrive is generated from the prior net (bvrnn.py:68-73) at the decoder's own state.  d_sel
+// (B,T): the selector (launch_conceal_select).  The frame's codes are only known inside the frame, so nothing is batched beforehand: the
+// program is encode's from the code epilogue on (dec.0 and the GRU's input gates sum their h half before their phi_z half), on every
+// schedule - a call that conceals runs it on all its frames, lost or not, so its result does not depend on where the losses are cut.
+int run_decode_conceal_body(const bvc_model *m, const Workspace &w, void *ws_base, const float *d_codes, const float *d_sel,
+                            const float *d_h0, int B, int64_t T, float *d_mel, float *d_hT, float *d_codes_out, float *d_prior,
+                            hipStream_t s) {
+    const int H = m->cfg.h_dim, Z = m->cfg.z_dim;
+    int rc;
+    if (Z > 3 * H) { set_error("bvc_bvrnn_decode_conceal: z_dim > 3 h_dim is not supported"); return BVC_EINVAL; }
+    float *codes = d_codes_out ? d_codes_out : w.part_gru;        // the filled codes feed phi_z: nobody's output goes to a tensor this program does not use
+    const int chains = flow_chains(m, B, s);
+    if (chains) return run_flow(m, w, true, chains, d_h0, B, T, d_sel, codes, d_prior, nullptr, d_mel, d_hT, s, d_codes);
+    if ((rc = init_state(w, d_h0, B, H, s))) return rc;
+    CallDesc d;
+    memset(&d, 0, sizeof(d));
+    d.p[DS_CODES] = codes; d.p[DS_BITS] = const_cast<float *>(d_sel); d.p[DS_PROB] = d_prior; d.p[DS_NOISE] = const_cast<float *>(d_codes);
+    d.T = T;
+    const int kind = STEP_CONCEAL | step_fold(m, false, T);
+    if (kind & STEP_FOLD) d.p[DS_KEEP_ENC] = w.pxB;      // ELU(dec.4) of every frame; dec.6, the decoder's output, behind the recurrence
+    else d.p[DS_MEL] = d_mel;
+    if ((rc = begin_call(m, w, d, count_kernels(build_step(m, w, B, kind)), s))) return rc;
+    if ((rc = run_recurrence(m, w, ws_base, B, T, kind, s))) return rc;
+    if (d_hT && (rc = read_state(w, B, H, T, d_hT, s))) return rc;
+    if ((kind & STEP_FOLD) && (rc = decode_epilogue(m, w.pxB, B, T, d_mel, s))) return rc;
+    return BVC_OK;
+}
+
+int run_decode_conceal(const bvc_model *m, const Workspace &w, void *ws_base, const float *d_codes, const float *d_sel, const float *d_h0,
+                       int B, int64_t T, float *d_mel, float *d_hT, float *d_codes_out, float *d_prior, hipStream_t s) {
+    const int rc = run_decode_conceal_body(m, w, ws_base, d_codes, d_sel, d_h0, B, T, d_mel, d_hT, d_codes_out, d_prior, s);
+    const int rc2 = mark_call_end(s);
+    return rc ? rc : rc2;
+}
+
+int need_prior(const bvc_model *m, const char *fn) {
+    if (m && !m->has_prior) { set_error("%s: the model was created without the prior.* tensors", fn); return BVC_EMISSING; }
+    return BVC_OK;
 }
 
 // ---- BVRNN.forward (bvrnn.py:86-160): the training-time pass, forward values only --------------------
@@ -1897,10 +1962,13 @@ struct bvc_stream_codec {
     uint8_t *packets = nullptr, *present = nullptr;
     float *bits_of(int k) const { return bitsbuf + (size_t)B * (k * (k - 1) / 2); }
     hipGraphExec_t graph[8][2] = {};    // [k][vocoder parity]
+    hipGraphExec_t graph_conceal[8][2] = {};      // ... of the ticks that conceal from the prior
+    int conceal = 0;                    // receive sessions: 0 = a lost frame is a frame of no bits, 1 = generated from the prior (bvc_stream_codec_set_conceal)
     bool use_graph = true;
     bool tick_flow = true;      // the ticks' recurrences on the persistent kernel where it is available (BVC_STREAM_FLOW=0: never)
     ~bvc_stream_codec() {
         for (auto &gk : graph) for (auto g : gk) if (g) (void)hipGraphExecDestroy(g);
+        for (auto &gk : graph_conceal) for (auto g : gk) if (g) (void)hipGraphExecDestroy(g);
         if (voc) bvc_vocoder_stream_destroy(voc);
         if (pool) (void)hipFree(pool);
     }
@@ -2026,6 +2094,12 @@ int stream_tick_body(bvc_stream_codec *st, int k, hipStream_t s) {
         // the wire -> codes: every row's own bit count, 0.5 for what did not arrive and for idle rows
         if ((rc = launch_unpack_rows(st->packets, st->present, m->cfg.var_bit ? st->bits_of(k) : nullptr, st->row_off, B, k, m->cfg.z_dim,
                                      st->kmax, st->codes, s))) return rc;
+        if (st->conceal) {
+            // lost frames of open rows are generated with the row's bit count (all z bits on a fixed-rate model); idle rows keep their 0.5
+            if ((rc = launch_conceal_select(st->present, st->kmax, m->cfg.var_bit ? st->bits_of(k) : nullptr, (float)m->cfg.z_dim, st->row_off, B, k,
+                                            w.bits, s))) return rc;
+            if ((rc = run_decode_conceal(m, w, st->ws, st->codes, w.bits, st->h_dec, B, k, st->melhat, st->h_dec, st->codes, nullptr, s))) return rc;
+        } else
         if ((rc = run_decode(m, w, st->ws, st->codes, st->h_dec, B, k, st->melhat, st->h_dec, s))) return rc;
         return bvc_vocoder_stream_push(st->voc, st->melhat, k, st->out_div, st->wav, s);
     }
@@ -2146,6 +2220,35 @@ int bvc_bvrnn_decode(const bvc_model *m, const float *d_codes, const float *d_h0
     if (rc) return rc;
     if (!d_codes || !d_mel) { set_error("null argument"); return BVC_EINVAL; }
     return run_decode(m, w, d_ws, d_codes, d_h0, B, T, d_mel, d_hT, (hipStream_t)stream);
+}
+
+int bvc_bvrnn_decode_conceal(const bvc_model *m, const float *d_codes, const uint8_t *d_present, const float *d_bits, const float *d_h0,
+                             int32_t B, int64_t T, float *d_mel, float *d_hT, float *d_codes_out, float *d_prior, void *d_ws,
+                             size_t ws_bytes, void *stream) {
+    if (int st_ = sticky_status(m)) return st_;
+    if (int rc_ = need_prior(m, "bvc_bvrnn_decode_conceal")) return rc_;
+    Workspace w;
+    int rc = check_ws(m, B, T, d_ws, ws_bytes, &w);
+    if (rc) return rc;
+    if (!d_codes || !d_present || !d_mel) { set_error("null argument"); return BVC_EINVAL; }
+    if (m->cfg.var_bit && !d_bits) { set_error("bits per frame required when var_bit=1"); return BVC_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = launch_conceal_select(d_present, T, m->cfg.var_bit ? d_bits : nullptr, (float)m->cfg.z_dim, nullptr, B, T, w.bits, s))) return rc;
+    return run_decode_conceal(m, w, d_ws, d_codes, w.bits, d_h0, B, T, d_mel, d_hT, d_codes_out, d_prior, s);
+}
+
+int bvc_decode_conceal(const bvc_model *m, const float *d_codes, const uint8_t *d_present, float bits_per_frame, int32_t B, int64_t T,
+                       int64_t length, float out_scale_div, float *d_wav, float *d_codes_out, void *d_ws, size_t ws_bytes, void *stream) {
+    if (int st_ = sticky_status(m)) return st_;
+    if (int rc_ = need_prior(m, "bvc_decode_conceal")) return rc_;
+    Workspace w;
+    int rc = check_ws(m, B, T, d_ws, ws_bytes, &w);
+    if (rc) return rc;
+    if (!d_codes || !d_present || !d_wav || length <= 0) { set_error("null argument or non-positive length"); return BVC_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = launch_conceal_select(d_present, T, nullptr, m->cfg.var_bit ? bits_per_frame : (float)m->cfg.z_dim, nullptr, B, T, w.bits, s))) return rc;
+    if ((rc = run_decode_conceal(m, w, d_ws, d_codes, w.bits, nullptr, B, T, w.mel, nullptr, d_codes_out, nullptr, s))) return rc;
+    return run_vocoder(m, w, w.mel, B, T, length, out_scale_div, d_wav, -1, nullptr, nullptr, nullptr, s);
 }
 
 int bvc_bvrnn_forward(const bvc_model *m, const float *d_mel, const float *d_bits, const uint8_t *h_use_gen,
@@ -2570,7 +2673,7 @@ static int stream_run_body(bvc_stream_codec *st, int k, hipStream_t s) {
     if (!warm) {
         rc = stream_tick_body(st, k, s);
     } else {
-        hipGraphExec_t &ge = st->graph[k][parity];
+        hipGraphExec_t &ge = (st->conceal ? st->graph_conceal : st->graph)[k][parity];
         if (!ge) {                                       // first warm tick of this shape: capture it (the capture does not execute)
             hipGraph_t graph = nullptr;
             const int vp = parity; const int64_t vf = st->voc ? st->voc->frames : 0;
@@ -2657,6 +2760,16 @@ int bvc_stream_codec_tick_recv(bvc_stream_codec *st, int32_t n_frames, void *str
     }
     st->frames += k;
     st->ticks += 1;
+    return BVC_OK;
+}
+
+int bvc_stream_codec_set_conceal(bvc_stream_codec *st, int32_t mode) {
+    if (!st) { set_error("null stream codec"); return BVC_EINVAL; }
+    if (int st_ = sticky_status(st->m)) return st_;
+    if (st->dir != BVC_STREAM_RECV) { set_error("bvc_stream_codec_set_conceal: not a receive session"); return BVC_EINVAL; }
+    if (mode != 0 && mode != 1) { set_error("bvc_stream_codec_set_conceal: mode %d is neither 0 (no bits) nor 1 (prior)", (int)mode); return BVC_EINVAL; }
+    if (int rc_ = need_prior(st->m, "bvc_stream_codec_set_conceal")) return rc_;
+    st->conceal = mode;                                      // host bookkeeping: the next tick reads it
     return BVC_OK;
 }
 

@@ -483,7 +483,8 @@ __device__ __forceinline__ void flow_stamp(const FlowCtx &c, int hopid, int whic
 // 1 KiB block; re-arm (poison) this workgroup's block of the other frame parity.
 template <int EPI, bool ADD, bool REARM_H, int NW>
 __device__ __forceinline__ void flow_publish(const FlowCtx &c, int hopid, const float *r, int n0, unsigned ytile, int ntiles, int out,
-                                             const f32x4 bias4, const f32x4 add4, const f32x4 mean4, const f32x4 std4, float bitsv) {
+                                             const f32x4 bias4, const f32x4 add4, const f32x4 mean4, const f32x4 std4, float bitsv,
+                                             const f32x4 recv4 = (f32x4){0.f, 0.f, 0.f, 0.f}) {
     const FlowWg &g = c.g;
     const auto &a = *c.a;
     const int lane = g.lane;
@@ -505,6 +506,14 @@ __device__ __forceinline__ void flow_publish(const FlowCtx &c, int hopid, const 
             if (a.var_bit) z = (bitsv > (float)(n0 + j)) ? z : (z != z ? z : 0.5f);    // z*m + 0.5*(1-m): NaN * 0 is NaN (bvrnn.py:193-194)
             o[j] = z;
         }
+    } else if (EPI == FE_CODE_SEL) {                   // the concealing decoder: bitsv is the selector (< 0: the frame arrived), recv4 the received codes
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            pr[j] = sigmoid1(v[j]);                    // the prior's probability (bvrnn.py:68-73)
+            float z = rintf(pr[j]);
+            z = (bitsv > (float)(n0 + j)) ? z : (z != z ? z : 0.5f);
+            o[j] = bitsv < 0.0f ? recv4[j] : z;        // a select: what a lost frame's codes hold reaches nothing
+        }
     } else {                                           // FE_MEL, bvrnn.py:202-204
         if (a.mel && c.rowok) *reinterpret_cast<f32x4 *>(a.mel + c.fr * (ntiles * 16) + n0) = v;
 #pragma unroll
@@ -520,7 +529,7 @@ __device__ __forceinline__ void flow_publish(const FlowCtx &c, int hopid, const 
     // consumed h(t), i.e. had all finished frame t-1: nobody reads h(t-1) any more (same tile shape as this layer's).
     if (REARM_H) __builtin_amdgcn_raw_buffer_store_b128(poison4, g.rs, (unsigned)(FB_H * 2 + (c.par ^ 1u)) * c.sb + ytile, 0, AUX_SC1);
     if (EPI == FE_ELU_KEEP && c.rowok && a.keep) *reinterpret_cast<f32x4 *>(a.keep + c.fr * (ntiles * 16) + n0) = o;     // (behind the hand-off stores; encode keeps u only for the fused forward)
-    if (EPI == FE_CODE && c.rowok) {                    // the call's outputs: behind the hand-off stores as well (-0.06 ms per step)
+    if ((EPI == FE_CODE || EPI == FE_CODE_SEL) && c.rowok) {      // the call's outputs: behind the hand-off stores as well (-0.06 ms per step)
         *reinterpret_cast<f32x4 *>(a.codes + c.fr * (ntiles * 16) + n0) = o;
         if (a.prob) *reinterpret_cast<f32x4 *>(a.prob + c.fr * (ntiles * 16) + n0) = pr;
     }
@@ -572,10 +581,15 @@ __device__ __forceinline__ void flow_layer(FlowCtx &c, int hopid, const FlowLin 
     // ---- epilogue operands of wave 0, requested up front
     f32x4 bias4 = {0.f, 0.f, 0.f, 0.f}, add4 = {0.f, 0.f, 0.f, 0.f}, mean4 = {0.f, 0.f, 0.f, 0.f}, std4 = {1.f, 1.f, 1.f, 1.f};
     float bitsv = 0.0f;
+    f32x4 recv4 = {0.f, 0.f, 0.f, 0.f};
     if (wave == 0) {
         if (l0.bias) bias4 = *reinterpret_cast<const f32x4 *>(l0.bias + n0);
         if (ADD && c.rowok) add4 = *reinterpret_cast<const f32x4 *>(a.part0 + c.fr * (ntiles * 16) + n0);
         if (EPI == FE_CODE && a.var_bit && c.rowok) bitsv = a.bits[c.fr];
+        if (EPI == FE_CODE_SEL && c.rowok) {               // the selector and the received granule (used only where the frame arrived)
+            bitsv = a.bits[c.fr];
+            recv4 = *reinterpret_cast<const f32x4 *>(a.codes_in + c.fr * (ntiles * 16) + n0);
+        }
         if (EPI == FE_MEL) {
             mean4 = *reinterpret_cast<const f32x4 *>(a.mean + n0);
             std4 = *reinterpret_cast<const f32x4 *>(a.stdv + n0);
@@ -634,7 +648,8 @@ __device__ __forceinline__ void flow_layer(FlowCtx &c, int hopid, const FlowLin 
         for (int u = 0; u < PERN; ++u) wn[u] = wload(ub, (unsigned)lane * 16u, u);
     }
     if (wave == 0) {
-        flow_publish<EPI, ADD, REARM_H, NW>(c, hopid, r, n0, ytile, ntiles, out, bias4, add4, mean4, std4, bitsv);
+        if constexpr (EPI == FE_CODE_SEL) flow_publish<EPI, ADD, REARM_H, NW>(c, hopid, r, n0, ytile, ntiles, out, bias4, add4, mean4, std4, bitsv, recv4);
+        else flow_publish<EPI, ADD, REARM_H, NW>(c, hopid, r, n0, ytile, ntiles, out, bias4, add4, mean4, std4, bitsv);
         if (BVC_FLOW_PARTNER_WAIT && NW == 8 && FGATE != -2) *c.pubflag = c.hopctr;
         if (LATE && c.pre_now) {
             const GPtr ub = uniform_ptr(nxt.w, ((size_t)g.ntile * nxt.wnb + wave * PERN) * g.wmul);
@@ -786,9 +801,14 @@ __device__ __forceinline__ void flow_layer_chains(FlowCtx &c, int hopid, const F
         ce.probe = c.probe && pk == 0 && g0 == 0;
         f32x4 add4 = {0.f, 0.f, 0.f, 0.f};
         float bitsv = 0.0f;
+        f32x4 recv4 = {0.f, 0.f, 0.f, 0.f};
         if (pub) {
             if (ADD && ce.rowok) add4 = *reinterpret_cast<const f32x4 *>(a.part0 + ce.fr * (ntiles * 16) + n0);
             if (EPI == FE_CODE && a.var_bit && ce.rowok) bitsv = a.bits[ce.fr];
+            if (EPI == FE_CODE_SEL && ce.rowok) {
+                bitsv = a.bits[ce.fr];
+                recv4 = *reinterpret_cast<const f32x4 *>(a.codes_in + ce.fr * (ntiles * 16) + n0);
+            }
         }
         float *rg = c.red_chain + (grp & 1) * (GM * NW * 256);
 #pragma unroll
@@ -798,7 +818,8 @@ __device__ __forceinline__ void flow_layer_chains(FlowCtx &c, int hopid, const F
         if (BVC_FLOW_DIAG && g0 == 0) flow_stamp(c, hopid, 4);
         if (pub) {
             const unsigned ytile = (unsigned)((ce.g.mtile * ntiles + g.ntile) * 1024 + lane * 16);
-            flow_publish<EPI, ADD, REARM_H, NW>(ce, hopid, rg + pk * (NW * 256), n0, ytile, ntiles, out, bias4, add4, mean4, std4, bitsv);
+            if constexpr (EPI == FE_CODE_SEL) flow_publish<EPI, ADD, REARM_H, NW>(ce, hopid, rg + pk * (NW * 256), n0, ytile, ntiles, out, bias4, add4, mean4, std4, bitsv, recv4);
+            else flow_publish<EPI, ADD, REARM_H, NW>(ce, hopid, rg + pk * (NW * 256), n0, ytile, ntiles, out, bias4, add4, mean4, std4, bitsv);
         }
     }
     if (BVC_FLOW_DIAG) flow_stamp(c, hopid, 5);
@@ -1079,9 +1100,14 @@ __device__ __forceinline__ void flow_gru_chains(FlowCtx &c, int hopid, int hb, c
 // under the products of the others.  Batches of more than 16 * (CUs / feature tiles) utterances (64 at h_dim 1024) run this way.
 // FOLD: 1 / 0: the folded hop (FlowArgs::pxc) is / is not compiled in; -1: both, chosen at run time.  (The interleaved-chain
 // kernels with both programs in them spill: they are instantiated once per program.)
-template <int PERH, bool ENCODE, bool FILL, int NW = 8, bool MULTI = false, int FOLD = -1>
+// CONCEAL: the third program, the concealing decoder (bvc_bvrnn_decode_conceal): the ENCODE program with the prior net in the encoder's
+// place - FlowArgs::enc0h / enc1 / enc2 then hold prior.{0,2,4}, the first layer has its own bias and no pre-computed half - and the code
+// epilogue selecting between the received codes and the generated bits (FE_CODE_SEL).  Everything behind layer 3 is the encode program.
+template <int PERH, bool ENCODE, bool FILL, int NW = 8, bool MULTI = false, int FOLD = -1, bool CONCEAL = false>
 __global__ __launch_bounds__(NW * 64, NW == 8 ? BVC_FLOW_WAVES_PER_SIMD : 1) void bvrnn_flow_kernel(const FlowArgs *a0) {
     static_assert(!(MULTI && FILL), "the filler quanta are per chain: not built for interleaved chains");
+    static_assert(!CONCEAL || ENCODE, "the concealing decoder is a variant of the encode program");
+    constexpr int EPI3 = CONCEAL ? FE_CODE_SEL : FE_CODE;      // layer 3's epilogue
     extern __shared__ __attribute__((aligned(16))) float lds[];     // [2][8][256] layer partials | [1 or 2][8][6][256] GRU partials
     const int tid = threadIdx.x;
     FlowCtx c;
@@ -1193,9 +1219,9 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? BVC_FLOW_WAVES_PER_SIMD : 1) voi
             auto &w8 = pick<P8>(k8, wb);  auto &w9 = pick<P9>(k9, wa);  auto &w12 = pick<P12>(k12, wa);  auto &w13 = pick<P13>(k13, wb);
             if (ENCODE) {
                 //         PER   epilogue  two    add    pre_in pre_out       rearm  filler
-                flow_layer<PERH, FE_ELU, false, true, true, true, PERH, false, G0, NW>(c, 1, L(a.enc0h), FB_H, L(a.enc0h), 0, hb, hb, FB_E1, wa, L(a.enc1), wb, gq, zero4, f_hh, &c.fgh[0]);
+                flow_layer<PERH, FE_ELU, false, !CONCEAL, true, true, PERH, false, G0, NW>(c, 1, L(a.enc0h), FB_H, L(a.enc0h), 0, hb, hb, FB_E1, wa, L(a.enc1), wb, gq, zero4, f_hh, &c.fgh[0]);
                 flow_layer<PERH, FE_ELU, false, false, true, false, PERH, true, G1, NW>(c, 2, L(a.enc1), FB_E1, L(a.enc1), 0, hb, hb, FB_E2, wb, L(a.enc1), wa, gq, zero4, f_hh, &c.fgh[1]);
-                flow_layer<PERH, FE_CODE, false, false, false, false, PERH, false, G2, NW>(c, 3, L(a.enc2), FB_E2, L(a.enc2), 0, hb, zb, FB_ZC, wa, L(a.enc2), wb, gq, zero4, f_hh, &c.fgh[2]);
+                flow_layer<PERH, EPI3, false, false, false, false, PERH, false, G2, NW>(c, 3, L(a.enc2), FB_E2, L(a.enc2), 0, hb, zb, FB_ZC, wa, L(a.enc2), wb, gq, zero4, f_hh, &c.fgh[2]);
                 flow_layer<1, FE_ELU, false, false, false, true, PERH, false, GP, NW>(c, 4, L(a.pz0), FB_ZC, L(a.pz0), 0, zb, hb, FB_Q1, w1, L(a.pz1), wa, gq, zero4, f_d0, &c.fd0);
                 flow_layer<PERH, FE_ELU, false, false, true, true, PERH, false, -2, NW>(c, 5, L(a.pz1), FB_Q1, L(a.pz1), 0, hb, hb, FB_Q2, wa, L(a.pz2), wb, gq);
                 if (FILL) {
@@ -1236,9 +1262,9 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? BVC_FLOW_WAVES_PER_SIMD : 1) voi
             // (flow_layer_chains), the two narrow-input layers, the two-segment dec.0 of encode and the GRU go chain by chain
             constexpr bool E = ENCODE;
             if (E) {
-                flow_layer_chains<PERH, FE_ELU, true, true, true, PERH, false, NW>(c, 1, L(a.enc0h), FB_H, hb, hb, FB_E1, wa, L(a.enc1), wb, mt0, nch, T);
+                flow_layer_chains<PERH, FE_ELU, !CONCEAL, true, true, PERH, false, NW>(c, 1, L(a.enc0h), FB_H, hb, hb, FB_E1, wa, L(a.enc1), wb, mt0, nch, T);
                 flow_layer_chains<PERH, FE_ELU, false, true, false, PERH, true, NW>(c, 2, L(a.enc1), FB_E1, hb, hb, FB_E2, wb, L(a.enc1), wa, mt0, nch, T);
-                flow_layer_chains<PERH, FE_CODE, false, false, false, PERH, false, NW>(c, 3, L(a.enc2), FB_E2, hb, zb, FB_ZC, wa, L(a.enc2), wb, mt0, nch, T);
+                flow_layer_chains<PERH, EPI3, false, false, false, PERH, false, NW>(c, 3, L(a.enc2), FB_E2, hb, zb, FB_ZC, wa, L(a.enc2), wb, mt0, nch, T);
                 FLOW_EACH_CHAIN(flow_layer<1, FE_ELU, false, false, false, true, PERH, false, -2, NW>(c, 4, L(a.pz0), FB_ZC, L(a.pz0), 0, zb, hb, FB_Q1, w1, L(a.pz1), wa, gq));
                 flow_layer_chains<PERH, FE_ELU, false, true, true, PERH, false, NW>(c, 5, L(a.pz1), FB_Q1, hb, hb, FB_Q2, wa, L(a.pz2), wb, mt0, nch, T);
                 flow_layer_chains<PERH, FE_ELU, false, true, false, PERH, false, NW>(c, 6, L(a.pz2), FB_Q2, hb, hb, FB_Q3, wb, L(a.pz2), wa, mt0, nch, T);
@@ -1355,10 +1381,10 @@ constexpr size_t FLOW_LDS = flow_lds(8);
 constexpr size_t FLOW_LDS_MULTI = FLOW_LDS + (size_t)2 * 4 * 8 * 256 * sizeof(float);  // + two slots of four chains' partial tiles: 128 KiB
 constexpr size_t FLOW_LDS_FILL = (size_t)(2 * 8 * 256 + 8 * 8 * 256 + 8 * 8 * 256) * sizeof(float) + 16;       // partials | stashes (over the GRU partials) | parked weights | flag: 144 KiB
 
-template <int PERH, bool ENC>
+template <int PERH, bool ENC, bool CONCEAL = false>
 static int flow_attr() {
-    BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bvrnn_flow_kernel<PERH, ENC, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLOW_LDS));
-    BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bvrnn_flow_kernel<PERH, ENC, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLOW_LDS_FILL));
+    BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bvrnn_flow_kernel<PERH, ENC, false, 8, false, -1, CONCEAL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLOW_LDS));
+    BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bvrnn_flow_kernel<PERH, ENC, true, 8, false, -1, CONCEAL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLOW_LDS_FILL));
     return BVC_OK;
 }
 
@@ -1378,6 +1404,10 @@ int flow_kernels_init() {
 
     if ((rc = flow_attr<1, true>()) || (rc = flow_attr<1, false>()) || (rc = flow_attr<2, true>()) || (rc = flow_attr<2, false>()) ||
         (rc = flow_attr<4, true>()) || (rc = flow_attr<4, false>()) || (rc = flow_attr<8, true>()) || (rc = flow_attr<8, false>())) return rc;
+    // the concealing decoder
+    BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bvrnn_flow_kernel<8, true, false, 8, true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLOW_LDS_MULTI));
+    BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bvrnn_flow_kernel<8, true, false, 8, true, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLOW_LDS_MULTI));
+    if ((rc = flow_attr<1, true, true>()) || (rc = flow_attr<2, true, true>()) || (rc = flow_attr<4, true, true>()) || (rc = flow_attr<8, true, true>())) return rc;
     return BVC_OK;
 }
 
@@ -1399,8 +1429,10 @@ __global__ void flow_set_args_kernel(FlowArgs *dst, FlowArgs v) {
 }
 
 template <int PERH>
-static void flow_launch_t(const FlowArgs *d_a, bool encode, bool fill, int grid, hipStream_t s) {
-    if (encode && fill)  hipLaunchKernelGGL((bvrnn_flow_kernel<PERH, true, true>), dim3(grid), dim3(512), FLOW_LDS_FILL, s, d_a);
+static void flow_launch_t(const FlowArgs *d_a, bool encode, bool fill, int grid, hipStream_t s, bool conceal) {
+    if (conceal && fill) hipLaunchKernelGGL((bvrnn_flow_kernel<PERH, true, true, 8, false, -1, true>), dim3(grid), dim3(512), FLOW_LDS_FILL, s, d_a);
+    else if (conceal)    hipLaunchKernelGGL((bvrnn_flow_kernel<PERH, true, false, 8, false, -1, true>), dim3(grid), dim3(512), FLOW_LDS, s, d_a);
+    else if (encode && fill)  hipLaunchKernelGGL((bvrnn_flow_kernel<PERH, true, true>), dim3(grid), dim3(512), FLOW_LDS_FILL, s, d_a);
     else if (encode)     hipLaunchKernelGGL((bvrnn_flow_kernel<PERH, true, false>), dim3(grid), dim3(512), FLOW_LDS, s, d_a);
     else if (fill)       hipLaunchKernelGGL((bvrnn_flow_kernel<PERH, false, true>), dim3(grid), dim3(512), FLOW_LDS_FILL, s, d_a);
     else                 hipLaunchKernelGGL((bvrnn_flow_kernel<PERH, false, false>), dim3(grid), dim3(512), FLOW_LDS, s, d_a);
@@ -1411,14 +1443,17 @@ static void flow_launch_t(const FlowArgs *d_a, bool encode, bool fill, int grid,
 // (A 4-wave form - bvrnn_flow_kernel<16, ., false, 4>: one wave per SIMD, 214 VGPRs, so that the vocoder of the same or of
 // another call could share the CUs with the recurrence - was built and measured: correct, but 27 % slower per frame, and with
 // four batches in flight 5,120 audio-s/s against 5,700.  NW stays a template parameter; only the 8-wave form is instantiated.)
-int launch_flow(const FlowArgs &a, FlowArgs *d_args, int perh, bool encode, bool fill, hipStream_t s, bool args_resident) {
+int launch_flow(const FlowArgs &a, FlowArgs *d_args, int perh, bool encode, bool fill, hipStream_t s, bool args_resident, bool conceal) {
     static_assert(sizeof(FlowArgs) % 4 == 0, "FlowArgs is copied in dwords");
+    if (conceal && (!encode || !a.codes_in || !a.codes || !a.bits)) { set_error("launch_flow: the concealing program needs the encode layout, codes and a selector"); return BVC_EINVAL; }
     if (!args_resident) hipLaunchKernelGGL(flow_set_args_kernel, dim3(1), dim3(256), 0, s, d_args, a);
     const FlowArgs *d_a = d_args;
     if (a.MG > 1) {                                        // interleaved chains: more utterance groups than workgroup slots per feature tile
         if (perh != 8) { set_error("launch_flow: interleaved chains are built for h_dim 1024 only"); return BVC_EINVAL; }
         const int grid_m = ((a.NTG + 7) / 8) * 8 * ((a.MT + a.MG - 1) / a.MG);
-        if (encode && a.pxc.w) hipLaunchKernelGGL((bvrnn_flow_kernel<8, true, false, 8, true, 1>), dim3(grid_m), dim3(512), FLOW_LDS_MULTI, s, d_a);
+        if (conceal && a.pxc.w) hipLaunchKernelGGL((bvrnn_flow_kernel<8, true, false, 8, true, 1, true>), dim3(grid_m), dim3(512), FLOW_LDS_MULTI, s, d_a);
+        else if (conceal) hipLaunchKernelGGL((bvrnn_flow_kernel<8, true, false, 8, true, 0, true>), dim3(grid_m), dim3(512), FLOW_LDS_MULTI, s, d_a);
+        else if (encode && a.pxc.w) hipLaunchKernelGGL((bvrnn_flow_kernel<8, true, false, 8, true, 1>), dim3(grid_m), dim3(512), FLOW_LDS_MULTI, s, d_a);
         else if (encode) hipLaunchKernelGGL((bvrnn_flow_kernel<8, true, false, 8, true, 0>), dim3(grid_m), dim3(512), FLOW_LDS_MULTI, s, d_a);
         else if (a.pxc.w) hipLaunchKernelGGL((bvrnn_flow_kernel<8, false, false, 8, true, 1>), dim3(grid_m), dim3(512), FLOW_LDS_MULTI, s, d_a);
         else        hipLaunchKernelGGL((bvrnn_flow_kernel<8, false, false, 8, true, 0>), dim3(grid_m), dim3(512), FLOW_LDS_MULTI, s, d_a);
@@ -1428,10 +1463,10 @@ int launch_flow(const FlowArgs &a, FlowArgs *d_args, int perh, bool encode, bool
     const int grid = ((a.NTG + 7) / 8) * 8 * a.MT;
 
     switch (perh) {
-        case 1: flow_launch_t<1>(d_a, encode, fill, grid, s); break;
-        case 2: flow_launch_t<2>(d_a, encode, fill, grid, s); break;
-        case 4: flow_launch_t<4>(d_a, encode, fill, grid, s); break;
-        case 8: flow_launch_t<8>(d_a, encode, fill, grid, s); break;
+        case 1: flow_launch_t<1>(d_a, encode, fill, grid, s, conceal); break;
+        case 2: flow_launch_t<2>(d_a, encode, fill, grid, s, conceal); break;
+        case 4: flow_launch_t<4>(d_a, encode, fill, grid, s, conceal); break;
+        case 8: flow_launch_t<8>(d_a, encode, fill, grid, s, conceal); break;
         default: set_error("launch_flow: unsupported blocks per wave %d", perh); return BVC_EINVAL;
     }
     BVC_HIP_TRY(hipGetLastError());

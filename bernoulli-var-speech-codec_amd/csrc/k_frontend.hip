@@ -297,6 +297,27 @@ int launch_unpack_rows(const unsigned char *in, const unsigned char *present, co
     return BVC_OK;
 }
 
+// ---- the concealing decoder's selector (bvc_bvrnn_decode_conceal): one float per (row, frame) that says what the code epilogue does
+__global__ void conceal_select_kernel(const unsigned char *__restrict__ present, long long kstride, const float *__restrict__ bits, float dflt,
+                                      const int *__restrict__ row_off, long long k, long long total, float *__restrict__ sel) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long b = i / k, t = i - b * k;
+        const bool take = (row_off && row_off[b] < 0) || present[b * kstride + t] != 0;
+        const float nb = bits ? bits[i] : dflt;
+        sel[i] = take ? -1.0f : (nb > 0.0f ? nb : 0.0f);     // (a NaN bit count generates no bits)
+    }
+}
+
+int launch_conceal_select(const unsigned char *present, long long kstride, const float *bits, float dflt, const int *row_off, int B,
+                          long long k, float *sel, hipStream_t s) {
+    const long long total = (long long)B * k;
+    if (total <= 0) return BVC_OK;
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(conceal_select_kernel, dim3(grid), dim3(256), 0, s, present, kstride, bits, dflt, row_off, k, total, sel);
+    BVC_HIP_TRY(hipGetLastError());
+    return BVC_OK;
+}
+
 // ---- mixed-length batches (bvc_encode_ragged): row b's own frame count T_b = ragged_frames(lens[b]) decides which of its frames are live.
 // bits (B, T): the row's bits per frame (d_bits[b], or `dflt` for every row) on live frames, 0 behind them - a var_bit coder then emits
 // 0.5 there by itself.

@@ -276,7 +276,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmParams p, int 
         } else if (epi == EPI_CODE) {
             const float pr = sigmoid1(v[0]);
             float z;
-            if (p.sample == CS_ENCODE) {
+            if (p.sample == CS_ENCODE || p.sample == CS_SELECT) {
                 z = rintf(pr);                                       // round half to even (torch.round)
             } else {                                                 // BVRNN.forward: straight-through forward value
                 float arg = pr;
@@ -286,7 +286,15 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmParams p, int 
                 }
                 z = __fadd_rn(__fsub_rn(rintf(arg), pr), pr);        // round(.) - p + p
             }
-            if (p.var_bit) {
+            if (p.sample == CS_SELECT) {                             // the concealing decoder: a SELECT between the received code and the generated bit
+                const Resolved bt = resolve<MF>(p.aux, dsc, mt16, p.tstep);
+                const float sel = bt.p[(long long)m * bt.ld];        // < 0: the frame arrived; else the bits a generated frame gets
+                z = (sel > (float)n) ? z : (z != z ? z : 0.5f);
+                if (sel < 0.0f) {                                    // (a lost frame's received codes are never read)
+                    const Resolved ci = resolve<MF>(p.y2, dsc, mt16, p.tstep);
+                    z = ci.p[(long long)m * ci.ld + n];
+                }
+            } else if (p.var_bit) {
                 const Resolved bt = resolve<MF>(p.aux, dsc, mt16, p.tstep);
                 const float bits = bt.p[(long long)m * bt.ld];
                 z = (bits > (float)n) ? z : (z != z ? z : 0.5f);     // z*m + 0.5*(1-m): a NaN stays a NaN under the mask too (NaN * 0)

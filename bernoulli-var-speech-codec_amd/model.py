@@ -292,8 +292,17 @@ class BVRNN(_OnDevice):
         return codes.to(out_dev), eng.deliver(hT.unsqueeze(0), out_dev)
 
     @torch.no_grad()
-    def decode(self, z, h):
-        """z (B,T,z_dim), h (1,B,h_dim) -> (mel (B,T,x_dim), h (1,B,h_dim))."""
+    def decode(self, z, h, present=None, bits=None, return_codes=False):
+        """z (B,T,z_dim), h (1,B,h_dim) -> (mel (B,T,x_dim), h (1,B,h_dim)).
+
+        ``present`` (B,T) turns concealment on (``bvc_bvrnn_decode_conceal``): a frame whose entry is 0 did not arrive and is generated
+        from the prior net at the decoder's own state - round(prior(h_t)), masked to ``bits[b, t]`` leading bits on a variable-rate
+        model (``bits`` (B,T) is then required) - whatever ``z`` holds there.  ``return_codes=True`` adds the codes with the gaps
+        filled and the prior's probabilities of every frame: (mel, h, codes_out, prior)."""
+        if present is not None:
+            return self._decode_conceal(z, h, present, bits, return_codes)
+        if return_codes or bits is not None:
+            raise ValueError("decode: bits / return_codes belong to concealment (pass present)")
         eng = self.engine(z)
         out_dev = z.device
         z = _prep(z, eng.device)
@@ -305,6 +314,33 @@ class BVRNN(_OnDevice):
         with torch.cuda.device(eng.device):
             _abi.check(eng.lib.bvc_bvrnn_decode(eng.handle, _abi.ptr(z), _abi.ptr(h0), B, T, _abi.ptr(mel),
                                                 _abi.ptr(hT), ws, nws, eng.stream()))
+        return mel.to(out_dev), eng.deliver(hT.unsqueeze(0), out_dev)
+
+
+    @torch.no_grad()
+    def _decode_conceal(self, z, h, present, bits, return_codes):
+        if self.varBit and bits is None:
+            raise ValueError("decode: a variable-rate model needs bits (B,T) to generate lost frames")
+        if z.dim() != 3 or tuple(present.shape) != tuple(z.shape[:2]) or (bits is not None and tuple(bits.shape) != tuple(z.shape[:2])):
+            raise ValueError("decode: z (B,T,z_dim) with present (B,T) and bits (B,T)")
+        eng = self.engine(z)
+        out_dev = z.device
+        z = _prep(z, eng.device)
+        B, T, _ = z.shape
+        pres = present.detach().to(eng.device).ne(0).to(torch.uint8).contiguous()
+        d_bits = _prep(bits, eng.device) if (bits is not None and self.varBit) else None
+        h0 = _prep(h.reshape(B, self.h_dim), eng.device)
+        mel = torch.empty(B, T, self.x_dim, device=eng.device)
+        hT = torch.empty(B, self.h_dim, device=eng.device)
+        codes = torch.empty(B, T, self.z_dim, device=eng.device) if return_codes else None
+        prior = torch.empty(B, T, self.z_dim, device=eng.device) if return_codes else None
+        ws, nws = eng.workspace(B, T)
+        with torch.cuda.device(eng.device):
+            _abi.check(eng.lib.bvc_bvrnn_decode_conceal(eng.handle, _abi.ptr(z), ctypes.c_void_p(pres.data_ptr()), _abi.ptr(d_bits),
+                                                        _abi.ptr(h0), B, T, _abi.ptr(mel), _abi.ptr(hT), _abi.ptr(codes),
+                                                        _abi.ptr(prior), ws, nws, eng.stream()))
+        if return_codes:
+            return mel.to(out_dev), hT.unsqueeze(0).to(out_dev), codes.to(out_dev), eng.deliver(prior, out_dev)
         return mel.to(out_dev), eng.deliver(hT.unsqueeze(0), out_dev)
 
 
@@ -431,14 +467,23 @@ class BVRNNCodecModel(_OnDevice):
         return eng.deliver(codes, out_dev)
 
     @torch.no_grad()
-    def decode(self, codes, length, frames=None):
+    def decode(self, codes, length, frames=None, lost=None, bitrate=None, return_codes=False):
         """Codes (batch, frames, z_dim) back to waveforms (batch, min(length, 256 * frames + 294)): coder decode from a
         zero state, vocoder, output gain undone - bvrnn_codec_model.py:64-71.
 
         Mixed-length batch: ``length`` (batch,) per row, and optionally ``frames`` (batch,) valid code frames per row (default
         min(frames, num_frames(length[b])), the frame count encode gives for that length).  Returns (batch, max n_b): row b equals
         ``decode(codes[b:b+1, :frames[b]], length[b])`` in its first n_b = min(length[b], 256 * frames[b] + 294) samples and is 0
-        after them (n_b = 0 for a row without frames)."""
+        after them (n_b = 0 for a row without frames).
+
+        Lost frames: ``lost`` (batch, frames) bool marks the frames that did not arrive; they are generated from the model's prior
+        net at the decoder's own state (``bvc_decode_conceal``), whatever ``codes`` holds there, with the bits per frame of
+        ``bitrate`` (required on a variable-rate model).  ``return_codes=True`` then returns (wav, codes with the gaps filled).  Not
+        together with a mixed-length batch."""
+        if lost is not None:
+            return self._decode_conceal(codes, length, frames, lost, bitrate, return_codes)
+        if return_codes:
+            raise ValueError("decode: return_codes belongs to concealment (pass lost)")
         if frames is not None or ragged.per_row(length, codes.shape[0], "length") is not None:
             return self._decode_ragged(codes, length, frames)
         eng = self.engine(codes)
@@ -454,6 +499,36 @@ class BVRNNCodecModel(_OnDevice):
             with torch.cuda.device(eng.device):
                 _abi.check(eng.lib.bvc_decode(eng.handle, _abi.ptr(codes), B, T, n, float(SCALING),
                                               _abi.ptr(wav), ws, nws, eng.stream()))
+        return eng.deliver(wav, out_dev)
+
+    @torch.no_grad()
+    def _decode_conceal(self, codes, length, frames, lost, bitrate, return_codes):
+        if frames is not None or ragged.per_row(length, codes.shape[0], "length") is not None:
+            raise ValueError("decode: lost frames in a mixed-length batch are not supported (decode the rows on their own)")
+        if self.conf["var_bit"] and bitrate is None:
+            raise ValueError("decode: a variable-rate model needs the bitrate to generate lost frames")
+        if codes.dim() != 3 or tuple(lost.shape) != tuple(codes.shape[:2]):
+            raise ValueError("decode: lost must be (batch, frames) like the codes")
+        eng = self.engine(codes)
+        out_dev = codes.device
+        codes = _prep(codes, eng.device)
+        B, T, Z = codes.shape
+        if Z != self.conf["z_dim"]:
+            raise RuntimeError(f"codes must have {self.conf['z_dim']} values per frame, got {Z}")
+        present = lost.detach().to(eng.device).eq(0).to(torch.uint8).contiguous()
+        n = _trimmed(eng.vocoder_length(T), length)
+        wav = torch.empty(B, n, device=eng.device)
+        filled = torch.empty(B, T, Z, device=eng.device) if return_codes else None
+        if n:
+            ws, nws = eng.workspace(B, T)
+            bits = self.bits_per_frame(bitrate) if self.conf["var_bit"] else float(Z)
+            with torch.cuda.device(eng.device):
+                _abi.check(eng.lib.bvc_decode_conceal(eng.handle, _abi.ptr(codes), ctypes.c_void_p(present.data_ptr()), float(bits), B, T,
+                                                      n, float(SCALING), _abi.ptr(wav), _abi.ptr(filled), ws, nws, eng.stream()))
+        elif return_codes:
+            raise ValueError("decode: the filled codes need a non-empty output (length > 0)")
+        if return_codes:
+            return eng.deliver(wav, out_dev), filled.to(out_dev)
         return eng.deliver(wav, out_dev)
 
     @torch.no_grad()

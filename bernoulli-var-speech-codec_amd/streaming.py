@@ -248,13 +248,22 @@ class StreamingCodec:
     ``active_bits`` leading bits in the layout of ``model.pack`` and zeros behind them.  ``"recv"``: ``push_packets(packets,
     present=None)`` with packets ``(batch, k, bytes_per_frame)``, 1 <= k <= ``kmax``, returns wav ``(batch, 256 k)``: the decoder and
     the generator only.  ``present (batch, k)``: 0 marks a frame that did not arrive; it is decoded as a frame of no bits (codes all
-    0.5) and the state moves on.  ``hop`` means nothing to a receive session, ``open`` always returns 0 there."""
+    0.5) and the state moves on.  ``hop`` means nothing to a receive session, ``open`` always returns 0 there.
+
+    ``conceal="prior"`` (receive sessions only; ``set_conceal`` switches between two pushes): a lost frame of an open slot is generated
+    from the model's prior net at the decoder's own state instead, with the slot's current bit count, and ``filled_codes()`` gives the
+    codes with the gaps filled; every stream equals ``model.decode(codes, n, lost=..., bitrate=...)`` of its own packets alone."""
 
     DIRECTIONS = {"duplex": 0, "send": 1, "recv": 2}
+    CONCEAL = {"none": 0, "prior": 1}
 
-    def __init__(self, model, batch, bitrate, hop=441, device=None, open_all=True, direction="duplex"):
+    def __init__(self, model, batch, bitrate, hop=441, device=None, open_all=True, direction="duplex", conceal="none"):
         if direction not in self.DIRECTIONS:
             raise ValueError(f"direction must be one of {sorted(self.DIRECTIONS)}")
+        if conceal not in self.CONCEAL:
+            raise ValueError(f"conceal must be one of {sorted(self.CONCEAL)}")
+        if conceal != "none" and direction != "recv":
+            raise ValueError("conceal: only a receive session has lost frames to conceal")
         self.direction = direction
         eng = model.engine(None if device is None else torch.empty(0, device=device))
         if direction == "recv":
@@ -290,6 +299,9 @@ class StreamingCodec:
         if not open_all:
             for b in range(batch):
                 self.close(b)
+        self.conceal = "none"
+        if conceal != "none":
+            self.set_conceal(conceal)
 
     def __del__(self):
         try:
@@ -332,6 +344,19 @@ class StreamingCodec:
         """The stream in `slot` ends with the first `n_last` samples of the next push's row (None: the whole hop; 0: it ended with
         the last push).  The slot drains from that push on and is idle once its last frame is out."""
         self._slot_call(self.eng.lib.bvc_stream_codec_finish(self.handle, int(slot), int(self.hop if n_last is None else n_last)))
+
+    def set_conceal(self, mode):
+        """What the next pushes do with a lost frame: "none" (a frame of no bits) or "prior" (generated from the prior net).
+        Receive sessions only."""
+        if mode not in self.CONCEAL:
+            raise ValueError(f"conceal must be one of {sorted(self.CONCEAL)}")
+        self._slot_call(self.eng.lib.bvc_stream_codec_set_conceal(self.handle, self.CONCEAL[mode]))
+        self.conceal = mode
+
+    def filled_codes(self, k):
+        """Receive session: the codes (batch, k, z_dim) the last push of k frames decoded - unpacked, and with ``conceal="prior"`` with
+        the lost frames filled; a view of the session's buffer, valid until the next push."""
+        return torch.as_tensor(_DeviceView(self._codes_ptr, (self.B, k, self.z)), device=self.dev)
 
     def slot_state(self, slot):
         """"idle", "waiting" (open, frame 0 still to come), "running" or "draining" (finished, frames still to come)."""

@@ -11,7 +11,7 @@
  *  - plain C, no torch/HIP types: `stream` is a hipStream_t passed as void* (NULL = default stream);
  *  - every pointer named d_* is DEVICE memory owned by the caller, contiguous float32;
  *    every pointer named h_* is HOST memory;
- *  - the compute entry points (bvc_stft_logmel, bvc_bvrnn_*, bvc_bigvgan, bvc_encode, bvc_decode,
+ *  - the compute entry points (bvc_stft_logmel, bvc_bvrnn_*, bvc_bigvgan, bvc_encode, bvc_decode, bvc_decode_conceal,
  *    bvc_encode_ragged, bvc_decode_ragged, bvc_vocoder_stream_push, bvc_pack/unpack_codes, bvc_resample_poly, bvc_peak_normalize) are
  *    asynchronous on `stream` and use only the caller-provided workspace.  They do not allocate or
  *    synchronise, with these exceptions: the first calls per process create a handful of HIP events (the
@@ -50,7 +50,8 @@ extern "C" {
                              * 3: + bvc_model_poll_status, bvc_forward
                              *    still 3 (new symbols only, nothing existing changed): + bvc_encode_ragged, bvc_decode_ragged;
                              *    + bvc_stream_codec_open / close / set_bits / slot_frames;
-                             *    + bvc_stream_codec_create_dir / packets / tick_recv / finish / slot_state */
+                             *    + bvc_stream_codec_create_dir / packets / tick_recv / finish / slot_state;
+                             *    + bvc_bvrnn_decode_conceal, bvc_decode_conceal, bvc_stream_codec_set_conceal */
 
 enum {
     BVC_OK = 0,
@@ -189,6 +190,23 @@ int bvc_bvrnn_decode(const bvc_model *m, const float *d_codes, const float *d_h0
                      int64_t T, float *d_mel, float *d_hT, void *d_ws, size_t ws_bytes,
                      void *stream);
 
+/* BVRNN.decode that conceals lost frames from the model's prior net (bvrnn.py:68-73; not in the reference, whose decoder has no notion of
+ * a lost frame).  d_present (B,T) uint8 marks the frames of d_codes (B,T,z_dim) that arrived.  Per row, with state h_t (h_0 = d_h0 or
+ * zeros), frame t:  p_t = prior(h_t), sigmoid included;  g_t = round-half-even(p_t), on a var_bit model 0.5 at positions >= d_bits[b,t]
+ * (bvrnn.py:193-194; d_bits (B,T), NULL unless var_bit; a fixed-rate model generates all z_dim bits);  z_t = present ? codes[b,t] : g_t;
+ * then phi_z, dec, phi_x((dec - mean) / std) and the GRU exactly as bvrnn.py:223-227.  z_t is a SELECT: whatever a lost position of
+ * d_codes holds - garbage, NaN, Inf - reaches nothing.  Outputs: d_mel (B,T,num_mels); optional d_hT (B,h_dim); optional d_codes_out
+ * (B,T,z_dim) = z_t, the codes with the gaps filled (may be d_codes itself); optional d_prior (B,T,z_dim) = p_t of EVERY frame.
+ * The result is a function of (codes, present, bits, h0) alone: the call runs ONE program on all its frames, lost or not, on every
+ * schedule (persistent, launch per layer, captured), so it does not depend on batching or on where a sequence is cut into calls
+ * (carry d_hT into the next call's d_h0).  That program cannot batch phi_z over all frames - a frame's codes exist only inside the frame
+ * - so it sums dec.0 and the GRU's input gates in BVRNN.encode's order, the h half before the phi_z half.  With every frame present it
+ * therefore agrees with bvc_bvrnn_decode to rounding, not bit for bit: the difference bvc_forward has against bvc_encode + bvc_decode
+ * (mel^ / h_T within 2e-5 / 5e-6 in the tests).  "decode_fold" applies.  BVC_EMISSING on a model created without prior.{0,2,4}.*. */
+int bvc_bvrnn_decode_conceal(const bvc_model *m, const float *d_codes, const uint8_t *d_present, const float *d_bits,
+                             const float *d_h0, int32_t B, int64_t T, float *d_mel, float *d_hT, float *d_codes_out,
+                             float *d_prior, void *d_ws, size_t ws_bytes, void *stream);
+
 /* BVRNN.forward (bvrnn.py:86-160), forward VALUES only (no autograd): the training-time pass with the
  * stochastic Bernoulli sampler round(u - 0.5 + p), the prior net and the KL term.
  *   d_mel (B,T,num_mels), d_bits (B,T) (NULL unless var_bit);
@@ -296,7 +314,8 @@ int  bvc_stream_codec_slot_frames(bvc_stream_codec *st, int32_t slot, int32_t *f
  *    unpacked d_codes).  Bytes and bits behind nbits_b are ignored.  A frame whose d_present byte is 0 is a LOST frame: it is
  *    decoded as a frame of no bits - codes all 0.5, what a variable-rate coder writes and reads at masked positions - whatever
  *    its bytes hold, and the GRU state moves on through it; the result equals bvc_decode of the same code tensor with those frames
- *    set to 0.5.  (A late packet is a lost packet; there is no reordering, no concealment from the model's prior.)  Idle rows
+ *    set to 0.5.  (A late packet is a lost packet; there is no reordering.  bvc_stream_codec_set_conceal(st, 1) generates lost frames from the
+ *    model's prior instead: below.)  Idle rows
  *    are all 0.5 whatever their bytes and d_present hold.  Slots: a receive tick is frame-aligned, so open reports delay 0 and the
  *    stream's frame 0 is the first frame of the next tick, in which - ahead of its own work, for those rows only, in one launch -
  *    h_dec, the row's age and its history in every buffer of the generator are reset.  set_bits changes nbits_b from the next
@@ -316,7 +335,14 @@ int  bvc_stream_codec_slot_frames(bvc_stream_codec *st, int32_t slot, int32_t *f
  *    a draining slot drops the rest.
  *  - slot_state: 0 idle, 1 waiting for its frame 0, 2 running, 3 draining.
  * Like the slot calls, finish and slot_state are host bookkeeping between two ticks; the tick that carries a finish out makes one
- * more small launch.  A duplex session on which finish is never called launches exactly what it launched before. */
+ * more small launch.  A duplex session on which finish is never called launches exactly what it launched before.
+ *  - set_conceal (RECV only; BVC_EINVAL on any other session, BVC_EMISSING on a model without prior.*): what a receive tick does with a
+ *    lost frame.  mode 0 (the default): a frame of no bits, as above.  mode 1: the tick runs bvc_bvrnn_decode_conceal with the carried
+ *    state - a lost frame of an open row is generated from the prior with the slot's current bit count (set_bits applies; all z_dim
+ *    bits when var_bit = 0), idle rows stay all 0.5 - and d_codes holds the FILLED codes afterwards; every stream's samples and codes
+ *    equal bvc_decode_conceal of that stream's own packets alone, bit for bit.  Host bookkeeping between two ticks like the slot
+ *    calls: it takes effect from the next tick.  A receive session on which it is never called launches exactly what it launched
+ *    before. */
 enum { BVC_STREAM_DUPLEX = 0, BVC_STREAM_SEND = 1, BVC_STREAM_RECV = 2 };
 int  bvc_stream_codec_create_dir(const bvc_model *m, int32_t B, int32_t hop_samples, float bits_per_frame, float scale,
                                  float out_scale_div, int32_t direction, bvc_stream_codec **out);
@@ -324,6 +350,7 @@ int  bvc_stream_codec_packets(bvc_stream_codec *st, uint8_t **d_packets, uint8_t
 int  bvc_stream_codec_tick_recv(bvc_stream_codec *st, int32_t n_frames, void *stream);
 int  bvc_stream_codec_finish(bvc_stream_codec *st, int32_t slot, int32_t n_last);
 int  bvc_stream_codec_slot_state(bvc_stream_codec *st, int32_t slot, int32_t *state);
+int  bvc_stream_codec_set_conceal(bvc_stream_codec *st, int32_t mode);
 
 /* BVRNNCodecModel.encode (bvrnn_codec_model.py:44-62): scale, log-mel, bits/frame =
  * bits_per_frame for every (b,t), zero initial state, BVRNN.encode.  d_wav (B,L) -> d_codes. */
@@ -333,6 +360,13 @@ int bvc_encode(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, flo
 /* BVRNNCodecModel.decode (bvrnn_codec_model.py:64-71): zero state, BVRNN.decode, vocoder, /scale. */
 int bvc_decode(const bvc_model *m, const float *d_codes, int32_t B, int64_t T, int64_t length,
                float out_scale_div, float *d_wav, void *d_ws, size_t ws_bytes, void *stream);
+
+/* bvc_decode with lost frames concealed from the prior: zero state, bvc_bvrnn_decode_conceal with bits_per_frame for every generated
+ * frame (ignored when var_bit = 0), vocoder, / out_scale_div.  d_codes_out (B,T,z_dim) optional: the filled codes.  BVC_EMISSING without
+ * the prior.* tensors. */
+int bvc_decode_conceal(const bvc_model *m, const float *d_codes, const uint8_t *d_present, float bits_per_frame, int32_t B, int64_t T,
+                       int64_t length, float out_scale_div, float *d_wav, float *d_codes_out, void *d_ws, size_t ws_bytes,
+                       void *stream);
 
 /* Mixed-length batches: utterances of their own lengths (and bitrates) in ONE call, each coded exactly as it would be alone.
  * d_lengths / d_frames are DEVICE int64 arrays (B).  The library cannot look at them without synchronising, so validating them is

@@ -9,7 +9,8 @@ streams start ("join": per-row reset of the GRU states, the generator histories 
 
 --direction send|recv|duplex [--loss P]: the same 256 streams and inputs through a session that runs one half (send: samples ->
 packets; recv: packets -> samples) or both (duplex, the default run's loopback tick).  recv replays the packets of a send run
-(not timed) in ticks of the frame counts that run emitted; --loss P marks a seeded share P of the frames as not arrived."""
+(not timed) in ticks of the frame counts that run emitted; --loss P marks a seeded share P of the frames as not arrived;
+--conceal none|prior (recv only): what the session does with them (none: frames of no bits; prior: generated from the prior net)."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -71,6 +72,9 @@ def churn():
 
 def direction(which):
     loss = float(sys.argv[sys.argv.index("--loss") + 1]) if "--loss" in sys.argv else 0.0
+    conceal = sys.argv[sys.argv.index("--conceal") + 1] if "--conceal" in sys.argv else None
+    if conceal is not None and which != "recv":
+        sys.exit("--conceal belongs to --direction recv")
     model = make_model()[0]
     x = synth.synthetic_speech(B, hop * hops, seed=3, kind="noise").to("cuda:0")
     lat, frames = [], 0
@@ -81,7 +85,7 @@ def direction(which):
         del tx
         g = torch.Generator().manual_seed(11)
         present = [(torch.rand(B, p.shape[1], generator=g) >= loss).to(torch.uint8).to("cuda:0") for p in sent]
-        sc = StreamingCodec(model, B, 3000, direction="recv")
+        sc = StreamingCodec(model, B, 3000, direction="recv", **({} if conceal is None else {"conceal": conceal}))
         for p, pr in zip(sent, present):
             torch.cuda.synchronize(); t0 = time.perf_counter()
             sc.push_packets(p, pr)
@@ -100,7 +104,7 @@ def direction(which):
     n = len(lat)
     lat = np.array(lat[50:]) * 1e3
     print(json.dumps({"config": f"BASELINE configs[4]: {B} streams x 20 ms hops @ 3 kbit/s, {which} session",
-                      "direction": which, "ticks": n, "timed_ticks": int(lat.size), "frames_lost": round(lost, 4),
+                      "direction": which, "conceal": conceal, "ticks": n, "timed_ticks": int(lat.size), "frames_lost": round(lost, 4),
                       "p50_ms": round(float(np.percentile(lat, 50)), 3), "p99_ms": round(float(np.percentile(lat, 99)), 3),
                       "mean_ms": round(float(lat.mean()), 3), "hop_budget_ms": 20.0, "frames_per_tick": round(frames / n, 3)}))
 
