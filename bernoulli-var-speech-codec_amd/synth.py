@@ -28,9 +28,12 @@ def _n(rng, shape, std=1.0, mean=0.0):
     return torch.from_numpy((mean + std * rng.standard_normal(size=shape)).astype(np.float32))
 
 
-def bvrnn_state_dict(conf, seed=1234, mel_stats=None):
+def bvrnn_state_dict(conf, seed=1234, mel_stats=None, gains=None):
     """mel_stats = (mean, std_lo, std_hi): replaces the default conditioning (mean ~ N(-4, 1), std in [0.6, 2.2]) - e.g. (-8.0, 0.05, 0.3),
-    the narrow bands a trained checkpoint may carry; every other tensor is the one the same seed gives without it."""
+    the narrow bands a trained checkpoint may carry; every other tensor is the one the same seed gives without it.
+    gains = (g_hidden, g_out, g_gru): weight AND bias of every Linear times g_hidden, except the last layers of enc and prior
+    (enc.4, prior.4: times g_out); the four rnn.* tensors times g_gru.  The default draw keeps |logit| < 0.5 and |h| < 0.7; (1.7, 8, 2.5)
+    reaches |logit| 8 and |h| 1, (2, 20, 3) saturates the sigmoids (tests/bvrnn_draws.py).  None: the draw as it always was, bit for bit."""
     rng = np.random.default_rng(seed)
     x, h, z = conf["num_mels"], conf["h_dim"], conf["z_dim"]
     sd = collections.OrderedDict()
@@ -58,6 +61,13 @@ def bvrnn_state_dict(conf, seed=1234, mel_stats=None):
         mean, lo, hi = mel_stats
         sd["mean_mel"] = _n(r2, (x,), 0.5, mean)
         sd["std_mel"] = torch.from_numpy(r2.uniform(lo, hi, size=(x,)).astype(np.float32))
+    if gains is not None:
+        g_hidden, g_out, g_gru = (np.float32(g) for g in gains)
+        for k in sd:
+            if k.startswith("rnn."):
+                sd[k] = sd[k] * g_gru
+            elif k.endswith(".weight") or k.endswith(".bias"):
+                sd[k] = sd[k] * (g_out if k.startswith(("enc.4.", "prior.4.")) else g_hidden)
     return sd
 
 
@@ -104,12 +114,13 @@ def generator_state_dict(conf, seed=4321):
     return sd
 
 
-def write_checkpoints(conf, directory, seed=1234, prefix="synthetic", mel_stats=None):
+def write_checkpoints(conf, directory, seed=1234, prefix="synthetic", mel_stats=None, gains=None):
     """Write both checkpoints in the reference format; returns (bvrnn_path, vocoder_path)."""
     os.makedirs(directory, exist_ok=True)
-    p1 = os.path.join(directory, f"{prefix}_bvrnn_h{conf['h_dim']}_seed{seed}{'_melstats' if mel_stats else ''}")
+    p1 = os.path.join(directory, f"{prefix}_bvrnn_h{conf['h_dim']}_seed{seed}{'_melstats' if mel_stats else ''}"
+                      f"{'_gains' + '_'.join(f'{g:g}' for g in gains) if gains else ''}")
     p2 = os.path.join(directory, f"{prefix}_bigvgan_seed{seed}")
-    torch.save({"vrnn": bvrnn_state_dict(conf, seed, mel_stats)}, p1)
+    torch.save({"vrnn": bvrnn_state_dict(conf, seed, mel_stats, gains)}, p1)
     torch.save({"generator": generator_state_dict(conf, seed + 1)}, p2)
     return p1, p2
 

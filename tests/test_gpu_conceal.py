@@ -11,6 +11,7 @@ import torch
 from conftest import load_golden
 
 import conceal_oracle as co
+from gpu_common import on_schedule
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -39,31 +40,6 @@ def conceal(model, codes, present, bits, h0=None):
     mel, hT, out, prior = model.bvrnn.decode(codes.to(DEV), h, present=present.to(DEV), bits=None if bits is None else bits.to(DEV),
                                              return_codes=True)
     return mel, hT[0], out, prior
-
-
-def on_schedule(model, schedule, fn):
-    """fn() on the persistent kernel, on the launch-per-layer kernels, or captured into a graph and replayed."""
-    if schedule in ("persistent", "layers"):
-        try:
-            model.set_recurrence(schedule)
-            out = fn()
-            torch.cuda.synchronize()
-        finally:
-            model.set_recurrence("auto")
-        return [o.clone() for o in out]
-    s = torch.cuda.Stream(DEV)
-    s.wait_stream(torch.cuda.current_stream(DEV))
-    with torch.cuda.stream(s):
-        fn()                                                   # warm call: this stream's workspace exists before the capture
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-        out = fn()
-    for o in out:
-        o.fill_(float("nan"))
-    g.replay()
-    torch.cuda.synchronize()
-    return [o.clone() for o in out]
 
 
 # ------------------------------------------------------------------------------------------------ 1: goldens
