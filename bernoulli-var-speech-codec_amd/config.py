@@ -41,8 +41,26 @@ def load_config(path):
     return conf
 
 
+def antialias_flags(conf):
+    """(per-stage list, post switch): where the generator wraps its SnakeBeta in ``Activation1d``
+    (third_party/BigVGAN/models.py:172-192; absent keys: nowhere)."""
+    v = conf["vocoder_config"]
+    n = len(v["upsample_rates"])
+    return [bool(f) for f in v.get("layers_antialias", [False] * n)], bool(v.get("antialias_post", False))
+
+
+def is_antialiased(conf):
+    stages, post = antialias_flags(conf)
+    return any(stages) or post
+
+
+NOT_CAUSAL = ("this generator has anti-aliased activations: every filtered AMP block looks 30 rows ahead, so it cannot run "
+              "incrementally or on mixed-length batches (decode equal-length batches offline)")
+
+
 def check_supported(conf):
-    """The HIP path covers what the two shipped TOMLs select; anything else fails loudly."""
+    """The HIP path covers the causal snakebeta generator, with or without anti-aliased activations per stage; anything else
+    fails loudly."""
     v = conf["vocoder_config"]
     bad = []
     if v.get("resblock", "1") != "1":
@@ -51,8 +69,9 @@ def check_supported(conf):
         bad.append("only activation='snakebeta' with snake_logscale=true is implemented")
     if any(v.get("layers_sym", [False])) or v.get("pre_sym", False) or v.get("post_sym", False):
         bad.append("only causal (non-symmetric) layers are implemented")
-    if any(v.get("layers_antialias", [False])) or v.get("antialias_post", False):
-        bad.append("anti-aliased activations are not implemented (both shipped configs disable them)")
+    aa = v.get("layers_antialias")
+    if aa is not None and len(aa) != len(v["upsample_rates"]):
+        bad.append(f"layers_antialias must have one entry per upsampling stage ({len(v['upsample_rates'])}), got {len(aa)}")
     for u, k in zip(v["upsample_rates"], v["upsample_kernel_sizes"]):
         if k != 2 * u:
             bad.append(f"transposed conv kernel {k} must be 2 x stride {u}")

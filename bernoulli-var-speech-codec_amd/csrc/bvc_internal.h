@@ -303,6 +303,8 @@ struct ConvLayer {               // one causal conv as implicit GEMM on fp32 MFM
     const float *bias;           // [cout] (for ConvT: bias replicated per phase)
     const float *act_a;          // exp(alpha) per input channel or nullptr (no input activation)
     const float *act_ib;         // 1/(exp(beta)+1e-9)
+    const float *aa_up;          // the input activation is anti-aliased (Activation1d): its 12-tap upsample.filter and
+    const float *aa_down;        // downsample.lowpass.filter, else nullptr
 };
 enum ConvEpi { CE_STORE = 0, CE_RES = 1, CE_RES_ACC = 2, CE_RES_ACC_DIV = 3 };
 // Streaming window: the tensors are (B, rows, C) buffers whose first rows are history; only rows from
@@ -334,13 +336,16 @@ int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *
                      int B, int epi, const float *res, const float *acc, float divisor, hipStream_t s,
                      const ConvWindow *win = nullptr, const long long *row_lim = nullptr);
 // one fused AMPBlock1 iteration: out = x + conv2(S2(conv1_dil(S1(x)))) (+acc, /divisor per epi); c2.dil == 1
+// layers with aa_up / aa_down (both layers of a pair or none): S1 and S2 are anti-aliased, the generic kernel's AA form runs
+// (valid rows per tile TR - (ks-1) - 10) and win must be null - the pair reads x[t - (ks-1)(d+1) - 10 .. t + 10]
 int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, long long L, float *out, int B, int epi,
                     const float *acc, float divisor, hipStream_t s, const ConvWindow *win = nullptr, unsigned kernels = AMPK_ALL);
 // SnakeBeta -> causal conv C->1 (k taps) -> tanh -> / div -> first n_out samples
 // n_rows (B) or nullptr: item b keeps its first n_rows[b] samples, the rest of its n_out are 0
 int launch_conv_post(const float *in, long long Lin, int C, int ks, const float *w, const float *bias,
                      const float *act_a, const float *act_ib, float div, float *wav, long long n_out,
-                     int B, hipStream_t s, const ConvWindow *win = nullptr, const long long *n_rows = nullptr);
+                     int B, hipStream_t s, const ConvWindow *win = nullptr, const long long *n_rows = nullptr,
+                     const float *aa_up = nullptr, const float *aa_down = nullptr);   // anti-aliased activation_post: offline, equal lengths
 // mixed-length decode: lim ((n_up + 1) x B) = per-item input rows of the upsamplers, L_0 = frames[b] (clamped into [0, T]),
 // L_i = (L_{i-1} + 1) * up_rates[i-1], then the samples kept, min(lengths[b], L_{n_up}) clamped into [0, n_max] (0 without frames)
 int launch_ragged_limits(long long *lim, const long long *frames, const long long *lengths, int B, long long T, long long n_max,

@@ -83,7 +83,9 @@ struct bvc_model {
     std::vector<std::vector<std::vector<AmpPair>>> amp;   // [stage][kernel][dilation]
     std::vector<int> stage_ch;                        // channels after each upsampler
     const float *post_a = nullptr, *post_ib = nullptr, *post_w = nullptr, *post_b = nullptr;
+    const float *post_up = nullptr, *post_down = nullptr;   // antialias_post: activation_post's two filters
     int post_c = 0, post_ks = 7;
+    bool antialiased = false;   // some stage, or activation_post, has anti-aliased activations: the generator is not causal
     // captured recurrent steps (hipGraph), keyed by (kind, batch, workspace)
     // (launch-per-layer schedule only) most recently used first; `idle` is recorded behind the entry's last replay, so an
     // entry is only destroyed once the GPU is done with it
@@ -273,6 +275,7 @@ int make_conv(bvc_model *m, const float *W, const float *bias, int nbias_rep, in
               const float *alpha, const float *beta, ConvLayer *c) {
     c->cin = cin; c->cout = cout; c->ntiles = (cout + 15) / 16; c->ks = ks; c->dil = dil;
     c->act_a = c->act_ib = nullptr;
+    c->aa_up = c->aa_down = nullptr;
     int rc;
     std::vector<float> wp = pack_conv(W, cout, cin, ks);
     if ((rc = upload(m, wp, &c->wp))) return rc;
@@ -416,10 +419,45 @@ int build_bvrnn(bvc_model *m, const TensorMap &tm) {
     return BVC_OK;
 }
 
+// where the generator wraps its SnakeBeta in Activation1d: optional tensors "layers_antialias" (n_up values, non-zero = the stage's
+// AMP blocks) and "antialias_post" (one value); bvc_config keeps its layout.  A flagged activation `name` has the reference's keys
+// name.act.alpha / name.act.beta / name.upsample.filter / name.downsample.lowpass.filter (alias_free_torch/act.py:18-20), a plain
+// one name.alpha / name.beta: a checkpoint of the other layout is missing tensors either way.
+const char *NOT_CAUSAL = "the model has anti-aliased activations: a filtered AMP block looks 30 rows ahead, so the generator is not causal";
+int find_activation(bvc_model *m, const TensorMap &tm, const std::string &name, int ch, bool filtered, const bvc_tensor **alpha,
+                    const bvc_tensor **beta, const float **up, const float **down) {
+    const std::string mid = filtered ? ".act" : "";
+    if (!(*alpha = find(tm, name + mid + ".alpha", ch))) return BVC_EMISSING;
+    if (!(*beta = find(tm, name + mid + ".beta", ch))) return BVC_EMISSING;
+    *up = *down = nullptr;
+    if (!filtered) return BVC_OK;
+    const bvc_tensor *fu, *fd;
+    if (!(fu = find(tm, name + ".upsample.filter", 12))) return BVC_EMISSING;
+    if (!(fd = find(tm, name + ".downsample.lowpass.filter", 12))) return BVC_EMISSING;
+    int rc;
+    if ((rc = upload_raw(m, fu->h_data, 12, up))) return rc;
+    return upload_raw(m, fd->h_data, 12, down);
+}
+
 int build_vocoder(bvc_model *m, const TensorMap &tm) {
     const bvc_config &c = m->cfg;
     int rc;
     const bvc_tensor *w, *b;
+    std::vector<bool> stage_aa(c.n_up, false);
+    bool post_aa = false;
+    if (tm.count("layers_antialias")) {
+        const bvc_tensor *t = find(tm, "layers_antialias", c.n_up);
+        if (!t) return BVC_EMISSING;
+        for (int i = 0; i < c.n_up; ++i) stage_aa[i] = t->h_data[i] != 0.0f;
+    }
+    if (tm.count("antialias_post")) {
+        const bvc_tensor *t = find(tm, "antialias_post", 1);
+        if (!t) return BVC_EMISSING;
+        post_aa = t->h_data[0] != 0.0f;
+    }
+    m->antialiased = post_aa;
+    for (int i = 0; i < c.n_up; ++i) m->antialiased = m->antialiased || stage_aa[i];
+    if (m->antialiased && !m->fused_amp) { set_error("anti-aliased activations run in the fused AMP kernels only (BVC_UNFUSED_AMP is set)"); return BVC_EINVAL; }
     const int c0 = c.upsample_initial_channel;
     if (!(w = find(tm, "conv_pre.weight", (int64_t)c0 * c.num_mels * 7))) return BVC_EMISSING;
     if (!(b = find(tm, "conv_pre.bias", c0))) return BVC_EMISSING;
@@ -445,10 +483,9 @@ int build_vocoder(bvc_model *m, const TensorMap &tm) {
             for (int d = 0; d < 3; ++d) {
                 const bvc_tensor *a1, *b1, *a2, *b2, *w1, *bb1, *w2, *bb2;
                 const std::string ds = std::to_string(d);
-                if (!(a1 = find(tm, pre + ".activations." + std::to_string(2 * d) + ".alpha", ch))) return BVC_EMISSING;
-                if (!(b1 = find(tm, pre + ".activations." + std::to_string(2 * d) + ".beta", ch))) return BVC_EMISSING;
-                if (!(a2 = find(tm, pre + ".activations." + std::to_string(2 * d + 1) + ".alpha", ch))) return BVC_EMISSING;
-                if (!(b2 = find(tm, pre + ".activations." + std::to_string(2 * d + 1) + ".beta", ch))) return BVC_EMISSING;
+                const float *up1, *down1, *up2, *down2;
+                if ((rc = find_activation(m, tm, pre + ".activations." + std::to_string(2 * d), ch, stage_aa[i], &a1, &b1, &up1, &down1))) return rc;
+                if ((rc = find_activation(m, tm, pre + ".activations." + std::to_string(2 * d + 1), ch, stage_aa[i], &a2, &b2, &up2, &down2))) return rc;
                 if (!(w1 = find(tm, pre + ".convs1." + ds + ".weight", (int64_t)ch * ch * ks))) return BVC_EMISSING;
                 if (!(bb1 = find(tm, pre + ".convs1." + ds + ".bias", ch))) return BVC_EMISSING;
                 if (!(w2 = find(tm, pre + ".convs2." + ds + ".weight", (int64_t)ch * ch * ks))) return BVC_EMISSING;
@@ -458,13 +495,13 @@ int build_vocoder(bvc_model *m, const TensorMap &tm) {
                                     b1->h_data, &ap.c1))) return rc;
                 if ((rc = make_conv(m, w2->h_data, bb2->h_data, 1, ch, ch, ks, 1, a2->h_data, b2->h_data, &ap.c2)))
                     return rc;
+                ap.c1.aa_up = up1; ap.c1.aa_down = down1; ap.c2.aa_up = up2; ap.c2.aa_down = down2;
             }
         }
     }
     m->post_c = ch;
     const bvc_tensor *pa, *pb;
-    if (!(pa = find(tm, "activation_post.alpha", ch))) return BVC_EMISSING;
-    if (!(pb = find(tm, "activation_post.beta", ch))) return BVC_EMISSING;
+    if ((rc = find_activation(m, tm, "activation_post", ch, post_aa, &pa, &pb, &m->post_up, &m->post_down))) return rc;
     std::vector<float> a(ch), ib(ch);
     for (int i = 0; i < ch; ++i) {
         a[i] = (float)std::exp((double)pa->h_data[i]);
@@ -1626,7 +1663,7 @@ int run_vocoder(const bvc_model *m, const Workspace &w, const float *d_mel, int 
     }
     const int64_t n_out = length < Lin ? length : Lin;
     return launch_conv_post(cur_in, Lin, m->post_c, m->post_ks, m->post_w, m->post_b, m->post_a, m->post_ib, div,
-                            d_wav, n_out, B, s, nullptr, lim ? lim + (size_t)c.n_up * B : nullptr);
+                            d_wav, n_out, B, s, nullptr, lim ? lim + (size_t)c.n_up * B : nullptr, m->post_up, m->post_down);
 }
 
 
@@ -2361,6 +2398,7 @@ int bvc_decode_ragged(const bvc_model *m, const float *d_codes, const int64_t *d
         set_error("null argument or non-positive n_max");
         return BVC_EINVAL;
     }
+    if (m->antialiased) { set_error("bvc_decode_ragged: %s (a row's end would read the next row's frames)", NOT_CAUSAL); return BVC_EINVAL; }
     if (n_max > bvc_vocoder_length(m, T)) {
         set_error("n_max %lld exceeds the generator's %lld samples for T=%lld", (long long)n_max,
                   (long long)bvc_vocoder_length(m, T), (long long)T);
@@ -2384,6 +2422,7 @@ int bvc_vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_
 
 static int vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_per_push, bool slide, bvc_vocoder_stream **out) {
     if (!m || !out || B <= 0 || max_frames_per_push <= 0) { set_error("bvc_vocoder_stream_create: bad arguments"); return BVC_EINVAL; }
+    if (m->antialiased) { set_error("bvc_vocoder_stream_create: %s", NOT_CAUSAL); return BVC_EINVAL; }
     const bvc_config &c = m->cfg;
     // the history must cover every receptive field and stay aligned with the transposed-conv views
     long long rate = 1;
@@ -2486,6 +2525,7 @@ int bvc_stream_codec_create_dir(const bvc_model *m, int32_t B, int32_t hop_sampl
     const bool enc = direction != BVC_STREAM_RECV, dec = direction != BVC_STREAM_SEND;
     if (!enc) hop_samples = 0;                               // a receive tick is given whole frames
     if (!m || !out || B <= 0 || (enc && hop_samples <= 0)) { set_error("bvc_stream_codec_create: bad arguments"); return BVC_EINVAL; }
+    if (dec && m->antialiased) { set_error("bvc_stream_codec_create: %s", NOT_CAUSAL); return BVC_EINVAL; }
     const bvc_config &c = m->cfg;
     if (enc && hop_samples <= c.pad_left) { set_error("bvc_stream_codec_create: the hop must exceed the left reflect padding (%d samples)", c.pad_left); return BVC_EINVAL; }
     std::unique_ptr<bvc_stream_codec> st(new bvc_stream_codec());
@@ -3098,6 +3138,7 @@ int bvc_test_vocoder_layer(const bvc_model *m, int32_t kind, int32_t stage, int3
                 set_error("bvc_test_vocoder_layer: epilogue %d (1 residual, 2 + running sum, 3 + running sum, / kernels; 2 and 3 need d_acc)", epi);
                 return BVC_EINVAL; }
             if (!m->fused_amp) { set_error("bvc_test_vocoder_layer: the model runs its AMP pairs unfused"); return BVC_EINVAL; }
+            if (window && m->antialiased) { set_error("bvc_test_vocoder_layer: %s - no streaming window", NOT_CAUSAL); return BVC_EINVAL; }
             if (window && (row_begin < 0 || row_begin >= L)) { set_error("bvc_test_vocoder_layer: row_begin outside the buffer"); return BVC_EINVAL; }
             const AmpPair &ap = m->amp[stage][block][iteration];
             rows = L; ch = m->stage_ch[stage];
@@ -3109,7 +3150,8 @@ int bvc_test_vocoder_layer(const bvc_model *m, int32_t kind, int32_t stage, int3
         case 3:                                                              // activation_post -> conv_post -> tanh -> / div, first `length` samples
             rows = length < L ? length : L; ch = 1;
             if (rows <= 0) { set_error("bvc_test_vocoder_layer: length %lld", (long long)length); return BVC_EINVAL; }
-            rc = launch_conv_post(d_x, L, m->post_c, m->post_ks, m->post_w, m->post_b, m->post_a, m->post_ib, div, d_out, rows, B, s);
+            rc = launch_conv_post(d_x, L, m->post_c, m->post_ks, m->post_w, m->post_b, m->post_a, m->post_ib, div, d_out, rows, B, s,
+                                  nullptr, nullptr, m->post_up, m->post_down);
             break;
         default: set_error("bvc_test_vocoder_layer: kind %d", kind); return BVC_EINVAL;
     }

@@ -257,6 +257,7 @@ struct AmpArgs {
     long long t_origin;           // global time of buffer row 0 (streaming); 0 offline
     const int *row_age;           // streaming sessions whose rows start at different times: frames since row b's own start (capped where
     int age_rate;                 // no row of a window lies before it any more); row b's t_origin is t_origin + age_rate * row_age[b]
+    const float *fu1, *fd1, *fu2, *fd2;   // anti-aliased pair (amp_pair_kernel<..., AA = true>): the 12-tap up / down filters of S1 and S2
 };
 __device__ __forceinline__ long long amp_t_origin(const AmpArgs &a, int b) {
     return a.row_age ? a.t_origin + (long long)a.age_rate * a.row_age[b] : a.t_origin;
@@ -271,13 +272,93 @@ __device__ unsigned long long g_phase[16];
 #else
 #define PHASE(i)
 #endif
+// ------------------------------------------------------------------------------------------------
+// Anti-aliased activation, Activation1d (alias_free_torch/act.py:8-28) around SnakeBeta S, on rows parked in LDS:
+//     up[2t]   = 2 sum_k f[2k+1] x[c(t+2-k)],  up[2t+1] = 2 sum_k f[2k] x[c(t+3-k)]     k = 0..5, c = clamp to the signal [0, L-1]
+//     a[n]     = S(up[n])                                                                 n in [0, 2L)
+//     y[t]     = sum_j g[j] a[clamp(2t-5+j, 0, 2L-1)]                                     j = 0..11
+// (resample.py:10-33: replicate pad 5, conv_transpose1d stride 2, times 2, crop 15; filter.py:86-95: replicate pad (5, 6), conv1d
+// stride 2).  Two clamps: a position outside [0, 2L) takes a[0] / a[2L-1], not an up value of clamped x.  y[t] reads x[t-5 .. t+5].
+// src holds the raw rows [src_first, src_first + nsrc) of the signal (global row numbers; stride S floats, C channels), dst takes
+// y of the rows [dst_first, dst_first + ndst); rows before time 0 are written as zeros (the convs' causal padding follows the
+// activation).  The caller guarantees that src covers dst's rows -5 .. +5 as far as they lie inside the signal; rows of dst
+// behind the signal's end get finite values nobody reads.
+// A thread owns two channels and a run of consecutive rows and slides a window of six (a[2t], a[2t+1]) pairs along it, so every
+// S(up[n]) is evaluated once per run (plus six pairs of warm-up per run); the packed-fp32 forms carry both channels.
+template <int C>
+__device__ __forceinline__ void aa_rows(const float *src, int src_first, int nsrc, long long L, float *dst, int dst_first, int ndst,
+                                        int S, const float *act_a, const float *act_ib, const float *fu, const float *fd) {
+    constexpr int C2 = C / 2, NRUN = 256 / C2;
+    const int tid = threadIdx.x;
+    const int run = tid / C2, c = (tid - run * C2) * 2;
+    const int R = (ndst + NRUN - 1) / NRUN;
+    const int j0 = run * R, j1 = j0 + R < ndst ? j0 + R : ndst;
+    if (j0 >= j1) return;
+    const int last = L - 1 > 0x7FFFFFFFll ? 0x7FFFFFFF : (int)(L - 1);
+    const int glo = src_first > 0 ? src_first : 0;                                   // rows of the signal that src holds
+    const int ghi = src_first + nsrc - 1 < last ? src_first + nsrc - 1 : last;
+    const f32x2 aa = *reinterpret_cast<const f32x2 *>(act_a + c), bb = *reinterpret_cast<const f32x2 *>(act_ib + c);
+    float f[12], g[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { f[k] = fu[k]; g[k] = fd[k]; }                      // (uniform: scalar registers)
+    // the pair (a[2t], a[2t+1]) as the down filter sees it: t outside the signal takes the end value on both places
+    auto pair = [&](int t, f32x2 &ev, f32x2 &od) {
+        const int tc = t < 0 ? 0 : (t > last ? last : t);
+        f32x2 xr[7];                                                                   // x[c(tc-3)] .. x[c(tc+3)]
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            int q = tc - 3 + k;
+            q = q < glo ? glo : (q > ghi ? ghi : q);
+            xr[k] = *reinterpret_cast<const f32x2 *>(src + (q - src_first) * S + c);
+        }
+        f32x2 ue = splat2(f[1]) * xr[5], uo = splat2(f[0]) * xr[6];
+#pragma unroll
+        for (int k = 1; k < 6; ++k) {
+            ue = __builtin_elementwise_fma(splat2(f[2 * k + 1]), xr[5 - k], ue);
+            uo = __builtin_elementwise_fma(splat2(f[2 * k]), xr[6 - k], uo);
+        }
+        ev = snakebeta2(ue * splat2(2.0f), aa, bb);
+        od = snakebeta2(uo * splat2(2.0f), aa, bb);
+        if (t < 0) od = ev;
+        if (t > last) ev = od;
+    };
+    // window for output row t: pairs t-3 .. t+2 (pe / po[0..5]); pair t+3 arrives with the row
+    f32x2 pe[6], po[6];
+    const int tfirst = dst_first + j0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) pair(tfirst - 3 + k, pe[k], po[k]);
+#pragma unroll 1
+    for (int j = j0; j < j1; ++j) {
+        const int t = dst_first + j;
+        f32x2 ne, no;
+        pair(t + 3, ne, no);
+        f32x2 y = splat2(g[0]) * po[0];                                               // a[2t-5] = a[2(t-3)+1]
+#pragma unroll
+        for (int k = 1; k < 6; ++k) {
+            y = __builtin_elementwise_fma(splat2(g[2 * k - 1]), pe[k], y);
+            y = __builtin_elementwise_fma(splat2(g[2 * k]), po[k], y);
+        }
+        y = __builtin_elementwise_fma(splat2(g[11]), ne, y);                          // a[2t+6] = a[2(t+3)]
+        if (t < 0) y = splat2(0.0f);
+        *reinterpret_cast<float2 *>(dst + j * S + c) = make_float2(y[0], y[1]);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { pe[k] = pe[k + 1]; po[k] = po[k + 1]; }
+        pe[5] = ne; po[5] = no;
+    }
+}
+
 // CS: how many of the four waves lie along the COLUMN tiles (1, 2 or 4); the other 4 / CS lie along the rows.  A wave computes MT row
 // tiles x NT / CS column tiles, a workgroup (4 / CS) * MT * 16 rows.  CS = 1 re-reads every weight fragment in all four waves
 // (from L2: the weight set of a conv does not fit L1) and feeds MT MFMAs with it; with the waves along the columns a fragment is
 // read once per workgroup and feeds CS * MT MFMAs at the same rows per workgroup - the C = 64 stage (180 KB of weights per conv
 // at ks = 11) 2.63 -> 2.36 ms per step with CS = 4, MT = 8.  Streaming hops (a hop's one or two new frames are a handful of
 // rows: row-split tiles would mostly compute rows nobody reads) use CS = 4 with MT = 2.
-template <int C, int MT, int OCC, bool ALIAS, int CS = 1>
+// AA: both activations of the pair are anti-aliased (aa_rows).  conv1 then runs on 10 more rows - TT = TR - (ks-1) - 10 - and
+// its raw result goes through a second LDS region U behind the first: phase 0 parks the raw x rows [t0-(ks-1)(d+1)-10, t0+TT+10)
+// in U, A1 of them becomes the S1 tile, conv1 + bias goes back to U (rows [t0-(ks-1)-5, .. + TR)), A2 of those - clamped to the
+// signal's rows 0 and L-1 - becomes the S2 tile of the rows [t0-(ks-1), t0+TT); conv2 and the epilogues are the plain kernel's.
+// The S2 tile always re-uses the S1 tile's LDS (ALIAS is ignored).  Offline only: a filtered stage is not causal.
+template <int C, int MT, int OCC, bool ALIAS, int CS = 1, bool AA = false>
 __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
 #ifdef BVC_PHASE_PROBE
     unsigned long long last_ = __builtin_readcyclecounter();
@@ -296,7 +377,8 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, g = lane >> 4;
     const int ks = a.ks, dil = a.dil;
-    const int TT = TR - (ks - 1);                          // valid output rows of this workgroup
+    constexpr int AAH = AA ? 5 : 0;                        // rows an anti-aliased activation reads beyond its own, each side
+    const int TT = TR - (ks - 1) - 2 * AAH;                // valid output rows of this workgroup
     // Workgroups are dealt round-robin to the 8 XCDs; neighbouring tiles share their halo rows, so each
     // XCD takes a contiguous run of tiles (the halo then hits in that XCD's L2).
     const unsigned nwg = gridDim.x, per = (nwg + 7u) >> 3;
@@ -307,14 +389,41 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
     const int halo1 = (ks - 1) * dil;
     const int rows1 = TR + halo1;                          // S1(x) rows [t0-(ks-1)-halo1, t0-(ks-1)+TR)
     float *t1 = lds;
-    float *t2 = ALIAS ? lds : lds + rows1 * S;             // S2(u) rows [t0-(ks-1), t0-(ks-1)+TR) (+ ks-1 spare): takes over
+    float *t2 = (ALIAS || AA) ? lds : lds + rows1 * S;     // S2(u) rows [t0-(ks-1), t0-(ks-1)+TR) (+ ks-1 spare): takes over
                                                            // the S1(x) tile once conv1 has consumed it (halves the LDS)
     const float *xb = a.x + (long long)b * a.bs;
-    const long long tbase = t0 - (ks - 1);                 // global row of local row 0 of phase 2 / t2
+    const long long tbase = t0 - (ks - 1) - AAH;           // global row of local row 0 of phase 2 (conv1's output rows)
+    const int rowsA = rows1 > TR + ks - 1 ? rows1 : TR + ks - 1;
+    float *traw = lds + rowsA * S;                         // AA: region U, rows1 + 10 rows (raw x, then conv1's raw result)
+    (void)traw;
 
     // ---- phase 1: activated input span.  All global loads of the span are issued before the first
     // SnakeBeta is evaluated (one exposed memory round trip per workgroup instead of one per row group).
-    {
+    if constexpr (AA) {
+        constexpr int NLD = ((TR + 10 * 5 + 2 * AAH) * C4 + 255) / 256;
+        f32x4 v[NLD];
+        const int total = (rows1 + 2 * AAH) * C4;
+        const __amdgpu_buffer_rsrc_t rs = rows_rsrc(xb, a.L, C);       // rows outside the signal read as zeros; aa_rows never reads them
+        const int xfirst = (int)(tbase - halo1) - AAH;
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int idx = tid + i * 256;
+            const int row = idx / C4, c4 = idx - row * C4;
+            v[i] = rows_load4(rs, xfirst + row, C, c4 * 4);
+        }
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int idx = tid + i * 256;
+            if (idx < total) {
+                const int row = idx / C4, c4 = idx - row * C4;
+                float2 *dst = reinterpret_cast<float2 *>(traw + row * S + c4 * 4);
+                dst[0] = make_float2(v[i][0], v[i][1]);
+                dst[1] = make_float2(v[i][2], v[i][3]);
+            }
+        }
+        __syncthreads();
+        aa_rows<C>(traw, xfirst, rows1 + 2 * AAH, a.L, t1, xfirst + AAH, rows1, S, a.a1, a.ib1, a.fu1, a.fd1);
+    } else {
         constexpr int NLD = ((TR + 10 * 5) * C4 + 255) / 256;       // ks <= 11, dil <= 5
         // The loads are UNCONDITIONAL (rows outside the signal read a clamped row and are zeroed afterwards): a load under a branch
         // made hipcc wait `vmcnt(0)` behind every other one - five exposed round trips per tile at C = 32 instead of one.
@@ -476,11 +585,29 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
     // ---- phase 2: u = conv1(S1(x)) ; t2 = S2(u + b1), zero before the start of the signal
     conv(t1, dil, a.w1);
     PHASE(1);
-    if (ALIAS) __syncthreads();                            // every wave is done with S1(x): its LDS becomes t2
-    for (int idx = tid; idx < (ks - 1) * S; idx += 256) t2[TR * S + idx] = 0.0f;    // spare rows read by discarded outputs
+    if (ALIAS || AA) __syncthreads();                      // every wave is done with S1(x): its LDS becomes t2
     // local rows before `zrow` lie before the start of the signal: zero there (the reference pads AFTER the activation)
     const long long zr64 = -(tbase + amp_t_origin(a, b));
     const int zrow = zr64 <= 0 ? 0 : (zr64 > TR ? TR : (int)zr64);
+    if constexpr (AA) {
+        // conv1 + bias, raw, to U (the raw x rows there were consumed before conv1 began); then A2 of U's rows, clamped to the
+        // signal, is the S2 tile of the TR - 10 rows from t0 - (ks-1) on; behind them zeros up to row TR + ks - 1 (read by discarded outputs)
+#pragma unroll
+        for (int n = 0; n < NTL; ++n) {
+            const int col = (nt0 + n) * 16 + r;
+            if (col < C) {
+                const float bias = a.b1[col];
+#pragma unroll
+                for (int i = 0; i < MT; ++i)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) traw[(mbase + i * 16 + g * 4 + e) * S + col] = acc[i][n][e] + bias;
+            }
+        }
+        for (int idx = tid; idx < (ks - 1 + 2 * AAH) * S; idx += 256) t2[(TR - 2 * AAH) * S + idx] = 0.0f;
+        __syncthreads();
+        aa_rows<C>(traw, (int)tbase, TR, a.L, t2, (int)tbase + AAH, TR - 2 * AAH, S, a.a2, a.ib2, a.fu2, a.fd2);
+    } else {
+    for (int idx = tid; idx < (ks - 1) * S; idx += 256) t2[TR * S + idx] = 0.0f;    // spare rows read by discarded outputs
     if constexpr (C == 8) {
         // Only 8 of the tile's 16 columns exist: lanes r >= 8 hold padding.  They take over rows g*4+2, g*4+3 of
         // column r-8 from their neighbour 8 lanes down (DPP row_shr:8), so that every lane evaluates ONE SnakeBeta
@@ -523,6 +650,8 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
         if (zrow > 0) s2_tile(std::true_type());
         else          s2_tile(std::false_type());
     }
+    }
+    (void)zrow;
     __syncthreads();
     PHASE(2);
 
@@ -548,7 +677,7 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
     PHASE(3);
     conv(t2, 1, a.w2);
     PHASE(4);
-    if (ALIAS) __syncthreads();                            // t2 is dead: the same LDS now stages the output tile
+    if (ALIAS || AA) __syncthreads();                      // t2 is dead: the same LDS now stages the output tile
 #pragma unroll
     for (int n = 0; n < NTL; ++n) {
         const int col = (nt0 + n) * 16 + r;
@@ -1086,15 +1215,18 @@ static bool amp16_slots_all() {
            amp16_slots<11, 5, (MT > 4 ? 4 : MT), Amp16Occ<11, MT>::V>() > 0;
 }
 
-template <int C, int MT, int OCC, bool ALIAS, int CS = 1>
+template <int C, int MT, int OCC, bool ALIAS, int CS = 1, bool AA = false>
 static int launch_amp_t(AmpArgs a, int B, hipStream_t s) {
     constexpr int TR = (4 / CS) * MT * 16;
-    const int TT = TR - (a.ks - 1);
+    const int TT = TR - (a.ks - 1) - (AA ? 10 : 0);
     a.tiles_per_batch = (int)((a.L - a.row_begin + TT - 1) / TT);
     if (a.tiles_per_batch <= 0) return BVC_OK;
     a.tpb_magic = tpb_magic_of((unsigned)a.tiles_per_batch);
     if ((unsigned long long)a.tiles_per_batch * a.tiles_per_batch * (unsigned long long)B >= 0x100000000ull) { set_error("vocoder: tile count beyond the reciprocal's range"); return BVC_EINVAL; }
-    const size_t lds = (size_t)((TR + (a.ks - 1) * a.dil) + (ALIAS ? 0 : TR + (a.ks - 1))) * (C + 2) * sizeof(float);
+    const int rows1 = TR + (a.ks - 1) * a.dil;
+    const size_t lds = AA ? (size_t)((rows1 > TR + a.ks - 1 ? rows1 : TR + a.ks - 1) + rows1 + 10) * (C + 2) * sizeof(float)
+                          : (size_t)(rows1 + (ALIAS ? 0 : TR + (a.ks - 1))) * (C + 2) * sizeof(float);
+    if (AA && a.L + TR > 0x7FFFFFFFll) { set_error("amp_pair: %lld rows are beyond the anti-aliased kernel's row index", a.L); return BVC_EINVAL; }
     if (lds > 160 * 1024 || TT <= 0) { set_error("amp_pair tile needs %zu B of LDS", lds); return BVC_EINVAL; }
     ProbeScope probe(PK_CONV, s);
     // grid rounded up to a multiple of 8 so that the XCD-contiguous renumbering covers every tile exactly once
@@ -1102,10 +1234,10 @@ static int launch_amp_t(AmpArgs a, int B, hipStream_t s) {
     a.ntile = ntile;
     {
         static bool attr = false;
-        if (!attr) { BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(amp_pair_kernel<C, MT, OCC, ALIAS, CS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; }
+        if (!attr) { BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(amp_pair_kernel<C, MT, OCC, ALIAS, CS, AA>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; }
     }
     g_last_amp_launch = {(long long)ntile, (long long)((ntile + 7u) & ~7u), TT};
-    hipLaunchKernelGGL((amp_pair_kernel<C, MT, OCC, ALIAS, CS>), dim3((ntile + 7u) & ~7u), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((amp_pair_kernel<C, MT, OCC, ALIAS, CS, AA>), dim3((ntile + 7u) & ~7u), dim3(256), lds, s, a);
     BVC_HIP_TRY(hipGetLastError());
     return BVC_OK;
 }
@@ -1146,6 +1278,20 @@ int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, lo
     a.t_origin = win ? win->t_origin : 0;
     a.row_age = win ? win->row_age : nullptr;
     a.age_rate = win ? win->age_rate : 0;
+    a.fu1 = c1.aa_up; a.fd1 = c1.aa_down; a.fu2 = c2.aa_up; a.fd2 = c2.aa_down;
+    if (c1.aa_up || c2.aa_up) {
+        // anti-aliased pair: the generic kernel with the filters around both activations, one tile shape per stage - the tallest whose
+        // two LDS regions leave the stage's workgroups per CU (C = 64: 96 rows, 78 KiB at ks = 11; C = 32 / 16: 128 rows; C = 8: 256)
+        if (!c1.aa_up || !c1.aa_down || !c2.aa_up || !c2.aa_down) { set_error("amp_pair: a pair is filtered on both activations or on none"); return BVC_EINVAL; }
+        if (win) { set_error("amp_pair: an anti-aliased pair looks ahead and has no streaming window"); return BVC_EINVAL; }
+        switch (c1.cin) {
+            case 64: return launch_amp_t<64, 6, 2, true, 4, true>(a, B, s);
+            case 32: return launch_amp_t<32, 2, 3, true, 1, true>(a, B, s);
+            case 16: return launch_amp_t<16, 2, 4, true, 1, true>(a, B, s);
+            case 8:  return launch_amp_t<8, 4, 4, true, 1, true>(a, B, s);
+            default: set_error("amp_pair: unsupported channel count %d", c1.cin); return BVC_EINVAL;
+        }
+    }
     // streaming hops compute a few new rows behind a 64-row history: the 128 / 256-row tiles of the offline sweep would spend
     // most of their MFMAs on rows nobody reads, so short windows take the smallest tile (4 waves x 16 rows)
     const long long new_rows = L - a.row_begin;
@@ -1335,12 +1481,54 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float *__restrict_
     wav[(long long)b * n_out + t] = tanhf(acc + bias[0]) / div;
 }
 
+// The same with an anti-aliased activation_post (antialias_post): the raw rows [t0 - (ks-1) - 5, t0 + 256 + 5) are parked first and
+// aa_rows turns them into the tile the conv reads (rows before time 0 zero, the signal's ends replicated).
+template <int C>
+__global__ __launch_bounds__(256) void conv_post_aa_kernel(const float *__restrict__ in, long long Lin, int ks,
+                                                           const float *__restrict__ w, const float *__restrict__ bias,
+                                                           const float *__restrict__ act_a, const float *__restrict__ act_ib,
+                                                           const float *__restrict__ fu, const float *__restrict__ fd, float div,
+                                                           float *__restrict__ wav, long long n_out, int tiles_per_batch) {
+    extern __shared__ __attribute__((aligned(16))) float tile[];     // [(256 + ks-1)][C] activated, then [(256 + ks-1 + 10)][C] raw
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / tiles_per_batch;
+    const long long t0 = (long long)(blockIdx.x % tiles_per_batch) * 256;
+    const int halo = ks - 1, nact = 256 + halo, nraw = nact + 10;
+    float *raw = tile + nact * C;
+    const float *inb = in + (long long)b * Lin * C;
+    const int first = (int)(t0 - halo) - 5;
+    for (int idx = tid; idx < nraw * C; idx += 256) {
+        const long long tg = first + idx / C;
+        raw[idx] = (tg >= 0 && tg < Lin) ? inb[tg * C + (idx % C)] : 0.0f;
+    }
+    __syncthreads();
+    aa_rows<C>(raw, first, nraw, Lin, tile, first + 5, nact, C, act_a, act_ib, fu, fd);
+    __syncthreads();
+    const long long t = t0 + tid;
+    if (t >= n_out) return;
+    float acc = 0.0f;
+    for (int j = 0; j < ks; ++j)
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc = fmaf(w[c * ks + j], tile[(tid + j) * C + c], acc);
+    wav[(long long)b * n_out + t] = tanhf(acc + bias[0]) / div;
+}
+
 int launch_conv_post(const float *in, long long Lin, int C, int ks, const float *w, const float *bias,
                      const float *act_a, const float *act_ib, float div, float *wav, long long n_out, int B,
-                     hipStream_t s, const ConvWindow *win, const long long *n_rows) {
+                     hipStream_t s, const ConvWindow *win, const long long *n_rows, const float *aa_up, const float *aa_down) {
     if (B <= 0 || n_out <= 0) return BVC_OK;
     if (C != 8) { set_error("conv_post: unsupported channel count %d", C); return BVC_EINVAL; }
     const int tiles = (int)((n_out + 255) / 256);
+    if (aa_up || aa_down) {
+        if (!aa_up || !aa_down || win || n_rows) { set_error("conv_post: an anti-aliased activation_post has no streaming window and no mixed lengths"); return BVC_EINVAL; }
+        if (Lin + 512 > 0x7FFFFFFFll) { set_error("conv_post: %lld rows are beyond the anti-aliased kernel's row index", Lin); return BVC_EINVAL; }
+        const size_t lds_aa = (size_t)(2 * (256 + ks - 1) + 10) * C * sizeof(float);
+        ProbeScope probe(PK_POST, s);
+        hipLaunchKernelGGL(conv_post_aa_kernel<8>, dim3((unsigned)(tiles * (long long)B)), dim3(256), lds_aa, s, in, Lin, ks,
+                           w, bias, act_a, act_ib, aa_up, aa_down, div, wav, n_out, tiles);
+        BVC_HIP_TRY(hipGetLastError());
+        return BVC_OK;
+    }
     const size_t lds = (size_t)(256 + ks - 1) * C * sizeof(float);
     ProbeScope probe(PK_POST, s);
     hipLaunchKernelGGL(conv_post_kernel<8>, dim3((unsigned)(tiles * (long long)B)), dim3(256), lds, s, in, Lin, ks,

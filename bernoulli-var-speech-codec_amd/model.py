@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from . import _abi, ragged, weights
-from .config import DEFAULT_CONFIG, load_config
+from .config import DEFAULT_CONFIG, NOT_CAUSAL, is_antialiased, load_config
 
 _ROOT = os.path.abspath(os.path.dirname(__file__))
 default_config = DEFAULT_CONFIG
@@ -485,6 +485,8 @@ class BVRNNCodecModel(_OnDevice):
         if return_codes:
             raise ValueError("decode: return_codes belongs to concealment (pass lost)")
         if frames is not None or ragged.per_row(length, codes.shape[0], "length") is not None:
+            if is_antialiased(self.conf):
+                raise ValueError("decode: " + NOT_CAUSAL)
             return self._decode_ragged(codes, length, frames)
         eng = self.engine(codes)
         out_dev = codes.device
@@ -602,6 +604,14 @@ class BVRNNCodecModel(_OnDevice):
         frames = [int(c.shape[0]) for c in codes_list]
         eng = self.engine(codes_list[0])
         out_dev = codes_list[0].device
+        if is_antialiased(self.conf):                     # equal-length items only: plain batches of at most max_batch rows
+            if len(set(frames)) > 1 or len(set(int(n) for n in lens)) > 1:
+                raise ValueError("decode_many: " + NOT_CAUSAL)
+            done = []
+            for a in range(0, len(codes_list), max(int(max_batch), 1)):
+                c = torch.stack([_prep(ci, eng.device) for ci in codes_list[a:a + max(int(max_batch), 1)]])
+                done += list(self.decode(c, int(lens[0])).to(out_dev))
+            return done
         perm, bounds, inv = ragged.batch_plan(frames, max_batch)
         done = []
         for a, e in bounds:

@@ -27,6 +27,7 @@ import math
 import torch
 
 from . import _abi
+from .config import NOT_CAUSAL, is_antialiased
 from .model import SCALING
 
 CONTEXT_FRAMES = 26      # ceil(6 + 1 + 15 + 1/8 + 120/64 + 1/64 + 120/128 + 1/128 + 120/256 + 6/256)
@@ -90,6 +91,8 @@ class VocoderStream:
     """Handle of the library's incremental generator state for `batch` parallel streams."""
 
     def __init__(self, engine, batch, max_frames_per_push):
+        if is_antialiased(engine.conf):
+            raise ValueError("VocoderStream: " + NOT_CAUSAL)
         self.eng = engine
         self.B = batch
         self.kmax = max_frames_per_push
@@ -130,6 +133,8 @@ class VocoderStream:
 
 class StreamingDecoder:
     def __init__(self, model, batch, device=None, incremental=True, max_frames_per_push=8):
+        if is_antialiased(model.conf):                         # (the context scheme counts on the same causality)
+            raise ValueError("StreamingDecoder: " + NOT_CAUSAL)
         self.m = model
         self.B = batch
         eng = model.engine(None if device is None else torch.empty(0, device=device))
@@ -264,6 +269,8 @@ class StreamingCodec:
             raise ValueError(f"conceal must be one of {sorted(self.CONCEAL)}")
         if conceal != "none" and direction != "recv":
             raise ValueError("conceal: only a receive session has lost frames to conceal")
+        if direction != "send" and is_antialiased(model.conf):
+            raise ValueError("StreamingCodec: " + NOT_CAUSAL)
         self.direction = direction
         eng = model.engine(None if device is None else torch.empty(0, device=device))
         if direction == "recv":

@@ -71,10 +71,34 @@ def bvrnn_state_dict(conf, seed=1234, mel_stats=None, gains=None):
     return sd
 
 
+def kaiser_sinc_filter12():
+    """The 12-tap Kaiser-windowed sinc low-pass both halves of ``Activation1d`` register (cutoff 0.25, half width 0.3:
+    alias_free_torch/filter.py:30-60 as resample.py:19-21,44-47 call it), shape (1, 1, 12) like the buffer."""
+    half = 6
+    A = 2.285 * (half - 1) * np.pi * (4 * 0.3) + 7.95
+    beta = 0.1102 * (A - 8.7) if A > 50.0 else (0.5842 * (A - 21.0) ** 0.4 + 0.07886 * (A - 21.0) if A >= 21.0 else 0.0)
+    window = torch.kaiser_window(12, beta=beta, periodic=False)
+    time = torch.arange(-half, half) + 0.5
+    f = 2 * 0.25 * window * torch.sinc(2 * 0.25 * time)
+    return (f / f.sum()).view(1, 1, 12)
+
+
 def generator_state_dict(conf, seed=4321):
+    """Key layout of the config it is given: an anti-aliased activation (``layers_antialias`` / ``antialias_post``) carries its
+    SnakeBeta under ``.act.`` and the two filter buffers; alpha / beta are the same draws at the same place of the stream."""
+    from .config import antialias_flags
     rng = np.random.default_rng(seed)
     v = conf["vocoder_config"]
     sd = collections.OrderedDict()
+    stages_aa, post_aa = antialias_flags(conf)
+
+    def act(name, ch, filtered):
+        mid = ".act" if filtered else ""
+        sd[f"{name}{mid}.alpha"] = _n(rng, (ch,), 0.3)
+        sd[f"{name}{mid}.beta"] = _n(rng, (ch,), 0.3)
+        if filtered:
+            sd[f"{name}.upsample.filter"] = kaiser_sinc_filter12()
+            sd[f"{name}.downsample.lowpass.filter"] = kaiser_sinc_filter12()
 
     def conv(name, cout, cin, k, gain):
         sd[f"{name}.bias"] = _u(rng, (cout,), 0.1)
@@ -106,10 +130,8 @@ def generator_state_dict(conf, seed=4321):
             for m in range(3):
                 conv(f"{pre}.convs2.{m}", ch, ch, ks, 0.35)
             for a in range(6):
-                sd[f"{pre}.activations.{a}.alpha"] = _n(rng, (ch,), 0.3)
-                sd[f"{pre}.activations.{a}.beta"] = _n(rng, (ch,), 0.3)
-    sd["activation_post.alpha"] = _n(rng, (ch,), 0.3)
-    sd["activation_post.beta"] = _n(rng, (ch,), 0.3)
+                act(f"{pre}.activations.{a}", ch, stages_aa[i])
+    act("activation_post", ch, post_aa)
     conv("conv_post", 1, ch, 7, 0.25)
     return sd
 

@@ -13,6 +13,7 @@ reference convolves with.  The re-layout into MFMA fragment order happens inside
 import torch
 
 from . import melbank
+from .config import antialias_flags
 
 
 def expected_bvrnn_keys(conf):
@@ -32,6 +33,14 @@ def expected_generator_keys(conf):
     def wn(name):
         keys.extend([f"{name}.bias", f"{name}.weight_g", f"{name}.weight_v"])
 
+    def act(name, filtered):
+        # an Activation1d registers its two 12-tap filters as buffers beside the wrapped SnakeBeta (alias_free_torch/act.py:18-20)
+        if filtered:
+            keys.extend([f"{name}.act.alpha", f"{name}.act.beta", f"{name}.upsample.filter", f"{name}.downsample.lowpass.filter"])
+        else:
+            keys.extend([f"{name}.alpha", f"{name}.beta"])
+
+    stages_aa, post_aa = antialias_flags(conf)
     wn("conv_pre")
     nk = len(v["resblock_kernel_sizes"])
     for i in range(len(v["upsample_rates"])):
@@ -42,8 +51,8 @@ def expected_generator_keys(conf):
         for m in range(3):
             wn(f"resblocks.{n}.convs2.{m}")
         for a in range(6):
-            keys += [f"resblocks.{n}.activations.{a}.alpha", f"resblocks.{n}.activations.{a}.beta"]
-    keys += ["activation_post.alpha", "activation_post.beta"]
+            act(f"resblocks.{n}.activations.{a}", stages_aa[n // nk])
+    act("activation_post", post_aa)
     wn("conv_post")
     return keys
 
@@ -81,6 +90,10 @@ def host_tensors(conf, vrnn_sd, gen_sd):
             continue
         else:
             out[k] = t
+    stages_aa, post_aa = antialias_flags(conf)
+    if any(stages_aa) or post_aa:                           # the flags travel as tensors: bvc_config keeps its layout
+        out["layers_antialias"] = torch.tensor([float(f) for f in stages_aa])
+        out["antialias_post"] = torch.tensor([float(post_aa)])
     out["mel_basis"] = torch.from_numpy(melbank.slaney_mel_basis(conf["fs"], conf["winsize"], conf["num_mels"],
                                                                 conf["fmin"], conf["fmax"]))
     out["hann_window"] = torch.hann_window(conf["winsize"], dtype=torch.float32)     # meldataset.py:70

@@ -89,7 +89,19 @@ typedef struct bvc_config {
  * "rnn.bias_hh_l0"; generator (models.py:132-205) with weight-norm ALREADY FOLDED by the caller:
  * "conv_pre.weight","conv_pre.bias","ups.0.1.weight",...,"resblocks.0.convs1.0.weight",...,
  * "resblocks.0.activations.0.alpha",...,"activation_post.alpha","conv_post.weight",...;
- * plus "mel_basis" (num_mels x (n_fft/2+1), the librosa.filters.mel matrix of meldataset.py:68). */
+ * plus "mel_basis" (num_mels x (n_fft/2+1), the librosa.filters.mel matrix of meldataset.py:68).
+ *
+ * Anti-aliased activations (vocoder_config.layers_antialias / antialias_post, models.py:69-93,172-192): two optional tensors say where
+ * the generator wraps its SnakeBeta in Activation1d (alias_free_torch/act.py:8-28) - "layers_antialias", n_up values, non-zero = every
+ * activation of that stage's AMP blocks; "antialias_post", one value, activation_post.  bvc_config keeps its layout.  A flagged
+ * activation NAME ("resblocks.K.activations.J", "activation_post") is read from the reference's keys of that module: "NAME.act.alpha",
+ * "NAME.act.beta", "NAME.upsample.filter", "NAME.downsample.lowpass.filter" (12 values each, the ones the reference convolves with);
+ * an unflagged one from "NAME.alpha" / "NAME.beta".  Tensors of the other layout are BVC_EMISSING either way.
+ * bvc_bigvgan, bvc_decode, bvc_forward, bvc_decode_conceal and bvc_test_vocoder_layer / _tap (window == 0) work unchanged for such a
+ * model.  What counts on the generator being causal returns BVC_EINVAL for it - bvc_vocoder_stream_create, bvc_stream_codec_create
+ * (bvc_stream_codec_create_dir unless BVC_STREAM_SEND), bvc_decode_ragged, bvc_test_vocoder_layer with window != 0: a filtered
+ * activation reads 5 rows ahead, an AMP block 30, so every output sample depends on later frames - about 53 ms of look-ahead when all
+ * four stages and the post activation are filtered (30 rows at each of 8 / 64 / 128 / 256 rows per frame, and 5 samples). */
 typedef struct bvc_tensor {
     const char  *name;
     const float *h_data;
