@@ -1,0 +1,232 @@
+// Host side of libbvcodec_hip.so, shared by its sources model.hip, recurrence.hip, generator.hip, stream_codec.hip and
+// bvcodec_abi.hip: the model, the workspace layout, the GEMM parameter helpers, the drivers of the offline paths and the state that
+// crosses a file boundary.  Host only.  What more than one source uses lives in namespace bvc, next to the launchers of
+// bvc_internal.h; everything else is local to its file.
+#pragma once
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
+#include <list>
+#include <mutex>
+
+#include "bvc_internal.h"
+
+namespace bvc {
+
+struct Linear { const float *w = nullptr, *wp = nullptr, *b = nullptr; int in = 0, out = 0; };   // w natural, wp fragment-packed
+
+struct AmpPair { ConvLayer c1, c2; };
+
+// ---- incremental (history-buffer) vocoder for streaming --------------------------------------------
+// Every activation tensor of the generator is kept as a (B, H + kmax*rate, C) buffer whose first H rows
+// are the last H rows of the previous hop; a hop computes only the rows of the new frames and then
+// rotates the last H rows to the front of the twin buffer (ping-pong: source and destination overlap
+// when fewer than H rows are new).
+struct StreamTensor { float *buf[2]; int C, H, rate; long long rows; };
+struct RotEntry { float *buf[2]; long long bs; int C, H, rate, pad_; };
+
+}  // namespace bvc
+
+struct bvc_model {
+    bvc_config cfg;
+    std::vector<void *> allocs;
+    // front-end
+    bvc::FrontendTables fe;
+    // BVRNN
+    const float *mean_mel = nullptr, *std_mel = nullptr;
+    bvc::Linear phi_x[3], phi_z[3], enc[3], dec[4];
+    bvc::Linear prior[3];            // only used by bvc_bvrnn_forward; optional (has_prior)
+    bool has_prior = false;
+    const float *w_ih = nullptr, *w_hh = nullptr, *b_ih = nullptr, *b_hh = nullptr;     // w_*: fragment-packed
+    const float *w_ih_il = nullptr, *w_hh_il = nullptr;   // gate-interleaved packing (pack_gru_interleaved): the GRU launches
+    const float *w_ih_nat = nullptr;      // natural [3H][2H] copy: the phi_z half is applied to all frames at once in decode
+    // vocoder
+    bvc::ConvLayer conv_pre;
+    std::vector<bvc::ConvLayer> ups;                       // n_up
+    std::vector<std::vector<std::vector<bvc::AmpPair>>> amp;   // [stage][kernel][dilation]
+    std::vector<int> stage_ch;                        // channels after each upsampler
+    const float *post_a = nullptr, *post_ib = nullptr, *post_w = nullptr, *post_b = nullptr;
+    const float *post_up = nullptr, *post_down = nullptr;   // antialias_post: activation_post's two filters
+    int post_c = 0, post_ks = 7;
+    bool antialiased = false;   // some stage, or activation_post, has anti-aliased activations: the generator is not causal
+    // captured recurrent steps (hipGraph), keyed by (kind, batch, workspace)
+    // (launch-per-layer schedule only) most recently used first; `idle` is recorded behind the entry's last replay, so an
+    // entry is only destroyed once the GPU is done with it
+    struct StepGraph { int kind; int B; void *ws; void *probe; hipGraphExec_t exec1, execN; hipEvent_t idle; };
+    mutable std::list<StepGraph> graphs;
+    mutable std::mutex graph_mu;
+    mutable hipStream_t cap_stream = nullptr, side_stream = nullptr;
+    mutable std::vector<hipEvent_t> cap_events;
+    bool side_branch = false;   // measured SLOWER on MI355X (cross-branch graph dependencies + no spare L2->CU bandwidth): opt-in
+    bool use_graph = true;
+    bool fused_amp = true;
+    unsigned amp_kernels = bvc::AMPK_ALL;   // stage-specific generator kernels in use (options vocoder_full_tiles / vocoder_c16_kernel)
+    bool precomp_pz = true;     // decode: the phi_z halves of dec.0 and of the GRU input product are batched over all frames
+    int mtw = 1;                // 16-row tiles per workgroup in the recurrent kernels (BVC_MTW = 1 | 2 | 4)
+    // persistent recurrence (k_flow.hip): hop tables of encode / decode, resident in device memory
+    // recurrence schedule: RS_PERSISTENT one launch per call (k_flow.hip), RS_LAYERS one launch per layer (hipGraph replay),
+    // RS_AUTO (default) persistent while calls come one at a time, layers while calls of several streams overlap
+    int recurrence = 2;         // BVC_RECURRENCE=persistent|layers|auto, bvc_model_set_option("recurrence")
+    mutable std::atomic<bool> flow_resident{false}; // the residency census found a full persistent grid co-resident on this device
+    mutable std::atomic<bool> census_due{false};    // a recurrence time-out was seen: the census runs again before the next persistent launch (another
+                                        // tenant may have arrived after bvc_model_create: the model then moves to the layer schedule)
+    mutable hipStream_t census_stream = nullptr;
+    mutable unsigned *census_ctr = nullptr;
+    int flow_perh = 0;          // k-blocks per wave of an h_dim-sized segment (0: h_dim not supported by the persistent kernel)
+    // sticky status word of the persistent kernels, in host-mapped pinned memory: a kernel whose wait timed out stores its
+    // code there; every compute entry point reads it WITHOUT synchronising (h_status) and reports BVC_ETIMEOUT once
+    volatile unsigned *h_status = nullptr;
+    unsigned *d_status = nullptr;       // device address of the same word
+    int cu_count = 0;                   // compute units of the device: a persistent launch needs one per workgroup
+    unsigned flow_spin_limit = 4000000u;   // polls before a wait gives up (> 1 s: only a workgroup that never became resident gets there)
+    int flow_debug_withhold = 0;        // tests only: workgroup 0 of a persistent launch returns at once (its peers time out)
+    int flow_debug_nofill = 0;          // tests only: no filler quanta (the plain layer program)
+    // decode_fold / encode_fold (default 1): the persistent kernels run phi_x.0(norm(dec.6(u))) - three maps without a non-linearity
+    // between them (bvrnn.py:80, :204 / :226) - as the one affine map px0_dec3 (folded in float64 at model creation): one wide layer
+    // instead of two narrow hops per frame.  Decode computes dec.6 itself, the decoder's output, as one batched GEMM behind the
+    // launch; encode does not need it (BVRNN.encode returns codes and states only).  In encode the folded layer feeds the next
+    // state and with it the next codes: same function, another rounding (like another order of summation) - every golden and the
+    // full-size parity runs give the same bits and the same largest probability deviation (1.2e-7) with and without it.
+    bvc::Linear px0_dec3{};
+    int decode_fold = 1;
+    int encode_fold = 1;
+
+    ~bvc_model() {
+        for (auto &g : graphs) { (void)hipGraphExecDestroy(g.exec1); (void)hipGraphExecDestroy(g.execN); if (g.idle) (void)hipEventDestroy(g.idle); }
+        if (census_stream) (void)hipStreamDestroy(census_stream);
+        if (census_ctr) (void)hipFree(census_ctr);
+        if (cap_stream) (void)hipStreamDestroy(cap_stream);
+        if (side_stream) (void)hipStreamDestroy(side_stream);
+        for (auto e : cap_events) (void)hipEventDestroy(e);
+        if (h_status) (void)hipHostFree(const_cast<unsigned *>(h_status));
+        for (void *p : allocs) (void)hipFree(p);
+    }
+};
+
+struct bvc_vocoder_stream {
+    const bvc_model *m = nullptr;
+    int B = 0, kmax = 0, parity = 0;
+    // slide: ONE buffer per tensor with room for cap_frames frames; the window of a hop starts `cursor` frames into it and the history is
+    // moved back to the front only when the room is used up (every cap_frames / kmax - 1 hops at least) instead of after every hop.  The
+    // addresses of a hop then change from hop to hop: not for a hop that is replayed from a graph (bvc_stream_codec's eager ticks only).
+    bool slide = false;
+    int cursor = 0, cap_frames = 0;
+    int64_t frames = 0;
+    float *pool = nullptr;
+    size_t pool_floats = 0;
+    bvc::RotEntry *d_tab = nullptr;
+    int n_ten = 0, max_hc4 = 0;
+    // rows that start at different times (bvc_stream_codec's slots): frames since each row's own start, capped at STREAM_WARM_FRAMES,
+    // in device memory owned by the session (nullptr: every row started with the state, `frames` decides)
+    const int *d_age = nullptr;
+    bvc::StreamTensor mel, y0;
+    std::vector<bvc::StreamTensor> X, XS;                  // per stage
+    std::vector<bvc::StreamTensor> P, Q;                   // per (stage, AMP block): each block's intermediates keep their own history
+    ~bvc_vocoder_stream() {
+        if (pool) (void)hipFree(pool);
+        if (d_tab) (void)hipFree(d_tab);
+    }
+};
+
+namespace bvc {
+
+// ---- state shared between the sources ---------------------------------------------------------------
+extern thread_local bool g_capturing;     // no event probes while THIS thread captures a stream (captures are thread-local)
+extern thread_local bool g_stream_tick;   // inside bvc_stream_codec_tick: a launch-per-layer recurrence is launched eagerly (the tick itself is the graph)
+extern thread_local bool g_tick_flow;     // ... of a tick that is NOT a graph: its recurrences may take the persistent kernel
+extern std::mutex g_flow_mu;              // persistent launches and the residency census, one at a time per process (recurrence.hip)
+
+// in-kernel timestamp probes for the graph-replayed recurrent kernels (wall_clock64, 100 MHz)
+struct KProbe {
+    bool enabled = false;
+    unsigned long long *dev = nullptr;
+    size_t capacity = 0;                   // in u64
+    long long T = 0; int nodes = 0;        // geometry of the last probed call
+};
+extern KProbe g_kprobe;
+
+// ---- workspace layout ---------------------------------------------------------------------------
+struct Workspace {
+    // encode
+    float *yn, *pxA, *pxB, *pxC;
+    float *step[16];            // per-step [B, max(H, ...)] scratch vectors
+    float *hbuf;                // [2][B][H] GRU state ping-pong (parity of the frame counter)
+    float *part_i, *part_h, *part_d;   // side-branch partial sums: W_ih[:,H:] phi_z + b_ih, W_hh h + b_hh, dec.0[:,H:] h
+    CallDesc *desc;             // per-call dynamic state read by the captured step kernels
+    float *mel, *bits;          // facade-level buffers
+    float *part_dec0, *part_gru; // decode: dec.0[:, :H] phi_z + b (B,T,H) and W_ih[:, H:] phi_z + b_ih (B,T,3H), all frames
+    float *flow;                // persistent recurrence: FB_COUNT x 2 fragment-packed [mt16][dmax] activation buffers
+    size_t flow_slot;           // floats per flow buffer
+    FlowArgs *flow_args;        // device copy of the persistent kernel's arguments
+    // vocoder
+    float *y0, *X, *P, *Q, *U, *XS;
+    size_t total;
+};
+
+int64_t stage_len(const bvc_model *m, int64_t T, int stage);    // length after upsampler `stage`
+void carve(const bvc_model *m, int B, int64_t T, char *base, Workspace *w);
+int check_ws(const bvc_model *m, int B, int64_t T, void *d_ws, size_t ws_bytes, Workspace *w);
+int sticky_status(const bvc_model *m);
+int need_prior(const bvc_model *m, const char *fn);
+extern const char *const NOT_CAUSAL;
+int flow_census(const bvc_model *m);
+
+// ---- GEMM parameters ----------------------------------------------------------------------------
+inline GemmSeg mkseg(DynPtr x, const float *w, int wnb, int K, int grp) { return GemmSeg{w, wnb, K, x, grp, 0}; }
+
+// keeps nb_total consistent with the segments
+inline void finish(GemmParams &p) { p.nb_total = 0; for (int i = 0; i < p.nseg; ++i) p.nb_total += p.seg[i].K / 16; }
+
+// y = x W^T (+ bias) over K columns of a fragment-packed W with wnb k-blocks per row tile: a Linear, a slice of one, or of the GRU's matrices
+inline GemmParams mat_params(DynPtr x, const float *wp, int wnb, int K, int M, int N, const float *bias, DynPtr y) {
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.nseg = 1;
+    p.seg[0] = mkseg(x, wp, wnb, K, 0);
+    p.M = M; p.N = N;
+    p.bias0 = bias;
+    p.y = y;
+    finish(p);
+    return p;
+}
+inline GemmParams lin_params(const Linear &l, DynPtr x, int M, DynPtr y) { return mat_params(x, l.wp, l.in / 16, l.in, M, l.out, l.b, y); }
+// the part of a Linear over a concatenated input that starts kb0 k-blocks in: l.w[:, 16 kb0 : 16 kb0 + K] x, with or without l.b
+inline GemmParams half_params(const Linear &l, int kb0, DynPtr x, int K, int M, DynPtr y, bool bias) {
+    return mat_params(x, l.wp + (size_t)kb0 * 256, l.in / 16, K, M, l.out, bias ? l.b : nullptr, y);
+}
+
+// linear over the concatenation [x1 | x2] (torch.cat at bvrnn.py:189,202)
+inline GemmParams lin2_params(const Linear &l, DynPtr x1, int K1, DynPtr x2, int K2, int M, DynPtr y) {
+    GemmParams p = lin_params(l, x1, M, y);
+    p.nseg = 2;
+    p.seg[0] = mkseg(x1, l.wp, l.in / 16, K1, 0);
+    p.seg[1] = mkseg(x2, l.wp + (size_t)(K1 / 16) * 256, l.in / 16, K2, 0);
+    finish(p);
+    return p;
+}
+
+// ---- schedules and drivers ----------------------------------------------------------------------
+enum { RS_PERSISTENT = 0, RS_LAYERS = 1, RS_AUTO = 2 };
+inline int flow_grid_tiles(const bvc_model *m) {          // feature tiles covered by a persistent grid (rounded up to 8: one per XCD)
+    const int H = m->cfg.h_dim, X = m->cfg.num_mels, Z = m->cfg.z_dim;
+    return ((H > X ? (H > Z ? H : Z) : (X > Z ? X : Z)) / 16 + 7) / 8 * 8;
+}
+int flow_chains_static(const bvc_model *m, int B);      // 0: not usable; else utterance groups per workgroup
+
+int run_encode(const bvc_model *m, const Workspace &w, void *ws_base, const float *d_mel, const float *d_bits, const float *d_h0, int B,
+               int64_t T, float *d_codes, float *d_all_h, float *d_hT, float *d_prob, hipStream_t s, float *d_melhat = nullptr);
+int run_decode(const bvc_model *m, const Workspace &w, void *ws_base, const float *d_codes, const float *d_h0, int B, int64_t T,
+               float *d_mel, float *d_hT, hipStream_t s);
+int run_decode_conceal(const bvc_model *m, const Workspace &w, void *ws_base, const float *d_codes, const float *d_sel, const float *d_h0,
+                       int B, int64_t T, float *d_mel, float *d_hT, float *d_codes_out, float *d_prior, hipStream_t s);
+int run_forward(const bvc_model *m, const Workspace &w, const float *d_mel, const float *d_bits, const uint8_t *h_use_gen, bool update_h,
+                bool update_h2, const float *d_noise, int B, int64_t T, float *d_dec, float *d_kld, float *d_z, float *d_prob,
+                float *d_prior, hipStream_t s);
+int run_vocoder(const bvc_model *m, const Workspace &w, const float *d_mel, int B, int64_t T, int64_t length, float div, float *d_wav,
+                int stop_after, const float **tap, int64_t *tap_len, int *tap_ch, hipStream_t s, const long long *lim = nullptr);
+
+const int64_t STREAM_WARM_FRAMES = 32;   // rate * 32 - 64 >= 60 = the longest receptive field of an AMP pair, for every stage rate >= 8
+const int STREAM_H = 64;     // history rows per stage: >= (ks-1)*dil + (ks-1) of every AMP pair (max 60) and a multiple of every rate
+int vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_per_push, bool slide, bvc_vocoder_stream **out);
+
+}  // namespace bvc

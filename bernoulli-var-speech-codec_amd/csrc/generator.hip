@@ -1,0 +1,256 @@
+// The generator (BigVGAN): the offline pass over a whole utterance and the incremental, history-buffer pass of the streaming paths.
+#include <algorithm>
+#include <memory>
+
+#include "bvc_host.h"
+
+using namespace bvc;
+
+namespace {
+
+// Iteration d of AMP block j: where its pair writes and how it ends.  Iterations 0 and 1 go to the block's own P and Q with the plain
+// residual; the last one goes to the stage's running sum XS - the first block stores, the others add, the last divides by the block count.
+enum { AMP_P = 0, AMP_Q = 1, AMP_XS = 2 };
+struct AmpTarget { int buf, epi; };
+inline AmpTarget amp_target(const bvc_config &c, int j, int d) {
+    if (d < 2) return {d == 0 ? AMP_P : AMP_Q, CE_RES};
+    if (j == 0 || c.n_resk == 1) return {AMP_XS, CE_RES};
+    return {AMP_XS, j + 1 < c.n_resk ? CE_RES_ACC : CE_RES_ACC_DIV};
+}
+
+// (one workgroup per (tensor, stream) with four 16-byte pieces in flight per thread measured slower: 67 against 56 us at 256 streams)
+__global__ __launch_bounds__(256) void stream_rotate_kernel(const RotEntry *__restrict__ tab, int k, int parity) {
+    const RotEntry e = tab[blockIdx.z];
+    const long long n4 = (long long)e.H * e.C / 4;
+    const float4 *src = reinterpret_cast<const float4 *>(e.buf[parity] + (long long)blockIdx.y * e.bs +
+                                                         (long long)k * e.rate * e.C);
+    float4 *dst = reinterpret_cast<float4 *>(e.buf[parity ^ 1] + (long long)blockIdx.y * e.bs);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) dst[i] = src[i];
+}
+
+__global__ __launch_bounds__(256) void stream_rows_in_kernel(const float *__restrict__ src, long long src_bs,
+                                                             float *__restrict__ dst, long long dst_bs, long long n) {
+    const float *s = src + (long long)blockIdx.y * src_bs;
+    float *d = dst + (long long)blockIdx.y * dst_bs;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) d[i] = s[i];
+}
+
+int stream_push(bvc_vocoder_stream *st, const float *d_mel, int k, float div, float *d_wav, hipStream_t s) {
+    const bvc_model *m = st->m;
+    const bvc_config &c = m->cfg;
+    const int B = st->B, p = st->parity;
+    int rc;
+    auto bs = [](const StreamTensor &t) { return t.rows * t.C; };
+    // first row of this hop's window of a tensor (its history; the new rows follow)
+    auto at = [&](const StreamTensor &t) { return t.buf[p] + (long long)st->cursor * t.rate * t.C; };
+    // new mel rows behind the history
+    stream_rows_in_kernel<<<dim3((unsigned)((k * st->mel.C + 255) / 256), B), 256, 0, s>>>(
+        d_mel, (long long)k * st->mel.C, at(st->mel) + (long long)st->mel.H * st->mel.C, bs(st->mel), (long long)k * st->mel.C);
+    BVC_HIP_TRY(hipGetLastError());
+    // conv_pre: mel rows [Hm, Hm+k) -> y0 rows [Hy, Hy+k)
+    {
+        ConvWindow w{bs(st->mel), bs(st->y0), st->mel.H, 0};
+        float *out = at(st->y0) + (long long)(st->y0.H - st->mel.H) * st->y0.C;
+        if ((rc = launch_conv_mfma(m->conv_pre, at(st->mel), st->mel.H + k, out, st->mel.H + k, B, CE_STORE, nullptr,
+                                   nullptr, 1.0f, s, &w))) return rc;
+    }
+    const StreamTensor *prev = &st->y0;
+    long long rate_prev = 1;
+    for (int i = 0; i < c.n_up; ++i) {
+        const int u = c.up_rates[i];
+        const StreamTensor &X = st->X[i], &XS = st->XS[i];
+        // transposed conv as a 2-tap conv over the view (rows/u, u*C): view row q <-> X rows [u*q, u*q+u)
+        {
+            const long long hq = X.H / u;                              // history rows of the view
+            const long long nq = rate_prev * k;                        // new view rows
+            ConvWindow w{bs(*prev), bs(X), hq, 0};
+            const float *in = at(*prev) + (long long)(prev->H - hq) * prev->C;
+            if ((rc = launch_conv_mfma(m->ups[i], in, hq + nq, at(X), hq + nq, B, CE_STORE, nullptr, nullptr, 1.0f, s, &w))) return rc;
+        }
+        const long long L = X.H + (long long)X.rate * k;
+        // t_origin only decides which rows lie before the start of the signal; from STREAM_WARM_FRAMES frames on none
+        // does, so the value is frozen there (a hop captured into a hipGraph then replays with identical arguments)
+        const long long fr = st->frames < STREAM_WARM_FRAMES ? st->frames : STREAM_WARM_FRAMES;
+        ConvWindow w{bs(X), bs(X), X.H, (long long)X.rate * fr - X.H};
+        if (st->d_age) { w.t_origin = -(long long)X.H; w.row_age = st->d_age; w.age_rate = X.rate; }    // per row, read by the kernel
+        for (int j = 0; j < c.n_resk; ++j) {
+            const StreamTensor &P = st->P[i * c.n_resk + j], &Q = st->Q[i * c.n_resk + j];
+            float *const bufs[3] = {at(P), at(Q), at(XS)};
+            const float *cur = at(X);
+            for (int d = 0; d < 3; ++d) {
+                const AmpPair &ap = m->amp[i][j][d];
+                const AmpTarget t = amp_target(c, j, d);
+                float *const dst = bufs[t.buf];
+                const int epi = t.epi;
+                if ((rc = launch_amp_pair(ap.c1, ap.c2, cur, L, dst, B, epi, at(XS), (float)c.n_resk, s, &w, m->amp_kernels))) return rc;
+                cur = dst;
+            }
+        }
+        prev = &XS;
+        rate_prev = X.rate;
+    }
+    {
+        ConvWindow w{bs(*prev), 0, prev->H, 0};
+        if ((rc = launch_conv_post(at(*prev), prev->H + rate_prev * k, m->post_c, m->post_ks, m->post_w, m->post_b,
+                                   m->post_a, m->post_ib, div, d_wav, rate_prev * k, B, s, &w))) return rc;
+    }
+    if (!st->slide) {
+        stream_rotate_kernel<<<dim3((unsigned)((st->max_hc4 + 255) / 256), B, st->n_ten), 256, 0, s>>>(st->d_tab, k, p);
+        st->parity ^= 1;
+    } else {
+        st->cursor += k;                                     // the next hop's window starts behind this hop's rows
+        if (st->cursor + st->kmax > st->cap_frames) {        // no room for another hop: history back to the front (the twin buffer IS the buffer)
+            stream_rotate_kernel<<<dim3((unsigned)((st->max_hc4 + 255) / 256), B, st->n_ten), 256, 0, s>>>(st->d_tab, st->cursor, 0);
+            st->cursor = 0;
+        }
+    }
+    BVC_HIP_TRY(hipGetLastError());
+    st->frames += k;
+    return BVC_OK;
+}
+
+}  // namespace
+
+namespace bvc {
+
+// Runs the generator; stop_after: -1 = everything, otherwise the tap index of bvc_test_vocoder_tap.
+// lim: nullptr, or the (n_up + 1) x B bounds of a mixed-length batch (launch_ragged_limits): the upsamplers' input rows per item, then
+// the samples each item keeps of `length`.
+int run_vocoder(const bvc_model *m, const Workspace &w, const float *d_mel, int B, int64_t T, int64_t length,
+                float div, float *d_wav, int stop_after, const float **tap, int64_t *tap_len, int *tap_ch,
+                hipStream_t s, const long long *lim) {
+    const bvc_config &c = m->cfg;
+    int rc;
+    // pad[6,0] + conv_pre (models.py:212-213); input is already time-major (B,T,80)
+    if ((rc = launch_conv_mfma(m->conv_pre, d_mel, T, w.y0, T, B, CE_STORE, nullptr, nullptr, 1.0f, s))) return rc;
+    if (stop_after == 0) { *tap = w.y0; *tap_len = T; *tap_ch = c.upsample_initial_channel; return BVC_OK; }
+    const float *cur_in = w.y0;
+    int64_t Lin = T;
+    for (int i = 0; i < c.n_up; ++i) {
+        const int C = m->stage_ch[i];
+        const int64_t L = (Lin + 1) * c.up_rates[i];
+        // ConvTranspose1d as a 2-tap conv with u*C columns over Lin+1 rows (models.py:216-217)
+        if ((rc = launch_conv_mfma(m->ups[i], cur_in, Lin, w.X, Lin + 1, B, CE_STORE, nullptr, nullptr, 1.0f, s, nullptr,
+                                   lim ? lim + (size_t)i * B : nullptr))) return rc;
+        if (stop_after == 1 + 2 * i) { *tap = w.X; *tap_len = L; *tap_ch = C; return BVC_OK; }
+        float *const bufs[3] = {w.P, w.Q, w.XS};
+        for (int j = 0; j < c.n_resk; ++j) {                            // three parallel AMP blocks
+            const float *cur = w.X;
+            for (int d = 0; d < 3; ++d) {
+                const AmpPair &ap = m->amp[i][j][d];
+                if (!m->fused_amp && (rc = launch_conv_mfma(ap.c1, cur, L, w.U, L, B, CE_STORE, nullptr, nullptr, 1.0f, s))) return rc;
+                const AmpTarget t = amp_target(c, j, d);
+                float *const dst = bufs[t.buf];
+                const int epi = t.epi;
+                if (m->fused_amp) {
+                    if ((rc = launch_amp_pair(ap.c1, ap.c2, cur, L, dst, B, epi, w.XS, (float)c.n_resk, s, nullptr, m->amp_kernels))) return rc;
+                } else if ((rc = launch_conv_mfma(ap.c2, w.U, L, dst, L, B, epi, cur, w.XS, (float)c.n_resk, s))) return rc;
+                cur = dst;
+            }
+        }
+        if (stop_after == 2 + 2 * i) { *tap = w.XS; *tap_len = L; *tap_ch = C; return BVC_OK; }
+        cur_in = w.XS;
+        Lin = L;
+    }
+    const int64_t n_out = length < Lin ? length : Lin;
+    return launch_conv_post(cur_in, Lin, m->post_c, m->post_ks, m->post_w, m->post_b, m->post_a, m->post_ib, div,
+                            d_wav, n_out, B, s, nullptr, lim ? lim + (size_t)c.n_up * B : nullptr, m->post_up, m->post_down);
+}
+
+int vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_per_push, bool slide, bvc_vocoder_stream **out) {
+    if (!m || !out || B <= 0 || max_frames_per_push <= 0) { set_error("bvc_vocoder_stream_create: bad arguments"); return BVC_EINVAL; }
+    if (m->antialiased) { set_error("bvc_vocoder_stream_create: %s", NOT_CAUSAL); return BVC_EINVAL; }
+    const bvc_config &c = m->cfg;
+    // the history must cover every receptive field and stay aligned with the transposed-conv views
+    long long rate = 1;
+    for (int i = 0; i < c.n_up; ++i) {
+        const int u = c.up_rates[i];
+        if (STREAM_H % u) { set_error("streaming vocoder: upsample rate %d does not divide the history (%d)", u, STREAM_H); return BVC_EINVAL; }
+        for (int j = 0; j < c.n_resk; ++j)
+            for (int d = 0; d < 3; ++d) {
+                const AmpPair &ap = m->amp[i][j][d];
+                if ((ap.c1.ks - 1) * ap.c1.dil + (ap.c2.ks - 1) * ap.c2.dil > STREAM_H) {
+                    set_error("streaming vocoder: AMP receptive field exceeds the history"); return BVC_EINVAL;
+                }
+            }
+        rate *= u;
+    }
+    if (m->post_ks - 1 > STREAM_H) { set_error("streaming vocoder: conv_post kernel exceeds the history"); return BVC_EINVAL; }
+    std::unique_ptr<bvc_vocoder_stream> st(new bvc_vocoder_stream());
+    st->m = m; st->B = B; st->kmax = max_frames_per_push;
+    st->slide = slide;
+    // frames of room behind the history: 32 (16 hops of one or two frames between two moves of the histories; 2.2 GB of buffers at 256 streams),
+    // more only where longer hops need it
+    st->cap_frames = slide ? std::max(2 * max_frames_per_push + 8, 32) : max_frames_per_push;
+    const long long room = st->cap_frames;
+    auto mk = [&](int C, int H, int r) { StreamTensor t; t.buf[0] = t.buf[1] = nullptr; t.C = C; t.H = H; t.rate = r; t.rows = H + (long long)r * room; return t; };
+    st->mel = mk(c.num_mels, (m->conv_pre.ks - 1) * m->conv_pre.dil, 1);
+    st->y0 = mk(c.upsample_initial_channel, STREAM_H / c.up_rates[0], 1);
+    if (st->y0.H < st->mel.H) st->y0.H = st->mel.H, st->y0.rows = st->y0.H + room;
+    rate = 1;
+    for (int i = 0; i < c.n_up; ++i) {
+        rate *= c.up_rates[i];
+        for (auto *v : {&st->X, &st->XS}) v->push_back(mk(m->stage_ch[i], STREAM_H, (int)rate));
+        for (int j = 0; j < c.n_resk; ++j)
+            for (auto *v : {&st->P, &st->Q}) v->push_back(mk(m->stage_ch[i], STREAM_H, (int)rate));
+    }
+    std::vector<StreamTensor *> all = {&st->mel, &st->y0};
+    for (auto *v : {&st->X, &st->XS, &st->P, &st->Q})
+        for (auto &t : *v) all.push_back(&t);
+    size_t total = 0;
+    const int copies = slide ? 1 : 2;
+    for (auto *t : all) {
+        total += copies * (size_t)B * t->rows * t->C;
+        // moving the history back to the front must not overlap itself: it happens with more than cap_frames - 2 kmax frames behind it
+        if (slide && (long long)(st->cap_frames - 2 * st->kmax + 1) * t->rate < t->H) { set_error("streaming vocoder: sliding window too short for its history"); return BVC_EINVAL; }
+    }
+    if (hipMalloc(reinterpret_cast<void **>(&st->pool), total * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("streaming vocoder: cannot allocate %zu bytes of history buffers", total * sizeof(float));
+        return BVC_ENOMEM;
+    }
+    st->pool_floats = total;
+    size_t off = 0;
+    std::vector<RotEntry> tab;
+    for (auto *t : all) {
+        for (int q = 0; q < copies; ++q) { t->buf[q] = st->pool + off; off += (size_t)B * t->rows * t->C; }
+        if (slide) t->buf[1] = t->buf[0];
+        RotEntry e; e.buf[0] = t->buf[0]; e.buf[1] = t->buf[1]; e.bs = t->rows * t->C; e.C = t->C; e.H = t->H; e.rate = t->rate; e.pad_ = 0;
+        tab.push_back(e);
+        if ((t->H * t->C) % 4) { set_error("streaming vocoder: history of a tensor is not a multiple of 4 floats"); return BVC_EINVAL; }
+        st->max_hc4 = std::max(st->max_hc4, t->H * t->C / 4);
+    }
+    st->n_ten = (int)tab.size();
+    BVC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&st->d_tab), tab.size() * sizeof(RotEntry)));
+    BVC_HIP_TRY(hipMemcpy(st->d_tab, tab.data(), tab.size() * sizeof(RotEntry), hipMemcpyHostToDevice));
+    BVC_HIP_TRY(hipMemset(st->pool, 0, total * sizeof(float)));
+    *out = st.release();
+    return BVC_OK;
+}
+
+}  // namespace bvc
+
+extern "C" {
+
+int bvc_vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_per_push, bvc_vocoder_stream **out) {
+    return vocoder_stream_create(m, B, max_frames_per_push, false, out);
+}
+
+void bvc_vocoder_stream_destroy(bvc_vocoder_stream *st) { delete st; }
+
+int bvc_vocoder_stream_reset(bvc_vocoder_stream *st, void *stream) {
+    if (!st) { set_error("null stream state"); return BVC_EINVAL; }
+    BVC_HIP_TRY(hipMemsetAsync(st->pool, 0, st->pool_floats * sizeof(float), (hipStream_t)stream));
+    st->parity = 0; st->frames = 0; st->cursor = 0;
+    return BVC_OK;
+}
+
+int bvc_vocoder_stream_push(bvc_vocoder_stream *st, const float *d_mel, int32_t k, float out_scale_div, float *d_wav,
+                            void *stream) {
+    if (!st || !d_mel || !d_wav) { set_error("null argument"); return BVC_EINVAL; }
+    if (int st_ = sticky_status(st->m)) return st_;
+    if (k <= 0 || k > st->kmax) { set_error("bvc_vocoder_stream_push: k=%d outside 1..%d", (int)k, st->kmax); return BVC_EINVAL; }
+    return stream_push(st, d_mel, k, out_scale_div, d_wav, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -1,0 +1,659 @@
+#include <algorithm>
+#include <memory>
+
+#include "bvc_host.h"
+
+using namespace bvc;
+
+// ---- whole-hop streaming codec (BASELINE configs[4]) -----------------------------------------------------
+// B parallel streams, a fixed hop of new samples per tick; one tick = front-end of the frames the hop completes ->
+// BVRNN.encode (state carried) -> BVRNN.decode (state carried) -> incremental vocoder.  Everything a tick touches
+// lives at fixed device addresses and everything that changes from tick to tick (how many samples are buffered)
+// is DEVICE state, so a tick with k new frames and vocoder parity p is the same launch sequence every time: it is
+// captured once per (k, p) into a hipGraph and replayed.
+namespace {
+
+struct StreamDev { int fill; int pad_[3]; };             // samples buffered: sbuf[:, 0] is sample 256*F - 256, F = frames emitted
+
+// row_off[b]: the row's delay in samples (its hop lands that far behind the session's fill level), < 0 for an idle row, whose hop is
+// zeros whatever the caller's d_in holds; = cap for a row that drains (sc_finish_kernel): n <= 0 below, nothing is written
+__global__ __launch_bounds__(256) void sc_append_kernel(const StreamDev *__restrict__ st, const float *__restrict__ xin, int hop,
+                                                        float *__restrict__ sbuf, int cap, const int *__restrict__ row_off) {
+    const int fill = st->fill;
+    const int off = row_off[blockIdx.y];
+    const int at = fill + (off < 0 ? 0 : off);
+    float *d = sbuf + (long long)blockIdx.y * cap + at;
+    const float *x = xin + (long long)blockIdx.y * hop;
+    const int n = hop < cap - at ? hop : cap - at;
+    if (off < 0) { for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d[i] = 0.0f; }
+    else         { for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d[i] = x[i]; }
+}
+// first tick only: samples -256..-1 of the reflect padding (meldataset.py:72-81): x[-i] = x[i]
+__global__ __launch_bounds__(256) void sc_reflect_left_kernel(float *__restrict__ sbuf, int cap, int pad) {
+    float *d = sbuf + (long long)blockIdx.x * cap;
+    for (int i = 1 + threadIdx.x; i <= pad; i += 256) d[pad - i] = d[pad + i];
+}
+__global__ __launch_bounds__(256) void sc_shift_kernel(const float *__restrict__ src, long long sstride, int soff,
+                                                       float *__restrict__ dst, long long dstride, int n) {
+    const float *a = src + (long long)blockIdx.y * sstride + soff;
+    float *d = dst + (long long)blockIdx.y * dstride;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d[i] = a[i];
+}
+// end of a tick: the fill level, and every row's age (frames since its own start, capped at `warm`: see bvc_vocoder_stream::d_age)
+__global__ void sc_advance_kernel(StreamDev *st, int delta, int *__restrict__ age, int B, int k, int warm) {
+    if (threadIdx.x == 0) st->fill += delta;
+    if (k > 0)
+        for (int b = threadIdx.x; b < B; b += blockDim.x) { const int a = age[b] + k; age[b] = a < warm ? a : warm; }
+}
+
+// ---- slots: rows of a session that are opened, closed and re-rated while the others keep running ----
+// The host keeps the book; what changed since the last tick travels as a kernel argument (up to SC_LIST rows per launch).
+const int SC_LIST = 64;
+enum { SC_SET_OFF = 1, SC_ZERO_TAIL = 2, SC_SET_BITS = 4 };
+struct SlotUpdate { int row, off, flags; float bits; };
+struct SlotUpdateList { int n; int pad_[3]; SlotUpdate e[SC_LIST]; };
+struct SlotRowList { int n; int pad_[3]; int row[SC_LIST]; };
+
+// before the append of a tick: new delay / idle mark, the closed stream's tail out of the sample buffer, bits per frame in every
+// (B, k) layout (bits_base: the layouts k = 1 .. kmax one behind the other)
+__global__ __launch_bounds__(256) void sc_slot_update_kernel(SlotUpdateList l, const StreamDev *__restrict__ st, int *__restrict__ row_off,
+                                                             float *__restrict__ sbuf, int cap, float *__restrict__ bits_base, int B, int kmax) {
+    const SlotUpdate u = l.e[blockIdx.x];
+    if ((u.flags & SC_SET_OFF) && threadIdx.x == 0) row_off[u.row] = u.off;
+    if (u.flags & SC_ZERO_TAIL) {
+        float *d = sbuf + (long long)u.row * cap;
+        for (int i = st->fill + threadIdx.x; i < cap; i += 256) d[i] = 0.0f;
+    }
+    if (u.flags & SC_SET_BITS) {
+        const int tri = kmax * (kmax + 1) / 2;             // layout k starts B * k (k - 1) / 2 floats in; entry i of the triangle is (k, j)
+        for (int i = threadIdx.x; i < tri; i += 256) {
+            int k = 1, j = i;
+            while (j >= k) { j -= k; ++k; }
+            bits_base[(long long)B * (k * (k - 1) / 2) + (long long)u.row * k + j] = u.bits;
+        }
+    }
+}
+
+// the tick that emits frame 0 of the rows in `l`, after the append: what a new session has at tick 0, for those rows only.
+// blockIdx.y < n_ten: that tensor's history rows of the generator (both copies, where the windows stand); blockIdx.y == n_ten: the left
+// reflect padding x[-i] = x[i] (the row's sample 0 sits `pad` samples into the buffer: its frame 0 is the first of this tick), both GRU
+// states, the row's age
+__global__ __launch_bounds__(256) void sc_slot_start_kernel(SlotRowList l, const RotEntry *__restrict__ tab, int n_ten, int cursor,
+                                                            float *__restrict__ sbuf, int cap, int pad, float *__restrict__ h_enc,
+                                                            float *__restrict__ h_dec, int Hd, int *__restrict__ age) {
+    const int row = l.row[blockIdx.z];
+    if ((int)blockIdx.y < n_ten) {
+        const RotEntry e = tab[blockIdx.y];
+        const long long n4 = (long long)e.H * e.C / 4;
+        const long long at = (long long)row * e.bs + (long long)cursor * e.rate * e.C;
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = 0; q < (e.buf[1] == e.buf[0] ? 1 : 2); ++q) {
+            float4 *d = reinterpret_cast<float4 *>(e.buf[q] + at);
+            for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) d[i] = z;
+        }
+        return;
+    }
+    if (blockIdx.x == 0) {
+        float *d = sbuf + (long long)row * cap;
+        for (int i = 1 + threadIdx.x; i <= pad; i += 256) d[pad - i] = d[pad + i];
+        if (threadIdx.x == 0) age[row] = 0;
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < Hd; i += gridDim.x * 256) {
+        h_enc[(long long)row * Hd + i] = 0.0f;
+        h_dec[(long long)row * Hd + i] = 0.0f;
+    }
+}
+
+// the same reset in a session that runs one half (bvc_stream_codec_create_dir).  h_dec != nullptr: the decoder half (generator histories,
+// h_dec, age; blockIdx.y as above); h_enc != nullptr: the encoder half (left reflect padding, h_enc; launched with n_ten = 0).
+__global__ __launch_bounds__(256) void sc_slot_start_half_kernel(SlotRowList l, const RotEntry *__restrict__ tab, int n_ten, int cursor,
+                                                                 float *__restrict__ sbuf, int cap, int pad, float *__restrict__ h_enc,
+                                                                 float *__restrict__ h_dec, int Hd, int *__restrict__ age) {
+    const int row = l.row[blockIdx.z];
+    if ((int)blockIdx.y < n_ten) {
+        const RotEntry e = tab[blockIdx.y];
+        const long long n4 = (long long)e.H * e.C / 4;
+        const long long at = (long long)row * e.bs + (long long)cursor * e.rate * e.C;
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = 0; q < (e.buf[1] == e.buf[0] ? 1 : 2); ++q) {
+            float4 *d = reinterpret_cast<float4 *>(e.buf[q] + at);
+            for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) d[i] = z;
+        }
+        return;
+    }
+    if (blockIdx.x == 0) {
+        if (h_enc) {
+            float *d = sbuf + (long long)row * cap;
+            for (int i = 1 + threadIdx.x; i <= pad; i += 256) d[pad - i] = d[pad + i];
+        }
+        if (h_dec && threadIdx.x == 0) age[row] = 0;
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < Hd; i += gridDim.x * 256) {
+        if (h_enc) h_enc[(long long)row * Hd + i] = 0.0f;
+        if (h_dec) h_dec[(long long)row * Hd + i] = 0.0f;
+    }
+}
+
+// end of a stream (bvc_stream_codec_finish), after the append of the tick that takes its last hop: of that hop only the first n_last
+// samples (SlotUpdate::off) are the stream's.  Directly behind them the right reflect padding of the front-end (meldataset.py:72-81):
+// with e = the index one behind the last sample, d[e + i] = d[e - 2 - i], i = 0 .. rpad - 1; zeros from there to the end of the row (the
+// rest of the hop is never used); and the row is marked as draining: row_off = cap, with which sc_append_kernel writes nothing (its n
+// is <= 0), so whatever the session holds for the row stays where it is while the row rides along.  The host has checked that the
+// stream is longer than rpad + 1 samples (all of them are still in the buffer: the frames that would drop them need the padding).
+__global__ __launch_bounds__(256) void sc_finish_kernel(SlotUpdateList l, const StreamDev *__restrict__ st, int *__restrict__ row_off,
+                                                        float *__restrict__ sbuf, int cap, int rpad) {
+    const SlotUpdate u = l.e[blockIdx.x];
+    float *d = sbuf + (long long)u.row * cap;
+    const int off = row_off[u.row];
+    int e = st->fill + (off < 0 ? 0 : off) + u.off;
+    e = e < rpad + 1 ? rpad + 1 : (e > cap ? cap : e);      // never out of the row, whatever the state says
+    const int pe = e + rpad < cap ? e + rpad : cap;
+    for (int i = e + threadIdx.x; i < pe; i += 256) d[i] = d[2 * e - 2 - i];
+    for (int i = pe + threadIdx.x; i < cap; i += 256) d[i] = 0.0f;
+    __syncthreads();                                         // every lane has read row_off
+    if (threadIdx.x == 0) row_off[u.row] = cap;
+}
+
+}  // namespace
+
+struct bvc_stream_codec {
+    const bvc_model *m = nullptr;
+    int B = 0, hop = 0, kmax = 0, cap = 0;
+    float bits = 0.0f, scale = 1.0f, out_div = 1.0f;
+    int fill = 0;                       // host mirror of StreamDev::fill (same arithmetic)
+    int64_t frames = 0, ticks = 0;
+    bool first = true;
+    // device memory (one allocation)
+    char *pool = nullptr;
+    StreamDev *d_state = nullptr;
+    float *d_in = nullptr, *sbuf = nullptr, *stmp = nullptr, *mel = nullptr, *bitsbuf = nullptr, *codes = nullptr, *melhat = nullptr,
+          *wav = nullptr, *h_enc = nullptr, *h_dec = nullptr;
+    void *ws = nullptr; size_t ws_bytes = 0;
+    bvc_vocoder_stream *voc = nullptr;
+    // slots: each row is a stream of its own (see include/bvcodec.h).  Device side: row_off (delay in samples, < 0 idle), age (frames
+    // since the row's start, capped), bitsbuf = the bits per (row, frame) in every (B, k) layout, k = 1 .. kmax, one behind the other
+    // (bits_of(k)): a tick - and a graph captured for its k - reads the layout of its own frame count.
+    struct Slot {
+        bool open = true, started = true;
+        int delay = 0, pending = 0;     // pending: SC_* flags that the next tick sends to the device
+        int64_t frame0 = 0;             // session frame that is the stream's frame 0
+        float bits = 0.0f;
+        int last_count = 0;             // frames of the last tick that belong to the stream, and the stream's index of the first
+        int64_t last_frame0 = 0;
+        int64_t open_tick = 0;          // the tick that took the stream's first hop
+        int fin_last = -1;              // bvc_stream_codec_finish: samples of the next tick's hop that are the stream's last (-1: none asked)
+        int64_t end_frame = -1;         // draining: the session frame behind the stream's last one (-1: not draining)
+    };
+    std::vector<Slot> slots;
+    int *row_off = nullptr, *age = nullptr;
+    int max_delay = 0;
+    int n_pending = 0, n_waiting = 0;   // slots with pending flags / open slots whose frame 0 is still to come
+    int n_finishing = 0;                // slots whose finish the next tick carries out
+    // directed sessions (bvc_stream_codec_create_dir): SEND has no decoder half (h_dec, melhat, wav, voc are null), RECV no encoder half
+    // (d_in, sbuf, stmp, mel, h_enc are null).  packets (B, kmax, bpf) / present (B, kmax): the wire side of both.
+    int dir = BVC_STREAM_DUPLEX, bpf = 0;
+    uint8_t *packets = nullptr, *present = nullptr;
+    float *bits_of(int k) const { return bitsbuf + (size_t)B * (k * (k - 1) / 2); }
+    hipGraphExec_t graph[8][2] = {};    // [k][vocoder parity]
+    hipGraphExec_t graph_conceal[8][2] = {};      // ... of the ticks that conceal from the prior
+    int conceal = 0;                    // receive sessions: 0 = a lost frame is a frame of no bits, 1 = generated from the prior (bvc_stream_codec_set_conceal)
+    bool use_graph = true;
+    bool tick_flow = true;      // the ticks' recurrences on the persistent kernel where it is available (BVC_STREAM_FLOW=0: never)
+    ~bvc_stream_codec() {
+        for (auto &gk : graph) for (auto g : gk) if (g) (void)hipGraphExecDestroy(g);
+        for (auto &gk : graph_conceal) for (auto g : gk) if (g) (void)hipGraphExecDestroy(g);
+        if (voc) bvc_vocoder_stream_destroy(voc);
+        if (pool) (void)hipFree(pool);
+    }
+};
+
+namespace {
+
+// Where a stream that joins a running session starts.  `samples` = samples per row the session has taken so far (ticks * hop_samples).
+// Frame f reads samples [hop f - pad, hop f - pad + n_fft), so the tick that completes it is the first whose samples reach
+// hop f - pad + n_fft.  The stream's sample 0 must be a session frame boundary hop * f0 not before its arrival; f0 is made the FIRST frame
+// of its tick, so that the row's reset lies between two ticks: the smallest such f0 >= ceil(samples / hop).  delay = hop * f0 - samples.
+// (bvcodec.streaming.join_plan is the same arithmetic; tests/test_stream_slots_cpu.py checks it against a simulation of the schedule.)
+int64_t tick_of_frame(int64_t f, int hop_samples, const bvc_config &c) {
+    const int64_t need = c.hop * f - c.pad_left + c.n_fft;
+    return (need + hop_samples - 1) / hop_samples - 1;
+}
+void join_plan(int64_t samples, int hop_samples, const bvc_config &c, int *delay, int64_t *frame0, int64_t *tick0) {
+    int64_t f = (samples + c.hop - 1) / c.hop;
+    while (f > 0 && tick_of_frame(f - 1, hop_samples, c) == tick_of_frame(f, hop_samples, c)) ++f;
+    *delay = (int)(c.hop * f - samples);
+    *frame0 = f;
+    if (tick0) *tick0 = tick_of_frame(f, hop_samples, c);
+}
+
+// pending slot changes -> device, in one launch per SC_LIST slots (before the tick's append)
+int stream_send_pending(bvc_stream_codec *st, hipStream_t s) {
+    SlotUpdateList l;
+    l.n = 0;
+    auto flush = [&]() -> int {
+        if (l.n == 0) return BVC_OK;
+        sc_slot_update_kernel<<<dim3(l.n), 256, 0, s>>>(l, st->d_state, st->row_off, st->sbuf, st->cap, st->bitsbuf, st->B, st->kmax);
+        BVC_HIP_TRY(hipGetLastError());
+        l.n = 0;
+        return BVC_OK;
+    };
+    int rc;
+    for (int b = 0; b < st->B && st->n_pending > 0; ++b) {
+        bvc_stream_codec::Slot &sl = st->slots[b];
+        if (!sl.pending) continue;
+        l.e[l.n++] = SlotUpdate{b, sl.open ? sl.delay : -1, st->sbuf ? sl.pending : (sl.pending & ~SC_ZERO_TAIL), sl.bits};   // (a receive session has no samples)
+        sl.pending = 0;
+        --st->n_pending;
+        if (l.n == SC_LIST && (rc = flush())) return rc;
+    }
+    st->n_pending = 0;
+    return flush();
+}
+
+// the rows whose frame 0 is the first frame of this tick (frames [f_begin, f_begin + k)): per-row reset, after the append
+int stream_start_rows(bvc_stream_codec *st, int64_t f_begin, int k, hipStream_t s) {
+    const bvc_config &c = st->m->cfg;
+    const bvc_vocoder_stream *v = st->voc;
+    SlotRowList l;
+    l.n = 0;
+    auto flush = [&]() -> int {
+        if (l.n == 0) return BVC_OK;
+        if (st->dir == BVC_STREAM_SEND) {                    // encoder half only: left reflect padding, h_enc
+            sc_slot_start_half_kernel<<<dim3(4, 1, (unsigned)l.n), 256, 0, s>>>(l, nullptr, 0, 0, st->sbuf, st->cap, c.pad_left, st->h_enc,
+                                                                                  nullptr, c.h_dim, st->age);
+        } else {
+            const unsigned gx = (unsigned)std::max(1, std::min(16, (v->max_hc4 + 255) / 256));
+            if (st->dir == BVC_STREAM_RECV)                  // decoder half only: generator histories, h_dec, age
+                sc_slot_start_half_kernel<<<dim3(gx, (unsigned)v->n_ten + 1, (unsigned)l.n), 256, 0, s>>>(
+                    l, v->d_tab, v->n_ten, v->slide ? v->cursor : 0, nullptr, 0, 0, nullptr, st->h_dec, c.h_dim, st->age);
+            else
+                sc_slot_start_kernel<<<dim3(gx, (unsigned)v->n_ten + 1, (unsigned)l.n), 256, 0, s>>>(
+                    l, v->d_tab, v->n_ten, v->slide ? v->cursor : 0, st->sbuf, st->cap, c.pad_left, st->h_enc, st->h_dec, c.h_dim, st->age);
+        }
+        BVC_HIP_TRY(hipGetLastError());
+        l.n = 0;
+        return BVC_OK;
+    };
+    int rc;
+    for (int b = 0; b < st->B && st->n_waiting > 0; ++b) {
+        bvc_stream_codec::Slot &sl = st->slots[b];
+        if (!sl.open || sl.started || sl.frame0 >= f_begin + k) continue;
+        if (sl.frame0 != f_begin) { set_error("bvc_stream_codec_tick: slot %d starts inside a tick (frame %lld of %lld+%d)", b, (long long)sl.frame0, (long long)f_begin, k); return BVC_EINVAL; }
+        sl.started = true;
+        --st->n_waiting;
+        l.row[l.n++] = b;
+        if (l.n == SC_LIST && (rc = flush())) return rc;
+    }
+    return flush();
+}
+
+// the rows whose stream ends with the hop this tick has just appended (bvc_stream_codec_finish): right reflect padding behind the last
+// sample, the row drains from here on.  One launch per SC_LIST rows, only in such a tick.
+int stream_finish_rows(bvc_stream_codec *st, hipStream_t s) {
+    const bvc_config &c = st->m->cfg;
+    SlotUpdateList l;
+    l.n = 0;
+    auto flush = [&]() -> int {
+        if (l.n == 0) return BVC_OK;
+        sc_finish_kernel<<<dim3(l.n), 256, 0, s>>>(l, st->d_state, st->row_off, st->sbuf, st->cap, c.n_fft - c.hop - c.pad_left);
+        BVC_HIP_TRY(hipGetLastError());
+        l.n = 0;
+        return BVC_OK;
+    };
+    int rc;
+    for (int b = 0; b < st->B && st->n_finishing > 0; ++b) {
+        bvc_stream_codec::Slot &sl = st->slots[b];
+        if (sl.fin_last < 0) continue;
+        // n samples in all -> bvc_num_frames(n) = n / hop frames, the same as the offline call
+        const int64_t n = (st->ticks - sl.open_tick) * st->hop + sl.fin_last;
+        sl.end_frame = sl.frame0 + n / c.hop;
+        l.e[l.n++] = SlotUpdate{b, sl.fin_last, 0, 0.0f};
+        sl.fin_last = -1;
+        --st->n_finishing;
+        if (l.n == SC_LIST && (rc = flush())) return rc;
+    }
+    st->n_finishing = 0;
+    return flush();
+}
+
+// the launches of one tick with k new frames (k > 0), in stream order
+int stream_tick_body(bvc_stream_codec *st, int k, hipStream_t s) {
+    const bvc_model *m = st->m;
+    const int B = st->B;
+    int rc;
+    Workspace w;
+    if ((rc = check_ws(m, B, k, st->ws, st->ws_bytes, &w))) return rc;
+    if (st->dir == BVC_STREAM_RECV) {
+        // the wire -> codes: every row's own bit count, 0.5 for what did not arrive and for idle rows
+        if ((rc = launch_unpack_rows(st->packets, st->present, m->cfg.var_bit ? st->bits_of(k) : nullptr, st->row_off, B, k, m->cfg.z_dim,
+                                     st->kmax, st->codes, s))) return rc;
+        if (st->conceal) {
+            // lost frames of open rows are generated with the row's bit count (all z bits on a fixed-rate model); idle rows keep their 0.5
+            if ((rc = launch_conceal_select(st->present, st->kmax, m->cfg.var_bit ? st->bits_of(k) : nullptr, (float)m->cfg.z_dim, st->row_off, B, k,
+                                            w.bits, s))) return rc;
+            if ((rc = run_decode_conceal(m, w, st->ws, st->codes, w.bits, st->h_dec, B, k, st->melhat, st->h_dec, st->codes, nullptr, s))) return rc;
+        } else
+        if ((rc = run_decode(m, w, st->ws, st->codes, st->h_dec, B, k, st->melhat, st->h_dec, s))) return rc;
+        return bvc_vocoder_stream_push(st->voc, st->melhat, k, st->out_div, st->wav, s);
+    }
+    // front-end on the sample buffer: frame j of this tick reads sbuf[:, 256 j : 256 j + 1024)
+    if ((rc = launch_stft_logmel(m->fe, st->sbuf, B, st->cap, k, 0, st->scale, st->mel, s))) return rc;
+    // drop the 256 k samples no later frame reads (through a scratch copy: the ranges overlap)
+    const int keep = st->cap - 256 * k;
+    sc_shift_kernel<<<dim3((unsigned)((keep + 255) / 256), B), 256, 0, s>>>(st->sbuf, st->cap, 256 * k, st->stmp, st->cap, keep);
+    sc_shift_kernel<<<dim3((unsigned)((keep + 255) / 256), B), 256, 0, s>>>(st->stmp, st->cap, 0, st->sbuf, st->cap, keep);
+    BVC_HIP_TRY(hipGetLastError());
+    if ((rc = run_encode(m, w, st->ws, st->mel, m->cfg.var_bit ? st->bits_of(k) : nullptr, st->h_enc, B, k, st->codes, nullptr, st->h_enc,
+                         nullptr, s))) return rc;
+    if (st->dir == BVC_STREAM_SEND)                          // codes -> the wire, and that is the tick
+        return launch_pack_rows(st->codes, m->cfg.var_bit ? st->bits_of(k) : nullptr, B, k, m->cfg.z_dim, st->kmax, st->packets, s);
+    if ((rc = run_decode(m, w, st->ws, st->codes, st->h_dec, B, k, st->melhat, st->h_dec, s))) return rc;
+    return bvc_vocoder_stream_push(st->voc, st->melhat, k, st->out_div, st->wav, s);
+}
+
+int slot_arg(bvc_stream_codec *st, int32_t slot, const char *fn) {
+    if (!st) { set_error("%s: null stream codec", fn); return BVC_EINVAL; }
+    if (slot < 0 || slot >= st->B) { set_error("%s: slot %d outside 0..%d", fn, (int)slot, st->B - 1); return BVC_EINVAL; }
+    return BVC_OK;
+}
+void slot_mark(bvc_stream_codec *st, bvc_stream_codec::Slot &sl, int flags) {
+    if (!sl.pending) ++st->n_pending;
+    sl.pending |= flags;
+}
+
+// one tick's body with k > 0 frames on the session's schedule: launched eagerly, or replayed from the hipGraph of its (k, vocoder parity)
+int stream_run_body(bvc_stream_codec *st, int k, hipStream_t s) {
+    const int B = st->B;
+    int rc = BVC_OK;
+    const int parity = st->voc ? st->voc->parity : 0;
+    const bool slide = st->voc && st->voc->slide;
+    // Which schedule?  Where the persistent recurrence kernel is available (flow_chains_static: the model's option, the
+    // residency census, the batch) the tick is launched eagerly and its two recurrences are one persistent launch each - at 256
+    // streams 1.53 ms per tick against 1.69 ms for the launch-per-layer recurrence, which gains nothing from a graph on the GPU
+    // side (1.68 eager / 1.70 replayed; the replay only saves host time).  Otherwise (recurrence = layers, no resident grid,
+    // BVC_STREAM_FLOW=0) the warm tick is one hipGraph of launch-per-layer kernels as before.  Same bits either way.
+    const bool tick_flow = st->tick_flow && flow_chains_static(st->m, B) != 0;
+    const bool warm = !tick_flow && !slide && st->use_graph && s != nullptr && st->frames >= STREAM_WARM_FRAMES;     // (the default stream cannot be captured)
+    g_stream_tick = true; g_tick_flow = tick_flow;
+    if (!warm) {
+        rc = stream_tick_body(st, k, s);
+    } else {
+        hipGraphExec_t &ge = (st->conceal ? st->graph_conceal : st->graph)[k][parity];
+        if (!ge) {                                       // first warm tick of this shape: capture it (the capture does not execute)
+            hipGraph_t graph = nullptr;
+            const int vp = parity; const int64_t vf = st->voc ? st->voc->frames : 0;
+            g_capturing = true;
+            hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+            if (e == hipSuccess) rc = stream_tick_body(st, k, s);
+            hipError_t e2 = (e == hipSuccess) ? hipStreamEndCapture(s, &graph) : e;
+            g_capturing = false;
+            if (st->voc) { st->voc->parity = vp; st->voc->frames = vf; }  // the captured push advanced the host-side bookkeeping: undo, the replay redoes it
+            if (!rc && (e2 != hipSuccess || !graph)) { set_error("bvc_stream_codec_tick: hipGraph capture failed: %s", hipGetErrorString(e2)); rc = BVC_EHIP; }
+            if (!rc && hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0) != hipSuccess) { set_error("bvc_stream_codec_tick: hipGraphInstantiate failed"); rc = BVC_EHIP; }
+            if (graph) (void)hipGraphDestroy(graph);
+        }
+        if (!rc) {
+            if (hipGraphLaunch(ge, s) != hipSuccess) { set_error("bvc_stream_codec_tick: hipGraphLaunch failed"); rc = BVC_EHIP; }
+            if (st->voc) { st->voc->parity ^= 1; st->voc->frames += k; }  // what stream_push() does on the host side
+        }
+    }
+    g_stream_tick = false; g_tick_flow = false;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bvc_stream_codec_create(const bvc_model *m, int32_t B, int32_t hop_samples, float bits_per_frame, float scale,
+                            float out_scale_div, bvc_stream_codec **out) {
+    return bvc_stream_codec_create_dir(m, B, hop_samples, bits_per_frame, scale, out_scale_div, BVC_STREAM_DUPLEX, out);
+}
+
+int bvc_stream_codec_create_dir(const bvc_model *m, int32_t B, int32_t hop_samples, float bits_per_frame, float scale,
+                                float out_scale_div, int32_t direction, bvc_stream_codec **out) {
+    if (direction != BVC_STREAM_DUPLEX && direction != BVC_STREAM_SEND && direction != BVC_STREAM_RECV) {
+        set_error("bvc_stream_codec_create_dir: direction %d is none of BVC_STREAM_DUPLEX / _SEND / _RECV", (int)direction); return BVC_EINVAL;
+    }
+    const bool enc = direction != BVC_STREAM_RECV, dec = direction != BVC_STREAM_SEND;
+    if (!enc) hop_samples = 0;                               // a receive tick is given whole frames
+    if (!m || !out || B <= 0 || (enc && hop_samples <= 0)) { set_error("bvc_stream_codec_create: bad arguments"); return BVC_EINVAL; }
+    if (dec && m->antialiased) { set_error("bvc_stream_codec_create: %s", NOT_CAUSAL); return BVC_EINVAL; }
+    const bvc_config &c = m->cfg;
+    if (enc && hop_samples <= c.pad_left) { set_error("bvc_stream_codec_create: the hop must exceed the left reflect padding (%d samples)", c.pad_left); return BVC_EINVAL; }
+    std::unique_ptr<bvc_stream_codec> st(new bvc_stream_codec());
+    st->m = m; st->B = B; st->hop = hop_samples; st->bits = bits_per_frame; st->scale = scale; st->out_div = out_scale_div;
+    st->dir = direction; st->bpf = (c.z_dim + 7) / 8;
+    // a receive tick takes up to 7 frames: whatever one tick of a send session emits (its own limit, the size of the graph table)
+    st->kmax = enc ? (hop_samples + c.hop - 1) / c.hop + 1 : 7;
+    if (st->kmax > 7) { set_error("bvc_stream_codec_create: hop too long (%d frames per tick)", st->kmax); return BVC_EINVAL; }
+    // the longest delay a joining stream can get (join_plan): the pattern of frames per tick repeats after hop / gcd(hop, hop_samples) ticks
+    for (int64_t t = 0; enc && t <= c.hop; ++t) {
+        int d; int64_t f0;
+        join_plan(t * hop_samples, hop_samples, c, &d, &f0, nullptr);
+        st->max_delay = std::max(st->max_delay, d);
+    }
+    // room for the window, the frames of a tick, a hop behind the longest delay - and with it for the right reflect padding of a stream
+    // that ends (bvc_stream_codec_finish): it ends at most fill + max_delay + hop_samples with fill < n_fft, and the n_fft - hop - pad_left
+    // = 512 samples behind that are within the hop * kmax >= 512 counted here
+    st->cap = enc ? c.n_fft + c.hop * st->kmax + hop_samples + st->max_delay : 0;
+    st->ws_bytes = bvc_workspace_bytes(m, B, st->kmax);
+    int spf = 1;                                             // samples per frame
+    for (int i = 0; i < c.n_up; ++i) spf *= c.up_rates[i];
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    // (a half that the session does not run gets no memory: its pointers stay null)
+    const size_t one = enc ? 1 : 0, two = dec ? 1 : 0, wire = direction != BVC_STREAM_DUPLEX ? 1 : 0;
+    const size_t o_state = take(sizeof(StreamDev)), o_in = take(one * B * hop_samples * 4), o_sbuf = take(one * B * st->cap * 4),
+                 o_stmp = take(one * B * st->cap * 4), o_mel = take(one * B * st->kmax * c.num_mels * 4),
+                 o_bits = take((size_t)B * (st->kmax * (st->kmax + 1) / 2) * 4), o_rowoff = take((size_t)B * 4), o_age = take((size_t)B * 4), o_codes = take((size_t)B * st->kmax * c.z_dim * 4),
+                 o_melhat = take(two * B * st->kmax * c.num_mels * 4), o_wav = take(two * B * st->kmax * spf * 4),
+                 o_he = take(one * B * c.h_dim * 4), o_hd = take(two * B * c.h_dim * 4), o_ws = take(st->ws_bytes),
+                 o_pk = take(wire * B * st->kmax * st->bpf), o_pr = take(wire * B * st->kmax);
+    if (hipMalloc(reinterpret_cast<void **>(&st->pool), off) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("bvc_stream_codec_create: cannot allocate %zu bytes", off);
+        return BVC_ENOMEM;
+    }
+    BVC_HIP_TRY(hipMemset(st->pool, 0, off));
+    char *p = st->pool;
+    st->d_state = reinterpret_cast<StreamDev *>(p + o_state);
+    st->bitsbuf = reinterpret_cast<float *>(p + o_bits); st->codes = reinterpret_cast<float *>(p + o_codes); st->ws = p + o_ws;
+    if (enc) {
+        st->d_in = reinterpret_cast<float *>(p + o_in); st->sbuf = reinterpret_cast<float *>(p + o_sbuf); st->stmp = reinterpret_cast<float *>(p + o_stmp);
+        st->mel = reinterpret_cast<float *>(p + o_mel); st->h_enc = reinterpret_cast<float *>(p + o_he);
+    }
+    if (dec) { st->melhat = reinterpret_cast<float *>(p + o_melhat); st->wav = reinterpret_cast<float *>(p + o_wav); st->h_dec = reinterpret_cast<float *>(p + o_hd); }
+    if (wire) { st->packets = reinterpret_cast<uint8_t *>(p + o_pk); st->present = reinterpret_cast<uint8_t *>(p + o_pr); }
+    st->row_off = reinterpret_cast<int *>(p + o_rowoff); st->age = reinterpret_cast<int *>(p + o_age);      // zero: every slot open, delay 0, age 0
+    st->slots.assign(B, bvc_stream_codec::Slot());
+    for (auto &sl : st->slots) sl.bits = bits_per_frame;
+    int rc;
+    if ((rc = launch_fill(st->bitsbuf, bits_per_frame, (long long)B * (st->kmax * (st->kmax + 1) / 2), nullptr))) return rc;
+    st->fill = c.pad_left;                                   // room for the left reflect padding of frame 0
+    StreamDev init{st->fill, {0, 0, 0}};
+    BVC_HIP_TRY(hipMemcpy(st->d_state, &init, sizeof(init), hipMemcpyHostToDevice));
+    { const char *ng = getenv("BVC_STREAM_NO_GRAPH"); st->use_graph = !(ng && ng[0] == '1'); }
+    { const char *tf = getenv("BVC_STREAM_FLOW"); st->tick_flow = !(tf && tf[0] == '0'); }
+    // ticks that are launched eagerly (persistent recurrence) let the generator's windows slide through their buffers instead of moving
+    // every history back after every hop (56 us of a 1.5 ms tick at 256 streams); BVC_STREAM_SLIDE=0: never
+    const char *sl = getenv("BVC_STREAM_SLIDE");
+    const bool slide = st->tick_flow && flow_chains_static(m, B) != 0 && !(sl && sl[0] == '0');
+    if (dec) {
+        if ((rc = vocoder_stream_create(m, B, st->kmax, slide, &st->voc))) return rc;
+        st->voc->d_age = st->age;
+    }
+    if (!enc) st->first = false;                             // no sample buffer, no left padding to write
+    BVC_HIP_TRY(hipDeviceSynchronize());
+    *out = st.release();
+    return BVC_OK;
+}
+
+void bvc_stream_codec_destroy(bvc_stream_codec *st) { delete st; }
+
+int bvc_stream_codec_buffers(bvc_stream_codec *st, float **d_in, float **d_codes, float **d_wav, int32_t *max_frames_per_tick) {
+    if (!st) { set_error("null stream codec"); return BVC_EINVAL; }
+    if (d_in) *d_in = st->d_in;
+    if (d_codes) *d_codes = st->codes;
+    if (d_wav) *d_wav = st->wav;
+    if (max_frames_per_tick) *max_frames_per_tick = st->kmax;
+    return BVC_OK;
+}
+
+int bvc_stream_codec_packets(bvc_stream_codec *st, uint8_t **d_packets, uint8_t **d_present, int32_t *bytes_per_frame) {
+    if (!st) { set_error("null stream codec"); return BVC_EINVAL; }
+    if (d_packets) *d_packets = st->packets;
+    if (d_present) *d_present = st->present;
+    if (bytes_per_frame) *bytes_per_frame = st->bpf;
+    return BVC_OK;
+}
+
+int bvc_stream_codec_open(bvc_stream_codec *st, int32_t slot, float bits_per_frame, int32_t *delay_samples) {
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_open")) return rc;
+    bvc_stream_codec::Slot &sl = st->slots[slot];
+    if (sl.open) { set_error("bvc_stream_codec_open: slot %d is open", (int)slot); return BVC_EINVAL; }
+    if (!(bits_per_frame >= 0.0f)) { set_error("bvc_stream_codec_open: bits per frame must not be negative"); return BVC_EINVAL; }
+    if (st->dir == BVC_STREAM_RECV) { sl.delay = 0; sl.frame0 = st->frames; }     // frame-aligned: frame 0 is the first frame of the next tick
+    else join_plan(st->ticks * st->hop, st->hop, st->m->cfg, &sl.delay, &sl.frame0, nullptr);
+    sl.open = true; sl.started = false; sl.bits = bits_per_frame;
+    sl.last_count = 0; sl.last_frame0 = 0;
+    sl.open_tick = st->ticks; sl.fin_last = -1; sl.end_frame = -1;
+    ++st->n_waiting;
+    slot_mark(st, sl, SC_SET_OFF | SC_SET_BITS);
+    if (delay_samples) *delay_samples = sl.delay;
+    return BVC_OK;
+}
+
+int bvc_stream_codec_close(bvc_stream_codec *st, int32_t slot) {
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_close")) return rc;
+    bvc_stream_codec::Slot &sl = st->slots[slot];
+    if (!sl.open) { set_error("bvc_stream_codec_close: slot %d is idle", (int)slot); return BVC_EINVAL; }
+    if (!sl.started) --st->n_waiting;
+    if (sl.fin_last >= 0) --st->n_finishing;                 // a finish that no tick has carried out yet is dropped with the stream,
+    sl.open = false; sl.started = false; sl.delay = 0;       // and so is the rest of a stream that drains
+    sl.last_count = 0; sl.last_frame0 = 0;
+    sl.fin_last = -1; sl.end_frame = -1;
+    slot_mark(st, sl, SC_SET_OFF | SC_ZERO_TAIL);
+    return BVC_OK;
+}
+
+int bvc_stream_codec_finish(bvc_stream_codec *st, int32_t slot, int32_t n_last) {
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_finish")) return rc;
+    if (st->dir == BVC_STREAM_RECV) { set_error("bvc_stream_codec_finish: a receive session has no samples to flush (close the slot)"); return BVC_EINVAL; }
+    bvc_stream_codec::Slot &sl = st->slots[slot];
+    const bvc_config &c = st->m->cfg;
+    if (!sl.open || !sl.started) { set_error("bvc_stream_codec_finish: slot %d is %s", (int)slot, sl.open ? "waiting for its frame 0" : "idle"); return BVC_EINVAL; }
+    if (sl.fin_last >= 0 || sl.end_frame >= 0) { set_error("bvc_stream_codec_finish: slot %d is draining already", (int)slot); return BVC_EINVAL; }
+    if (n_last < 0 || n_last > st->hop) { set_error("bvc_stream_codec_finish: n_last %d outside 0..%d", (int)n_last, st->hop); return BVC_EINVAL; }
+    const int64_t n = (st->ticks - sl.open_tick) * st->hop + n_last;
+    if (n <= c.n_fft - c.hop - c.pad_left) { set_error("bvc_stream_codec_finish: a stream of %lld samples is too short for the right reflect padding", (long long)n); return BVC_EINVAL; }
+    sl.fin_last = n_last;
+    ++st->n_finishing;
+    return BVC_OK;
+}
+
+int bvc_stream_codec_slot_state(bvc_stream_codec *st, int32_t slot, int32_t *state) {
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_slot_state")) return rc;
+    const bvc_stream_codec::Slot &sl = st->slots[slot];
+    if (state) *state = !sl.open ? 0 : (!sl.started ? 1 : ((sl.fin_last >= 0 || sl.end_frame >= 0) ? 3 : 2));
+    return BVC_OK;
+}
+
+int bvc_stream_codec_set_bits(bvc_stream_codec *st, int32_t slot, float bits_per_frame) {
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_set_bits")) return rc;
+    if (!st->m->cfg.var_bit) { set_error("bvc_stream_codec_set_bits: the model has a fixed bitrate (var_bit = 0)"); return BVC_EINVAL; }
+    bvc_stream_codec::Slot &sl = st->slots[slot];
+    if (!sl.open) { set_error("bvc_stream_codec_set_bits: slot %d is idle", (int)slot); return BVC_EINVAL; }
+    if (!(bits_per_frame >= 0.0f)) { set_error("bvc_stream_codec_set_bits: bits per frame must not be negative"); return BVC_EINVAL; }
+    sl.bits = bits_per_frame;
+    slot_mark(st, sl, SC_SET_BITS);
+    return BVC_OK;
+}
+
+int bvc_stream_codec_slot_frames(bvc_stream_codec *st, int32_t slot, int32_t *first, int32_t *count, int64_t *stream_frame0) {
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_slot_frames")) return rc;
+    const bvc_stream_codec::Slot &sl = st->slots[slot];
+    if (first) *first = 0;                                   // a stream's frame 0 is the first frame of its tick
+    if (count) *count = sl.last_count;
+    if (stream_frame0) *stream_frame0 = sl.last_frame0;
+    return BVC_OK;
+}
+
+int bvc_stream_codec_tick(bvc_stream_codec *st, int32_t *n_frames, void *stream) {
+    if (!st) { set_error("null stream codec"); return BVC_EINVAL; }
+    if (int st_ = sticky_status(st->m)) return st_;
+    if (st->dir == BVC_STREAM_RECV) { set_error("bvc_stream_codec_tick: a receive session takes packets (bvc_stream_codec_tick_recv)"); return BVC_EINVAL; }
+    const bvc_config &c = st->m->cfg;
+    hipStream_t s = (hipStream_t)stream;
+    const int B = st->B;
+    // the hop joins the sample buffer (device-side fill level), frame 0's left reflect padding once the first samples are there
+    if (st->n_pending > 0) { if (int rc_ = stream_send_pending(st, s)) return rc_; }
+    sc_append_kernel<<<dim3((unsigned)((st->hop + 255) / 256), B), 256, 0, s>>>(st->d_state, st->d_in, st->hop, st->sbuf, st->cap, st->row_off);
+    if (st->first) {
+        sc_reflect_left_kernel<<<dim3(B), 256, 0, s>>>(st->sbuf, st->cap, c.pad_left);
+        st->first = false;
+    }
+    BVC_HIP_TRY(hipGetLastError());
+    if (st->n_finishing > 0) { if (int rc_ = stream_finish_rows(st, s)) return rc_; }
+    const int fill = st->fill + st->hop;
+    const int k = fill >= c.n_fft ? (fill - c.n_fft) / c.hop + 1 : 0;
+    if (k > st->kmax) { set_error("bvc_stream_codec_tick: internal frame count %d", k); return BVC_EINVAL; }
+    int rc = BVC_OK;
+    if (k > 0 && st->n_waiting > 0 && (rc = stream_start_rows(st, st->frames, k, s))) return rc;
+    if (k > 0 && (rc = stream_run_body(st, k, s))) return rc;
+    sc_advance_kernel<<<1, 64, 0, s>>>(st->d_state, st->hop - c.hop * k, st->age, B, k, (int)STREAM_WARM_FRAMES);
+    BVC_HIP_TRY(hipGetLastError());
+    for (auto &sl : st->slots) {
+        const bool live = sl.open && sl.started && k > 0;
+        sl.last_count = live ? k : 0;
+        sl.last_frame0 = live ? st->frames - sl.frame0 : 0;
+        if (sl.end_frame < 0) continue;
+        // a draining stream: only the frames below its end are its own, and with the last of them the row is idle of its own accord
+        // (what a close does: the next tick clears what the row still holds)
+        if (st->frames + sl.last_count > sl.end_frame) sl.last_count = (int)(sl.end_frame - st->frames);
+        if (st->frames + k >= sl.end_frame) {
+            sl.open = false; sl.started = false; sl.delay = 0; sl.end_frame = -1;
+            slot_mark(st, sl, SC_SET_OFF | SC_ZERO_TAIL);
+        }
+    }
+    st->fill = fill - c.hop * k;
+    st->frames += k;
+    st->ticks += 1;
+    if (n_frames) *n_frames = k;
+    return BVC_OK;
+}
+
+int bvc_stream_codec_tick_recv(bvc_stream_codec *st, int32_t n_frames, void *stream) {
+    if (!st) { set_error("null stream codec"); return BVC_EINVAL; }
+    if (int st_ = sticky_status(st->m)) return st_;
+    if (st->dir != BVC_STREAM_RECV) { set_error("bvc_stream_codec_tick_recv: not a receive session (bvc_stream_codec_tick)"); return BVC_EINVAL; }
+    if (n_frames < 1 || n_frames > st->kmax) { set_error("bvc_stream_codec_tick_recv: n_frames %d outside 1..%d", (int)n_frames, st->kmax); return BVC_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    const int k = n_frames;
+    int rc = BVC_OK;
+    if (st->n_pending > 0 && (rc = stream_send_pending(st, s))) return rc;
+    if (st->n_waiting > 0 && (rc = stream_start_rows(st, st->frames, k, s))) return rc;
+    if ((rc = stream_run_body(st, k, s))) return rc;
+    sc_advance_kernel<<<1, 64, 0, s>>>(st->d_state, 0, st->age, st->B, k, (int)STREAM_WARM_FRAMES);     // every row's age: the generator reads it
+    BVC_HIP_TRY(hipGetLastError());
+    for (auto &sl : st->slots) {
+        const bool live = sl.open && sl.started;
+        sl.last_count = live ? k : 0;
+        sl.last_frame0 = live ? st->frames - sl.frame0 : 0;
+    }
+    st->frames += k;
+    st->ticks += 1;
+    return BVC_OK;
+}
+
+int bvc_stream_codec_set_conceal(bvc_stream_codec *st, int32_t mode) {
+    if (!st) { set_error("null stream codec"); return BVC_EINVAL; }
+    if (int st_ = sticky_status(st->m)) return st_;
+    if (st->dir != BVC_STREAM_RECV) { set_error("bvc_stream_codec_set_conceal: not a receive session"); return BVC_EINVAL; }
+    if (mode != 0 && mode != 1) { set_error("bvc_stream_codec_set_conceal: mode %d is neither 0 (no bits) nor 1 (prior)", (int)mode); return BVC_EINVAL; }
+    if (int rc_ = need_prior(st->m, "bvc_stream_codec_set_conceal")) return rc_;
+    st->conceal = mode;                                      // host bookkeeping: the next tick reads it
+    return BVC_OK;
+}
+
+}  // extern "C"

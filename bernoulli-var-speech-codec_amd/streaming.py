@@ -190,7 +190,7 @@ def join_plan(samples_so_far, hop, frame=256, pad_left=256, n_fft=1024):
     from 0).  A stream's frame grid is fixed by its sample 0, the session's by tick 0: the library delays the row by ``delay`` samples
     so that the stream's sample 0 becomes session sample frame * start_frame, where start_frame is the first frame at or behind the
     stream's arrival that is the FIRST frame of its tick (the row's reset then lies between two ticks).  Pure host arithmetic, the
-    same as the library's (csrc/bvcodec_abi.hip: join_plan)."""
+    same as the library's (csrc/stream_codec.hip: join_plan)."""
     def tick_of(f):
         return -(-(frame * f - pad_left + n_fft) // hop) - 1
     f = -(-samples_so_far // frame)
@@ -207,7 +207,7 @@ def finish_plan(open_tick, finish_tick, n_last, hop, frame=256, pad_left=256, n_
     + n_last samples in all, total_frames = n // frame = the frames of the offline ``encode``.  The list says for tick finish_tick
     and every later one up to the tick that emits the last frame how many of that tick's frames are the stream's (``slot_frames``'s
     count); after the last entry the slot is idle.  Frames the stream got before tick finish_tick: total_frames minus the counts.
-    Pure host arithmetic, the same as the library's (csrc/bvcodec_abi.hip: stream_finish_rows and the end of bvc_stream_codec_tick)."""
+    Pure host arithmetic, the same as the library's (csrc/stream_codec.hip: stream_finish_rows and the end of bvc_stream_codec_tick)."""
     def emitted_before(t):                                  # session frames emitted by the ticks before tick t
         have = pad_left + t * hop
         return (have - n_fft) // frame + 1 if have >= n_fft else 0

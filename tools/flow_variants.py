@@ -33,7 +33,7 @@ def build(specs):
     for name, o, p in procs:
         if p.wait():
             raise SystemExit(f"variant {name}: compile failed")
-        objs = [os.path.join(CSRC, f) for f in ("bvcodec_abi.o", "k_gemm.o", "k_frontend.o", "k_vocoder.o")] + [o]
+        objs = [os.path.join(CSRC, f) for f in ("bvcodec_abi.o", "model.o", "recurrence.o", "generator.o", "stream_codec.o", "k_gemm.o", "k_frontend.o", "k_vocoder.o")] + [o]
         lib = os.path.join(VDIR, f"libbvcodec_{name}.so")
         subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
         print("built", lib)
