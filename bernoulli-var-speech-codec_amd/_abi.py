@@ -74,6 +74,8 @@ SIGNATURES = {
     "bvc_stream_codec_finish": (ctypes.c_int, [_vp, _i32, _i32]),
     "bvc_stream_codec_slot_state": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i32)]),
     "bvc_stream_codec_set_conceal": (ctypes.c_int, [_vp, _i32]),
+    "bvc_stream_codec_set_repair": (ctypes.c_int, [_vp, _i32]),
+    "bvc_stream_codec_late": (ctypes.c_int, [_vp, _i32, _i64, _vp, ctypes.POINTER(_i32)]),
     "bvc_encode": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _f, _vp, _vp, _sz, _vp]),
     "bvc_decode": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i64, _f, _vp, _vp, _sz, _vp]),
     "bvc_forward": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _f, _i64, _f, _vp, _vp, _vp, _sz, _vp]),

@@ -154,6 +154,71 @@ __global__ __launch_bounds__(256) void sc_finish_kernel(SlotUpdateList l, const 
     if (threadIdx.x == 0) row_off[u.row] = cap;
 }
 
+// ---- repair window (bvc_stream_codec_set_repair / _late): a receive session keeps, for the ticks that hold its last W frames, the decoder
+// state in front of the tick and what the tick was given (bytes, present, bits per frame), so that a packet that arrives late can be put
+// where it belonged and the recurrence replayed from there.  Ring slot r of tick t = t % ring_n; per slot h (B, Hd), packets (B, kmax,
+// bpf), present (B, kmax), bits (B, kmax), the slots `hs` floats / `pks` bytes / `prs` bytes / `bs` floats apart.
+const int SC_LATE_BYTES = 16;                            // bytes per frame a late packet can carry in a kernel argument (z_dim <= 128)
+const int SC_CHUNKS = 64;                                // ticks a replay can span: the window is at most 64 frames
+struct LateEntry { int row, slot, j, pad_; unsigned char bytes[SC_LATE_BYTES]; };
+struct LateList { int n; int pad_[3]; LateEntry e[SC_LIST]; };
+struct ReplayChunk { int slot, k, off; };                // ring slot, frames of that tick, (row, frame) pairs of the pass in front of it
+struct ReplayPlan { int n_chunks, n_rows, row0, pad_; int row[SC_LIST]; ReplayChunk c[SC_CHUNKS]; };
+
+// one launch per receive tick of a session with a window, behind the tick's row starts: everything the tick is about to read
+__global__ __launch_bounds__(256) void sc_snapshot_kernel(const float *__restrict__ h_dec, long long n_h4, float *__restrict__ ring_h,
+                                                          const unsigned char *__restrict__ pk, long long n_pk, unsigned char *__restrict__ ring_pk,
+                                                          const unsigned char *__restrict__ pr, long long n_pr, unsigned char *__restrict__ ring_pr,
+                                                          unsigned char *__restrict__ host_pr, const float *__restrict__ bits_k,
+                                                          float *__restrict__ ring_bits, int B, int k, int kmax) {
+    const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
+    for (long long i = i0; i < n_h4; i += step) reinterpret_cast<float4 *>(ring_h)[i] = reinterpret_cast<const float4 *>(h_dec)[i];
+    const long long n_pk16 = n_pk / 16;
+    for (long long i = i0; i < n_pk16; i += step) reinterpret_cast<uint4 *>(ring_pk)[i] = reinterpret_cast<const uint4 *>(pk)[i];
+    for (long long i = n_pk16 * 16 + i0; i < n_pk; i += step) ring_pk[i] = pk[i];
+    for (long long i = i0; i < n_pr; i += step) { const unsigned char v = pr[i]; ring_pr[i] = v; host_pr[i] = v; }
+    for (long long i = i0; i < (long long)B * k; i += step) { const long long b = i / k; ring_bits[b * kmax + (i - b * k)] = bits_k[i]; }
+}
+
+// the late packets queued since the last tick: bytes and present = 1 into the ring
+__global__ __launch_bounds__(64) void sc_late_patch_kernel(LateList l, unsigned char *__restrict__ ring_pk, long long pks,
+                                                           unsigned char *__restrict__ ring_pr, long long prs, int kmax, int bpf) {
+    const LateEntry e = l.e[blockIdx.x];
+    const long long f = (long long)e.row * kmax + e.j;
+    if ((int)threadIdx.x < bpf) ring_pk[e.slot * pks + f * bpf + threadIdx.x] = e.bytes[threadIdx.x];
+    if (threadIdx.x == 0) ring_pr[e.slot * prs + f] = 1;
+}
+
+// a replay pass: the listed rows' ring entries of the pass's ticks into a compact batch, tick after tick ((B', k) each, B' = the rows of
+// the whole pass, this launch's first row being compact row row0), and their snapshot states of the first tick.  blockIdx = (tick, row).
+__global__ __launch_bounds__(256) void sc_replay_gather_kernel(ReplayPlan p, const float *__restrict__ ring_h, long long hs,
+                                                               const unsigned char *__restrict__ ring_pk, long long pks,
+                                                               const unsigned char *__restrict__ ring_pr, long long prs,
+                                                               const float *__restrict__ ring_bits, long long bs, int Hd, int kmax, int bpf,
+                                                               float *__restrict__ r_h, unsigned char *__restrict__ r_pk,
+                                                               unsigned char *__restrict__ r_pr, float *__restrict__ r_bits) {
+    const ReplayChunk c = p.c[blockIdx.x];
+    const int row = p.row[blockIdx.y], bp = p.row0 + (int)blockIdx.y;
+    const long long src = (long long)row * kmax, dst = (long long)c.off + (long long)bp * c.k;
+    for (int i = threadIdx.x; i < c.k * bpf; i += 256) r_pk[dst * bpf + i] = ring_pk[c.slot * pks + src * bpf + i];
+    for (int i = threadIdx.x; i < c.k; i += 256) {
+        r_pr[dst + i] = ring_pr[c.slot * prs + src + i];
+        r_bits[dst + i] = ring_bits[c.slot * bs + src + i];
+    }
+    if (blockIdx.x == 0) {
+        const float4 *a = reinterpret_cast<const float4 *>(ring_h + c.slot * hs + (long long)row * Hd);
+        float4 *d = reinterpret_cast<float4 *>(r_h + (long long)bp * Hd);
+        for (int i = threadIdx.x; i < Hd / 4; i += 256) d[i] = a[i];
+    }
+}
+
+// the pass's states back into the rows of a (B, Hd) tensor: the snapshot of the next retained tick, or h_dec itself
+__global__ __launch_bounds__(256) void sc_replay_scatter_kernel(SlotRowList l, int row0, const float *__restrict__ r_h, float *__restrict__ dst, int Hd) {
+    const float4 *a = reinterpret_cast<const float4 *>(r_h + (long long)(row0 + (int)blockIdx.x) * Hd);
+    float4 *d = reinterpret_cast<float4 *>(dst + (long long)l.row[blockIdx.x] * Hd);
+    for (int i = threadIdx.x; i < Hd / 4; i += 256) d[i] = a[i];
+}
+
 }  // namespace
 
 struct bvc_stream_codec {
@@ -197,12 +262,34 @@ struct bvc_stream_codec {
     hipGraphExec_t graph[8][2] = {};    // [k][vocoder parity]
     hipGraphExec_t graph_conceal[8][2] = {};      // ... of the ticks that conceal from the prior
     int conceal = 0;                    // receive sessions: 0 = a lost frame is a frame of no bits, 1 = generated from the prior (bvc_stream_codec_set_conceal)
+    // repair window (bvc_stream_codec_set_repair; receive sessions): 0 = off, nothing below is allocated and no tick launches more
+    struct RingTick { int64_t f0 = 0; int k = 0; bool valid = false; hipEvent_t ev = nullptr; };    // session frames [f0, f0 + k)
+    struct LateReq { int row, slot, j; int64_t tick; unsigned char bytes[SC_LATE_BYTES]; };
+    int repair_w = 0, ring_n = 0;
+    std::vector<RingTick> ring;         // slot of tick t: t % ring_n
+    std::vector<LateReq> late;          // taken since the last tick: the next tick applies them
+    char *ring_pool = nullptr;
+    float *ring_h = nullptr, *ring_bits = nullptr, *r_h = nullptr, *r_bits = nullptr, *r_sel = nullptr, *r_codes = nullptr;
+    uint8_t *ring_pk = nullptr, *ring_pr = nullptr, *r_pk = nullptr, *r_pr = nullptr;
+    uint8_t *h_present = nullptr, *d_hpresent = nullptr;    // host-mapped mirror of ring_pr: what `late` looks at (and marks)
+    int *r_zero = nullptr;              // row_off of a replay: every (row, frame) of the compact batch belongs to a running stream
+    long long ring_hs = 0, ring_pks = 0, ring_prs = 0, ring_bs = 0;
+    bool tick_retained(const RingTick &t) const { return t.valid && t.f0 + t.k > frames - repair_w; }
+    void repair_free() {
+        for (auto &t : ring) if (t.ev) (void)hipEventDestroy(t.ev);
+        ring.clear(); late.clear();
+        if (ring_pool) (void)hipFree(ring_pool);
+        if (h_present) (void)hipHostFree(h_present);
+        ring_pool = nullptr; h_present = d_hpresent = nullptr;
+        repair_w = ring_n = 0;
+    }
     bool use_graph = true;
     bool tick_flow = true;      // the ticks' recurrences on the persistent kernel where it is available (BVC_STREAM_FLOW=0: never)
     ~bvc_stream_codec() {
         for (auto &gk : graph) for (auto g : gk) if (g) (void)hipGraphExecDestroy(g);
         for (auto &gk : graph_conceal) for (auto g : gk) if (g) (void)hipGraphExecDestroy(g);
         if (voc) bvc_vocoder_stream_destroy(voc);
+        repair_free();
         if (pool) (void)hipFree(pool);
     }
 };
@@ -401,6 +488,118 @@ int stream_run_body(bvc_stream_codec *st, int k, hipStream_t s) {
     return rc;
 }
 
+// ---- repair window, host side ----
+// a receive tick of a session with a window, behind stream_start_rows and outside the tick's body (a graph tick replays unchanged; the ring
+// position is an argument): the state in front of the tick and what the tick reads.  The event tells `late` when the host mirror is there.
+int stream_snapshot(bvc_stream_codec *st, int k, hipStream_t s) {
+    const int B = st->B, r = (int)(st->ticks % st->ring_n);
+    bvc_stream_codec::RingTick &t = st->ring[r];
+    t.f0 = st->frames; t.k = k; t.valid = true;
+    const long long n_h4 = (long long)B * st->m->cfg.h_dim / 4, n_pk = (long long)B * st->kmax * st->bpf, n_pr = (long long)B * st->kmax;
+    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(1024, (n_h4 + 255) / 256));
+    sc_snapshot_kernel<<<dim3(grid), 256, 0, s>>>(st->h_dec, n_h4, st->ring_h + r * st->ring_hs, st->packets, n_pk, st->ring_pk + r * st->ring_pks,
+                                                  st->present, n_pr, st->ring_pr + r * st->ring_prs, st->d_hpresent + r * st->ring_prs,
+                                                  st->bits_of(k), st->ring_bits + r * st->ring_bs, B, k, st->kmax);
+    BVC_HIP_TRY(hipGetLastError());
+    BVC_HIP_TRY(hipEventRecord(t.ev, s));
+    return BVC_OK;
+}
+
+// forgets what the ring holds (set_conceal, set_repair: a frame is replayed by the program that first decoded it, or not at all)
+void ring_clear(bvc_stream_codec *st) {
+    for (auto &t : st->ring) t.valid = false;
+    st->late.clear();
+}
+
+// Head of a receive tick, outside any graph: the late packets taken since the last tick go into the ring, and every row that got one is
+// decoded again from the snapshot in front of its earliest late frame up to now, tick by tick as the session's ticks did it (the same
+// launches on (B', k) of the ring's bytes, present marks and bits per frame - a row decodes to the same bits alone or in a batch, a tick
+// to the same bits whatever came in one call before it).  Rows with the same first tick form one pass.  Behind every tick of a pass the
+// rows' states go into the next tick's snapshot (a later late packet of the row then starts from a repaired state), behind the last
+// into h_dec.  The mel frames go to melhat, which the tick overwrites; the filled codes stay in the replay's own buffer.
+// (bvcodec.streaming.repair_plan states the same acceptance and pass arithmetic.)
+int stream_apply_late(bvc_stream_codec *st, hipStream_t s) {
+    const bvc_model *m = st->m;
+    const bvc_config &c = m->cfg;
+    const int B = st->B;
+    int rc = BVC_OK;
+    {
+        LateList l;
+        l.n = 0;
+        for (size_t i = 0; i < st->late.size(); ++i) {
+            const bvc_stream_codec::LateReq &q = st->late[i];
+            LateEntry &e = l.e[l.n++];
+            e.row = q.row; e.slot = q.slot; e.j = q.j; e.pad_ = 0;
+            memcpy(e.bytes, q.bytes, SC_LATE_BYTES);
+            if (l.n == SC_LIST || i + 1 == st->late.size()) {
+                sc_late_patch_kernel<<<dim3(l.n), 64, 0, s>>>(l, st->ring_pk, st->ring_pks, st->ring_pr, st->ring_prs, st->kmax, st->bpf);
+                BVC_HIP_TRY(hipGetLastError());
+                l.n = 0;
+            }
+        }
+    }
+    // every row's first tick, and the passes: oldest first (their rows are disjoint, the order does not matter to the result)
+    std::vector<int64_t> first(B, -1);
+    for (const auto &q : st->late) if (first[q.row] < 0 || q.tick < first[q.row]) first[q.row] = q.tick;
+    st->late.clear();
+    std::vector<int64_t> starts;
+    for (int b = 0; b < B; ++b) if (first[b] >= 0) starts.push_back(first[b]);
+    std::sort(starts.begin(), starts.end());
+    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
+    const bool tick_flow_on = st->tick_flow;
+    for (int64_t t0 : starts) {
+        std::vector<int> rows;
+        for (int b = 0; b < B; ++b) if (first[b] == t0) rows.push_back(b);
+        const int Bp = (int)rows.size(), n_chunks = (int)(st->ticks - t0);
+        if (n_chunks < 1 || n_chunks > SC_CHUNKS || n_chunks > st->ring_n) { set_error("bvc_stream_codec_tick_recv: internal replay span %d", n_chunks); return BVC_EINVAL; }
+        ReplayPlan p;
+        p.n_chunks = n_chunks; p.pad_ = 0;
+        int frames = 0;
+        for (int i = 0; i < n_chunks; ++i) {
+            const int r = (int)((t0 + i) % st->ring_n);
+            if (!st->ring[r].valid) { set_error("bvc_stream_codec_tick_recv: internal replay through a tick that is not retained"); return BVC_EINVAL; }
+            p.c[i] = ReplayChunk{r, st->ring[r].k, Bp * frames};
+            frames += st->ring[r].k;
+        }
+        if (frames > st->repair_w + st->kmax - 1) { set_error("bvc_stream_codec_tick_recv: internal replay length %d", frames); return BVC_EINVAL; }
+        for (int g = 0; g < Bp; g += SC_LIST) {
+            p.row0 = g; p.n_rows = std::min(SC_LIST, Bp - g);
+            for (int i = 0; i < p.n_rows; ++i) p.row[i] = rows[g + i];
+            sc_replay_gather_kernel<<<dim3((unsigned)n_chunks, (unsigned)p.n_rows), 256, 0, s>>>(
+                p, st->ring_h, st->ring_hs, st->ring_pk, st->ring_pks, st->ring_pr, st->ring_prs, st->ring_bits, st->ring_bs, c.h_dim, st->kmax,
+                st->bpf, st->r_h, st->r_pk, st->r_pr, st->r_bits);
+            BVC_HIP_TRY(hipGetLastError());
+        }
+        // every (row, frame) of the pass is a row of one frame to these two: the ring's bits per frame, not the slots' current ones
+        const int N = Bp * frames;
+        const float *bits = c.var_bit ? st->r_bits : nullptr;
+        if ((rc = launch_unpack_rows(st->r_pk, st->r_pr, bits, st->r_zero, N, 1, c.z_dim, 1, st->r_codes, s))) return rc;
+        if (st->conceal && (rc = launch_conceal_select(st->r_pr, 1, bits, (float)c.z_dim, nullptr, N, 1, st->r_sel, s))) return rc;
+        const bool tick_flow = tick_flow_on && flow_chains_static(m, Bp) != 0;
+        g_stream_tick = true; g_tick_flow = tick_flow;
+        for (int i = 0; i < n_chunks && !rc; ++i) {
+            const int k = p.c[i].k;
+            float *codes = st->r_codes + (size_t)p.c[i].off * c.z_dim;
+            Workspace w;
+            if ((rc = check_ws(m, Bp, k, st->ws, st->ws_bytes, &w))) break;
+            if (st->conceal) rc = run_decode_conceal(m, w, st->ws, codes, st->r_sel + p.c[i].off, st->r_h, Bp, k, st->melhat, st->r_h, codes, nullptr, s);
+            else rc = run_decode(m, w, st->ws, codes, st->r_h, Bp, k, st->melhat, st->r_h, s);
+            if (rc) break;
+            float *dst = i + 1 < n_chunks ? st->ring_h + p.c[i + 1].slot * st->ring_hs : st->h_dec;
+            SlotRowList l;
+            for (int g = 0; g < Bp; g += SC_LIST) {
+                l.n = std::min(SC_LIST, Bp - g);
+                for (int q = 0; q < l.n; ++q) l.row[q] = rows[g + q];
+                sc_replay_scatter_kernel<<<dim3((unsigned)l.n), 256, 0, s>>>(l, g, st->r_h, dst, c.h_dim);
+                if (hipGetLastError() != hipSuccess) { set_error("bvc_stream_codec_tick_recv: the replay's scatter launch failed"); rc = BVC_EHIP; break; }
+            }
+        }
+        g_stream_tick = false; g_tick_flow = false;
+        if (rc) return rc;
+    }
+    return BVC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -533,6 +732,8 @@ int bvc_stream_codec_close(bvc_stream_codec *st, int32_t slot) {
     sl.open = false; sl.started = false; sl.delay = 0;       // and so is the rest of a stream that drains
     sl.last_count = 0; sl.last_frame0 = 0;
     sl.fin_last = -1; sl.end_frame = -1;
+    st->late.erase(std::remove_if(st->late.begin(), st->late.end(), [&](const bvc_stream_codec::LateReq &q) { return q.row == slot; }),
+                   st->late.end());                          // late packets of the stream that no tick has applied go with it
     slot_mark(st, sl, SC_SET_OFF | SC_ZERO_TAIL);
     return BVC_OK;
 }
@@ -632,7 +833,9 @@ int bvc_stream_codec_tick_recv(bvc_stream_codec *st, int32_t n_frames, void *str
     const int k = n_frames;
     int rc = BVC_OK;
     if (st->n_pending > 0 && (rc = stream_send_pending(st, s))) return rc;
+    if (!st->late.empty() && (rc = stream_apply_late(st, s))) return rc;
     if (st->n_waiting > 0 && (rc = stream_start_rows(st, st->frames, k, s))) return rc;
+    if (st->repair_w > 0 && (rc = stream_snapshot(st, k, s))) return rc;
     if ((rc = stream_run_body(st, k, s))) return rc;
     sc_advance_kernel<<<1, 64, 0, s>>>(st->d_state, 0, st->age, st->B, k, (int)STREAM_WARM_FRAMES);     // every row's age: the generator reads it
     BVC_HIP_TRY(hipGetLastError());
@@ -653,7 +856,86 @@ int bvc_stream_codec_set_conceal(bvc_stream_codec *st, int32_t mode) {
     if (mode != 0 && mode != 1) { set_error("bvc_stream_codec_set_conceal: mode %d is neither 0 (no bits) nor 1 (prior)", (int)mode); return BVC_EINVAL; }
     if (int rc_ = need_prior(st->m, "bvc_stream_codec_set_conceal")) return rc_;
     st->conceal = mode;                                      // host bookkeeping: the next tick reads it
+    ring_clear(st);                                          // the two programs agree only to rounding: no replay across the switch
     return BVC_OK;
+}
+
+int bvc_stream_codec_set_repair(bvc_stream_codec *st, int32_t window_frames) {
+    if (!st) { set_error("null stream codec"); return BVC_EINVAL; }
+    if (st->dir != BVC_STREAM_RECV) { set_error("bvc_stream_codec_set_repair: not a receive session"); return BVC_EINVAL; }
+    if (window_frames < 0 || window_frames > 64) { set_error("bvc_stream_codec_set_repair: window of %d frames outside 0..64", (int)window_frames); return BVC_EINVAL; }
+    if (window_frames > 0 && st->bpf > SC_LATE_BYTES) { set_error("bvc_stream_codec_set_repair: frames of %d bytes (at most %d)", st->bpf, SC_LATE_BYTES); return BVC_EINVAL; }
+    if (window_frames == st->repair_w) { ring_clear(st); return BVC_OK; }
+    if (window_frames == 0) { BVC_HIP_TRY(hipDeviceSynchronize()); st->repair_free(); return BVC_OK; }
+    // the ring (a tick holds at least one frame: at most W ticks are retained) and the replay's compact batch, (B, T') with T' up to
+    // W + kmax - 1 frames: the oldest retained tick holds one of the last W frames and up to kmax - 1 older ones.  A pass runs tick by
+    // tick, so the recurrences find their workspace in the session's own.
+    const bvc_config &c = st->m->cfg;
+    const int W = window_frames, B = st->B, kmax = st->kmax, Tm = W + kmax - 1;
+    auto up16 = [](long long n) { return (n + 15) / 16 * 16; };
+    const long long hs = (long long)B * c.h_dim, pks = up16((long long)B * kmax * st->bpf), prs = up16((long long)B * kmax), bs = (long long)B * kmax;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_h = take((size_t)W * hs * 4), o_pk = take((size_t)W * pks), o_pr = take((size_t)W * prs), o_bits = take((size_t)W * bs * 4),
+                 o_rh = take((size_t)hs * 4), o_rpk = take((size_t)B * Tm * st->bpf), o_rpr = take((size_t)B * Tm), o_rbits = take((size_t)B * Tm * 4),
+                 o_rsel = take((size_t)B * Tm * 4), o_rcodes = take((size_t)B * Tm * c.z_dim * 4), o_rzero = take((size_t)B * Tm * 4);
+    char *pool = nullptr;
+    uint8_t *hp = nullptr, *dhp = nullptr;
+    std::vector<bvc_stream_codec::RingTick> ring(W);
+    bool ok = hipMalloc(reinterpret_cast<void **>(&pool), off) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void **>(&hp), (size_t)W * prs, hipHostMallocMapped) == hipSuccess;
+    ok = ok && hipHostGetDevicePointer(reinterpret_cast<void **>(&dhp), hp, 0) == hipSuccess;
+    for (auto &t : ring) ok = ok && hipEventCreateWithFlags(&t.ev, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipMemset(pool, 0, off) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {                                               // the session is as before
+        (void)hipGetLastError();
+        for (auto &t : ring) if (t.ev) (void)hipEventDestroy(t.ev);
+        if (pool) (void)hipFree(pool);
+        if (hp) (void)hipHostFree(hp);
+        set_error("bvc_stream_codec_set_repair: cannot allocate %zu bytes for a window of %d frames", off, W);
+        return BVC_ENOMEM;
+    }
+    memset(hp, 0, (size_t)W * prs);
+    st->repair_free();
+    st->repair_w = W; st->ring_n = W; st->ring = ring;
+    st->ring_pool = pool; st->h_present = hp; st->d_hpresent = dhp;
+    st->ring_hs = hs; st->ring_pks = pks; st->ring_prs = prs; st->ring_bs = bs;
+    st->ring_h = reinterpret_cast<float *>(pool + o_h); st->ring_pk = reinterpret_cast<uint8_t *>(pool + o_pk);
+    st->ring_pr = reinterpret_cast<uint8_t *>(pool + o_pr); st->ring_bits = reinterpret_cast<float *>(pool + o_bits);
+    st->r_h = reinterpret_cast<float *>(pool + o_rh); st->r_pk = reinterpret_cast<uint8_t *>(pool + o_rpk);
+    st->r_pr = reinterpret_cast<uint8_t *>(pool + o_rpr); st->r_bits = reinterpret_cast<float *>(pool + o_rbits);
+    st->r_sel = reinterpret_cast<float *>(pool + o_rsel); st->r_codes = reinterpret_cast<float *>(pool + o_rcodes);
+    st->r_zero = reinterpret_cast<int *>(pool + o_rzero);
+    return BVC_OK;
+}
+
+int bvc_stream_codec_late(bvc_stream_codec *st, int32_t slot, int64_t stream_frame, const uint8_t *packet, int32_t *taken) {
+    if (taken) *taken = 0;
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_late")) return rc;
+    if (st->dir != BVC_STREAM_RECV) { set_error("bvc_stream_codec_late: not a receive session"); return BVC_EINVAL; }
+    if (!packet) { set_error("bvc_stream_codec_late: null packet"); return BVC_EINVAL; }
+    const bvc_stream_codec::Slot &sl = st->slots[slot];
+    if (st->repair_w <= 0 || !sl.open || !sl.started || stream_frame < 0) return BVC_OK;      // no window, or no running stream of which this is a frame
+    if (stream_frame >= st->frames - sl.frame0) return BVC_OK;                               // not decoded yet: it belongs into the next tick
+    const int64_t f = sl.frame0 + stream_frame;             // the session's count
+    const int64_t n_ticks = std::min<int64_t>(st->ticks, st->ring_n);
+    for (int64_t t = st->ticks - n_ticks; t < st->ticks; ++t) {
+        const int r = (int)(t % st->ring_n);
+        bvc_stream_codec::RingTick &rt = st->ring[r];
+        if (!st->tick_retained(rt) || f < rt.f0 || f >= rt.f0 + rt.k) continue;
+        BVC_HIP_TRY(hipEventSynchronize(rt.ev));             // the tick's snapshot has written the mirror
+        uint8_t *pr = st->h_present + r * st->ring_prs + (size_t)slot * st->kmax + (f - rt.f0);
+        if (*pr) return BVC_OK;                              // it arrived in time, or late once already
+        *pr = 1;
+        bvc_stream_codec::LateReq q;
+        q.row = slot; q.slot = r; q.j = (int)(f - rt.f0); q.tick = t;
+        memset(q.bytes, 0, sizeof(q.bytes));
+        memcpy(q.bytes, packet, (size_t)st->bpf);
+        st->late.push_back(q);
+        if (taken) *taken = 1;
+        return BVC_OK;
+    }
+    return BVC_OK;                                           // older than the window (or from before a set_conceal / set_repair)
 }
 
 }  // extern "C"

@@ -225,6 +225,51 @@ def finish_plan(open_tick, finish_tick, n_last, hop, frame=256, pad_left=256, n_
         t += 1
 
 
+def generator_reach(vocoder_config):
+    """Frames behind mel frame f whose samples frame f still reaches through the causal generator: conv_pre looks 6 frames back, every
+    stage one input row through its upsampler and (ks - 1) * (d + 1) rows through each AMP pair of its widest block, conv_post 6 samples -
+    6 + sum_stages (1 / rate_in + max_ks (ks - 1) * sum_d (d + 1) / rate_out) + 6 / 256 = 25.45 for the shipped generator, so frame f
+    changes samples of the frames f .. f + 26 and none later (``CONTEXT_FRAMES``)."""
+    reach, rate = 6.0, 1
+    for r in vocoder_config["upsample_rates"]:
+        rate_in, rate = rate, rate * r
+        reach += 1.0 / rate_in + max((ks - 1) * sum(d + 1 for d in ds) for ks, ds in
+                                     zip(vocoder_config["resblock_kernel_sizes"], vocoder_config["resblock_dilation_sizes"])) / rate
+    return math.ceil(reach + 6.0 / rate)
+
+
+def repair_plan(ticks, window, requests):
+    """What a receive session with a repair window of ``window`` frames does with late packets: ``(taken, passes)``.
+
+    ``ticks``: ``[(first_frame, count), ...]``, the session's ticks in order since the ring was last cleared (creation, ``set_repair``,
+    ``set_conceal``), in session frames; the session has decoded ``first_frame + count`` of the last entry.  A tick is *retained* while
+    it holds any of the last ``window`` decoded frames.  ``requests``: ``[(row, stream_frame0, stream_frame, lost), ...]``, the ``late``
+    calls since the last tick in order: the slot, the session frame that is frame 0 of the slot's current stream (None: the slot is not
+    running), the frame's index in that stream, and whether the tick that decoded it was given it as not present.
+
+    ``taken[i]``: the frame belongs to the running stream (index >= 0), has been decoded, lies in a retained tick, was lost and has not
+    been handed in by an earlier request.  ``passes``: ``[(tick_index, [rows]), ...]``, oldest first: every row with a taken packet is
+    decoded again from the snapshot in front of the tick that holds its earliest late frame - the newest retained tick whose first
+    frame is not behind it - through the last tick; rows that start at the same tick share a pass.  Pure host arithmetic, the same as
+    the library's (csrc/stream_codec.hip: bvc_stream_codec_late and stream_apply_late)."""
+    done = ticks[-1][0] + ticks[-1][1] if ticks else 0
+    retained = [i for i, (f0, k) in enumerate(ticks) if f0 + k > done - window] if window > 0 else []
+    taken, seen, first = [], set(), {}
+    for row, frame0, stream_frame, lost in requests:
+        ok = frame0 is not None and stream_frame >= 0 and frame0 + stream_frame < done
+        at = None
+        if ok:
+            f = frame0 + stream_frame
+            at = next((i for i in retained if ticks[i][0] <= f < ticks[i][0] + ticks[i][1]), None)
+            ok = at is not None and bool(lost) and (row, f) not in seen
+        if ok:
+            seen.add((row, f))
+            first[row] = min(first.get(row, at), at)
+        taken.append(ok)
+    passes = [(t, sorted(r for r in first if first[r] == t)) for t in sorted(set(first.values()))]
+    return taken, passes
+
+
 class StreamingCodec:
     """BASELINE configs[4]: `batch` parallel streams, a fixed hop of new samples per tick, encode + decode of the frames
     each hop completes in ONE library call (``bvc_stream_codec_tick``: one persistent launch per recurrence where that
@@ -257,18 +302,31 @@ class StreamingCodec:
 
     ``conceal="prior"`` (receive sessions only; ``set_conceal`` switches between two pushes): a lost frame of an open slot is generated
     from the model's prior net at the decoder's own state instead, with the slot's current bit count, and ``filled_codes()`` gives the
-    codes with the gaps filled; every stream equals ``model.decode(codes, n, lost=..., bitrate=...)`` of its own packets alone."""
+    codes with the gaps filled; every stream equals ``model.decode(codes, n, lost=..., bitrate=...)`` of its own packets alone.
+
+    ``repair=W`` (receive sessions only, 0 .. 64 frames, 0 = off; ``set_repair`` changes it between two pushes): a network mostly
+    reorders, and a frame decoded without its bits leaves the decoder's state off the sender's for as long as the model remembers.
+    With a window the session keeps the decoder state in front of, and the input of, every push that holds one of its last W frames.
+    ``late(slot, stream_frame, packet)`` hands in a frame that was pushed as not present (``stream_frame`` counts as the third value of
+    ``slot_frames`` does) and returns whether it was taken: the slot is running, the frame is its current stream's, still within the
+    window and still marked lost (``repair_plan`` states the rule).  The next push first decodes every such row again from the kept
+    state in front of its earliest late frame - with the bit counts those frames had, generating again what is still lost - and
+    continues from a state that is bit for bit that of a session which got the packet in time: its ``filled_codes`` equal that
+    session's from this push on, its samples once the generator's history has flushed (``CONTEXT_FRAMES`` later).  What was
+    returned before is not touched.  ``set_conceal`` and ``set_repair`` empty the window."""
 
     DIRECTIONS = {"duplex": 0, "send": 1, "recv": 2}
     CONCEAL = {"none": 0, "prior": 1}
 
-    def __init__(self, model, batch, bitrate, hop=441, device=None, open_all=True, direction="duplex", conceal="none"):
+    def __init__(self, model, batch, bitrate, hop=441, device=None, open_all=True, direction="duplex", conceal="none", repair=0):
         if direction not in self.DIRECTIONS:
             raise ValueError(f"direction must be one of {sorted(self.DIRECTIONS)}")
         if conceal not in self.CONCEAL:
             raise ValueError(f"conceal must be one of {sorted(self.CONCEAL)}")
         if conceal != "none" and direction != "recv":
             raise ValueError("conceal: only a receive session has lost frames to conceal")
+        if repair and direction != "recv":
+            raise ValueError("repair: only a receive session has late packets to repair from")
         if direction != "send" and is_antialiased(model.conf):
             raise ValueError("StreamingCodec: " + NOT_CAUSAL)
         self.direction = direction
@@ -309,6 +367,9 @@ class StreamingCodec:
         self.conceal = "none"
         if conceal != "none":
             self.set_conceal(conceal)
+        self.repair = 0
+        if repair:
+            self.set_repair(repair)
 
     def __del__(self):
         try:
@@ -359,6 +420,25 @@ class StreamingCodec:
             raise ValueError(f"conceal must be one of {sorted(self.CONCEAL)}")
         self._slot_call(self.eng.lib.bvc_stream_codec_set_conceal(self.handle, self.CONCEAL[mode]))
         self.conceal = mode
+
+    def set_repair(self, window):
+        """The repair window in frames (0 .. 64, 0: off) from the next push on; empties the window.  Receive sessions only."""
+        with torch.cuda.device(self.dev):
+            self._slot_call(self.eng.lib.bvc_stream_codec_set_repair(self.handle, int(window)))
+        self.repair = int(window)
+
+    def late(self, slot, stream_frame, packet):
+        """A frame of the stream in `slot` that was pushed as not present: its index in the stream and its bytes (uint8 tensor or
+        bytes; fewer than ``bytes_per_frame`` are taken as the leading ones).  True if the next push repairs the row with it."""
+        raw = bytes(packet) if isinstance(packet, (bytes, bytearray)) else bytes(packet.detach().to("cpu", torch.uint8).reshape(-1).tolist())
+        if len(raw) > self.bytes_per_frame:
+            raise ValueError(f"late: a frame has at most {self.bytes_per_frame} bytes")
+        buf = (ctypes.c_uint8 * self.bytes_per_frame)(*raw)
+        taken = ctypes.c_int32()
+        with torch.cuda.device(self.dev):
+            self._slot_call(self.eng.lib.bvc_stream_codec_late(self.handle, int(slot), int(stream_frame), ctypes.cast(buf, ctypes.c_void_p),
+                                                               ctypes.byref(taken)))
+        return bool(taken.value)
 
     def filled_codes(self, k):
         """Receive session: the codes (batch, k, z_dim) the last push of k frames decoded - unpacked, and with ``conceal="prior"`` with

@@ -326,7 +326,7 @@ int  bvc_stream_codec_slot_frames(bvc_stream_codec *st, int32_t slot, int32_t *f
  *    unpacked d_codes).  Bytes and bits behind nbits_b are ignored.  A frame whose d_present byte is 0 is a LOST frame: it is
  *    decoded as a frame of no bits - codes all 0.5, what a variable-rate coder writes and reads at masked positions - whatever
  *    its bytes hold, and the GRU state moves on through it; the result equals bvc_decode of the same code tensor with those frames
- *    set to 0.5.  (A late packet is a lost packet; there is no reordering.  bvc_stream_codec_set_conceal(st, 1) generates lost frames from the
+ *    set to 0.5.  (A late packet is a lost packet unless the session has a repair window: bvc_stream_codec_set_repair below.  bvc_stream_codec_set_conceal(st, 1) generates lost frames from the
  *    model's prior instead: below.)  Idle rows
  *    are all 0.5 whatever their bytes and d_present hold.  Slots: a receive tick is frame-aligned, so open reports delay 0 and the
  *    stream's frame 0 is the first frame of the next tick, in which - ahead of its own work, for those rows only, in one launch -
@@ -363,6 +363,35 @@ int  bvc_stream_codec_tick_recv(bvc_stream_codec *st, int32_t n_frames, void *st
 int  bvc_stream_codec_finish(bvc_stream_codec *st, int32_t slot, int32_t n_last);
 int  bvc_stream_codec_slot_state(bvc_stream_codec *st, int32_t slot, int32_t *state);
 int  bvc_stream_codec_set_conceal(bvc_stream_codec *st, int32_t mode);
+
+/* Repair window (RECV only; BVC_EINVAL on any other session): a network mostly reorders, and the codec is closed-loop - once the decoder
+ * has stepped through a frame with the wrong code its state is no longer the sender's.  With a window of W frames (0 .. 64; 0, the
+ * default: off - such a session launches exactly what it launched before and allocates nothing) the session retains, for every tick
+ * that holds any of the last W decoded frames, h_dec in front of the tick (taken behind the tick's row starts: a stream that begins
+ * with the tick is kept at its zero state) and per (row, frame) of the tick the packet bytes as given, the d_present byte and the bits
+ * per frame in force: one more small launch per tick, outside the tick's graph.
+ *  - late(slot, stream_frame, packet, taken): the bytes (host memory, bytes_per_frame of them) of ONE frame that a tick was given as
+ *    not present; stream_frame counts in the slot's own stream, as slot_frames' stream_frame0 does.  Host bookkeeping between two ticks,
+ *    like open / close / set_bits.  *taken = 1 if the slot is running, the frame belongs to its current stream, lies in a retained
+ *    tick and is still marked lost.  *taken = 0 - no error, the session untouched - if the frame is older than the window, arrived in
+ *    time, was handed in late before, or has not been decoded yet (put it into the next tick), and for an idle or waiting slot.
+ *    BVC_EINVAL: a slot out of range, a session that is not a receive session.
+ *  - At the head of the next bvc_stream_codec_tick_recv, before that tick's own frames and outside any graph, the packets taken since
+ *    the last tick are written into the ring (bytes, present = 1) and every row that got one is decoded again from the retained state
+ *    in front of its earliest late frame up to now: tick by tick what the session's ticks ran for those frames, on a compact batch of
+ *    those rows - unpacked with the RING's bits per frame, not the slot's current ones; with set_conceal(1) a frame that is still lost
+ *    inside the span is generated again, from the repaired state.  Rows with the same first tick share a pass.  The mel frames and
+ *    filled codes of a pass are dropped, its last state goes to h_dec and the states in between into the ring, so a second late packet
+ *    of the row replays from a repaired state.  Then the tick runs as ever.
+ *  - From that tick on the row's filled codes and its state equal, bit for bit, those of a session that was given the packet in time;
+ *    its samples equal that session's once the generator's history has flushed, 26 frames later.  Samples already returned are not
+ *    touched, other rows never differ.
+ *  - set_conceal and set_repair forget what the ring holds (the two recurrence programs agree only to rounding: a frame is replayed by
+ *    the program that first decoded it): late packets for frames before such a call are not taken.  close drops what the slot's
+ *    stream still had queued.  set_repair allocates the ring and the replay's buffers ((B, W + max_frames_per_tick - 1) frames);
+ *    BVC_ENOMEM, the session as before, if they cannot be had; it synchronises the device. */
+int  bvc_stream_codec_set_repair(bvc_stream_codec *st, int32_t window_frames);
+int  bvc_stream_codec_late(bvc_stream_codec *st, int32_t slot, int64_t stream_frame, const uint8_t *packet, int32_t *taken);
 
 /* BVRNNCodecModel.encode (bvrnn_codec_model.py:44-62): scale, log-mel, bits/frame =
  * bits_per_frame for every (b,t), zero initial state, BVRNN.encode.  d_wav (B,L) -> d_codes. */

@@ -10,7 +10,13 @@ streams start ("join": per-row reset of the GRU states, the generator histories 
 --direction send|recv|duplex [--loss P]: the same 256 streams and inputs through a session that runs one half (send: samples ->
 packets; recv: packets -> samples) or both (duplex, the default run's loopback tick).  recv replays the packets of a send run
 (not timed) in ticks of the frame counts that run emitted; --loss P marks a seeded share P of the frames as not arrived;
---conceal none|prior (recv only): what the session does with them (none: frames of no bits; prior: generated from the prior net)."""
+--conceal none|prior (recv only): what the session does with them (none: frames of no bits; prior: generated from the prior net);
+--repair W (recv only): the session keeps a repair window of W frames (no packet arrives late: what the window itself costs a tick).
+
+--late P [--delay D] [--repair W] [--conceal none|prior]: a receive session with a repair window (default 16 frames) in which a seeded
+share P of the frames is pushed as not arrived and handed in with ``late`` D ticks afterwards (default 2).  A tick's time includes
+its ``late`` calls.  Reports the ticks that repair nothing ("steady") and those that replay ("repair") separately, with the passes
+(groups of rows that replay from the same tick) per repair tick."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -70,11 +76,57 @@ def churn():
     print(json.dumps(out))
 
 
+def argval(name, default, cast):
+    return cast(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+def late():
+    share, delay, W = argval("--late", 0.01, float), argval("--delay", 2, int), argval("--repair", 16, int)
+    conceal = argval("--conceal", "none", str)
+    model = make_model()[0]
+    x = synth.synthetic_speech(B, hop * hops, seed=3, kind="noise").to("cuda:0")
+    tx = StreamingCodec(model, B, 3000, hop=hop, direction="send")
+    sent = [tx.push(x[:, i * hop:(i + 1) * hop])[0].clone() for i in range(hops)]
+    sent = [p for p in sent if p.shape[1]]
+    del tx
+    g = torch.Generator().manual_seed(11)
+    lost = [torch.rand(B, p.shape[1], generator=g) < share for p in sent]
+    first = np.cumsum([0] + [p.shape[1] for p in sent])
+    host = [p.cpu().numpy() for p in sent]
+    sc = StreamingCodec(model, B, 3000, direction="recv", conceal=conceal, repair=W)
+    lat, passes, rows, taken, asked = [], [], [], 0, 0
+    for t, (p, lo) in enumerate(zip(sent, lost)):
+        due = lost[t - delay].nonzero().tolist() if t >= delay else []
+        present = (~lo).to(torch.uint8).to("cuda:0")
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        got = [sc.late(b, int(first[t - delay]) + j, host[t - delay][b, j].tobytes()) for b, j in due]
+        sc.push_packets(p, present)
+        torch.cuda.synchronize(); lat.append((time.perf_counter() - t0) * 1e3)
+        asked += len(due); taken += sum(got)
+        passes.append(1 if any(got) else 0)                 # the frames of ONE earlier tick: their rows start together
+        rows.append(len({b for (b, j), ok in zip(due, got) if ok}))
+    model.check_status()
+    lat, passes, rows = np.array(lat[50:]), np.array(passes[50:]), np.array(rows[50:])
+    out = {"config": f"BASELINE configs[4]: {B} streams x 20 ms hops @ 3 kbit/s, recv session, repair window {W} frames, "
+                     f"{share:.0%} of the frames {delay} ticks late", "conceal": conceal, "late_taken": taken, "late_handed_in": asked,
+           "hop_budget_ms": 20.0}
+    for name, sel in (("steady", passes == 0), ("repair", passes > 0)):
+        if sel.any():
+            v = lat[sel]
+            out[name] = {"ticks": int(v.size), "p50_ms": round(float(np.percentile(v, 50)), 3), "p99_ms": round(float(np.percentile(v, 99)), 3),
+                         "max_ms": round(float(v.max()), 3)}
+    if (passes > 0).any():
+        out["passes_per_repair_tick"] = round(float(passes[passes > 0].mean()), 2)
+        out["rows_per_repair_tick"] = round(float(rows[passes > 0].mean()), 1)
+    print(json.dumps(out))
+
+
 def direction(which):
     loss = float(sys.argv[sys.argv.index("--loss") + 1]) if "--loss" in sys.argv else 0.0
     conceal = sys.argv[sys.argv.index("--conceal") + 1] if "--conceal" in sys.argv else None
-    if conceal is not None and which != "recv":
-        sys.exit("--conceal belongs to --direction recv")
+    repair = argval("--repair", 0, int)
+    if (conceal is not None or repair) and which != "recv":
+        sys.exit("--conceal and --repair belong to --direction recv")
     model = make_model()[0]
     x = synth.synthetic_speech(B, hop * hops, seed=3, kind="noise").to("cuda:0")
     lat, frames = [], 0
@@ -85,7 +137,7 @@ def direction(which):
         del tx
         g = torch.Generator().manual_seed(11)
         present = [(torch.rand(B, p.shape[1], generator=g) >= loss).to(torch.uint8).to("cuda:0") for p in sent]
-        sc = StreamingCodec(model, B, 3000, direction="recv", **({} if conceal is None else {"conceal": conceal}))
+        sc = StreamingCodec(model, B, 3000, direction="recv", repair=repair, **({} if conceal is None else {"conceal": conceal}))
         for p, pr in zip(sent, present):
             torch.cuda.synchronize(); t0 = time.perf_counter()
             sc.push_packets(p, pr)
@@ -104,13 +156,16 @@ def direction(which):
     n = len(lat)
     lat = np.array(lat[50:]) * 1e3
     print(json.dumps({"config": f"BASELINE configs[4]: {B} streams x 20 ms hops @ 3 kbit/s, {which} session",
-                      "direction": which, "conceal": conceal, "ticks": n, "timed_ticks": int(lat.size), "frames_lost": round(lost, 4),
+                      "direction": which, "conceal": conceal, "repair": repair, "ticks": n, "timed_ticks": int(lat.size), "frames_lost": round(lost, 4),
                       "p50_ms": round(float(np.percentile(lat, 50)), 3), "p99_ms": round(float(np.percentile(lat, 99)), 3),
                       "mean_ms": round(float(lat.mean()), 3), "hop_budget_ms": 20.0, "frames_per_tick": round(frames / n, 3)}))
 
 
 if "--churn" in sys.argv:
     churn()
+    sys.exit(0)
+if "--late" in sys.argv:
+    late()
     sys.exit(0)
 if "--direction" in sys.argv:
     which = sys.argv[sys.argv.index("--direction") + 1]
