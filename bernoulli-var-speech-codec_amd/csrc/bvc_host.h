@@ -135,6 +135,13 @@ extern thread_local bool g_capturing;     // no event probes while THIS thread c
 extern thread_local bool g_stream_tick;   // inside bvc_stream_codec_tick: a launch-per-layer recurrence is launched eagerly (the tick itself is the graph)
 extern thread_local bool g_tick_flow;     // ... of a tick that is NOT a graph: its recurrences may take the persistent kernel
 extern std::mutex g_flow_mu;              // persistent launches and the residency census, one at a time per process (recurrence.hip)
+// the two tick flags for a scope (a tick's body, a replay pass): no path out of it leaves them set
+struct TickFlags {
+    explicit TickFlags(bool flow) { g_stream_tick = true; g_tick_flow = flow; }
+    ~TickFlags() { g_stream_tick = false; g_tick_flow = false; }
+    TickFlags(const TickFlags &) = delete;
+    TickFlags &operator=(const TickFlags &) = delete;
+};
 
 // in-kernel timestamp probes for the graph-replayed recurrent kernels (wall_clock64, 100 MHz)
 struct KProbe {

@@ -1,5 +1,6 @@
 #include <algorithm>
 #include <memory>
+#include <utility>
 
 #include "bvc_host.h"
 
@@ -77,38 +78,11 @@ __global__ __launch_bounds__(256) void sc_slot_update_kernel(SlotUpdateList l, c
 // the tick that emits frame 0 of the rows in `l`, after the append: what a new session has at tick 0, for those rows only.
 // blockIdx.y < n_ten: that tensor's history rows of the generator (both copies, where the windows stand); blockIdx.y == n_ten: the left
 // reflect padding x[-i] = x[i] (the row's sample 0 sits `pad` samples into the buffer: its frame 0 is the first of this tick), both GRU
-// states, the row's age
+// states, the row's age.  A session that runs one half (bvc_stream_codec_create_dir) resets that half: h_dec != nullptr is the decoder half
+// (generator histories, h_dec, age), h_enc != nullptr the encoder half (left reflect padding, h_enc; alone it is launched with n_ten = 0).
 __global__ __launch_bounds__(256) void sc_slot_start_kernel(SlotRowList l, const RotEntry *__restrict__ tab, int n_ten, int cursor,
                                                             float *__restrict__ sbuf, int cap, int pad, float *__restrict__ h_enc,
                                                             float *__restrict__ h_dec, int Hd, int *__restrict__ age) {
-    const int row = l.row[blockIdx.z];
-    if ((int)blockIdx.y < n_ten) {
-        const RotEntry e = tab[blockIdx.y];
-        const long long n4 = (long long)e.H * e.C / 4;
-        const long long at = (long long)row * e.bs + (long long)cursor * e.rate * e.C;
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int q = 0; q < (e.buf[1] == e.buf[0] ? 1 : 2); ++q) {
-            float4 *d = reinterpret_cast<float4 *>(e.buf[q] + at);
-            for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) d[i] = z;
-        }
-        return;
-    }
-    if (blockIdx.x == 0) {
-        float *d = sbuf + (long long)row * cap;
-        for (int i = 1 + threadIdx.x; i <= pad; i += 256) d[pad - i] = d[pad + i];
-        if (threadIdx.x == 0) age[row] = 0;
-    }
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < Hd; i += gridDim.x * 256) {
-        h_enc[(long long)row * Hd + i] = 0.0f;
-        h_dec[(long long)row * Hd + i] = 0.0f;
-    }
-}
-
-// the same reset in a session that runs one half (bvc_stream_codec_create_dir).  h_dec != nullptr: the decoder half (generator histories,
-// h_dec, age; blockIdx.y as above); h_enc != nullptr: the encoder half (left reflect padding, h_enc; launched with n_ten = 0).
-__global__ __launch_bounds__(256) void sc_slot_start_half_kernel(SlotRowList l, const RotEntry *__restrict__ tab, int n_ten, int cursor,
-                                                                 float *__restrict__ sbuf, int cap, int pad, float *__restrict__ h_enc,
-                                                                 float *__restrict__ h_dec, int Hd, int *__restrict__ age) {
     const int row = l.row[blockIdx.z];
     if ((int)blockIdx.y < n_ten) {
         const RotEntry e = tab[blockIdx.y];
@@ -156,7 +130,7 @@ __global__ __launch_bounds__(256) void sc_finish_kernel(SlotUpdateList l, const 
 
 // ---- repair window (bvc_stream_codec_set_repair / _late): a receive session keeps, for the ticks that hold its last W frames, the decoder
 // state in front of the tick and what the tick was given (bytes, present, bits per frame), so that a packet that arrives late can be put
-// where it belonged and the recurrence replayed from there.  Ring slot r of tick t = t % ring_n; per slot h (B, Hd), packets (B, kmax,
+// where it belonged and the recurrence replayed from there.  Ring slot r of tick t = t % n; per slot h (B, Hd), packets (B, kmax,
 // bpf), present (B, kmax), bits (B, kmax), the slots `hs` floats / `pks` bytes / `prs` bytes / `bs` floats apart.
 const int SC_LATE_BYTES = 16;                            // bytes per frame a late packet can carry in a kernel argument (z_dim <= 128)
 const int SC_CHUNKS = 64;                                // ticks a replay can span: the window is at most 64 frames
@@ -259,37 +233,44 @@ struct bvc_stream_codec {
     int dir = BVC_STREAM_DUPLEX, bpf = 0;
     uint8_t *packets = nullptr, *present = nullptr;
     float *bits_of(int k) const { return bitsbuf + (size_t)B * (k * (k - 1) / 2); }
-    hipGraphExec_t graph[8][2] = {};    // [k][vocoder parity]
-    hipGraphExec_t graph_conceal[8][2] = {};      // ... of the ticks that conceal from the prior
+    const float *tick_bits(int k) const { return m->cfg.var_bit ? bits_of(k) : nullptr; }     // a fixed-rate model reads no bit counts
+    hipGraphExec_t graph[2][8][2] = {}; // [conceal][k][vocoder parity]
     int conceal = 0;                    // receive sessions: 0 = a lost frame is a frame of no bits, 1 = generated from the prior (bvc_stream_codec_set_conceal)
-    // repair window (bvc_stream_codec_set_repair; receive sessions): 0 = off, nothing below is allocated and no tick launches more
-    struct RingTick { int64_t f0 = 0; int k = 0; bool valid = false; hipEvent_t ev = nullptr; };    // session frames [f0, f0 + k)
-    struct LateReq { int row, slot, j; int64_t tick; unsigned char bytes[SC_LATE_BYTES]; };
-    int repair_w = 0, ring_n = 0;
-    std::vector<RingTick> ring;         // slot of tick t: t % ring_n
-    std::vector<LateReq> late;          // taken since the last tick: the next tick applies them
-    char *ring_pool = nullptr;
-    float *ring_h = nullptr, *ring_bits = nullptr, *r_h = nullptr, *r_bits = nullptr, *r_sel = nullptr, *r_codes = nullptr;
-    uint8_t *ring_pk = nullptr, *ring_pr = nullptr, *r_pk = nullptr, *r_pr = nullptr;
-    uint8_t *h_present = nullptr, *d_hpresent = nullptr;    // host-mapped mirror of ring_pr: what `late` looks at (and marks)
-    int *r_zero = nullptr;              // row_off of a replay: every (row, frame) of the compact batch belongs to a running stream
-    long long ring_hs = 0, ring_pks = 0, ring_prs = 0, ring_bs = 0;
-    bool tick_retained(const RingTick &t) const { return t.valid && t.f0 + t.k > frames - repair_w; }
-    void repair_free() {
-        for (auto &t : ring) if (t.ev) (void)hipEventDestroy(t.ev);
-        ring.clear(); late.clear();
-        if (ring_pool) (void)hipFree(ring_pool);
-        if (h_present) (void)hipHostFree(h_present);
-        ring_pool = nullptr; h_present = d_hpresent = nullptr;
-        repair_w = ring_n = 0;
-    }
+    // repair window (bvc_stream_codec_set_repair; receive sessions): w = 0 is off, nothing is allocated and no tick launches more.  Owns the
+    // ring, the replay's buffers, the host mirror and the events; bvc_stream_codec_set_repair builds one aside and moves it in.
+    struct RepairMem {                  // (plain values: a move swaps them as one)
+        int w = 0, n = 0;               // frames of the window / ticks the ring holds
+        char *pool = nullptr;
+        float *ring_h = nullptr, *ring_bits = nullptr, *r_h = nullptr, *r_bits = nullptr, *r_sel = nullptr, *r_codes = nullptr;
+        uint8_t *ring_pk = nullptr, *ring_pr = nullptr, *r_pk = nullptr, *r_pr = nullptr;
+        uint8_t *h_present = nullptr, *d_hpresent = nullptr;    // host-mapped mirror of ring_pr: what `late` looks at (and marks)
+        int *r_zero = nullptr;          // row_off of a replay: every (row, frame) of the compact batch belongs to a running stream
+        long long hs = 0, pks = 0, prs = 0, bs = 0;
+    };
+    struct RepairWindow : RepairMem {
+        struct RingTick { int64_t f0 = 0; int k = 0; bool valid = false; hipEvent_t ev = nullptr; };    // session frames [f0, f0 + k)
+        struct LateReq { int row, slot, j; int64_t tick; unsigned char bytes[SC_LATE_BYTES]; };
+        std::vector<RingTick> ring;     // slot of tick t: t % n
+        std::vector<LateReq> late;      // taken since the last tick: the next tick applies them
+        RepairWindow() = default;
+        RepairWindow(RepairWindow &&o) noexcept { swap(o); }
+        RepairWindow &operator=(RepairWindow &&o) noexcept { swap(o); return *this; }     // o leaves with what this held, and releases it
+        void swap(RepairWindow &o) noexcept { std::swap<RepairMem>(*this, o); ring.swap(o.ring); late.swap(o.late); }
+        // forgets what the ring holds (set_conceal, set_repair: a frame is replayed by the program that first decoded it, or not at all)
+        void clear() { for (auto &t : ring) t.valid = false; late.clear(); }
+        ~RepairWindow() {
+            for (auto &t : ring) if (t.ev) (void)hipEventDestroy(t.ev);
+            if (pool) (void)hipFree(pool);
+            if (h_present) (void)hipHostFree(h_present);
+        }
+    };
+    RepairWindow rep;
+    bool tick_retained(const RepairWindow::RingTick &t) const { return t.valid && t.f0 + t.k > frames - rep.w; }
     bool use_graph = true;
     bool tick_flow = true;      // the ticks' recurrences on the persistent kernel where it is available (BVC_STREAM_FLOW=0: never)
     ~bvc_stream_codec() {
-        for (auto &gk : graph) for (auto g : gk) if (g) (void)hipGraphExecDestroy(g);
-        for (auto &gk : graph_conceal) for (auto g : gk) if (g) (void)hipGraphExecDestroy(g);
+        for (auto &gc : graph) for (auto &gk : gc) for (auto g : gk) if (g) (void)hipGraphExecDestroy(g);
         if (voc) bvc_vocoder_stream_destroy(voc);
-        repair_free();
         if (pool) (void)hipFree(pool);
     }
 };
@@ -313,94 +294,104 @@ void join_plan(int64_t samples, int hop_samples, const bvc_config &c, int *delay
     if (tick0) *tick0 = tick_of_frame(f, hop_samples, c);
 }
 
-// pending slot changes -> device, in one launch per SC_LIST slots (before the tick's append)
-int stream_send_pending(bvc_stream_codec *st, hipStream_t s) {
-    SlotUpdateList l;
+// Items 0 .. n - 1 to the device in lists of up to SC_LIST entries.  fill(l, i) adds item i's entry to l, or none, and does the host's
+// bookkeeping for it; it returns BVC_OK, an error code, or LIST_DONE when no later item has an entry.  launch(l, first) sends a full
+// list, or the last partial one; `first` entries went in the launches before it.  Stops at the first error code.
+const int LIST_DONE = 1;
+template <class List, class Fill, class Launch>
+int send_lists(int n, Fill fill, Launch launch) {
+    List l;
     l.n = 0;
+    int first = 0;
     auto flush = [&]() -> int {
         if (l.n == 0) return BVC_OK;
-        sc_slot_update_kernel<<<dim3(l.n), 256, 0, s>>>(l, st->d_state, st->row_off, st->sbuf, st->cap, st->bitsbuf, st->B, st->kmax);
+        launch(l, first);
         BVC_HIP_TRY(hipGetLastError());
+        first += l.n;
         l.n = 0;
         return BVC_OK;
     };
-    int rc;
-    for (int b = 0; b < st->B && st->n_pending > 0; ++b) {
+    for (int i = 0; i < n; ++i) {
+        int rc = fill(l, i);
+        if (rc == LIST_DONE) break;
+        if (rc || (l.n == SC_LIST && (rc = flush()))) return rc;
+    }
+    return flush();
+}
+
+// pending slot changes -> device, in one launch per SC_LIST slots (before the tick's append)
+int stream_send_pending(bvc_stream_codec *st, hipStream_t s) {
+    const int rc = send_lists<SlotUpdateList>(st->B, [&](SlotUpdateList &l, int b) -> int {
+        if (st->n_pending <= 0) return LIST_DONE;
         bvc_stream_codec::Slot &sl = st->slots[b];
-        if (!sl.pending) continue;
+        if (!sl.pending) return BVC_OK;
         l.e[l.n++] = SlotUpdate{b, sl.open ? sl.delay : -1, st->sbuf ? sl.pending : (sl.pending & ~SC_ZERO_TAIL), sl.bits};   // (a receive session has no samples)
         sl.pending = 0;
         --st->n_pending;
-        if (l.n == SC_LIST && (rc = flush())) return rc;
-    }
-    st->n_pending = 0;
-    return flush();
+        return BVC_OK;
+    }, [&](const SlotUpdateList &l, int) {
+        sc_slot_update_kernel<<<dim3(l.n), 256, 0, s>>>(l, st->d_state, st->row_off, st->sbuf, st->cap, st->bitsbuf, st->B, st->kmax);
+    });
+    if (!rc) st->n_pending = 0;                              // (every pending slot has been visited: a guard against a miscount)
+    return rc;
 }
 
 // the rows whose frame 0 is the first frame of this tick (frames [f_begin, f_begin + k)): per-row reset, after the append
 int stream_start_rows(bvc_stream_codec *st, int64_t f_begin, int k, hipStream_t s) {
     const bvc_config &c = st->m->cfg;
     const bvc_vocoder_stream *v = st->voc;
-    SlotRowList l;
-    l.n = 0;
-    auto flush = [&]() -> int {
-        if (l.n == 0) return BVC_OK;
-        if (st->dir == BVC_STREAM_SEND) {                    // encoder half only: left reflect padding, h_enc
-            sc_slot_start_half_kernel<<<dim3(4, 1, (unsigned)l.n), 256, 0, s>>>(l, nullptr, 0, 0, st->sbuf, st->cap, c.pad_left, st->h_enc,
-                                                                                  nullptr, c.h_dim, st->age);
-        } else {
-            const unsigned gx = (unsigned)std::max(1, std::min(16, (v->max_hc4 + 255) / 256));
-            if (st->dir == BVC_STREAM_RECV)                  // decoder half only: generator histories, h_dec, age
-                sc_slot_start_half_kernel<<<dim3(gx, (unsigned)v->n_ten + 1, (unsigned)l.n), 256, 0, s>>>(
-                    l, v->d_tab, v->n_ten, v->slide ? v->cursor : 0, nullptr, 0, 0, nullptr, st->h_dec, c.h_dim, st->age);
-            else
-                sc_slot_start_kernel<<<dim3(gx, (unsigned)v->n_ten + 1, (unsigned)l.n), 256, 0, s>>>(
-                    l, v->d_tab, v->n_ten, v->slide ? v->cursor : 0, st->sbuf, st->cap, c.pad_left, st->h_enc, st->h_dec, c.h_dim, st->age);
-        }
-        BVC_HIP_TRY(hipGetLastError());
-        l.n = 0;
-        return BVC_OK;
-    };
-    int rc;
-    for (int b = 0; b < st->B && st->n_waiting > 0; ++b) {
+    // the halves the session runs.  With a decoder half one blockIdx.y per generator tensor and one more; a send session has no generator
+    // (voc is null exactly there: bvc_stream_codec_create_dir makes it for the decoder half): n_ten = 0 and a grid of its own.  The
+    // pointers of a half that is not there are null in the session already, and a receive session's cap is 0.
+    const bool enc = st->dir != BVC_STREAM_RECV;
+    const int n_ten = v ? v->n_ten : 0;
+    const unsigned gx = v ? (unsigned)std::max(1, std::min(16, (v->max_hc4 + 255) / 256)) : 4u;
+    return send_lists<SlotRowList>(st->B, [&](SlotRowList &l, int b) -> int {
+        if (st->n_waiting <= 0) return LIST_DONE;
         bvc_stream_codec::Slot &sl = st->slots[b];
-        if (!sl.open || sl.started || sl.frame0 >= f_begin + k) continue;
+        if (!sl.open || sl.started || sl.frame0 >= f_begin + k) return BVC_OK;
         if (sl.frame0 != f_begin) { set_error("bvc_stream_codec_tick: slot %d starts inside a tick (frame %lld of %lld+%d)", b, (long long)sl.frame0, (long long)f_begin, k); return BVC_EINVAL; }
         sl.started = true;
         --st->n_waiting;
         l.row[l.n++] = b;
-        if (l.n == SC_LIST && (rc = flush())) return rc;
-    }
-    return flush();
+        return BVC_OK;
+    }, [&](const SlotRowList &l, int) {
+        sc_slot_start_kernel<<<dim3(gx, (unsigned)n_ten + 1, (unsigned)l.n), 256, 0, s>>>(
+            l, v ? v->d_tab : nullptr, n_ten, v && v->slide ? v->cursor : 0, st->sbuf, st->cap, enc ? c.pad_left : 0, st->h_enc, st->h_dec,
+            c.h_dim, st->age);
+    });
 }
 
 // the rows whose stream ends with the hop this tick has just appended (bvc_stream_codec_finish): right reflect padding behind the last
 // sample, the row drains from here on.  One launch per SC_LIST rows, only in such a tick.
 int stream_finish_rows(bvc_stream_codec *st, hipStream_t s) {
     const bvc_config &c = st->m->cfg;
-    SlotUpdateList l;
-    l.n = 0;
-    auto flush = [&]() -> int {
-        if (l.n == 0) return BVC_OK;
-        sc_finish_kernel<<<dim3(l.n), 256, 0, s>>>(l, st->d_state, st->row_off, st->sbuf, st->cap, c.n_fft - c.hop - c.pad_left);
-        BVC_HIP_TRY(hipGetLastError());
-        l.n = 0;
-        return BVC_OK;
-    };
-    int rc;
-    for (int b = 0; b < st->B && st->n_finishing > 0; ++b) {
+    const int rc = send_lists<SlotUpdateList>(st->B, [&](SlotUpdateList &l, int b) -> int {
+        if (st->n_finishing <= 0) return LIST_DONE;
         bvc_stream_codec::Slot &sl = st->slots[b];
-        if (sl.fin_last < 0) continue;
+        if (sl.fin_last < 0) return BVC_OK;
         // n samples in all -> bvc_num_frames(n) = n / hop frames, the same as the offline call
         const int64_t n = (st->ticks - sl.open_tick) * st->hop + sl.fin_last;
         sl.end_frame = sl.frame0 + n / c.hop;
         l.e[l.n++] = SlotUpdate{b, sl.fin_last, 0, 0.0f};
         sl.fin_last = -1;
         --st->n_finishing;
-        if (l.n == SC_LIST && (rc = flush())) return rc;
-    }
-    st->n_finishing = 0;
-    return flush();
+        return BVC_OK;
+    }, [&](const SlotUpdateList &l, int) {
+        sc_finish_kernel<<<dim3(l.n), 256, 0, s>>>(l, st->d_state, st->row_off, st->sbuf, st->cap, c.n_fft - c.hop - c.pad_left);
+    });
+    if (!rc) st->n_finishing = 0;
+    return rc;
+}
+
+// the decode half of a tick, or of a tick that a replay decodes again: k frames of B rows from state h to state h, the mel frames to
+// melhat.  A session that conceals generates the frames that `sel` marks and writes what it filled in back into `codes`.  (check_ws only
+// adds up offsets on the host, the same ones for the same (B, k): a tick that has laid its workspace out already pays that sum twice.)
+int decode_frames(bvc_stream_codec *st, int B, int k, float *codes, const float *sel, float *h, hipStream_t s) {
+    Workspace w;
+    if (int rc = check_ws(st->m, B, k, st->ws, st->ws_bytes, &w)) return rc;
+    if (st->conceal) return run_decode_conceal(st->m, w, st->ws, codes, sel, h, B, k, st->melhat, h, codes, nullptr, s);
+    return run_decode(st->m, w, st->ws, codes, h, B, k, st->melhat, h, s);
 }
 
 // the launches of one tick with k new frames (k > 0), in stream order
@@ -412,29 +403,22 @@ int stream_tick_body(bvc_stream_codec *st, int k, hipStream_t s) {
     if ((rc = check_ws(m, B, k, st->ws, st->ws_bytes, &w))) return rc;
     if (st->dir == BVC_STREAM_RECV) {
         // the wire -> codes: every row's own bit count, 0.5 for what did not arrive and for idle rows
-        if ((rc = launch_unpack_rows(st->packets, st->present, m->cfg.var_bit ? st->bits_of(k) : nullptr, st->row_off, B, k, m->cfg.z_dim,
-                                     st->kmax, st->codes, s))) return rc;
-        if (st->conceal) {
-            // lost frames of open rows are generated with the row's bit count (all z bits on a fixed-rate model); idle rows keep their 0.5
-            if ((rc = launch_conceal_select(st->present, st->kmax, m->cfg.var_bit ? st->bits_of(k) : nullptr, (float)m->cfg.z_dim, st->row_off, B, k,
-                                            w.bits, s))) return rc;
-            if ((rc = run_decode_conceal(m, w, st->ws, st->codes, w.bits, st->h_dec, B, k, st->melhat, st->h_dec, st->codes, nullptr, s))) return rc;
-        } else
-        if ((rc = run_decode(m, w, st->ws, st->codes, st->h_dec, B, k, st->melhat, st->h_dec, s))) return rc;
-        return bvc_vocoder_stream_push(st->voc, st->melhat, k, st->out_div, st->wav, s);
+        if ((rc = launch_unpack_rows(st->packets, st->present, st->tick_bits(k), st->row_off, B, k, m->cfg.z_dim, st->kmax, st->codes, s))) return rc;
+        // lost frames of open rows are generated with the row's bit count (all z bits on a fixed-rate model); idle rows keep their 0.5
+        if (st->conceal && (rc = launch_conceal_select(st->present, st->kmax, st->tick_bits(k), (float)m->cfg.z_dim, st->row_off, B, k, w.bits, s))) return rc;
+    } else {
+        // front-end on the sample buffer: frame j of this tick reads sbuf[:, 256 j : 256 j + 1024)
+        if ((rc = launch_stft_logmel(m->fe, st->sbuf, B, st->cap, k, 0, st->scale, st->mel, s))) return rc;
+        // drop the 256 k samples no later frame reads (through a scratch copy: the ranges overlap)
+        const int keep = st->cap - 256 * k;
+        sc_shift_kernel<<<dim3((unsigned)((keep + 255) / 256), B), 256, 0, s>>>(st->sbuf, st->cap, 256 * k, st->stmp, st->cap, keep);
+        sc_shift_kernel<<<dim3((unsigned)((keep + 255) / 256), B), 256, 0, s>>>(st->stmp, st->cap, 0, st->sbuf, st->cap, keep);
+        BVC_HIP_TRY(hipGetLastError());
+        if ((rc = run_encode(m, w, st->ws, st->mel, st->tick_bits(k), st->h_enc, B, k, st->codes, nullptr, st->h_enc, nullptr, s))) return rc;
+        if (st->dir == BVC_STREAM_SEND)                      // codes -> the wire, and that is the tick
+            return launch_pack_rows(st->codes, st->tick_bits(k), B, k, m->cfg.z_dim, st->kmax, st->packets, s);
     }
-    // front-end on the sample buffer: frame j of this tick reads sbuf[:, 256 j : 256 j + 1024)
-    if ((rc = launch_stft_logmel(m->fe, st->sbuf, B, st->cap, k, 0, st->scale, st->mel, s))) return rc;
-    // drop the 256 k samples no later frame reads (through a scratch copy: the ranges overlap)
-    const int keep = st->cap - 256 * k;
-    sc_shift_kernel<<<dim3((unsigned)((keep + 255) / 256), B), 256, 0, s>>>(st->sbuf, st->cap, 256 * k, st->stmp, st->cap, keep);
-    sc_shift_kernel<<<dim3((unsigned)((keep + 255) / 256), B), 256, 0, s>>>(st->stmp, st->cap, 0, st->sbuf, st->cap, keep);
-    BVC_HIP_TRY(hipGetLastError());
-    if ((rc = run_encode(m, w, st->ws, st->mel, m->cfg.var_bit ? st->bits_of(k) : nullptr, st->h_enc, B, k, st->codes, nullptr, st->h_enc,
-                         nullptr, s))) return rc;
-    if (st->dir == BVC_STREAM_SEND)                          // codes -> the wire, and that is the tick
-        return launch_pack_rows(st->codes, m->cfg.var_bit ? st->bits_of(k) : nullptr, B, k, m->cfg.z_dim, st->kmax, st->packets, s);
-    if ((rc = run_decode(m, w, st->ws, st->codes, st->h_dec, B, k, st->melhat, st->h_dec, s))) return rc;
+    if ((rc = decode_frames(st, B, k, st->codes, w.bits, st->h_dec, s))) return rc;
     return bvc_vocoder_stream_push(st->voc, st->melhat, k, st->out_div, st->wav, s);
 }
 
@@ -461,11 +445,11 @@ int stream_run_body(bvc_stream_codec *st, int k, hipStream_t s) {
     // BVC_STREAM_FLOW=0) the warm tick is one hipGraph of launch-per-layer kernels as before.  Same bits either way.
     const bool tick_flow = st->tick_flow && flow_chains_static(st->m, B) != 0;
     const bool warm = !tick_flow && !slide && st->use_graph && s != nullptr && st->frames >= STREAM_WARM_FRAMES;     // (the default stream cannot be captured)
-    g_stream_tick = true; g_tick_flow = tick_flow;
+    TickFlags flags(tick_flow);
     if (!warm) {
         rc = stream_tick_body(st, k, s);
     } else {
-        hipGraphExec_t &ge = (st->conceal ? st->graph_conceal : st->graph)[k][parity];
+        hipGraphExec_t &ge = st->graph[st->conceal][k][parity];
         if (!ge) {                                       // first warm tick of this shape: capture it (the capture does not execute)
             hipGraph_t graph = nullptr;
             const int vp = parity; const int64_t vf = st->voc ? st->voc->frames : 0;
@@ -484,7 +468,6 @@ int stream_run_body(bvc_stream_codec *st, int k, hipStream_t s) {
             if (st->voc) { st->voc->parity ^= 1; st->voc->frames += k; }  // what stream_push() does on the host side
         }
     }
-    g_stream_tick = false; g_tick_flow = false;
     return rc;
 }
 
@@ -492,23 +475,18 @@ int stream_run_body(bvc_stream_codec *st, int k, hipStream_t s) {
 // a receive tick of a session with a window, behind stream_start_rows and outside the tick's body (a graph tick replays unchanged; the ring
 // position is an argument): the state in front of the tick and what the tick reads.  The event tells `late` when the host mirror is there.
 int stream_snapshot(bvc_stream_codec *st, int k, hipStream_t s) {
-    const int B = st->B, r = (int)(st->ticks % st->ring_n);
-    bvc_stream_codec::RingTick &t = st->ring[r];
+    bvc_stream_codec::RepairWindow &rw = st->rep;
+    const int B = st->B, r = (int)(st->ticks % rw.n);
+    auto &t = rw.ring[r];
     t.f0 = st->frames; t.k = k; t.valid = true;
     const long long n_h4 = (long long)B * st->m->cfg.h_dim / 4, n_pk = (long long)B * st->kmax * st->bpf, n_pr = (long long)B * st->kmax;
     const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(1024, (n_h4 + 255) / 256));
-    sc_snapshot_kernel<<<dim3(grid), 256, 0, s>>>(st->h_dec, n_h4, st->ring_h + r * st->ring_hs, st->packets, n_pk, st->ring_pk + r * st->ring_pks,
-                                                  st->present, n_pr, st->ring_pr + r * st->ring_prs, st->d_hpresent + r * st->ring_prs,
-                                                  st->bits_of(k), st->ring_bits + r * st->ring_bs, B, k, st->kmax);
+    sc_snapshot_kernel<<<dim3(grid), 256, 0, s>>>(st->h_dec, n_h4, rw.ring_h + r * rw.hs, st->packets, n_pk, rw.ring_pk + r * rw.pks, st->present, n_pr,
+                                                  rw.ring_pr + r * rw.prs, rw.d_hpresent + r * rw.prs, st->bits_of(k), rw.ring_bits + r * rw.bs, B, k,
+                                                  st->kmax);
     BVC_HIP_TRY(hipGetLastError());
     BVC_HIP_TRY(hipEventRecord(t.ev, s));
     return BVC_OK;
-}
-
-// forgets what the ring holds (set_conceal, set_repair: a frame is replayed by the program that first decoded it, or not at all)
-void ring_clear(bvc_stream_codec *st) {
-    for (auto &t : st->ring) t.valid = false;
-    st->late.clear();
 }
 
 // Head of a receive tick, outside any graph: the late packets taken since the last tick go into the ring, and every row that got one is
@@ -521,84 +499,96 @@ void ring_clear(bvc_stream_codec *st) {
 int stream_apply_late(bvc_stream_codec *st, hipStream_t s) {
     const bvc_model *m = st->m;
     const bvc_config &c = m->cfg;
+    bvc_stream_codec::RepairWindow &rw = st->rep;
     const int B = st->B;
-    int rc = BVC_OK;
-    {
-        LateList l;
-        l.n = 0;
-        for (size_t i = 0; i < st->late.size(); ++i) {
-            const bvc_stream_codec::LateReq &q = st->late[i];
-            LateEntry &e = l.e[l.n++];
-            e.row = q.row; e.slot = q.slot; e.j = q.j; e.pad_ = 0;
-            memcpy(e.bytes, q.bytes, SC_LATE_BYTES);
-            if (l.n == SC_LIST || i + 1 == st->late.size()) {
-                sc_late_patch_kernel<<<dim3(l.n), 64, 0, s>>>(l, st->ring_pk, st->ring_pks, st->ring_pr, st->ring_prs, st->kmax, st->bpf);
-                BVC_HIP_TRY(hipGetLastError());
-                l.n = 0;
-            }
-        }
-    }
+    int rc = send_lists<LateList>((int)rw.late.size(), [&](LateList &l, int i) -> int {
+        const auto &q = rw.late[i];
+        LateEntry &e = l.e[l.n++];
+        e.row = q.row; e.slot = q.slot; e.j = q.j; e.pad_ = 0;
+        memcpy(e.bytes, q.bytes, SC_LATE_BYTES);
+        return BVC_OK;
+    }, [&](const LateList &l, int) { sc_late_patch_kernel<<<dim3(l.n), 64, 0, s>>>(l, rw.ring_pk, rw.pks, rw.ring_pr, rw.prs, st->kmax, st->bpf); });
+    if (rc) return rc;
     // every row's first tick, and the passes: oldest first (their rows are disjoint, the order does not matter to the result)
     std::vector<int64_t> first(B, -1);
-    for (const auto &q : st->late) if (first[q.row] < 0 || q.tick < first[q.row]) first[q.row] = q.tick;
-    st->late.clear();
+    for (const auto &q : rw.late) if (first[q.row] < 0 || q.tick < first[q.row]) first[q.row] = q.tick;
+    rw.late.clear();
     std::vector<int64_t> starts;
     for (int b = 0; b < B; ++b) if (first[b] >= 0) starts.push_back(first[b]);
     std::sort(starts.begin(), starts.end());
     starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
-    const bool tick_flow_on = st->tick_flow;
     for (int64_t t0 : starts) {
         std::vector<int> rows;
         for (int b = 0; b < B; ++b) if (first[b] == t0) rows.push_back(b);
         const int Bp = (int)rows.size(), n_chunks = (int)(st->ticks - t0);
-        if (n_chunks < 1 || n_chunks > SC_CHUNKS || n_chunks > st->ring_n) { set_error("bvc_stream_codec_tick_recv: internal replay span %d", n_chunks); return BVC_EINVAL; }
+        if (n_chunks < 1 || n_chunks > SC_CHUNKS || n_chunks > rw.n) { set_error("bvc_stream_codec_tick_recv: internal replay span %d", n_chunks); return BVC_EINVAL; }
         ReplayPlan p;
         p.n_chunks = n_chunks; p.pad_ = 0;
         int frames = 0;
         for (int i = 0; i < n_chunks; ++i) {
-            const int r = (int)((t0 + i) % st->ring_n);
-            if (!st->ring[r].valid) { set_error("bvc_stream_codec_tick_recv: internal replay through a tick that is not retained"); return BVC_EINVAL; }
-            p.c[i] = ReplayChunk{r, st->ring[r].k, Bp * frames};
-            frames += st->ring[r].k;
+            const int r = (int)((t0 + i) % rw.n);
+            if (!rw.ring[r].valid) { set_error("bvc_stream_codec_tick_recv: internal replay through a tick that is not retained"); return BVC_EINVAL; }
+            p.c[i] = ReplayChunk{r, rw.ring[r].k, Bp * frames};
+            frames += rw.ring[r].k;
         }
-        if (frames > st->repair_w + st->kmax - 1) { set_error("bvc_stream_codec_tick_recv: internal replay length %d", frames); return BVC_EINVAL; }
-        for (int g = 0; g < Bp; g += SC_LIST) {
-            p.row0 = g; p.n_rows = std::min(SC_LIST, Bp - g);
-            for (int i = 0; i < p.n_rows; ++i) p.row[i] = rows[g + i];
-            sc_replay_gather_kernel<<<dim3((unsigned)n_chunks, (unsigned)p.n_rows), 256, 0, s>>>(
-                p, st->ring_h, st->ring_hs, st->ring_pk, st->ring_pks, st->ring_pr, st->ring_prs, st->ring_bits, st->ring_bs, c.h_dim, st->kmax,
-                st->bpf, st->r_h, st->r_pk, st->r_pr, st->r_bits);
-            BVC_HIP_TRY(hipGetLastError());
-        }
+        if (frames > rw.w + st->kmax - 1) { set_error("bvc_stream_codec_tick_recv: internal replay length %d", frames); return BVC_EINVAL; }
+        // the pass's rows in groups of SC_LIST: row0 is the group's first compact row
+        auto put_row = [&](SlotRowList &l, int i) -> int { l.row[l.n++] = rows[i]; return BVC_OK; };
+        if ((rc = send_lists<SlotRowList>(Bp, put_row, [&](const SlotRowList &l, int row0) {
+                p.row0 = row0; p.n_rows = l.n;
+                std::copy(l.row, l.row + l.n, p.row);
+                sc_replay_gather_kernel<<<dim3((unsigned)n_chunks, (unsigned)l.n), 256, 0, s>>>(
+                    p, rw.ring_h, rw.hs, rw.ring_pk, rw.pks, rw.ring_pr, rw.prs, rw.ring_bits, rw.bs, c.h_dim, st->kmax, st->bpf, rw.r_h, rw.r_pk,
+                    rw.r_pr, rw.r_bits);
+            }))) return rc;
         // every (row, frame) of the pass is a row of one frame to these two: the ring's bits per frame, not the slots' current ones
         const int N = Bp * frames;
-        const float *bits = c.var_bit ? st->r_bits : nullptr;
-        if ((rc = launch_unpack_rows(st->r_pk, st->r_pr, bits, st->r_zero, N, 1, c.z_dim, 1, st->r_codes, s))) return rc;
-        if (st->conceal && (rc = launch_conceal_select(st->r_pr, 1, bits, (float)c.z_dim, nullptr, N, 1, st->r_sel, s))) return rc;
-        const bool tick_flow = tick_flow_on && flow_chains_static(m, Bp) != 0;
-        g_stream_tick = true; g_tick_flow = tick_flow;
-        for (int i = 0; i < n_chunks && !rc; ++i) {
-            const int k = p.c[i].k;
-            float *codes = st->r_codes + (size_t)p.c[i].off * c.z_dim;
-            Workspace w;
-            if ((rc = check_ws(m, Bp, k, st->ws, st->ws_bytes, &w))) break;
-            if (st->conceal) rc = run_decode_conceal(m, w, st->ws, codes, st->r_sel + p.c[i].off, st->r_h, Bp, k, st->melhat, st->r_h, codes, nullptr, s);
-            else rc = run_decode(m, w, st->ws, codes, st->r_h, Bp, k, st->melhat, st->r_h, s);
-            if (rc) break;
-            float *dst = i + 1 < n_chunks ? st->ring_h + p.c[i + 1].slot * st->ring_hs : st->h_dec;
-            SlotRowList l;
-            for (int g = 0; g < Bp; g += SC_LIST) {
-                l.n = std::min(SC_LIST, Bp - g);
-                for (int q = 0; q < l.n; ++q) l.row[q] = rows[g + q];
-                sc_replay_scatter_kernel<<<dim3((unsigned)l.n), 256, 0, s>>>(l, g, st->r_h, dst, c.h_dim);
-                if (hipGetLastError() != hipSuccess) { set_error("bvc_stream_codec_tick_recv: the replay's scatter launch failed"); rc = BVC_EHIP; break; }
-            }
+        const float *bits = c.var_bit ? rw.r_bits : nullptr;
+        if ((rc = launch_unpack_rows(rw.r_pk, rw.r_pr, bits, rw.r_zero, N, 1, c.z_dim, 1, rw.r_codes, s))) return rc;
+        if (st->conceal && (rc = launch_conceal_select(rw.r_pr, 1, bits, (float)c.z_dim, nullptr, N, 1, rw.r_sel, s))) return rc;
+        TickFlags flags(st->tick_flow && flow_chains_static(m, Bp) != 0);
+        for (int i = 0; i < n_chunks; ++i) {
+            if ((rc = decode_frames(st, Bp, p.c[i].k, rw.r_codes + (size_t)p.c[i].off * c.z_dim, rw.r_sel + p.c[i].off, rw.r_h, s))) return rc;
+            float *dst = i + 1 < n_chunks ? rw.ring_h + p.c[i + 1].slot * rw.hs : st->h_dec;
+            rc = send_lists<SlotRowList>(Bp, put_row, [&](const SlotRowList &l, int row0) {
+                sc_replay_scatter_kernel<<<dim3((unsigned)l.n), 256, 0, s>>>(l, row0, rw.r_h, dst, c.h_dim);
+            });
+            if (rc) { set_error("bvc_stream_codec_tick_recv: the replay's scatter launch failed"); return rc; }
         }
-        g_stream_tick = false; g_tick_flow = false;
-        if (rc) return rc;
     }
     return BVC_OK;
 }
+
+// The tail of a tick of k frames: the fill level and the rows' ages on the device, what bvc_stream_codec_slot_frames answers, the
+// session's counts.  The slot loop is written for a send-side tick; a receive tick has k > 0 and no slot that drains (finish is refused
+// there, end_frame stays -1), with which it comes to last_count = k and last_frame0 = frames - frame0 for every running stream.
+int end_tick(bvc_stream_codec *st, int k, int fill_delta, hipStream_t s) {
+    sc_advance_kernel<<<1, 64, 0, s>>>(st->d_state, fill_delta, st->age, st->B, k, (int)STREAM_WARM_FRAMES);
+    BVC_HIP_TRY(hipGetLastError());
+    for (auto &sl : st->slots) {
+        const bool live = sl.open && sl.started && k > 0;
+        sl.last_count = live ? k : 0;
+        sl.last_frame0 = live ? st->frames - sl.frame0 : 0;
+        if (sl.end_frame < 0) continue;
+        // a draining stream: only the frames below its end are its own, and with the last of them the row is idle of its own accord
+        // (what a close does: the next tick clears what the row still holds)
+        if (st->frames + sl.last_count > sl.end_frame) sl.last_count = (int)(sl.end_frame - st->frames);
+        if (st->frames + k >= sl.end_frame) {
+            sl.open = false; sl.started = false; sl.delay = 0; sl.end_frame = -1;
+            slot_mark(st, sl, SC_SET_OFF | SC_ZERO_TAIL);
+        }
+    }
+    st->frames += k;
+    st->ticks += 1;
+    return BVC_OK;
+}
+
+// one device allocation cut into regions, each 256-byte aligned: take() while the sizes are added up, at<T>() once there is a base
+struct PoolLayout {
+    size_t bytes = 0;
+    size_t take(size_t n) { const size_t o = bytes; bytes += (n + 255) & ~(size_t)255; return o; }
+    template <class T> static T *at(char *base, size_t off) { return reinterpret_cast<T *>(base + off); }
+};
 
 }  // namespace
 
@@ -639,32 +629,31 @@ int bvc_stream_codec_create_dir(const bvc_model *m, int32_t B, int32_t hop_sampl
     st->ws_bytes = bvc_workspace_bytes(m, B, st->kmax);
     int spf = 1;                                             // samples per frame
     for (int i = 0; i < c.n_up; ++i) spf *= c.up_rates[i];
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    PoolLayout pl;
     // (a half that the session does not run gets no memory: its pointers stay null)
     const size_t one = enc ? 1 : 0, two = dec ? 1 : 0, wire = direction != BVC_STREAM_DUPLEX ? 1 : 0;
-    const size_t o_state = take(sizeof(StreamDev)), o_in = take(one * B * hop_samples * 4), o_sbuf = take(one * B * st->cap * 4),
-                 o_stmp = take(one * B * st->cap * 4), o_mel = take(one * B * st->kmax * c.num_mels * 4),
-                 o_bits = take((size_t)B * (st->kmax * (st->kmax + 1) / 2) * 4), o_rowoff = take((size_t)B * 4), o_age = take((size_t)B * 4), o_codes = take((size_t)B * st->kmax * c.z_dim * 4),
-                 o_melhat = take(two * B * st->kmax * c.num_mels * 4), o_wav = take(two * B * st->kmax * spf * 4),
-                 o_he = take(one * B * c.h_dim * 4), o_hd = take(two * B * c.h_dim * 4), o_ws = take(st->ws_bytes),
-                 o_pk = take(wire * B * st->kmax * st->bpf), o_pr = take(wire * B * st->kmax);
-    if (hipMalloc(reinterpret_cast<void **>(&st->pool), off) != hipSuccess) {
+    const size_t o_state = pl.take(sizeof(StreamDev)), o_in = pl.take(one * B * hop_samples * 4), o_sbuf = pl.take(one * B * st->cap * 4),
+                 o_stmp = pl.take(one * B * st->cap * 4), o_mel = pl.take(one * B * st->kmax * c.num_mels * 4),
+                 o_bits = pl.take((size_t)B * (st->kmax * (st->kmax + 1) / 2) * 4), o_rowoff = pl.take((size_t)B * 4), o_age = pl.take((size_t)B * 4), o_codes = pl.take((size_t)B * st->kmax * c.z_dim * 4),
+                 o_melhat = pl.take(two * B * st->kmax * c.num_mels * 4), o_wav = pl.take(two * B * st->kmax * spf * 4),
+                 o_he = pl.take(one * B * c.h_dim * 4), o_hd = pl.take(two * B * c.h_dim * 4), o_ws = pl.take(st->ws_bytes),
+                 o_pk = pl.take(wire * B * st->kmax * st->bpf), o_pr = pl.take(wire * B * st->kmax);
+    if (hipMalloc(reinterpret_cast<void **>(&st->pool), pl.bytes) != hipSuccess) {
         (void)hipGetLastError();
-        set_error("bvc_stream_codec_create: cannot allocate %zu bytes", off);
+        set_error("bvc_stream_codec_create: cannot allocate %zu bytes", pl.bytes);
         return BVC_ENOMEM;
     }
-    BVC_HIP_TRY(hipMemset(st->pool, 0, off));
+    BVC_HIP_TRY(hipMemset(st->pool, 0, pl.bytes));
     char *p = st->pool;
-    st->d_state = reinterpret_cast<StreamDev *>(p + o_state);
-    st->bitsbuf = reinterpret_cast<float *>(p + o_bits); st->codes = reinterpret_cast<float *>(p + o_codes); st->ws = p + o_ws;
+    st->d_state = pl.at<StreamDev>(p, o_state);
+    st->bitsbuf = pl.at<float>(p, o_bits); st->codes = pl.at<float>(p, o_codes); st->ws = p + o_ws;
     if (enc) {
-        st->d_in = reinterpret_cast<float *>(p + o_in); st->sbuf = reinterpret_cast<float *>(p + o_sbuf); st->stmp = reinterpret_cast<float *>(p + o_stmp);
-        st->mel = reinterpret_cast<float *>(p + o_mel); st->h_enc = reinterpret_cast<float *>(p + o_he);
+        st->d_in = pl.at<float>(p, o_in); st->sbuf = pl.at<float>(p, o_sbuf); st->stmp = pl.at<float>(p, o_stmp);
+        st->mel = pl.at<float>(p, o_mel); st->h_enc = pl.at<float>(p, o_he);
     }
-    if (dec) { st->melhat = reinterpret_cast<float *>(p + o_melhat); st->wav = reinterpret_cast<float *>(p + o_wav); st->h_dec = reinterpret_cast<float *>(p + o_hd); }
-    if (wire) { st->packets = reinterpret_cast<uint8_t *>(p + o_pk); st->present = reinterpret_cast<uint8_t *>(p + o_pr); }
-    st->row_off = reinterpret_cast<int *>(p + o_rowoff); st->age = reinterpret_cast<int *>(p + o_age);      // zero: every slot open, delay 0, age 0
+    if (dec) { st->melhat = pl.at<float>(p, o_melhat); st->wav = pl.at<float>(p, o_wav); st->h_dec = pl.at<float>(p, o_hd); }
+    if (wire) { st->packets = pl.at<uint8_t>(p, o_pk); st->present = pl.at<uint8_t>(p, o_pr); }
+    st->row_off = pl.at<int>(p, o_rowoff); st->age = pl.at<int>(p, o_age);          // zero: every slot open, delay 0, age 0
     st->slots.assign(B, bvc_stream_codec::Slot());
     for (auto &sl : st->slots) sl.bits = bits_per_frame;
     int rc;
@@ -732,8 +721,8 @@ int bvc_stream_codec_close(bvc_stream_codec *st, int32_t slot) {
     sl.open = false; sl.started = false; sl.delay = 0;       // and so is the rest of a stream that drains
     sl.last_count = 0; sl.last_frame0 = 0;
     sl.fin_last = -1; sl.end_frame = -1;
-    st->late.erase(std::remove_if(st->late.begin(), st->late.end(), [&](const bvc_stream_codec::LateReq &q) { return q.row == slot; }),
-                   st->late.end());                          // late packets of the stream that no tick has applied go with it
+    auto &late = st->rep.late;                               // late packets of the stream that no tick has applied go with it
+    late.erase(std::remove_if(late.begin(), late.end(), [&](const bvc_stream_codec::RepairWindow::LateReq &q) { return q.row == slot; }), late.end());
     slot_mark(st, sl, SC_SET_OFF | SC_ZERO_TAIL);
     return BVC_OK;
 }
@@ -802,24 +791,8 @@ int bvc_stream_codec_tick(bvc_stream_codec *st, int32_t *n_frames, void *stream)
     int rc = BVC_OK;
     if (k > 0 && st->n_waiting > 0 && (rc = stream_start_rows(st, st->frames, k, s))) return rc;
     if (k > 0 && (rc = stream_run_body(st, k, s))) return rc;
-    sc_advance_kernel<<<1, 64, 0, s>>>(st->d_state, st->hop - c.hop * k, st->age, B, k, (int)STREAM_WARM_FRAMES);
-    BVC_HIP_TRY(hipGetLastError());
-    for (auto &sl : st->slots) {
-        const bool live = sl.open && sl.started && k > 0;
-        sl.last_count = live ? k : 0;
-        sl.last_frame0 = live ? st->frames - sl.frame0 : 0;
-        if (sl.end_frame < 0) continue;
-        // a draining stream: only the frames below its end are its own, and with the last of them the row is idle of its own accord
-        // (what a close does: the next tick clears what the row still holds)
-        if (st->frames + sl.last_count > sl.end_frame) sl.last_count = (int)(sl.end_frame - st->frames);
-        if (st->frames + k >= sl.end_frame) {
-            sl.open = false; sl.started = false; sl.delay = 0; sl.end_frame = -1;
-            slot_mark(st, sl, SC_SET_OFF | SC_ZERO_TAIL);
-        }
-    }
+    if ((rc = end_tick(st, k, st->hop - c.hop * k, s))) return rc;
     st->fill = fill - c.hop * k;
-    st->frames += k;
-    st->ticks += 1;
     if (n_frames) *n_frames = k;
     return BVC_OK;
 }
@@ -833,20 +806,11 @@ int bvc_stream_codec_tick_recv(bvc_stream_codec *st, int32_t n_frames, void *str
     const int k = n_frames;
     int rc = BVC_OK;
     if (st->n_pending > 0 && (rc = stream_send_pending(st, s))) return rc;
-    if (!st->late.empty() && (rc = stream_apply_late(st, s))) return rc;
+    if (!st->rep.late.empty() && (rc = stream_apply_late(st, s))) return rc;
     if (st->n_waiting > 0 && (rc = stream_start_rows(st, st->frames, k, s))) return rc;
-    if (st->repair_w > 0 && (rc = stream_snapshot(st, k, s))) return rc;
+    if (st->rep.w > 0 && (rc = stream_snapshot(st, k, s))) return rc;
     if ((rc = stream_run_body(st, k, s))) return rc;
-    sc_advance_kernel<<<1, 64, 0, s>>>(st->d_state, 0, st->age, st->B, k, (int)STREAM_WARM_FRAMES);     // every row's age: the generator reads it
-    BVC_HIP_TRY(hipGetLastError());
-    for (auto &sl : st->slots) {
-        const bool live = sl.open && sl.started;
-        sl.last_count = live ? k : 0;
-        sl.last_frame0 = live ? st->frames - sl.frame0 : 0;
-    }
-    st->frames += k;
-    st->ticks += 1;
-    return BVC_OK;
+    return end_tick(st, k, 0, s);                            // (every row's age: the generator reads it)
 }
 
 int bvc_stream_codec_set_conceal(bvc_stream_codec *st, int32_t mode) {
@@ -856,7 +820,7 @@ int bvc_stream_codec_set_conceal(bvc_stream_codec *st, int32_t mode) {
     if (mode != 0 && mode != 1) { set_error("bvc_stream_codec_set_conceal: mode %d is neither 0 (no bits) nor 1 (prior)", (int)mode); return BVC_EINVAL; }
     if (int rc_ = need_prior(st->m, "bvc_stream_codec_set_conceal")) return rc_;
     st->conceal = mode;                                      // host bookkeeping: the next tick reads it
-    ring_clear(st);                                          // the two programs agree only to rounding: no replay across the switch
+    st->rep.clear();                                         // the two programs agree only to rounding: no replay across the switch
     return BVC_OK;
 }
 
@@ -865,47 +829,38 @@ int bvc_stream_codec_set_repair(bvc_stream_codec *st, int32_t window_frames) {
     if (st->dir != BVC_STREAM_RECV) { set_error("bvc_stream_codec_set_repair: not a receive session"); return BVC_EINVAL; }
     if (window_frames < 0 || window_frames > 64) { set_error("bvc_stream_codec_set_repair: window of %d frames outside 0..64", (int)window_frames); return BVC_EINVAL; }
     if (window_frames > 0 && st->bpf > SC_LATE_BYTES) { set_error("bvc_stream_codec_set_repair: frames of %d bytes (at most %d)", st->bpf, SC_LATE_BYTES); return BVC_EINVAL; }
-    if (window_frames == st->repair_w) { ring_clear(st); return BVC_OK; }
-    if (window_frames == 0) { BVC_HIP_TRY(hipDeviceSynchronize()); st->repair_free(); return BVC_OK; }
+    if (window_frames == st->rep.w) { st->rep.clear(); return BVC_OK; }
+    if (window_frames == 0) { BVC_HIP_TRY(hipDeviceSynchronize()); st->rep = bvc_stream_codec::RepairWindow(); return BVC_OK; }
     // the ring (a tick holds at least one frame: at most W ticks are retained) and the replay's compact batch, (B, T') with T' up to
     // W + kmax - 1 frames: the oldest retained tick holds one of the last W frames and up to kmax - 1 older ones.  A pass runs tick by
     // tick, so the recurrences find their workspace in the session's own.
     const bvc_config &c = st->m->cfg;
     const int W = window_frames, B = st->B, kmax = st->kmax, Tm = W + kmax - 1;
     auto up16 = [](long long n) { return (n + 15) / 16 * 16; };
-    const long long hs = (long long)B * c.h_dim, pks = up16((long long)B * kmax * st->bpf), prs = up16((long long)B * kmax), bs = (long long)B * kmax;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_h = take((size_t)W * hs * 4), o_pk = take((size_t)W * pks), o_pr = take((size_t)W * prs), o_bits = take((size_t)W * bs * 4),
-                 o_rh = take((size_t)hs * 4), o_rpk = take((size_t)B * Tm * st->bpf), o_rpr = take((size_t)B * Tm), o_rbits = take((size_t)B * Tm * 4),
-                 o_rsel = take((size_t)B * Tm * 4), o_rcodes = take((size_t)B * Tm * c.z_dim * 4), o_rzero = take((size_t)B * Tm * 4);
-    char *pool = nullptr;
-    uint8_t *hp = nullptr, *dhp = nullptr;
-    std::vector<bvc_stream_codec::RingTick> ring(W);
-    bool ok = hipMalloc(reinterpret_cast<void **>(&pool), off) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void **>(&hp), (size_t)W * prs, hipHostMallocMapped) == hipSuccess;
-    ok = ok && hipHostGetDevicePointer(reinterpret_cast<void **>(&dhp), hp, 0) == hipSuccess;
-    for (auto &t : ring) ok = ok && hipEventCreateWithFlags(&t.ev, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMemset(pool, 0, off) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) {                                               // the session is as before
+    bvc_stream_codec::RepairWindow rw;                       // built aside: whatever fails, it goes with what it got and the session is as before
+    rw.w = rw.n = W;
+    rw.hs = (long long)B * c.h_dim; rw.pks = up16((long long)B * kmax * st->bpf); rw.prs = up16((long long)B * kmax); rw.bs = (long long)B * kmax;
+    PoolLayout pl;
+    const size_t o_h = pl.take((size_t)W * rw.hs * 4), o_pk = pl.take((size_t)W * rw.pks), o_pr = pl.take((size_t)W * rw.prs), o_bits = pl.take((size_t)W * rw.bs * 4),
+                 o_rh = pl.take((size_t)rw.hs * 4), o_rpk = pl.take((size_t)B * Tm * st->bpf), o_rpr = pl.take((size_t)B * Tm), o_rbits = pl.take((size_t)B * Tm * 4),
+                 o_rsel = pl.take((size_t)B * Tm * 4), o_rcodes = pl.take((size_t)B * Tm * c.z_dim * 4), o_rzero = pl.take((size_t)B * Tm * 4);
+    rw.ring.resize(W);
+    bool ok = hipMalloc(reinterpret_cast<void **>(&rw.pool), pl.bytes) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void **>(&rw.h_present), (size_t)W * rw.prs, hipHostMallocMapped) == hipSuccess;
+    ok = ok && hipHostGetDevicePointer(reinterpret_cast<void **>(&rw.d_hpresent), rw.h_present, 0) == hipSuccess;
+    for (auto &t : rw.ring) ok = ok && hipEventCreateWithFlags(&t.ev, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipMemset(rw.pool, 0, pl.bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
         (void)hipGetLastError();
-        for (auto &t : ring) if (t.ev) (void)hipEventDestroy(t.ev);
-        if (pool) (void)hipFree(pool);
-        if (hp) (void)hipHostFree(hp);
-        set_error("bvc_stream_codec_set_repair: cannot allocate %zu bytes for a window of %d frames", off, W);
+        set_error("bvc_stream_codec_set_repair: cannot allocate %zu bytes for a window of %d frames", pl.bytes, W);
         return BVC_ENOMEM;
     }
-    memset(hp, 0, (size_t)W * prs);
-    st->repair_free();
-    st->repair_w = W; st->ring_n = W; st->ring = ring;
-    st->ring_pool = pool; st->h_present = hp; st->d_hpresent = dhp;
-    st->ring_hs = hs; st->ring_pks = pks; st->ring_prs = prs; st->ring_bs = bs;
-    st->ring_h = reinterpret_cast<float *>(pool + o_h); st->ring_pk = reinterpret_cast<uint8_t *>(pool + o_pk);
-    st->ring_pr = reinterpret_cast<uint8_t *>(pool + o_pr); st->ring_bits = reinterpret_cast<float *>(pool + o_bits);
-    st->r_h = reinterpret_cast<float *>(pool + o_rh); st->r_pk = reinterpret_cast<uint8_t *>(pool + o_rpk);
-    st->r_pr = reinterpret_cast<uint8_t *>(pool + o_rpr); st->r_bits = reinterpret_cast<float *>(pool + o_rbits);
-    st->r_sel = reinterpret_cast<float *>(pool + o_rsel); st->r_codes = reinterpret_cast<float *>(pool + o_rcodes);
-    st->r_zero = reinterpret_cast<int *>(pool + o_rzero);
+    memset(rw.h_present, 0, (size_t)W * rw.prs);
+    char *p = rw.pool;
+    rw.ring_h = pl.at<float>(p, o_h); rw.ring_pk = pl.at<uint8_t>(p, o_pk); rw.ring_pr = pl.at<uint8_t>(p, o_pr); rw.ring_bits = pl.at<float>(p, o_bits);
+    rw.r_h = pl.at<float>(p, o_rh); rw.r_pk = pl.at<uint8_t>(p, o_rpk); rw.r_pr = pl.at<uint8_t>(p, o_rpr); rw.r_bits = pl.at<float>(p, o_rbits);
+    rw.r_sel = pl.at<float>(p, o_rsel); rw.r_codes = pl.at<float>(p, o_rcodes); rw.r_zero = pl.at<int>(p, o_rzero);
+    st->rep = std::move(rw);                                 // (the window the session had goes with rw)
     return BVC_OK;
 }
 
@@ -915,23 +870,24 @@ int bvc_stream_codec_late(bvc_stream_codec *st, int32_t slot, int64_t stream_fra
     if (st->dir != BVC_STREAM_RECV) { set_error("bvc_stream_codec_late: not a receive session"); return BVC_EINVAL; }
     if (!packet) { set_error("bvc_stream_codec_late: null packet"); return BVC_EINVAL; }
     const bvc_stream_codec::Slot &sl = st->slots[slot];
-    if (st->repair_w <= 0 || !sl.open || !sl.started || stream_frame < 0) return BVC_OK;      // no window, or no running stream of which this is a frame
+    if (st->rep.w <= 0 || !sl.open || !sl.started || stream_frame < 0) return BVC_OK;      // no window, or no running stream of which this is a frame
     if (stream_frame >= st->frames - sl.frame0) return BVC_OK;                               // not decoded yet: it belongs into the next tick
     const int64_t f = sl.frame0 + stream_frame;             // the session's count
-    const int64_t n_ticks = std::min<int64_t>(st->ticks, st->ring_n);
+    bvc_stream_codec::RepairWindow &rw = st->rep;
+    const int64_t n_ticks = std::min<int64_t>(st->ticks, rw.n);
     for (int64_t t = st->ticks - n_ticks; t < st->ticks; ++t) {
-        const int r = (int)(t % st->ring_n);
-        bvc_stream_codec::RingTick &rt = st->ring[r];
+        const int r = (int)(t % rw.n);
+        auto &rt = rw.ring[r];
         if (!st->tick_retained(rt) || f < rt.f0 || f >= rt.f0 + rt.k) continue;
         BVC_HIP_TRY(hipEventSynchronize(rt.ev));             // the tick's snapshot has written the mirror
-        uint8_t *pr = st->h_present + r * st->ring_prs + (size_t)slot * st->kmax + (f - rt.f0);
+        uint8_t *pr = rw.h_present + r * rw.prs + (size_t)slot * st->kmax + (f - rt.f0);
         if (*pr) return BVC_OK;                              // it arrived in time, or late once already
         *pr = 1;
-        bvc_stream_codec::LateReq q;
+        bvc_stream_codec::RepairWindow::LateReq q;
         q.row = slot; q.slot = r; q.j = (int)(f - rt.f0); q.tick = t;
         memset(q.bytes, 0, sizeof(q.bytes));
         memcpy(q.bytes, packet, (size_t)st->bpf);
-        st->late.push_back(q);
+        rw.late.push_back(q);
         if (taken) *taken = 1;
         return BVC_OK;
     }

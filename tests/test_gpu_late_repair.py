@@ -243,6 +243,32 @@ def test_forty_rows_twelve_of_them_late_in_one_tick():
     model.check_status()
 
 
+def test_more_late_rows_than_one_list_holds():
+    """Every per-tick list of the library holds 64 entries; here each kind is sent as two.  All 80 slots are opened in front of the first
+    push: 80 pending slot updates and 80 row starts.  66 rows lose frame 20 (one pass of 66 rows: two gather groups, and two scatter groups
+    behind each of its ticks), 4 others lose frame 17 of an earlier tick (a second pass), and all 70 packets are handed in in front of one
+    push two ticks later (two patch lists)."""
+    model = mk(True)
+    B = 80
+    packets = send_packets(model, True, B, 42)
+    F = packets.shape[1]
+    ticks = chunks(F)
+    early = [3, 28, 53, 78]                                                          # one row of every rate
+    many = [b for b in range(B) if b % 8 != 7 and b not in early]
+    assert len(many) == 66 and tick_of(ticks, 17) < tick_of(ticks, 20)
+    frames = {b: 20 for b in many}
+    frames.update({b: 17 for b in early})
+    at = tick_of(ticks, 20) + 2
+    lost = mask(B, F, [(b, f) for b, f in frames.items()])
+    kw = dict(conceal="prior", repair=16)
+    ontime = run(model, packets, ticks, mask(B, F, []), **kw)
+    late = run(model, packets, ticks, lost, {at: [("late", b, f, f) for b, f in sorted(frames.items())]}, **kw)
+    never = run(model, packets, ticks, lost, **kw)
+    assert late[2] == [True] * 70
+    assert_repaired(late, ontime, never, set(frames), ticks[at][0], B)
+    model.check_status()
+
+
 # ------------------------------------------------------------------------------------------------ 7: slot life
 @pytest.mark.parametrize("conceal", ["none", "prior"])
 def test_slot_life(conceal):
