@@ -37,85 +37,70 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
+// Compile-time tunables (tools/flow_variants.py builds and times variants; the values here are what ships):
+#ifndef BVC_FLOW_DIAG
+#define BVC_FLOW_DIAG 0            // 1: the probing lane also stamps flags-seen / products-done / barrier-passed (include/bvcodec.h; flow_variants.py run --diag)
+#endif
+#ifndef BVC_FLOW_WAVES_PER_SIMD
+#define BVC_FLOW_WAVES_PER_SIMD 2  // launch bound of the 8-wave kernels, i.e. their register budget (build.py: BVC_FLOW_WAVES)
+#endif
+#ifndef BVC_FLOW_POLL_SLEEP
+#define BVC_FLOW_POLL_SLEEP 1      // s_sleep units (64 clocks) between two polls of a wave (0 / 4 / 12 measured: +-0.1 ms, the waits end within one or two polls)
+#endif
+#ifndef BVC_FLOW_PARTNER_WAIT
+#define BVC_FLOW_PARTNER_WAIT 1    // the wave that shares wave 0's SIMD (wave 4) starts its quantum's products only once wave 0 has issued the
+#endif                             // publishing store (its MFMAs take issue slots from the epilogue everybody waits for)
+#ifndef BVC_FLOW_PARKV
+#define BVC_FLOW_PARKV 2           // (filler form; 0 off, 1 two layers) the weights of dec.2 and dec.4, in decode also phi_x.4 - this wave's 8 blocks each - stay
+#endif                             // in registers for the whole launch (165 of 256 VGPRs): 128 KiB (decode 192) per compute unit and frame less to pull from
+                                   // the L2, whose fill path into the compute units is what the kernel is bound by
+#ifndef BVC_FLOW_PARKL
+#define BVC_FLOW_PARKL 1           // (filler form) the FIRST layer's weights (enc.0 / dec.0, the half that multiplies h) stay in LDS for the whole launch - the
+#endif                             // 64 KiB that the kernel's 128 KiB left of a compute unit's 160 - instead of being requested by every frame's GRU
+                                   // layer, at the most crowded point of the frame
 #ifndef BVC_GRU_ROUNDS_FILL
 #define BVC_GRU_ROUNDS_FILL 4      // rounds in which the GRU layer's remaining weights (phi_x third) pass through the registers
 #endif
-// Compile-time switches (tools/flow_variants.py builds and times variants):
-//   BVC_FLOW_EARLYW       1: the next layer's weights are requested right behind this layer's operand requests instead of in front of
-//                         the reduction barrier (the default place).  Worth 0.6 ms per step while spill reloads sat in the epilogues
-//                         (they wait, in order, for everything in flight); costs 1.4 ms without them: 54.3 against 52.8 ms per step
-//   BVC_FLOW_LATEW        1: ... or behind the reduction barrier (nothing but the quantum's weights in front of it)
-//   BVC_FLOW_STASH        1 (default): a wave keeps the operand blocks its filler quanta multiply (h, phi_z: fetched and verified for the
-//                         layer that consumes them first) in LDS, so a quantum requests its weights only
-//   BVC_FLOW_PARTNER_WAIT 1 (default): the wave that shares wave 0's SIMD (wave 4) starts its quantum's products only once wave 0 has
-//                         issued the publishing store (its MFMAs take issue slots from the epilogue everybody waits for)
-//   BVC_FILL_EARLY        1: a quantum's weights are requested inside the layer's segment too (behind the next layer's weights) instead of
-//                         in front of the reduction barrier
-//   BVC_FLOW_DIAG         1: the probing lane also stamps flags-seen / products-done / barrier-passed (tools/flow_variants.py run --diag)
-// What these are about: a compute unit takes vector-memory requests in order, 64 B per clock (1 KiB per wave-instruction = 16
+#ifndef BVC_GRU_DEPTH
+#define BVC_GRU_DEPTH 3            // register sets that stream runs through (2: the request for round i + 1 in front of round i's products; up to all four rounds)
+#endif
+#ifndef BVC_GRU_FENCE
+#define BVC_GRU_FENCE 1            // scheduling fences around the rounds of the GRU layer's weight stream (see flow_gru)
+#endif
+#ifndef BVC_CHAIN_G
+#define BVC_CHAIN_G 4              // chains per reduction group of flow_layer_chains (three and more chains per workgroup)
+#endif
+#ifndef BVC_FLOW_EARLYW
+#define BVC_FLOW_EARLYW 0          // 1: the next layer's weights are requested right behind this layer's operand requests instead of in front of the
+#endif                             // reduction barrier.  A measured loser (54.3 against 52.8 ms per step, profiles/r03_flow_variants.txt: v5 / v5_noew) that
+                                   // is still here because hipcc orders a few instructions of the two narrowest concealing kernels differently without its dead arm
+// What the request order is about: a compute unit takes vector-memory requests in order, 64 B per clock (1 KiB per wave-instruction = 16
 // clocks), and a wave that issues a request into a full queue stalls.  Everything requested in front of the reduction barrier
 // therefore holds the barrier - and the publishing store behind it - back: 24 KiB per wave there (next weights, quantum weights,
 // quantum operands) cost every filler layer more than a microsecond (stamps: products -> barrier 1.2-1.8 us, 0.2-0.5 without).
-// Measured and dropped: two or three flag polls in flight per wave (57.9 / 59.2 against 55.7 ms per step: the polls
-// themselves load the hand-off path); quanta requested behind the publishing store and multiplied a layer later, with and without a
-// pre-issued poll of the next layer's flags (shorter layer spans, 43.8 against 45.2 us per encode frame, but wave 0 leaves each layer
-// later: 55.0-55.9 against 54.1 ms per step); the ELU epilogue split over four waves (wave j reduces and activates output j of every
-// lane, wave 0 gathers through LDS and publishes: barrier -> published stays at 0.45 us, 53.8 against 52.8 ms per step - unlike the
-// GRU cell's, which did shrink from 1.5 to 0.8 us that way, the linear layers' epilogue is not bound by its instruction count).
-#ifndef BVC_FLOW_EARLYW
-#define BVC_FLOW_EARLYW 0
-#endif
-#ifndef BVC_FLOW_LATEW
-#define BVC_FLOW_LATEW 0
-#endif
-#ifndef BVC_FLOW_STASH
-#define BVC_FLOW_STASH 1
-#endif
-#ifndef BVC_FLOW_PARTNER_WAIT
-#define BVC_FLOW_PARTNER_WAIT 1
-#endif
-#ifndef BVC_FILL_EARLY
-#define BVC_FILL_EARLY 0
-#endif
-//   BVC_GRU_FAST          1: the GRU layer's remaining product, W_ih[:, :H] phi_x(d_t) (24 KiB of weights per wave, the layer
-//                         was bound by that stream), gets half its weights requested a layer early (inside phi_x.4's segment), a quarter
-//                         parked in LDS for the whole launch, and only the last quarter streamed inside the layer (h_dim 1024, filler form).
-//                         Measured without effect (52.76 ms per step either way): with its h and phi_z parts taken out by the quanta the layer
-//                         is bound by the 192 MFMAs its two waves per SIMD issue, not by the weight stream any more.  Off by default.
-#ifndef BVC_GRU_FAST
-#define BVC_GRU_FAST 0
-#endif
-//   (what round 4 measured and did not keep - resident rounds of the GRU stream, other request orders, fences in the chain kernels - is in
-//   profiles/r04_flow_variants.txt)
-//   BVC_GRU_FENCE         1 (default): scheduling fences around the rounds of the GRU layer's weight stream (see flow_gru)
-//   BVC_GRU_DEPTH         register sets the stream runs through (default 3; 2: the request for round i + 1 in front of round i's products; up to all four rounds)
-//   BVC_FLOW_PARKV        2 (default; 0 off, 1 two layers): (filler form) the weights of two wide layers (three in decode) - this wave's 8 blocks each - stay in registers for the whole launch
-//                         (the filler kernels use 165 of the 256 VGPRs a wave may have): 128 KiB (decode 192) per compute unit and frame less to pull from
-//                         the L2, whose fill path into the compute units is what the kernel is bound by
-#ifndef BVC_FLOW_PARKV
-#define BVC_FLOW_PARKV 2
-#endif
-//   BVC_FLOW_PARKL        1 (default): (filler form) the FIRST layer's weights (enc.0 / dec.0, the half that multiplies h) stay in LDS for the whole launch - the
-//                         64 KiB that the kernel's 128 KiB left of a compute unit's 160 - instead of being requested by every frame's GRU layer,
-//                         at the most crowded point of the frame
-#ifndef BVC_FLOW_PARKL
-#define BVC_FLOW_PARKL 1
-#endif
-#ifndef BVC_FLOW_PARK_SET
-#define BVC_FLOW_PARK_SET 1                          // which two: 1 dec.2 + dec.4, 0 phi_x.2 + phi_x.4
-#endif
-#ifndef BVC_GRU_FENCE
-#define BVC_GRU_FENCE 1
-#endif
-#ifndef BVC_GRU_DEPTH
-#define BVC_GRU_DEPTH 3
-#endif
-#ifndef BVC_FLOW_POLL_SLEEP
-#define BVC_FLOW_POLL_SLEEP 1                        // s_sleep units (64 clocks) between two polls of a wave
-#endif
-#ifndef BVC_FLOW_DIAG
-#define BVC_FLOW_DIAG 0
-#endif
+//
+// Measured and dropped - no longer compiled; last built at 2defbdd (DESIGN.md section 4 names the switch each form was built under there).
+// ms are per step (64 x 5 s); r03 / r04 = profiles/r03_flow_variants.txt / profiles/r04_flow_variants.txt.
+//   next layer's weights requested behind the reduction barrier instead of in front of it: 53.1 against 52.8 (r03: v6_latew)
+//   a quantum's weights requested inside the layer's segment too: 56.5 against 54.3 (r03: v5_fe)
+//   a quantum's operand blocks re-fetched from memory instead of kept in this wave's LDS stash: the stash took 20 % off the
+//       L2 -> CU traffic, 54.2 against 55.1 (r03: stash0e / earlyw)
+//   GRU layer's phi_x weights half requested a layer early, a quarter parked in LDS, a quarter streamed (h_dim 1024, filler form,
+//       in place of BVC_FLOW_PARKL - one use of the parking region): 52.76 either way (r03: v6), +0.4 against the fenced stream (r04: gfast) - with its
+//       h and phi_z parts taken out by the quanta the layer is bound by the 192 MFMAs its two waves per SIMD issue, not by the weight stream
+//   operand blocks requested without polling their flags first, requested again while one holds the sentinel: 47.9-48.0
+//       against 45.9 (r04: spec); the same for the first chain of flow_layer_chains: groups of four chains lose 2 % (r04: g4s)
+//   sentinel checks wherever hipcc schedules them - in front of the first product, block 0 requested second to last - instead of fenced
+//       behind the last product: 48.6 against 48.2 (r04: maxchk / inord)
+//   sentinel check as four compares and three ors per 16 bytes instead of an unsigned maximum: 49.9 against 48.5 (r04: base / maxchk)
+//   phi_x.2 + phi_x.4 as the register-resident layers instead of dec.2 + dec.4: 46.9 against 46.55 (r04: s0v2 / s1v2)
+//   two or three flag polls in flight per wave (retired earlier): 57.9 / 59.2 against 55.7 - the polls themselves load the hand-off path (r03: poll2 / poll3)
+//   quanta requested behind the publishing store and multiplied a layer later, with and without a pre-issued poll of the next layer's flags:
+//       shorter layer spans, 43.8 against 45.2 us per encode frame, but wave 0 leaves each layer later: 55.0-55.9 against 54.1 (r03: pipe*)
+//   the ELU epilogue split over four waves (wave j reduces and activates output j of every lane, wave 0 gathers through LDS and publishes):
+//       barrier -> published stays at 0.45 us, 53.8 against 52.8 (r03: v7_split) - unlike the GRU cell's, which did shrink from 1.5 to 0.8 us
+//       that way, the linear layers' epilogue is not bound by its instruction count
+//   resident rounds of the GRU stream, other request orders, fences in the chain kernels: r04
 constexpr int AUX_SC1 = 16;
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
@@ -137,29 +122,16 @@ struct FlowWg {
     unsigned *status;
 };
 
-//   BVC_FLOW_MAXCHK       1 (default): "does a fetched block still hold the sentinel" as an unsigned maximum over the block's dwords (two v_max3_u32 and a
-//                         compare per 16 bytes instead of four compares and three ors); nothing but the sentinel itself may then lie at or above
-//                         it: publishable() maps every such bit pattern (negative NaNs with an all-ones payload top) to the canonical NaN
-#ifndef BVC_FLOW_SPEC
-#define BVC_FLOW_SPEC 0         // lin_segment: 1 = operand blocks requested without polling their flags first (verified and requested again while one holds the sentinel)
-#endif
-#ifndef BVC_CHAIN_SPEC
-#define BVC_CHAIN_SPEC 0        // flow_layer_chains: the first chain's operand blocks are requested without polling their flags first
-#endif
-#ifndef BVC_CHAIN_G
-#define BVC_CHAIN_G 4           // chains per reduction group of flow_layer_chains (three and more chains per workgroup)
-#endif
-#ifndef BVC_FLOW_MAXCHK
-#define BVC_FLOW_MAXCHK 1
-#endif
+// "Does a fetched block still hold the sentinel" as an unsigned maximum over the block's dwords (two v_max3_u32 and a compare per 16 bytes);
+// nothing but the sentinel itself may then lie at or above it: publishable() maps every such bit pattern (negative NaNs with an all-ones
+// payload top) to the canonical NaN.
 __device__ __forceinline__ unsigned umax3(unsigned a, unsigned b, unsigned c) {
     unsigned r;
     asm("v_max3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
 __device__ __forceinline__ bool is_poison4(const u32x4 v) {
-    if (BVC_FLOW_MAXCHK) return umax3(umax3(v[0], v[1], v[2]), v[3], 0u) >= FLOW_POISON;
-    return v[0] == FLOW_POISON || v[1] == FLOW_POISON || v[2] == FLOW_POISON || v[3] == FLOW_POISON;
+    return umax3(umax3(v[0], v[1], v[2]), v[3], 0u) >= FLOW_POISON;
 }
 
 // Operand blocks [kb0, kb0 + PER) of utterance group g.mtile from the flow buffer at byte offset `buf`
@@ -190,19 +162,16 @@ __device__ __forceinline__ FlowSrc flow_wait(const FlowWg &g, unsigned buf, int 
     return s;
 }
 
-//   BVC_FLOW_INORDER      1 (default): a segment's operand blocks are requested strictly in k order and multiplied in that order, each as soon as IT has
-//                         arrived (a wave's loads return in order), with the sentinel checks behind the last product.  hipcc otherwise
-//                         schedules the checks - which need every block - in front of the first product and requests block 0 second to
-//                         last: all eight blocks then have to be there before the first MFMA issues
-#ifndef BVC_FLOW_INORDER
-#define BVC_FLOW_INORDER 1
-#endif
+// A segment's operand blocks are requested strictly in k order and multiplied in that order, each as soon as IT has arrived (a wave's loads
+// return in order), with the sentinel checks behind the last product.  The scheduling fences make that true: hipcc otherwise schedules the
+// checks - which need every block - in front of the first product and requests block 0 second to last, so that all eight blocks have to be
+// there before the first MFMA issues.
 template <int PER>
 __device__ __forceinline__ void flow_issue(const FlowWg &g, const FlowSrc &s, u32x4 (&xr)[PER]) {
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
         xr[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(g.rs, s.vl, s.base + (unsigned)u * 1024u, AUX_SC1));
-        if (BVC_FLOW_INORDER) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -226,19 +195,17 @@ typedef u32x4 __attribute__((address_space(3))) *LdsX;      // this wave's stash
 struct SegHook {
     const float *nw; int nwnb; bool pre;           // next layer's packed weights, k-blocks per row; request them here?
     unsigned long long *st_flags, *st_done;       // BVC_FLOW_DIAG: where to stamp "flags seen" / "products done" (or null)
-    LdsX stash;                                    // BVC_FLOW_STASH: keep the verified operand blocks of this segment there (or null)
-    const float *fw; size_t fblock; int fstride;   // BVC_FILL_EARLY: the layer's filler quantum - weights, first block, blocks between k-blocks (fw null: none)
-    const float *gw; size_t gblock;                // BVC_GRU_FAST: the GRU layer's first GRU_EARLY_BLOCKS weight blocks are requested here (gw null: none)
+    LdsX stash;                                    // keep the verified operand blocks of this segment there (or null)
 };
-constexpr int GRU_EARLY_BLOCKS = 12;               // rounds 0 and 1 of four: 4 k-blocks x 3 gates (gate-interleaved: consecutive 1 KiB blocks)
-__device__ __forceinline__ SegHook no_hook() { return SegHook{nullptr, 0, false, nullptr, nullptr, (LdsX)0, nullptr, 0, 1, nullptr, 0}; }
+__device__ __forceinline__ SegHook no_hook() { return SegHook{nullptr, 0, false, nullptr, nullptr, (LdsX)0}; }
 
 // acc += W[ntile rows][segment] . X[segment]   for this wave's share of the segment's k-blocks
-// GRUPRE / FEARLY: (compile time) the hook carries GRU weights / a filler quantum's weights to request behind the operands.
-template <int PER, int PERN, bool GRUPRE = false, bool FEARLY = false>
+// (FEARLY: unused.  It and the constant of that name in flow_layer are what is left of a dropped experiment, the quantum's weights
+// requested in here: without them hipcc orders a few instructions of the two narrowest concealing kernels differently.)
+template <int PER, int PERN, bool FEARLY = false>
 __device__ __forceinline__ void lin_segment(const FlowWg &g, const float *w, int wnb, int nb, unsigned buf, bool w_ready,
                                             f32x4 (&wv)[PER], f32x4 &acc, bool &give_up, unsigned code, int kb_off,
-                                            const SegHook &hk, f32x4 (&wn)[PERN], f32x4 (&fwv)[PERN], f32x4 (&gqv)[GRU_EARLY_BLOCKS]) {
+                                            const SegHook &hk, f32x4 (&wn)[PERN]) {
     const int kb0 = kb_off + g.wave * PER;
     if (PER == 1 && kb0 >= nb) return;                     // wave-uniform: fewer k-blocks than waves
     if (!w_ready) {
@@ -247,13 +214,7 @@ __device__ __forceinline__ void lin_segment(const FlowWg &g, const float *w, int
         for (int u = 0; u < PER; ++u) wv[u] = wload(ub, (unsigned)g.lane * 16u, u);
     }
     unsigned spins = 0;
-    FlowSrc src;
-    if (BVC_FLOW_SPEC) {                                   // no flag poll: the blocks themselves are requested until none holds the sentinel
-        src.base = __builtin_amdgcn_readfirstlane(buf + (unsigned)(g.mtile * nb + kb0) * 1024u);
-        src.vl = (unsigned)g.lane * 16u;
-    } else {
-        src = flow_wait<PER>(g, buf, nb, kb0, give_up, code, spins);
-    }
+    const FlowSrc src = flow_wait<PER>(g, buf, nb, kb0, give_up, code, spins);
     if (BVC_FLOW_DIAG && hk.st_flags) *hk.st_flags = __builtin_amdgcn_s_memrealtime();
     const f32x4 acc_in = acc;
     u32x4 xr[PER];
@@ -264,16 +225,6 @@ __device__ __forceinline__ void lin_segment(const FlowWg &g, const float *w, int
 #pragma unroll
         for (int u = 0; u < PERN; ++u) wn[u] = wload(ub, (unsigned)g.lane * 16u, u);
     }
-    if (GRUPRE) {                                          // the first half of the GRU layer's weights
-        const GPtr ug = uniform_ptr(hk.gw, hk.gblock * g.wmul);
-#pragma unroll
-        for (int i = 0; i < GRU_EARLY_BLOCKS; ++i) gqv[i] = wload(ug, (unsigned)g.lane * 16u, i);
-    }
-    if (FEARLY) {                                          // the layer's filler quantum's weights (zero blocks if it has none)
-        const GPtr uf = uniform_ptr(hk.fw, hk.fblock * g.wmul);
-#pragma unroll
-        for (int u = 0; u < PERN; ++u) fwv[u] = hk.fw ? wload(uf, (unsigned)g.lane * 16u, u * hk.fstride) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
     for (;;) {
         // The blocks are multiplied as they arrive (the loads return in order); whether one of them still held the
         // sentinel is only known at the end: then the products are thrown away and everything is fetched again.
@@ -281,19 +232,16 @@ __device__ __forceinline__ void lin_segment(const FlowWg &g, const float *w, int
         bool bad = false;
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
-            if (!BVC_FLOW_INORDER) bad |= is_poison4(xr[u]);
             const f32x4 xv = __builtin_bit_cast(f32x4, xr[u]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) a2 = mfma16(wv[u][e], xv[e], a2);
-            if (BVC_FLOW_INORDER) __builtin_amdgcn_sched_barrier(0);       // block u's products before block u + 1 is waited for
+            __builtin_amdgcn_sched_barrier(0);                             // block u's products before block u + 1 is waited for
         }
-        if (BVC_FLOW_INORDER) {
 #pragma unroll
-            for (int u = 0; u < PER; ++u) bad |= is_poison4(xr[u]);
-        }
+        for (int u = 0; u < PER; ++u) bad |= is_poison4(xr[u]);
         if (!(__any(bad) && !give_up)) {
             acc = a2;
-            if (BVC_FLOW_STASH && hk.stash) {
+            if (hk.stash) {
 #pragma unroll
                 for (int u = 0; u < PER; ++u) hk.stash[(kb_off / 8 * PER + u) * 64 + g.lane] = xr[u];
             }
@@ -310,8 +258,8 @@ __device__ __forceinline__ void lin_segment(const FlowWg &g, const float *w, int
 template <int PER>
 __device__ __forceinline__ void lin_segment(const FlowWg &g, const float *w, int wnb, int nb, unsigned buf, bool w_ready,
                                             f32x4 (&wv)[PER], f32x4 &acc, bool &give_up, unsigned code, int kb_off = 0) {
-    f32x4 none[1], nof[1], nog[GRU_EARLY_BLOCKS];
-    lin_segment<PER, 1>(g, w, wnb, nb, buf, w_ready, wv, acc, give_up, code, kb_off, no_hook(), none, nof, nog);
+    f32x4 none[1];
+    lin_segment<PER, 1>(g, w, wnb, nb, buf, w_ready, wv, acc, give_up, code, kb_off, no_hook(), none);
 }
 
 // One round of a GRU segment: HALF k-blocks x 3 gates of weights (gate-interleaved [n/16][k/16][gate][lane][4]).
@@ -331,19 +279,6 @@ __device__ __forceinline__ void gru_round(const f32x4 (&w3)[HALF][3], const u32x
         for (int e = 0; e < 4; ++e)
 #pragma unroll
             for (int q = 0; q < 3; ++q) acc[q] = mfma16(w3[u][q][e], xv[e], acc[q]);
-    }
-}
-
-// the same round on six consecutive weight blocks [k-block][gate] (BVC_GRU_FAST)
-template <int PER>
-__device__ __forceinline__ void gru_round6(const f32x4 *w6, const u32x4 (&xr)[PER], int h0, f32x4 (&acc)[3]) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const f32x4 xv = __builtin_bit_cast(f32x4, xr[h0 + u]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) acc[q] = mfma16(w6[u * 3 + q][e], xv[e], acc[q]);
     }
 }
 
@@ -389,6 +324,8 @@ __device__ __forceinline__ bool fill_active(const FlowWg &g, const FlowFill &f) 
 }
 template <int PER, int GATE>
 __device__ __forceinline__ void fill_issue(const FlowWg &g, const FlowFill &f, f32x4 (&wv)[PER], u32x4 (&xr)[PER]) {
+    // (xr: unused, like FlowFill::buf - the quantum's operands come out of the stash.  Both are still here because hipcc compiles several
+    // of the kernels to different instructions without them, the h_dim 1024 filler kernels among them.)
     if (!fill_active<PER, GATE>(g, f)) {                   // (defined on every path: no stale value stays live across the frame loop)
 #pragma unroll
         for (int u = 0; u < PER; ++u) { wv[u] = (f32x4){0.f, 0.f, 0.f, 0.f}; xr[u] = (u32x4){0u, 0u, 0u, 0u}; }
@@ -399,15 +336,13 @@ __device__ __forceinline__ void fill_issue(const FlowWg &g, const FlowFill &f, f
     const GPtr ub = uniform_ptr(f.w, (GATE >= 0 ? ((size_t)g.ntile * f.wnb + kb0) * 3 + GATE : (size_t)g.ntile * f.wnb + kb0) * g.wmul);
 #pragma unroll
     for (int u = 0; u < PER; ++u) wv[u] = wload(ub, l16, GATE >= 0 ? u * 3 : u);
-    if (!BVC_FLOW_STASH) gru_issue_known<PER>(g, f.buf, f.nb, xr);
 }
 template <int PER, int GATE>
-__device__ __forceinline__ void fill_multiply(const FlowWg &g, const FlowFill &f, const f32x4 (&wv)[PER], const u32x4 (&xr)[PER], f32x4 &acc,
-                                              LdsX stash) {
+__device__ __forceinline__ void fill_multiply(const FlowWg &g, const FlowFill &f, const f32x4 (&wv)[PER], f32x4 &acc, LdsX stash) {
     if (!fill_active<PER, GATE>(g, f)) return;
     u32x4 xs[PER];
 #pragma unroll
-    for (int u = 0; u < PER; ++u) xs[u] = BVC_FLOW_STASH ? stash[u * 64 + g.lane] : xr[u];
+    for (int u = 0; u < PER; ++u) xs[u] = stash[u * 64 + g.lane];
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
         const f32x4 xv = __builtin_bit_cast(f32x4, xs[u]);
@@ -420,7 +355,7 @@ __device__ __forceinline__ u32x4 publishable(f32x4 o, bool rowok) {
     u32x4 b = __builtin_bit_cast(u32x4, o);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        if (BVC_FLOW_MAXCHK ? b[j] >= FLOW_POISON : b[j] == FLOW_POISON) b[j] = 0x7FC00000u;       // never publish the sentinel as data
+        if (b[j] >= FLOW_POISON) b[j] = 0x7FC00000u;       // never publish the sentinel as data
         if (!rowok) b[j] = 0u;                             // padding rows of the last utterance group stay zero
     }
     return b;
@@ -451,9 +386,8 @@ struct FlowCtx {
     float *red_chain;        // MULTI: [2][4][NW][256] partial tiles of a group of chains (flow_layer_chains)
     unsigned sb;             // bytes per flow buffer slot: kept in a register (every layer needs it before its first request; a scalar
                              // load there is a cache round trip on the critical path)
-    LdsX stash;              // BVC_FLOW_STASH: this wave's operand blocks of the quanta's input
-    LdsX gpark;              // BVC_GRU_FAST: this wave's parked quarter of the GRU layer's weights: [6 blocks][lane]
-    LdsX lpark;              // BVC_FLOW_PARKL: this wave's eight blocks of the first layer's weights (same LDS as gpark: one or the other)
+    LdsX stash;              // this wave's operand blocks of the quanta's input (fetched and verified for the layer that consumes them first)
+    LdsX lpark;              // BVC_FLOW_PARKL: this wave's eight blocks of the first layer's weights
     volatile unsigned __attribute__((address_space(3))) *pubflag;      // BVC_FLOW_PARTNER_WAIT: hop count of wave 0's last publishing store
     unsigned par;            // frame parity
     long long t, fr;         // frame; (utterance, frame) index of this lane's row
@@ -540,13 +474,11 @@ __device__ __forceinline__ void flow_publish(const FlowCtx &c, int hopid, const 
 // One layer: y = epi( sum_s W_s . x_s + bias [+ addend] ).  PER k-blocks per wave and segment (compile time), one or
 // two segments (the one whose input is produced last comes last), PRE_IN: wv already holds segment 0's weights,
 // PRE_OUT: request `nxt`'s weights (PERN blocks per wave) into wn (inside the last segment, or before the reduction).
-// FGATE != -2: a filler quantum rides on this layer - its weights are requested in front of the reduction barrier (or inside the
-// segment: BVC_FILL_EARLY) and multiplied behind the barrier, in the shadow of the epilogue and the hand-off.
-// GRUPRE: (BVC_GRU_FAST) this is the layer in front of the GRU layer - the first half of the GRU's weights is requested inside its segment (gq).
-template <int PER, int EPI, bool TWO, bool ADD, bool PRE_IN, bool PRE_OUT, int PERN, bool REARM_H = false, int FGATE = -2, int NW = 8, bool GRUPRE = false>
+// FGATE != -2: a filler quantum rides on this layer - its weights are requested in front of the reduction barrier and multiplied
+// behind the barrier, in the shadow of the epilogue and the hand-off.
+template <int PER, int EPI, bool TWO, bool ADD, bool PRE_IN, bool PRE_OUT, int PERN, bool REARM_H = false, int FGATE = -2, int NW = 8>
 __device__ __forceinline__ void flow_layer(FlowCtx &c, int hopid, const FlowLin l0, int src0, const FlowLin l1, int src1,
                                            int nb, int ntiles, int out, f32x4 (&wv)[PER], const FlowLin nxt, f32x4 (&wn)[PERN],
-                                           f32x4 (&gq)[GRU_EARLY_BLOCKS],
                                            const f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, const FlowFill fill = FlowFill{nullptr, 0, 0, 0u},
                                            f32x4 *facc = nullptr) {
     const FlowWg &g = c.g;
@@ -560,11 +492,7 @@ __device__ __forceinline__ void flow_layer(FlowCtx &c, int hopid, const FlowLin 
         }
         if (FGATE != -2) {                                 // nothing else to do in this layer: the whole quantum right away
             fill_issue<PERN, FGATE>(g, fill, fw, fx);
-            fill_multiply<PERN, FGATE>(g, fill, fw, fx, *facc, c.stash);
-        }
-        if (BVC_GRU_FAST && GRUPRE) {
-#pragma unroll
-            for (int i = 0; i < GRU_EARLY_BLOCKS; ++i) gq[i] = (f32x4){0.f, 0.f, 0.f, 0.f};     // defined on every path (see wn)
+            fill_multiply<PERN, FGATE>(g, fill, fw, *facc, c.stash);
         }
         return;
     }
@@ -598,37 +526,28 @@ __device__ __forceinline__ void flow_layer(FlowCtx &c, int hopid, const FlowLin 
     f32x4 acc = acc0;
     // EARLY: the next layer's weights are requested inside the (last) segment, right behind its operand requests
     constexpr bool EARLY = BVC_FLOW_EARLYW && PRE_OUT && PER > 1;
-    constexpr bool FEARLY = BVC_FILL_EARLY && FGATE != -2 && PER > 1;
+    constexpr bool FEARLY = false;
     SegHook hk = no_hook();
     if (BVC_FLOW_DIAG) { hk.st_flags = flow_stamp_slot(c, hopid, 2); hk.st_done = flow_stamp_slot(c, hopid, 3); }
     // the layer behind which the first quantum of a product is requested is the one that fetches that product's input
-    if (BVC_FLOW_STASH && FGATE == 0) hk.stash = c.stash;
+    if (FGATE == 0) hk.stash = c.stash;
     if (PER == 1) {                                        // a narrow input (<= 8 k-blocks): one block per wave and pass
         for (int off = 0; off < nb; off += NW)
-            lin_segment<PER, PERN>(g, l0.w, l0.wnb, nb, (unsigned)(src0 * 2 + c.par) * c.sb, false, wv, acc, c.give_up, code, off, hk, wn, fw, gq);
+            lin_segment<PER, PERN>(g, l0.w, l0.wnb, nb, (unsigned)(src0 * 2 + c.par) * c.sb, false, wv, acc, c.give_up, code, off, hk, wn);
         if (TWO)                                           // (h_dim <= 128 without filler quanta: dec.0 of encode has both halves here)
             for (int off = 0; off < nb; off += NW)
-                lin_segment<PER, PERN>(g, l1.w, l1.wnb, nb, (unsigned)(src1 * 2 + c.par) * c.sb, false, wv, acc, c.give_up, code, off, hk, wn, fw, gq);
+                lin_segment<PER, PERN>(g, l1.w, l1.wnb, nb, (unsigned)(src1 * 2 + c.par) * c.sb, false, wv, acc, c.give_up, code, off, hk, wn);
     } else {
         SegHook hl = hk;
         if (EARLY) { hl.nw = nxt.w; hl.nwnb = nxt.wnb; hl.pre = c.pre_now; }
-        constexpr bool GP = BVC_GRU_FAST && GRUPRE;
-        if (GP) { hl.gw = a.w_ihx; hl.gblock = ((size_t)g.ntile * 2 * a.hb + wave * PER) * 3; }
-        if (FEARLY && fill_active<PERN, FGATE>(g, fill)) {
-            static_assert(!FEARLY || BVC_FLOW_STASH, "BVC_FILL_EARLY requests the quantum's weights only: its input must come from the stash");
-            hl.fw = fill.w;
-            hl.fblock = FGATE >= 0 ? ((size_t)g.ntile * fill.wnb + wave * PERN) * 3 + FGATE : (size_t)g.ntile * fill.wnb + wave * PERN;
-            hl.fstride = FGATE >= 0 ? 3 : 1;
-        }
         if (TWO) {
             lin_segment<PER>(g, l0.w, l0.wnb, nb, (unsigned)(src0 * 2 + c.par) * c.sb, PRE_IN, wv, acc, c.give_up, code);
-            lin_segment<PER, PERN, GP, FEARLY>(g, l1.w, l1.wnb, nb, (unsigned)(src1 * 2 + c.par) * c.sb, false, wv, acc, c.give_up, code, 0, hl, wn, fw, gq);
+            lin_segment<PER, PERN, FEARLY>(g, l1.w, l1.wnb, nb, (unsigned)(src1 * 2 + c.par) * c.sb, false, wv, acc, c.give_up, code, 0, hl, wn);
         } else {
-            lin_segment<PER, PERN, GP, FEARLY>(g, l0.w, l0.wnb, nb, (unsigned)(src0 * 2 + c.par) * c.sb, PRE_IN, wv, acc, c.give_up, code, 0, hl, wn, fw, gq);
+            lin_segment<PER, PERN, FEARLY>(g, l0.w, l0.wnb, nb, (unsigned)(src0 * 2 + c.par) * c.sb, PRE_IN, wv, acc, c.give_up, code, 0, hl, wn);
         }
     }
-    constexpr bool LATE = BVC_FLOW_LATEW && PRE_OUT && !EARLY;
-    if (PRE_OUT && !EARLY && !LATE && c.pre_now) {         // the next layer's weights travel during the reduction and the wait
+    if (PRE_OUT && !EARLY && c.pre_now) {         // the next layer's weights travel during the reduction and the wait
         const GPtr ub = uniform_ptr(nxt.w, ((size_t)g.ntile * nxt.wnb + wave * PERN) * g.wmul);
 #pragma unroll
         for (int u = 0; u < PERN; ++u) wn[u] = wload(ub, (unsigned)lane * 16u, u);
@@ -636,32 +555,22 @@ __device__ __forceinline__ void flow_layer(FlowCtx &c, int hopid, const FlowLin 
     // The quantum's operands are requested in front of the barrier and multiplied behind it.  (Round 2 measured the other orders with
     // the quantum's input re-fetched from memory: the publishing wave requesting its own behind its store, or every wave behind the
     // store: 56.8 / 59.1 against 56.4 ms per step - the quantum's own fetch is then exposed behind the layer.)
-    if (FGATE != -2 && !FEARLY) fill_issue<PERN, FGATE>(g, fill, fw, fx);
+    if (FGATE != -2) fill_issue<PERN, FGATE>(g, fill, fw, fx);
     float *r = c.red_lin + (c.hopctr & 1u) * (NW * 256);
     ++c.hopctr;
     *reinterpret_cast<f32x4 *>(r + (wave * 64 + lane) * 4) = acc;
     __syncthreads();
     if (BVC_FLOW_DIAG) flow_stamp(c, hopid, 4);
-    if (LATE && wave != 0 && c.pre_now) {                  // (wave 0: behind its store)
-        const GPtr ub = uniform_ptr(nxt.w, ((size_t)g.ntile * nxt.wnb + wave * PERN) * g.wmul);
-#pragma unroll
-        for (int u = 0; u < PERN; ++u) wn[u] = wload(ub, (unsigned)lane * 16u, u);
-    }
     if (wave == 0) {
         if constexpr (EPI == FE_CODE_SEL) flow_publish<EPI, ADD, REARM_H, NW>(c, hopid, r, n0, ytile, ntiles, out, bias4, add4, mean4, std4, bitsv, recv4);
         else flow_publish<EPI, ADD, REARM_H, NW>(c, hopid, r, n0, ytile, ntiles, out, bias4, add4, mean4, std4, bitsv);
         if (BVC_FLOW_PARTNER_WAIT && NW == 8 && FGATE != -2) *c.pubflag = c.hopctr;
-        if (LATE && c.pre_now) {
-            const GPtr ub = uniform_ptr(nxt.w, ((size_t)g.ntile * nxt.wnb + wave * PERN) * g.wmul);
-#pragma unroll
-            for (int u = 0; u < PERN; ++u) wn[u] = wload(ub, (unsigned)lane * 16u, u);
-        }
     } else if (BVC_FLOW_PARTNER_WAIT && NW == 8 && wave == 4 && FGATE != -2) {
         // waves 0 and 4 share a SIMD: this wave's MFMAs would take issue slots from the epilogue everybody is waiting for
         // (stamps: barrier -> published 0.87 us with the partner multiplying, 0.46 with it waiting, 0.42 in layers without a quantum)
         for (int i = 0; i < 4096 && *c.pubflag != c.hopctr; ++i) __builtin_amdgcn_s_sleep(2);
     }
-    if (FGATE != -2) fill_multiply<PERN, FGATE>(g, fill, fw, fx, *facc, c.stash);
+    if (FGATE != -2) fill_multiply<PERN, FGATE>(g, fill, fw, *facc, c.stash);
     if (BVC_FLOW_DIAG) flow_stamp(c, hopid, 5);
 }
 
@@ -734,13 +643,7 @@ __device__ __forceinline__ void flow_layer_chains(FlowCtx &c, int hopid, const F
         // the first chain of this pass (of this group): wait for its producers, request its blocks
         if (TWO || g0 == 0) {
             g.mtile = mt0 + g0;
-            FlowSrc s0;
-            if (BVC_CHAIN_SPEC) {                          // no flag poll (a round trip to the fabric): request the blocks, verify them below
-                s0.base = __builtin_amdgcn_readfirstlane(bufp + (unsigned)(g.mtile * nb + kb0) * 1024u);
-                s0.vl = (unsigned)lane * 16u;
-            } else {
-                s0 = flow_wait<PER>(g, bufp, nb, kb0, c.give_up, code, spins);
-            }
+            const FlowSrc s0 = flow_wait<PER>(g, bufp, nb, kb0, c.give_up, code, spins);
             flow_issue<PER>(g, s0, xc);
         }
 #pragma unroll
@@ -899,7 +802,7 @@ __device__ __forceinline__ void gru_epilogue(const FlowCtx &c, int hopid, int hb
 // GRU cell (PyTorch gate order r, z, n; bvrnn.py:206,227): gh = W_hh h, gi = W_ih [phi_x_gen ; phi_z]; in decode the
 // phi_z half of gi (+ b_ih) arrives pre-computed (a.part_gru).  Segments in the order their inputs become ready.
 template <int PER, bool ENCODE, int PERN, bool FILL, int NW = 8>
-__device__ __forceinline__ void flow_gru(FlowCtx &c, int hopid, int hb, const FlowLin nxt, f32x4 (&wn)[PERN], f32x4 (&gq)[GRU_EARLY_BLOCKS]) {
+__device__ __forceinline__ void flow_gru(FlowCtx &c, int hopid, int hb, const FlowLin nxt, f32x4 (&wn)[PERN]) {
     const FlowWg &g = c.g;
     const auto &a = *c.a;
     if (g.ntile >= hb) {
@@ -929,29 +832,7 @@ __device__ __forceinline__ void flow_gru(FlowCtx &c, int hopid, int hb, const Fl
     // h(t) and (encode) phi_z(z_t) are complete and were verified by this very wave earlier in the frame: their blocks are
     // requested at once and multiplied while phi_x(d_t), the input produced last, is still on its way
     // The weights stream through two register sets: the request for round i+1 is issued before round i is multiplied.
-    if constexpr (FILL && PER == 8 && BVC_GRU_FAST) {
-        // Four rounds of two k-blocks x three gates, in k order (the same sums as the generic form below).  Rounds 0 and 1 were requested
-        // a layer ago (gq), round 2 has been in LDS since the launch began, round 3 is requested into the registers round 0 leaves.
-        const unsigned l16 = (unsigned)lane * 16u;
-        const GPtr ux = uniform_ptr(a.w_ihx, ((size_t)g.ntile * 2 * hb + wave * PER) * 3 * g.wmul);
-        u32x4 xa[PER];
-        gru_fetch_fresh<PER>(g, (unsigned)(FB_G3 * 2 + c.par) * c.sb, hb, xa, c.give_up, code);
-        if (BVC_FLOW_DIAG) flow_stamp(c, hopid, 2);        // (here: flags seen AND operands fetched)
-        // (scheduling fences: hoisting the later rounds' loads above the earlier rounds' products would need registers that are not there)
-        gru_round6<PER>(gq, xa, 0, gi);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) gq[i] = wload(ux, l16, 18 + i);                       // round 3: k-blocks 6, 7
-        __builtin_amdgcn_sched_barrier(0);
-        gru_round6<PER>(gq + 6, xa, 2, gi);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) gq[6 + i] = __builtin_bit_cast(f32x4, c.gpark[i * 64 + lane]);    // round 2: k-blocks 4, 5
-        __builtin_amdgcn_sched_barrier(0);
-        gru_round6<PER>(gq + 6, xa, 4, gi);
-        gru_round6<PER>(gq, xa, 6, gi);
-        __builtin_amdgcn_sched_barrier(0);
-    } else if (!(PER == 1 && wave >= hb)) {                // (wave-uniform) a wave without a k-block of its own contributes zeros
+    if (!(PER == 1 && wave >= hb)) {                       // (wave-uniform) a wave without a k-block of its own contributes zeros
         constexpr int HALF = FILL ? (PER >= BVC_GRU_ROUNDS_FILL ? PER / BVC_GRU_ROUNDS_FILL : 1) : (PER >= 4 ? PER / 4 : 1);       // k-blocks per round
         constexpr int RPS = PER / HALF;                    // rounds per segment
         constexpr int NSEG = FILL ? 1 : (ENCODE ? 3 : 2);  // FILL: the h and phi_z products were accumulated earlier in the frame
@@ -1080,9 +961,6 @@ __device__ __forceinline__ void flow_gru_chains(FlowCtx &c, int hopid, int hb, c
 
 // PERH: k-blocks per wave of an h_dim-sized operand (h_dim = 128 * PERH, or h_dim <= 128 for PERH = 1: then a wave owns at
 // most one k-block); the z_dim- and num_mels-sized operands (<= 128) always have one k-block per wave.
-#ifndef BVC_FLOW_WAVES_PER_SIMD
-#define BVC_FLOW_WAVES_PER_SIMD 2
-#endif
 // MULTI: one layer of the static program, chain by chain
 #define FLOW_EACH_CHAIN(...)                                                                                            \
     for (int ci_ = 0; ci_ < nch; ++ci_) {                                                                               \
@@ -1115,15 +993,13 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? BVC_FLOW_WAVES_PER_SIMD : 1) voi
     c.a = ap;
     // LDS: [2][NW][256] layer partials | [NW][6][256] GRU partials | MULTI: [2][4][NW][256] partials of a group of chains.  Filler kernels: the waves' operand stashes
     // (NW x 8 KiB) lie over the GRU partials - the stashes are dead from the last quantum (layer 9) to the next frame's first layer,
-    // whose operand, h(t+1), exists only after wave 0 has read the partials -, then the parked weights (NW x 8 KiB: the first layer's, BVC_FLOW_PARKL;
-    // or a quarter of the GRU layer's, BVC_GRU_FAST), then the flag.
+    // whose operand, h(t+1), exists only after wave 0 has read the partials -, then the parked weights (NW x 8 KiB: the first layer's, BVC_FLOW_PARKL),
+    // then the flag.
     c.red_lin = lds;
     c.red_gru = lds + 2 * NW * 256;
     c.red_chain = lds + 2 * NW * 256 + NW * 6 * 256;      // (MULTI only: FLOW_LDS_MULTI)
     c.stash = (LdsX)(lds + 2 * NW * 256) + (tid >> 6) * (PERH * 64);
-    c.gpark = (LdsX)(lds + 2 * NW * 256 + NW * 8 * 256) + (tid >> 6) * (6 * 64);
     c.lpark = (LdsX)(lds + 2 * NW * 256 + NW * 8 * 256) + (tid >> 6) * (8 * 64);
-    static_assert(!(BVC_FLOW_PARKL && BVC_GRU_FAST), "one use of the parking region");
     c.pubflag = (volatile unsigned __attribute__((address_space(3))) *)(lds + 2 * NW * 256 + NW * 8 * 256 + NW * 8 * 256);
     if (FILL && tid == 0) c.pubflag[0] = 0xFFFFFFFFu;
     c.g.lane = tid & 63;
@@ -1153,22 +1029,13 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? BVC_FLOW_WAVES_PER_SIMD : 1) voi
     const long long T = ap->T;
     const bool hfull = c.g.ntile < hb;                     // this workgroup owns a tile of the h_dim-wide layers
     f32x4 wa[PERH], wb[PERH], w1[1];
-    f32x4 gq[GRU_EARLY_BLOCKS];                            // BVC_GRU_FAST: the GRU layer's early-requested weights (rounds 0, 1)
-    constexpr bool GFAST = FILL && PERH == 8 && BVC_GRU_FAST && !MULTI;
-    constexpr bool GPRE = GFAST;
-    if (GFAST && hfull) {                                  // park round 2 (k-blocks 4, 5 x three gates) of this wave's share of W_ih[:, :H]
-        const GPtr ux = uniform_ptr(ap->w_ihx, (((size_t)c.g.ntile * 2 * hb + c.g.wave * PERH) * 3 + 12) * c.g.wmul);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) c.gpark[i * 64 + c.g.lane] = __builtin_bit_cast(u32x4, wload(ux, (unsigned)c.g.lane * 16u, i));
-    }
     // BVC_FLOW_PARKV: wide layers whose weights - this wave's eight blocks each - stay in registers for the whole launch.  Layers that
     // carry a filler quantum first (their waves request two weight sets in front of the reduction barrier otherwise): dec.2, dec.4; decode has
     // registers for a third: phi_x.4
     constexpr bool PK = BVC_FLOW_PARKV && FILL && !MULTI;
     constexpr bool PL = BVC_FLOW_PARKL && FILL && !MULTI && PERH == 8;
-    constexpr bool P8 = PK && BVC_FLOW_PARK_SET == 1, P9 = PK && (BVC_FLOW_PARK_SET == 1 || (!ENCODE && BVC_FLOW_PARKV >= 2)),
-                   P12 = PK && BVC_FLOW_PARK_SET == 0, P13 = PK && (BVC_FLOW_PARK_SET == 0 || (!ENCODE && BVC_FLOW_PARKV >= 2));
-    f32x4 k8[P8 ? PERH : 1], k9[P9 ? PERH : 1], k12[P12 ? PERH : 1], k13[P13 ? PERH : 1];
+    constexpr bool P8 = PK, P9 = PK, P13 = PK && !ENCODE && BVC_FLOW_PARKV >= 2;
+    f32x4 k8[P8 ? PERH : 1], k9[P9 ? PERH : 1], k13[P13 ? PERH : 1];
     {
         auto park = [&](auto &k, const FlowLin l) {
             const GPtr u = uniform_ptr(l.w, hfull ? (size_t)c.g.ntile * l.wnb + c.g.wave * PERH : 0);
@@ -1177,7 +1044,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? BVC_FLOW_WAVES_PER_SIMD : 1) voi
         };
         if constexpr (P8) park(k8, L(ap->dec1));
         if constexpr (P9) park(k9, L(ap->dec2));
-        if constexpr (P12) park(k12, L(ap->px1));
         if constexpr (P13) park(k13, L(ap->px2));
     }
     {
@@ -1215,48 +1081,48 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? BVC_FLOW_WAVES_PER_SIMD : 1) voi
         const FlowFill f_hh = {a.w_hh, hb, hb, hsrc}, f_d0 = {a.dec0h.w, a.dec0h.wnb, hb, hsrc}, f_iz = {a.w_ihz, 2 * hb, hb, zsrc};
         const bool folded = FOLD < 0 ? a.pxc.w != nullptr : FOLD == 1;      // (uniform) dec.6 -> norm -> phi_x.0 folded into one layer (FlowArgs::pxc)
         if constexpr (!MULTI) {
-            // (wK: the weights of wide layer K - prefetched into wa / wb by the layer in front of it, or resident in registers: P8 .. P13)
-            auto &w8 = pick<P8>(k8, wb);  auto &w9 = pick<P9>(k9, wa);  auto &w12 = pick<P12>(k12, wa);  auto &w13 = pick<P13>(k13, wb);
+            // (wK: the weights of wide layer K - prefetched into wa / wb by the layer in front of it, or resident in registers: P8, P9, P13)
+            auto &w8 = pick<P8>(k8, wb);  auto &w9 = pick<P9>(k9, wa);  auto &w13 = pick<P13>(k13, wb);
             if (ENCODE) {
                 //         PER   epilogue  two    add    pre_in pre_out       rearm  filler
-                flow_layer<PERH, FE_ELU, false, !CONCEAL, true, true, PERH, false, G0, NW>(c, 1, L(a.enc0h), FB_H, L(a.enc0h), 0, hb, hb, FB_E1, wa, L(a.enc1), wb, gq, zero4, f_hh, &c.fgh[0]);
-                flow_layer<PERH, FE_ELU, false, false, true, false, PERH, true, G1, NW>(c, 2, L(a.enc1), FB_E1, L(a.enc1), 0, hb, hb, FB_E2, wb, L(a.enc1), wa, gq, zero4, f_hh, &c.fgh[1]);
-                flow_layer<PERH, EPI3, false, false, false, false, PERH, false, G2, NW>(c, 3, L(a.enc2), FB_E2, L(a.enc2), 0, hb, zb, FB_ZC, wa, L(a.enc2), wb, gq, zero4, f_hh, &c.fgh[2]);
-                flow_layer<1, FE_ELU, false, false, false, true, PERH, false, GP, NW>(c, 4, L(a.pz0), FB_ZC, L(a.pz0), 0, zb, hb, FB_Q1, w1, L(a.pz1), wa, gq, zero4, f_d0, &c.fd0);
-                flow_layer<PERH, FE_ELU, false, false, true, true, PERH, false, -2, NW>(c, 5, L(a.pz1), FB_Q1, L(a.pz1), 0, hb, hb, FB_Q2, wa, L(a.pz2), wb, gq);
+                flow_layer<PERH, FE_ELU, false, !CONCEAL, true, true, PERH, false, G0, NW>(c, 1, L(a.enc0h), FB_H, L(a.enc0h), 0, hb, hb, FB_E1, wa, L(a.enc1), wb, zero4, f_hh, &c.fgh[0]);
+                flow_layer<PERH, FE_ELU, false, false, true, false, PERH, true, G1, NW>(c, 2, L(a.enc1), FB_E1, L(a.enc1), 0, hb, hb, FB_E2, wb, L(a.enc1), wa, zero4, f_hh, &c.fgh[1]);
+                flow_layer<PERH, EPI3, false, false, false, false, PERH, false, G2, NW>(c, 3, L(a.enc2), FB_E2, L(a.enc2), 0, hb, zb, FB_ZC, wa, L(a.enc2), wb, zero4, f_hh, &c.fgh[2]);
+                flow_layer<1, FE_ELU, false, false, false, true, PERH, false, GP, NW>(c, 4, L(a.pz0), FB_ZC, L(a.pz0), 0, zb, hb, FB_Q1, w1, L(a.pz1), wa, zero4, f_d0, &c.fd0);
+                flow_layer<PERH, FE_ELU, false, false, true, true, PERH, false, -2, NW>(c, 5, L(a.pz1), FB_Q1, L(a.pz1), 0, hb, hb, FB_Q2, wa, L(a.pz2), wb);
                 if (FILL) {
                     FlowLin d0 = L(a.dec0z);                   // dec.0: only the phi_z half is left; the bias travels with dec0h
                     d0.bias = a.dec0h.bias;
-                    flow_layer<PERH, FE_ELU, false, false, true, true, PERH, false, -2, NW>(c, 6, L(a.pz2), FB_Q2, L(a.pz2), 0, hb, hb, FB_Q3, wb, d0, wa, gq);
-                    flow_layer<PERH, FE_ELU, false, false, true, !P8, PERH, false, G0, NW>(c, 7, d0, FB_Q3, d0, 0, hb, hb, FB_D1, wa, L(a.dec1), wb, gq, c.fd0, f_iz, &c.fgi[0]);
+                    flow_layer<PERH, FE_ELU, false, false, true, true, PERH, false, -2, NW>(c, 6, L(a.pz2), FB_Q2, L(a.pz2), 0, hb, hb, FB_Q3, wb, d0, wa);
+                    flow_layer<PERH, FE_ELU, false, false, true, !P8, PERH, false, G0, NW>(c, 7, d0, FB_Q3, d0, 0, hb, hb, FB_D1, wa, L(a.dec1), wb, c.fd0, f_iz, &c.fgi[0]);
                 } else {
-                    flow_layer<PERH, FE_ELU, false, false, true, true, PERH, false, -2, NW>(c, 6, L(a.pz2), FB_Q2, L(a.pz2), 0, hb, hb, FB_Q3, wb, L(a.dec0h), wa, gq);
-                    flow_layer<PERH, FE_ELU, true, false, true, true, PERH, false, -2, NW>(c, 7, L(a.dec0h), FB_H, L(a.dec0z), FB_Q3, hb, hb, FB_D1, wa, L(a.dec1), wb, gq);
+                    flow_layer<PERH, FE_ELU, false, false, true, true, PERH, false, -2, NW>(c, 6, L(a.pz2), FB_Q2, L(a.pz2), 0, hb, hb, FB_Q3, wb, L(a.dec0h), wa);
+                    flow_layer<PERH, FE_ELU, true, false, true, true, PERH, false, -2, NW>(c, 7, L(a.dec0h), FB_H, L(a.dec0z), FB_Q3, hb, hb, FB_D1, wa, L(a.dec1), wb);
                 }
-                flow_layer<PERH, FE_ELU, false, false, true, !P9, PERH, false, G1, NW>(c, 8, L(a.dec1), FB_D1, L(a.dec1), 0, hb, hb, FB_D2, w8, L(a.dec2), wa, gq, zero4, f_iz, &c.fgi[1]);
+                flow_layer<PERH, FE_ELU, false, false, true, !P9, PERH, false, G1, NW>(c, 8, L(a.dec1), FB_D1, L(a.dec1), 0, hb, hb, FB_D2, w8, L(a.dec2), wa, zero4, f_iz, &c.fgi[1]);
                 if (folded) {
-                    flow_layer<PERH, FE_ELU_KEEP, false, false, true, true, PERH, false, G2, NW>(c, 9, L(a.dec2), FB_D2, L(a.dec2), 0, hb, hb, FB_D3, w9, L(a.pxc), wb, gq, zero4, f_iz, &c.fgi[2]);
-                    flow_layer<PERH, FE_ELU, false, false, true, !P12, PERH, false, -2, NW>(c, 11, L(a.pxc), FB_D3, L(a.pxc), 0, hb, hb, FB_G1, wb, L(a.px1), wa, gq);
+                    flow_layer<PERH, FE_ELU_KEEP, false, false, true, true, PERH, false, G2, NW>(c, 9, L(a.dec2), FB_D2, L(a.dec2), 0, hb, hb, FB_D3, w9, L(a.pxc), wb, zero4, f_iz, &c.fgi[2]);
+                    flow_layer<PERH, FE_ELU, false, false, true, true, PERH, false, -2, NW>(c, 11, L(a.pxc), FB_D3, L(a.pxc), 0, hb, hb, FB_G1, wb, L(a.px1), wa);
                 } else {
-                    flow_layer<PERH, FE_ELU, false, false, true, false, PERH, false, G2, NW>(c, 9, L(a.dec2), FB_D2, L(a.dec2), 0, hb, hb, FB_D3, w9, L(a.dec2), wb, gq, zero4, f_iz, &c.fgi[2]);
-                    flow_layer<PERH, FE_MEL, false, false, false, false, PERH, false, -2, NW>(c, 10, L(a.dec3), FB_D3, L(a.dec3), 0, hb, xb, FB_DN, wa, L(a.dec3), wb, gq);
+                    flow_layer<PERH, FE_ELU, false, false, true, false, PERH, false, G2, NW>(c, 9, L(a.dec2), FB_D2, L(a.dec2), 0, hb, hb, FB_D3, w9, L(a.dec2), wb, zero4, f_iz, &c.fgi[2]);
+                    flow_layer<PERH, FE_MEL, false, false, false, false, PERH, false, -2, NW>(c, 10, L(a.dec3), FB_D3, L(a.dec3), 0, hb, xb, FB_DN, wa, L(a.dec3), wb);
                 }
             } else {
-                flow_layer<PERH, FE_ELU, false, true, true, !P8, PERH, false, G0, NW>(c, 7, L(a.dec0h), FB_H, L(a.dec0h), 0, hb, hb, FB_D1, wa, L(a.dec1), wb, gq, zero4, f_hh, &c.fgh[0]);
-                flow_layer<PERH, FE_ELU, false, false, true, !P9, PERH, true, G1, NW>(c, 8, L(a.dec1), FB_D1, L(a.dec1), 0, hb, hb, FB_D2, w8, L(a.dec2), wa, gq, zero4, f_hh, &c.fgh[1]);
+                flow_layer<PERH, FE_ELU, false, true, true, !P8, PERH, false, G0, NW>(c, 7, L(a.dec0h), FB_H, L(a.dec0h), 0, hb, hb, FB_D1, wa, L(a.dec1), wb, zero4, f_hh, &c.fgh[0]);
+                flow_layer<PERH, FE_ELU, false, false, true, !P9, PERH, true, G1, NW>(c, 8, L(a.dec1), FB_D1, L(a.dec1), 0, hb, hb, FB_D2, w8, L(a.dec2), wa, zero4, f_hh, &c.fgh[1]);
                 if (folded) {                              // dec.4 (its output is kept for all frames) -> phi_x.0 o norm o dec.6 as one wide layer
-                    flow_layer<PERH, FE_ELU_KEEP, false, false, true, true, PERH, false, G2, NW>(c, 9, L(a.dec2), FB_D2, L(a.dec2), 0, hb, hb, FB_D3, w9, L(a.pxc), wb, gq, zero4, f_hh, &c.fgh[2]);
-                    flow_layer<PERH, FE_ELU, false, false, true, !P12, PERH, false, -2, NW>(c, 11, L(a.pxc), FB_D3, L(a.pxc), 0, hb, hb, FB_G1, wb, L(a.px1), wa, gq);
+                    flow_layer<PERH, FE_ELU_KEEP, false, false, true, true, PERH, false, G2, NW>(c, 9, L(a.dec2), FB_D2, L(a.dec2), 0, hb, hb, FB_D3, w9, L(a.pxc), wb, zero4, f_hh, &c.fgh[2]);
+                    flow_layer<PERH, FE_ELU, false, false, true, true, PERH, false, -2, NW>(c, 11, L(a.pxc), FB_D3, L(a.pxc), 0, hb, hb, FB_G1, wb, L(a.px1), wa);
                 } else {
-                    flow_layer<PERH, FE_ELU, false, false, true, false, PERH, false, G2, NW>(c, 9, L(a.dec2), FB_D2, L(a.dec2), 0, hb, hb, FB_D3, w9, L(a.dec2), wb, gq, zero4, f_hh, &c.fgh[2]);
-                    flow_layer<PERH, FE_MEL, false, false, false, false, PERH, false, -2, NW>(c, 10, L(a.dec3), FB_D3, L(a.dec3), 0, hb, xb, FB_DN, wa, L(a.dec3), wb, gq);
+                    flow_layer<PERH, FE_ELU, false, false, true, false, PERH, false, G2, NW>(c, 9, L(a.dec2), FB_D2, L(a.dec2), 0, hb, hb, FB_D3, w9, L(a.dec2), wb, zero4, f_hh, &c.fgh[2]);
+                    flow_layer<PERH, FE_MEL, false, false, false, false, PERH, false, -2, NW>(c, 10, L(a.dec3), FB_D3, L(a.dec3), 0, hb, xb, FB_DN, wa, L(a.dec3), wb);
                 }
             }
             if (!folded)
-                flow_layer<1, FE_ELU, false, false, false, !P12, PERH, false, -2, NW>(c, 11, L(a.px0), FB_DN, L(a.px0), 0, xb, hb, FB_G1, w1, L(a.px1), wa, gq);
-            flow_layer<PERH, FE_ELU, false, false, true, !P13, PERH, false, -2, NW>(c, 12, L(a.px1), FB_G1, L(a.px1), 0, hb, hb, FB_G2, w12, L(a.px2), wb, gq);
-            flow_layer<PERH, FE_ELU, false, false, true, false, PERH, false, -2, NW, GPRE>(c, 13, L(a.px2), FB_G2, L(a.px2), 0, hb, hb, FB_G3, w13, L(a.px2), wa, gq);
-            flow_gru<PERH, ENCODE, PERH, FILL, NW>(c, 14, hb, ENCODE ? L(a.enc0h) : L(a.dec0h), wa, gq);
+                flow_layer<1, FE_ELU, false, false, false, true, PERH, false, -2, NW>(c, 11, L(a.px0), FB_DN, L(a.px0), 0, xb, hb, FB_G1, w1, L(a.px1), wa);
+            flow_layer<PERH, FE_ELU, false, false, true, !P13, PERH, false, -2, NW>(c, 12, L(a.px1), FB_G1, L(a.px1), 0, hb, hb, FB_G2, wa, L(a.px2), wb);
+            flow_layer<PERH, FE_ELU, false, false, true, false, PERH, false, -2, NW>(c, 13, L(a.px2), FB_G2, L(a.px2), 0, hb, hb, FB_G3, w13, L(a.px2), wa);
+            flow_gru<PERH, ENCODE, PERH, FILL, NW>(c, 14, hb, ENCODE ? L(a.enc0h) : L(a.dec0h), wa);
         } else {
             // the same program on interleaved chains (no filler quanta): wide single-segment layers pipeline their chains
             // (flow_layer_chains), the two narrow-input layers, the two-segment dec.0 of encode and the GRU go chain by chain
@@ -1265,7 +1131,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? BVC_FLOW_WAVES_PER_SIMD : 1) voi
                 flow_layer_chains<PERH, FE_ELU, !CONCEAL, true, true, PERH, false, NW>(c, 1, L(a.enc0h), FB_H, hb, hb, FB_E1, wa, L(a.enc1), wb, mt0, nch, T);
                 flow_layer_chains<PERH, FE_ELU, false, true, false, PERH, true, NW>(c, 2, L(a.enc1), FB_E1, hb, hb, FB_E2, wb, L(a.enc1), wa, mt0, nch, T);
                 flow_layer_chains<PERH, EPI3, false, false, false, PERH, false, NW>(c, 3, L(a.enc2), FB_E2, hb, zb, FB_ZC, wa, L(a.enc2), wb, mt0, nch, T);
-                FLOW_EACH_CHAIN(flow_layer<1, FE_ELU, false, false, false, true, PERH, false, -2, NW>(c, 4, L(a.pz0), FB_ZC, L(a.pz0), 0, zb, hb, FB_Q1, w1, L(a.pz1), wa, gq));
+                FLOW_EACH_CHAIN(flow_layer<1, FE_ELU, false, false, false, true, PERH, false, -2, NW>(c, 4, L(a.pz0), FB_ZC, L(a.pz0), 0, zb, hb, FB_Q1, w1, L(a.pz1), wa));
                 flow_layer_chains<PERH, FE_ELU, false, true, true, PERH, false, NW>(c, 5, L(a.pz1), FB_Q1, hb, hb, FB_Q2, wa, L(a.pz2), wb, mt0, nch, T);
                 flow_layer_chains<PERH, FE_ELU, false, true, false, PERH, false, NW>(c, 6, L(a.pz2), FB_Q2, hb, hb, FB_Q3, wb, L(a.pz2), wa, mt0, nch, T);
                 // two segments share the weight registers: the first segment's weights are fetched per chain
@@ -1296,7 +1162,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? BVC_FLOW_WAVES_PER_SIMD : 1) voi
             }
             if (!folded) {
                 flow_layer_chains<PERH, FE_MEL, false, false, false, PERH, false, NW>(c, 10, L(a.dec3), FB_D3, hb, xb, FB_DN, wa, L(a.dec3), wb, mt0, nch, T);
-                FLOW_EACH_CHAIN(flow_layer<1, FE_ELU, false, false, false, true, PERH, false, -2, NW>(c, 11, L(a.px0), FB_DN, L(a.px0), 0, xb, hb, FB_G1, w1, L(a.px1), wa, gq));
+                FLOW_EACH_CHAIN(flow_layer<1, FE_ELU, false, false, false, true, PERH, false, -2, NW>(c, 11, L(a.px0), FB_DN, L(a.px0), 0, xb, hb, FB_G1, w1, L(a.px1), wa));
             }
             flow_layer_chains<PERH, FE_ELU, false, true, true, PERH, false, NW>(c, 12, L(a.px1), FB_G1, hb, hb, FB_G2, wa, L(a.px2), wb, mt0, nch, T);
             flow_layer_chains<PERH, FE_ELU, false, true, false, PERH, false, NW>(c, 13, L(a.px2), FB_G2, hb, hb, FB_G3, wb, L(a.px2), wa, mt0, nch, T);

@@ -1,7 +1,7 @@
 """Builds variant libraries of the persistent recurrence (k_flow.hip with extra -D switches) next to the product library, and
 times them against each other on the GPU box.
 
-    python tools/flow_variants.py build base: earlyw:-DBVC_FLOW_EARLYW=1 "poll2:-DBVC_FLOW_POLLDEPTH=2"     (here: cross-compiles)
+    python tools/flow_variants.py build base: depth2:-DBVC_GRU_DEPTH=2 "g2diag:-DBVC_CHAIN_G=2 -DBVC_FLOW_DIAG=1"     (here: cross-compiles)
     python tools/flow_variants.py run [--seconds 5] [--batch 64] [--reps 5] [--diag] name...                (on the GPU box)
 
 Every variant runs in its own process (BVC_LIB selects the library); codes / mel of every variant are compared with the first one.
@@ -15,7 +15,6 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bernoulli-var-speech-codec_amd", "csrc")
 VDIR = os.path.join(CSRC, "variants")
-FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 
 def build(specs):
@@ -28,12 +27,12 @@ def build(specs):
     for spec in specs:
         name, _, defs = spec.partition(":")
         o = os.path.join(VDIR, f"k_flow_{name}.o")
-        cmd = [hipcc] + FLAGS + defs.split() + ["-c", os.path.join(CSRC, "k_flow.hip"), "-o", o]
+        cmd = [hipcc] + b.FLAGS + defs.split() + ["-c", os.path.join(CSRC, "k_flow.hip"), "-o", o]
         procs.append((name, o, subprocess.Popen(cmd)))
     for name, o, p in procs:
         if p.wait():
             raise SystemExit(f"variant {name}: compile failed")
-        objs = [os.path.join(CSRC, f) for f in ("bvcodec_abi.o", "model.o", "recurrence.o", "generator.o", "stream_codec.o", "k_gemm.o", "k_frontend.o", "k_vocoder.o")] + [o]
+        objs = [os.path.join(CSRC, f.replace(".hip", ".o")) for f in b.SOURCES if f != "k_flow.hip"] + [o]
         lib = os.path.join(VDIR, f"libbvcodec_{name}.so")
         subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
         print("built", lib)
