@@ -56,22 +56,69 @@ def is_antialiased(conf):
 
 NOT_CAUSAL = ("this generator has anti-aliased activations: every filtered AMP block looks 30 rows ahead, so it cannot run "
               "incrementally or on mixed-length batches (decode equal-length batches offline)")
+NOT_CAUSAL_SYM = ("this generator has symmetric layers: a symmetric layer reads as many rows ahead as behind, so it cannot run "
+                  "incrementally or on mixed-length batches (decode equal-length batches offline)")
+
+
+def symmetric_flags(conf):
+    """(per-stage list, pre switch, post switch): where the generator pads symmetrically instead of causally - ``layers_sym[i]``
+    upsampler i and the stage's AMP blocks, ``pre_sym`` conv_pre, ``post_sym`` conv_post (third_party/BigVGAN/models.py:35-44,
+    151-155,209-213,230-233; absent keys: nowhere)."""
+    v = conf["vocoder_config"]
+    n = len(v["upsample_rates"])
+    return [bool(f) for f in v.get("layers_sym", [False] * n)], bool(v.get("pre_sym", False)), bool(v.get("post_sym", False))
+
+
+def is_symmetric(conf):
+    stages, pre, post = symmetric_flags(conf)
+    return any(stages) or pre or post
+
+
+def is_causal(conf):
+    """Every output sample depends on earlier frames only: what streaming and mixed-length decoding count on."""
+    return not (is_antialiased(conf) or is_symmetric(conf))
+
+
+def not_causal_message(conf):
+    """Why a non-causal generator is refused: a filtered one keeps its text, a symmetric, unfiltered one says so."""
+    return NOT_CAUSAL if is_antialiased(conf) else NOT_CAUSAL_SYM
+
+
+def generator_length(conf, T, stages=False):
+    """Samples the generator makes of T frames: L_0 = T, L_{i+1} = L_i * u_i behind a symmetric upsampler (ConvTranspose1d with
+    padding (k - u) / 2, k = 2u), (L_i + 1) * u_i behind a causal one.  ``stages``: the list of the stage lengths instead."""
+    sym = symmetric_flags(conf)[0]
+    L, out = int(T), []
+    for u, s in zip(conf["vocoder_config"]["upsample_rates"], sym):
+        L = L * u if s else (L + 1) * u
+        out.append(L)
+    return out if stages else L
 
 
 def check_supported(conf):
-    """The HIP path covers the causal snakebeta generator, with or without anti-aliased activations per stage; anything else
-    fails loudly."""
+    """The HIP path covers the snakebeta generator with causal or symmetric layers, and anti-aliased activations on causal stages;
+    anything else fails loudly."""
     v = conf["vocoder_config"]
     bad = []
     if v.get("resblock", "1") != "1":
         bad.append("vocoder_config.resblock must be '1'")
     if v.get("activation", "snakebeta") != "snakebeta" or not v.get("snake_logscale", True):
         bad.append("only activation='snakebeta' with snake_logscale=true is implemented")
-    if any(v.get("layers_sym", [False])) or v.get("pre_sym", False) or v.get("post_sym", False):
-        bad.append("only causal (non-symmetric) layers are implemented")
     aa = v.get("layers_antialias")
     if aa is not None and len(aa) != len(v["upsample_rates"]):
         bad.append(f"layers_antialias must have one entry per upsampling stage ({len(v['upsample_rates'])}), got {len(aa)}")
+    sym = v.get("layers_sym")
+    if sym is not None and len(sym) != len(v["upsample_rates"]):
+        bad.append(f"layers_sym must have one entry per upsampling stage ({len(v['upsample_rates'])}), got {len(sym)}")
+    elif sym is not None and any(sym):
+        if any(k % 2 == 0 for k in v["resblock_kernel_sizes"]):
+            bad.append("a symmetric stage (layers_sym) needs odd resblock_kernel_sizes")
+        if aa is not None and len(aa) == len(sym) and any(a and s for a, s in zip(aa, sym)):
+            bad.append("filtered (anti-aliased) stages are implemented as causal stages only: layers_sym and layers_antialias "
+                       "are set on the same stage")
+    if v.get("post_sym", False) and v.get("antialias_post", False):
+        bad.append("a filtered (anti-aliased) activation_post is implemented in front of a causal conv_post only: post_sym and "
+                   "antialias_post are both set")
     for u, k in zip(v["upsample_rates"], v["upsample_kernel_sizes"]):
         if k != 2 * u:
             bad.append(f"transposed conv kernel {k} must be 2 x stride {u}")

@@ -49,6 +49,10 @@ struct bvc_model {
     const float *post_up = nullptr, *post_down = nullptr;   // antialias_post: activation_post's two filters
     int post_c = 0, post_ks = 7;
     bool antialiased = false;   // some stage, or activation_post, has anti-aliased activations: the generator is not causal
+    std::vector<bool> stage_sym;        // layers_sym: upsampler i and the stage's AMP blocks pad symmetrically (models.py:35-44,151-155)
+    bool pre_sym = false, post_sym = false;   // conv_pre / conv_post pad [3, 3] instead of [6, 0]
+    bool symmetric = false;     // any of them
+    bool noncausal = false;     // antialiased || symmetric: what streaming, the windowed test entry and mixed lengths refuse
     // captured recurrent steps (hipGraph), keyed by (kind, batch, workspace)
     // (launch-per-layer schedule only) most recently used first; `idle` is recorded behind the entry's last replay, so an
     // entry is only destroyed once the GPU is done with it
@@ -176,6 +180,7 @@ int check_ws(const bvc_model *m, int B, int64_t T, void *d_ws, size_t ws_bytes, 
 int sticky_status(const bvc_model *m);
 int need_prior(const bvc_model *m, const char *fn);
 extern const char *const NOT_CAUSAL;
+const char *not_causal(const bvc_model *m);     // why a noncausal model is refused: NOT_CAUSAL for a filtered one, else the symmetric text
 int flow_census(const bvc_model *m);
 
 // ---- GEMM parameters ----------------------------------------------------------------------------
@@ -230,7 +235,10 @@ int run_forward(const bvc_model *m, const Workspace &w, const float *d_mel, cons
                 bool update_h2, const float *d_noise, int B, int64_t T, float *d_dec, float *d_kld, float *d_z, float *d_prob,
                 float *d_prior, hipStream_t s);
 int run_vocoder(const bvc_model *m, const Workspace &w, const float *d_mel, int B, int64_t T, int64_t length, float div, float *d_wav,
-                int stop_after, const float **tap, int64_t *tap_len, int *tap_ch, hipStream_t s, const long long *lim = nullptr);
+                int stop_after, const float **tap, int64_t *tap_len, int *tap_ch, hipStream_t s, const long long *lim = nullptr,
+                int64_t *tap_bs = nullptr);     // tap_bs: floats between the tap's batch items (a symmetric stage works on a view)
+
+int copy_rows(const float *src, long long src_bs, float *dst, long long dst_bs, long long n, int B, hipStream_t s);   // generator.hip
 
 const int64_t STREAM_WARM_FRAMES = 32;   // rate * 32 - 64 >= 60 = the longest receptive field of an AMP pair, for every stage rate >= 8
 const int STREAM_H = 64;     // history rows per stage: >= (ks-1)*dil + (ks-1) of every AMP pair (max 60) and a multiple of every rate

@@ -334,18 +334,25 @@ int launch_snakebeta_test(const float *x, long long n, float a, float ib, float 
 // row_lim (B) or nullptr: input rows of item b from row_lim[b] on read as zeros (a mixed-length batch; row_lim[b] <= Lin)
 int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *out, long long Lout,
                      int B, int epi, const float *res, const float *acc, float divisor, hipStream_t s,
-                     const ConvWindow *win = nullptr, const long long *row_lim = nullptr);
+                     const ConvWindow *win = nullptr, const long long *row_lim = nullptr,
+                     long long in_bs = 0,      // floats between the input's batch items where that is not Lin * cin (offline: a symmetric stage's view)
+                     int shift = 0);           // 3: conv_pre of a pre_sym generator, out[t] = b + sum_j w[j] in[t - 3 + j] (pad [3, 3]); offline
 // one fused AMPBlock1 iteration: out = x + conv2(S2(conv1_dil(S1(x)))) (+acc, /divisor per epi); c2.dil == 1
 // layers with aa_up / aa_down (both layers of a pair or none): S1 and S2 are anti-aliased, the generic kernel's AA form runs
 // (valid rows per tile TR - (ks-1) - 10) and win must be null - the pair reads x[t - (ks-1)(d+1) - 10 .. t + 10]
 int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, long long L, float *out, int B, int epi,
-                    const float *acc, float divisor, hipStream_t s, const ConvWindow *win = nullptr, unsigned kernels = AMPK_ALL);
+                    const float *acc, float divisor, hipStream_t s, const ConvWindow *win = nullptr, unsigned kernels = AMPK_ALL,
+                    bool sym = false,         // symmetric pair (ks odd): the generic kernel's SYM form, out[t] reads x[t - h .. t + h], h = (ks-1)(d+1)/2;
+                    long long bs = 0);        // win must be null.  bs: floats between the batch items of x / out / acc where that is not L * C
+                                              // (sym only: the stage works on a view of the upsampler's rows; rows outside [0, L) read as zeros)
 // SnakeBeta -> causal conv C->1 (k taps) -> tanh -> / div -> first n_out samples
 // n_rows (B) or nullptr: item b keeps its first n_rows[b] samples, the rest of its n_out are 0
 int launch_conv_post(const float *in, long long Lin, int C, int ks, const float *w, const float *bias,
                      const float *act_a, const float *act_ib, float div, float *wav, long long n_out,
                      int B, hipStream_t s, const ConvWindow *win = nullptr, const long long *n_rows = nullptr,
-                     const float *aa_up = nullptr, const float *aa_down = nullptr);   // anti-aliased activation_post: offline, equal lengths
+                     const float *aa_up = nullptr, const float *aa_down = nullptr,    // anti-aliased activation_post: offline, equal lengths
+                     bool sym = false,         // post_sym: pad [3, 3], sample t reads rows t - 3 .. t + 3 (7 taps; offline, equal lengths, not filtered)
+                     long long in_bs = 0);     // floats between the input's batch items where that is not Lin * C (offline)
 // mixed-length decode: lim ((n_up + 1) x B) = per-item input rows of the upsamplers, L_0 = frames[b] (clamped into [0, T]),
 // L_i = (L_{i-1} + 1) * up_rates[i-1], then the samples kept, min(lengths[b], L_{n_up}) clamped into [0, n_max] (0 without frames)
 int launch_ragged_limits(long long *lim, const long long *frames, const long long *lengths, int B, long long T, long long n_max,

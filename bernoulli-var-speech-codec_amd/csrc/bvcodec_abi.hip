@@ -228,7 +228,7 @@ int bvc_decode_ragged(const bvc_model *m, const float *d_codes, const int64_t *d
     int rc = enter(m, B, nullptr, &T, d_ws, ws_bytes, &w, d_codes && d_frames && d_lengths && d_wav && n_max > 0,
                    "null argument or non-positive n_max");
     if (rc) return rc;
-    if (m->antialiased) { set_error("bvc_decode_ragged: %s (a row's end would read the next row's frames)", NOT_CAUSAL); return BVC_EINVAL; }
+    if (m->noncausal) { set_error("bvc_decode_ragged: %s (a row's end would read the next row's frames)", not_causal(m)); return BVC_EINVAL; }
     if (n_max > bvc_vocoder_length(m, T)) {
         set_error("n_max %lld exceeds the generator's %lld samples for T=%lld", (long long)n_max,
                   (long long)bvc_vocoder_length(m, T), (long long)T);
@@ -428,10 +428,12 @@ int bvc_test_vocoder_tap(const bvc_model *m, const float *d_mel, int32_t B, int6
     const float *tap = nullptr;
     int64_t len = 0;
     int ch = 0;
+    int64_t tap_bs = 0;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = run_vocoder(m, w, d_mel, B, T, 1, 1.0f, nullptr, which, &tap, &len, &ch, s))) return rc;
+    if ((rc = run_vocoder(m, w, d_mel, B, T, 1, 1.0f, nullptr, which, &tap, &len, &ch, s, nullptr, &tap_bs))) return rc;
     const long long n = (long long)B * len * ch;
     if (out_numel_per_batch) *out_numel_per_batch = len * ch;
+    if (d_out && tap_bs != len * ch) return copy_rows(tap, tap_bs, d_out, len * ch, len * ch, B, s);     // a symmetric stage's view
     if (d_out) {
         hipLaunchKernelGGL(tap_copy_kernel, dim3(1024), dim3(256), 0, s, tap, d_out, n);
         BVC_HIP_TRY(hipGetLastError());
@@ -452,11 +454,29 @@ int bvc_test_vocoder_layer(const bvc_model *m, int32_t kind, int32_t stage, int3
     switch (kind) {
         case 0:                                                              // conv_pre (as run_vocoder launches it)
             rows = L; ch = c.upsample_initial_channel;
-            rc = launch_conv_mfma(m->conv_pre, d_x, L, d_out, L, B, CE_STORE, nullptr, nullptr, 1.0f, s);
+            rc = launch_conv_mfma(m->conv_pre, d_x, L, d_out, L, B, CE_STORE, nullptr, nullptr, 1.0f, s, nullptr, nullptr, 0, m->pre_sym ? 3 : 0);
             break;
         case 1:                                                              // upsampler `stage`: 2-tap conv with u * C columns over L + 1 rows
             if (stage < 0 || stage >= c.n_up) { set_error("bvc_test_vocoder_layer: no upsampler %d", stage); return BVC_EINVAL; }
             rows = (L + 1) * c.up_rates[stage]; ch = m->stage_ch[stage];
+            if (m->stage_sym[stage]) {
+                // a symmetric upsampler: the causal rows into a buffer of this call, then the view the stage works on - L * rate rows from
+                // row rate / 2 on - into d_out
+                const int u = c.up_rates[stage];
+                const long long full = rows * ch;
+                float *tmp = nullptr;
+                if (hipMalloc(reinterpret_cast<void **>(&tmp), (size_t)B * full * sizeof(float)) != hipSuccess) {
+                    (void)hipGetLastError();
+                    set_error("bvc_test_vocoder_layer: cannot allocate the causal rows"); return BVC_ENOMEM;
+                }
+                rows = L * u;
+                rc = launch_conv_mfma(m->ups[stage], d_x, L, tmp, L + 1, B, CE_STORE, nullptr, nullptr, 1.0f, s);
+                if (!rc) rc = copy_rows(tmp + (long long)(u / 2) * ch, full, d_out, rows * ch, rows * ch, B, s);
+                const hipError_t e1 = hipStreamSynchronize(s);
+                (void)hipFree(tmp);
+                if (!rc && e1 != hipSuccess) { set_error("bvc_test_vocoder_layer: %s", hipGetErrorString(e1)); rc = BVC_EHIP; }
+                break;
+            }
             rc = launch_conv_mfma(m->ups[stage], d_x, L, d_out, L + 1, B, CE_STORE, nullptr, nullptr, 1.0f, s);
             break;
         case 2: {                                                            // AMP pair (stage, block, iteration)
@@ -466,20 +486,21 @@ int bvc_test_vocoder_layer(const bvc_model *m, int32_t kind, int32_t stage, int3
                 set_error("bvc_test_vocoder_layer: epilogue %d (1 residual, 2 + running sum, 3 + running sum, / kernels; 2 and 3 need d_acc)", epi);
                 return BVC_EINVAL; }
             if (!m->fused_amp) { set_error("bvc_test_vocoder_layer: the model runs its AMP pairs unfused"); return BVC_EINVAL; }
-            if (window && m->antialiased) { set_error("bvc_test_vocoder_layer: %s - no streaming window", NOT_CAUSAL); return BVC_EINVAL; }
+            if (window && m->noncausal) { set_error("bvc_test_vocoder_layer: %s - no streaming window", not_causal(m)); return BVC_EINVAL; }
             if (window && (row_begin < 0 || row_begin >= L)) { set_error("bvc_test_vocoder_layer: row_begin outside the buffer"); return BVC_EINVAL; }
             const AmpPair &ap = m->amp[stage][block][iteration];
             rows = L; ch = m->stage_ch[stage];
             const long long bs = (long long)L * ch;
             ConvWindow w{bs, bs, row_begin, t_origin};
-            rc = launch_amp_pair(ap.c1, ap.c2, d_x, L, d_out, B, epi, d_acc, (float)c.n_resk, s, window ? &w : nullptr, m->amp_kernels);
+            rc = launch_amp_pair(ap.c1, ap.c2, d_x, L, d_out, B, epi, d_acc, (float)c.n_resk, s, window ? &w : nullptr, m->amp_kernels,
+                                 m->stage_sym[stage]);
             break;
         }
         case 3:                                                              // activation_post -> conv_post -> tanh -> / div, first `length` samples
             rows = length < L ? length : L; ch = 1;
             if (rows <= 0) { set_error("bvc_test_vocoder_layer: length %lld", (long long)length); return BVC_EINVAL; }
             rc = launch_conv_post(d_x, L, m->post_c, m->post_ks, m->post_w, m->post_b, m->post_a, m->post_ib, div, d_out, rows, B, s,
-                                  nullptr, nullptr, m->post_up, m->post_down);
+                                  nullptr, nullptr, m->post_up, m->post_down, m->post_sym);
             break;
         default: set_error("bvc_test_vocoder_layer: kind %d", kind); return BVC_EINVAL;
     }

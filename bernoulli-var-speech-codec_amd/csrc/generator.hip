@@ -116,26 +116,35 @@ namespace bvc {
 // Runs the generator; stop_after: -1 = everything, otherwise the tap index of bvc_test_vocoder_tap.
 // lim: nullptr, or the (n_up + 1) x B bounds of a mixed-length batch (launch_ragged_limits): the upsamplers' input rows per item, then
 // the samples each item keeps of `length`.
+// A symmetric stage (layers_sym[i]) works on a VIEW of the causal upsampler result: ConvTranspose1d(padding = (k-u)/2), k = 2u, is rows
+// [u/2, u/2 + Lin u) of the (Lin+1) u causal rows, so the stage's x starts u/2 rows into w.X, has L = Lin u rows and the full buffer's
+// batch stride; P, Q and XS take the same stride, which the next upsampler (or conv_post) reads them with.  The pair kernel's descriptor
+// ends at the view's L rows: the u/2 discarded rows behind them - not zeros in memory - read as zeros.
 int run_vocoder(const bvc_model *m, const Workspace &w, const float *d_mel, int B, int64_t T, int64_t length,
                 float div, float *d_wav, int stop_after, const float **tap, int64_t *tap_len, int *tap_ch,
-                hipStream_t s, const long long *lim) {
+                hipStream_t s, const long long *lim, int64_t *tap_bs) {
     const bvc_config &c = m->cfg;
     int rc;
-    // pad[6,0] + conv_pre (models.py:212-213); input is already time-major (B,T,80)
-    if ((rc = launch_conv_mfma(m->conv_pre, d_mel, T, w.y0, T, B, CE_STORE, nullptr, nullptr, 1.0f, s))) return rc;
-    if (stop_after == 0) { *tap = w.y0; *tap_len = T; *tap_ch = c.upsample_initial_channel; return BVC_OK; }
+    if (lim && m->noncausal) { set_error("mixed-length decode: %s", not_causal(m)); return BVC_EINVAL; }
+    auto give = [&](const float *p, int64_t len, int ch, int64_t bs) { *tap = p; *tap_len = len; *tap_ch = ch; if (tap_bs) *tap_bs = bs; return BVC_OK; };
+    // pad[6,0] (pre_sym: [3,3]) + conv_pre (models.py:209-213); input is already time-major (B,T,80)
+    if ((rc = launch_conv_mfma(m->conv_pre, d_mel, T, w.y0, T, B, CE_STORE, nullptr, nullptr, 1.0f, s, nullptr, nullptr, 0, m->pre_sym ? 3 : 0))) return rc;
+    if (stop_after == 0) return give(w.y0, T, c.upsample_initial_channel, T * c.upsample_initial_channel);
     const float *cur_in = w.y0;
-    int64_t Lin = T;
+    int64_t Lin = T, in_bs = 0;                                         // in_bs: the input's batch stride where it is not dense
     for (int i = 0; i < c.n_up; ++i) {
-        const int C = m->stage_ch[i];
-        const int64_t L = (Lin + 1) * c.up_rates[i];
+        const int C = m->stage_ch[i], u = c.up_rates[i];
+        const bool sym = m->stage_sym[i];
+        const int64_t Lfull = (Lin + 1) * u, L = sym ? Lin * u : Lfull;
+        const int64_t bs = sym ? Lfull * C : 0;                         // 0: dense, L * C
         // ConvTranspose1d as a 2-tap conv with u*C columns over Lin+1 rows (models.py:216-217)
         if ((rc = launch_conv_mfma(m->ups[i], cur_in, Lin, w.X, Lin + 1, B, CE_STORE, nullptr, nullptr, 1.0f, s, nullptr,
-                                   lim ? lim + (size_t)i * B : nullptr))) return rc;
-        if (stop_after == 1 + 2 * i) { *tap = w.X; *tap_len = L; *tap_ch = C; return BVC_OK; }
+                                   lim ? lim + (size_t)i * B : nullptr, in_bs))) return rc;
+        const float *const x0 = sym ? w.X + (size_t)(u / 2) * C : w.X;
+        if (stop_after == 1 + 2 * i) return give(x0, L, C, sym ? bs : L * C);
         float *const bufs[3] = {w.P, w.Q, w.XS};
         for (int j = 0; j < c.n_resk; ++j) {                            // three parallel AMP blocks
-            const float *cur = w.X;
+            const float *cur = x0;
             for (int d = 0; d < 3; ++d) {
                 const AmpPair &ap = m->amp[i][j][d];
                 if (!m->fused_amp && (rc = launch_conv_mfma(ap.c1, cur, L, w.U, L, B, CE_STORE, nullptr, nullptr, 1.0f, s))) return rc;
@@ -143,23 +152,38 @@ int run_vocoder(const bvc_model *m, const Workspace &w, const float *d_mel, int 
                 float *const dst = bufs[t.buf];
                 const int epi = t.epi;
                 if (m->fused_amp) {
-                    if ((rc = launch_amp_pair(ap.c1, ap.c2, cur, L, dst, B, epi, w.XS, (float)c.n_resk, s, nullptr, m->amp_kernels))) return rc;
+                    if ((rc = launch_amp_pair(ap.c1, ap.c2, cur, L, dst, B, epi, w.XS, (float)c.n_resk, s, nullptr, m->amp_kernels, sym, bs))) return rc;
                 } else if ((rc = launch_conv_mfma(ap.c2, w.U, L, dst, L, B, epi, cur, w.XS, (float)c.n_resk, s))) return rc;
                 cur = dst;
             }
         }
-        if (stop_after == 2 + 2 * i) { *tap = w.XS; *tap_len = L; *tap_ch = C; return BVC_OK; }
+        if (stop_after == 2 + 2 * i) return give(w.XS, L, C, sym ? bs : L * C);
         cur_in = w.XS;
         Lin = L;
+        in_bs = bs;
     }
     const int64_t n_out = length < Lin ? length : Lin;
+    if (in_bs && m->post_up) {                               // the filtered conv_post reads a dense signal: the symmetric last stage's rows move up
+        if ((rc = copy_rows(cur_in, in_bs, w.P, Lin * m->post_c, Lin * m->post_c, B, s))) return rc;
+        cur_in = w.P; in_bs = 0;
+    }
     return launch_conv_post(cur_in, Lin, m->post_c, m->post_ks, m->post_w, m->post_b, m->post_a, m->post_ib, div,
-                            d_wav, n_out, B, s, nullptr, lim ? lim + (size_t)c.n_up * B : nullptr, m->post_up, m->post_down);
+                            d_wav, n_out, B, s, nullptr, lim ? lim + (size_t)c.n_up * B : nullptr, m->post_up, m->post_down,
+                            m->post_sym, in_bs);
+}
+
+// dst[b][0 .. n) = src[b][0 .. n) for B items src_bs / dst_bs floats apart
+int copy_rows(const float *src, long long src_bs, float *dst, long long dst_bs, long long n, int B, hipStream_t s) {
+    if (B <= 0 || n <= 0) return BVC_OK;
+    const long long blocks = (n + 255) / 256;
+    stream_rows_in_kernel<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096), B), 256, 0, s>>>(src, src_bs, dst, dst_bs, n);
+    BVC_HIP_TRY(hipGetLastError());
+    return BVC_OK;
 }
 
 int vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_per_push, bool slide, bvc_vocoder_stream **out) {
     if (!m || !out || B <= 0 || max_frames_per_push <= 0) { set_error("bvc_vocoder_stream_create: bad arguments"); return BVC_EINVAL; }
-    if (m->antialiased) { set_error("bvc_vocoder_stream_create: %s", NOT_CAUSAL); return BVC_EINVAL; }
+    if (m->noncausal) { set_error("bvc_vocoder_stream_create: %s", not_causal(m)); return BVC_EINVAL; }
     const bvc_config &c = m->cfg;
     // the history must cover every receptive field and stay aligned with the transposed-conv views
     long long rate = 1;

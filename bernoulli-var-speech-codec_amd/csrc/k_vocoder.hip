@@ -135,7 +135,9 @@ __device__ __forceinline__ f32x2 snakebeta2(f32x2 x, f32x2 a, f32x2 ib) {
 // CIN: input channels; NTW: 16-column tiles per wave; MT: 16-row tiles per wave.  The four waves of a workgroup split the
 // rows (each wave MT row tiles x the same NTW column tiles) or, NSPLIT, the columns (all waves the same MT row tiles, each its
 // own NTW column tiles): the second form is for streaming hops, whose one or two new frames are a handful of rows.
-template <int CIN, int NTW, int MT, bool NSPLIT = false>
+// SHIFT: the input window starts SHIFT rows later - conv_pre of a pre_sym generator pads [3, 3] instead of [6, 0] (models.py:209-213),
+// out[t] = b + sum_j w[j] in[t - (ks-1) + SHIFT + j]; rows behind the input's end are zeros like the rows before its start.
+template <int CIN, int NTW, int MT, bool NSPLIT = false, int SHIFT = 0>
 __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float tile[];
     constexpr int S = CIN + 2;                 // LDS row stride (floats): (S/2) odd -> conflict-free
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
     const float *inb = a.in + (long long)b * a.in_bs;
     for (int idx = tid; idx < rows * C4; idx += 256) {
         const int row = idx / C4, c4 = idx - row * C4;
-        const long long tg = t0 - halo + row;
+        const long long tg = t0 - halo + SHIFT + row;
         f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
         if (tg >= 0 && tg < lin) {
             v = *reinterpret_cast<const f32x4 *>(inb + tg * CIN + c4 * 4);
@@ -358,8 +360,15 @@ __device__ __forceinline__ void aa_rows(const float *src, int src_first, int nsr
 // in U, A1 of them becomes the S1 tile, conv1 + bias goes back to U (rows [t0-(ks-1)-5, .. + TR)), A2 of those - clamped to the
 // signal's rows 0 and L-1 - becomes the S2 tile of the rows [t0-(ks-1), t0+TT); conv2 and the epilogues are the plain kernel's.
 // The S2 tile always re-uses the S1 tile's LDS (ALIAS is ignored).  Offline only: a filtered stage is not causal.
-template <int C, int MT, int OCC, bool ALIAS, int CS = 1, bool AA = false>
+// SYM: both convs pad symmetrically (AMPBlock1(symmetric=True), models.py:35-44,106-119; ks odd): conv1 (ks-1) d / 2 rows on each side,
+// conv2 (ks-1) / 2, so out[t] reads x[t - h .. t + h], h = (ks-1)(d+1)/2.  The same tile with its windows shifted: the S1 span starts
+// (ks-1) d / 2 rows before conv1's first row instead of (ks-1) d, conv1's rows start (ks-1) / 2 before the tile instead of ks - 1, and the
+// S2 rows behind the signal's end are zeros like the ones before its start (the reference pads AFTER the activation on both sides; the
+// S1 rows there read as zeros through the descriptor, whatever lies behind the signal in memory).  LDS, TR, TT, the MFMA loops, the
+// order of summation and the epilogues are the causal kernel's.  Offline only, and not with AA.
+template <int C, int MT, int OCC, bool ALIAS, int CS = 1, bool AA = false, bool SYM = false>
 __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
+    static_assert(!(SYM && AA), "a filtered stage is a causal stage");
 #ifdef BVC_PHASE_PROBE
     unsigned long long last_ = __builtin_readcyclecounter();
 #endif
@@ -392,7 +401,7 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
     float *t2 = (ALIAS || AA) ? lds : lds + rows1 * S;     // S2(u) rows [t0-(ks-1), t0-(ks-1)+TR) (+ ks-1 spare): takes over
                                                            // the S1(x) tile once conv1 has consumed it (halves the LDS)
     const float *xb = a.x + (long long)b * a.bs;
-    const long long tbase = t0 - (ks - 1) - AAH;           // global row of local row 0 of phase 2 (conv1's output rows)
+    const long long tbase = t0 - (SYM ? (ks - 1) / 2 : ks - 1) - AAH;      // global row of local row 0 of phase 2 (conv1's output rows)
     const int rowsA = rows1 > TR + ks - 1 ? rows1 : TR + ks - 1;
     float *traw = lds + rowsA * S;                         // AA: region U, rows1 + 10 rows (raw x, then conv1's raw result)
     (void)traw;
@@ -430,7 +439,7 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
         f32x4 v[NLD];
         const int total = rows1 * C4;
         const __amdgpu_buffer_rsrc_t rs = rows_rsrc(xb, a.L, C);       // rows outside the signal read as zeros (rows_load4)
-        const int tfirst = (int)(tbase - halo1);
+        const int tfirst = (int)(tbase - (SYM ? halo1 / 2 : halo1));
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int idx = tid + i * 256;
@@ -589,6 +598,9 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
     // local rows before `zrow` lie before the start of the signal: zero there (the reference pads AFTER the activation)
     const long long zr64 = -(tbase + amp_t_origin(a, b));
     const int zrow = zr64 <= 0 ? 0 : (zr64 > TR ? TR : (int)zr64);
+    // SYM: local rows from `zend` on lie behind the end of the signal: zero there too
+    const long long ze64 = a.L - tbase;
+    const int zend = !SYM ? TR : (ze64 <= 0 ? 0 : (ze64 > TR ? TR : (int)ze64));
     if constexpr (AA) {
         // conv1 + bias, raw, to U (the raw x rows there were consumed before conv1 began); then A2 of U's rows, clamped to the
         // signal, is the S2 tile of the TR - 10 rows from t0 - (ks-1) on; behind them zeros up to row TR + ks - 1 (read by discarded outputs)
@@ -622,8 +634,8 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
             const float v0 = r < 8 ? a0 : hi0, v1 = r < 8 ? a1 : hi1;
             const int row = mbase + i * 16 + g * 4 + e0;
             const f32x2 s2 = snakebeta2((f32x2){v0 + bias, v1 + bias}, splat2(aa), splat2(bb));
-            t2[row * S + col] = row >= zrow ? s2[0] : 0.0f;
-            t2[(row + 1) * S + col] = row + 1 >= zrow ? s2[1] : 0.0f;
+            t2[row * S + col] = (row >= zrow && (!SYM || row < zend)) ? s2[0] : 0.0f;
+            t2[(row + 1) * S + col] = (row + 1 >= zrow && (!SYM || row + 1 < zend)) ? s2[1] : 0.0f;
         }
     } else {
         // (all tiles but the first of a signal lie wholly inside it: no row to zero - two selects per pair less; the test is uniform)
@@ -641,17 +653,17 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
                             const int row = mbase + i * 16 + g * 4 + e;
                             const f32x2 u2 = (f32x2){acc[i][n][e] + bias, acc[i][n][e + 1] + bias};
                             const f32x2 s2 = snakebeta2(u2, splat2(aa), splat2(bb));
-                            t2[row * S + col] = (!EDGE || row >= zrow) ? s2[0] : 0.0f;
-                            t2[(row + 1) * S + col] = (!EDGE || row + 1 >= zrow) ? s2[1] : 0.0f;
+                            t2[row * S + col] = (!EDGE || (row >= zrow && (!SYM || row < zend))) ? s2[0] : 0.0f;
+                            t2[(row + 1) * S + col] = (!EDGE || (row + 1 >= zrow && (!SYM || row + 1 < zend))) ? s2[1] : 0.0f;
                         }
                 }
             }
         };
-        if (zrow > 0) s2_tile(std::true_type());
-        else          s2_tile(std::false_type());
+        if (zrow > 0 || (SYM && zend < TR)) s2_tile(std::true_type());
+        else                                s2_tile(std::false_type());
     }
     }
-    (void)zrow;
+    (void)zrow; (void)zend;
     __syncthreads();
     PHASE(2);
 
@@ -1215,7 +1227,7 @@ static bool amp16_slots_all() {
            amp16_slots<11, 5, (MT > 4 ? 4 : MT), Amp16Occ<11, MT>::V>() > 0;
 }
 
-template <int C, int MT, int OCC, bool ALIAS, int CS = 1, bool AA = false>
+template <int C, int MT, int OCC, bool ALIAS, int CS = 1, bool AA = false, bool SYM = false>
 static int launch_amp_t(AmpArgs a, int B, hipStream_t s) {
     constexpr int TR = (4 / CS) * MT * 16;
     const int TT = TR - (a.ks - 1) - (AA ? 10 : 0);
@@ -1234,10 +1246,10 @@ static int launch_amp_t(AmpArgs a, int B, hipStream_t s) {
     a.ntile = ntile;
     {
         static bool attr = false;
-        if (!attr) { BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(amp_pair_kernel<C, MT, OCC, ALIAS, CS, AA>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; }
+        if (!attr) { BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(amp_pair_kernel<C, MT, OCC, ALIAS, CS, AA, SYM>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; }
     }
     g_last_amp_launch = {(long long)ntile, (long long)((ntile + 7u) & ~7u), TT};
-    hipLaunchKernelGGL((amp_pair_kernel<C, MT, OCC, ALIAS, CS, AA>), dim3((ntile + 7u) & ~7u), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((amp_pair_kernel<C, MT, OCC, ALIAS, CS, AA, SYM>), dim3((ntile + 7u) & ~7u), dim3(256), lds, s, a);
     BVC_HIP_TRY(hipGetLastError());
     return BVC_OK;
 }
@@ -1258,7 +1270,7 @@ TilePlan amp_pair_cut(long long L, int B, int ks, int force_height, bool legacy)
 }
 
 int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, long long L, float *out, int B, int epi,
-                    const float *acc, float divisor, hipStream_t s, const ConvWindow *win, unsigned kernels) {
+                    const float *acc, float divisor, hipStream_t s, const ConvWindow *win, unsigned kernels, bool sym, long long bs) {
     if (B <= 0 || L <= 0) return BVC_OK;
     if (c1.cin != c1.cout || c2.cin != c1.cin || c2.ks != c1.ks || c2.dil != 1 || !c1.act_a || !c2.act_a) {
         set_error("amp_pair: unsupported layer pair");
@@ -1273,7 +1285,7 @@ int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, lo
         a.w1 = c1.wp4; a.w2 = c2.wp4;
     }
     a.divisor = divisor; a.epi = epi; a.ks = c1.ks; a.dil = c1.dil; a.tiles_per_batch = 0;
-    a.bs = win ? win->in_bs : L * c1.cin;
+    a.bs = win ? win->in_bs : (bs ? bs : L * c1.cin);
     a.row_begin = win ? win->row_begin : 0;
     a.t_origin = win ? win->t_origin : 0;
     a.row_age = win ? win->row_age : nullptr;
@@ -1292,6 +1304,22 @@ int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, lo
             default: set_error("amp_pair: unsupported channel count %d", c1.cin); return BVC_EINVAL;
         }
     }
+    if (sym) {
+        // symmetric pair: the generic kernel's SYM form at every channel count, with the tile shape the causal generic kernel has there
+        // (C = 64: the tallest, 128 rows)
+        if (c1.aa_up || c2.aa_up) { set_error("amp_pair: a filtered pair is a causal pair"); return BVC_EINVAL; }
+        if (win) { set_error("amp_pair: a symmetric pair looks ahead and has no streaming window"); return BVC_EINVAL; }
+        if (c1.ks % 2 == 0) { set_error("amp_pair: a symmetric pair needs an odd kernel size (got %d)", c1.ks); return BVC_EINVAL; }
+        if (L + 512 > 0x7FFFFFFFll / c1.cin / 4) { set_error("amp_pair: %lld rows are beyond the symmetric kernel's row index", L); return BVC_EINVAL; }
+        switch (c1.cin) {
+            case 64: return launch_amp_t<64, 8, 2, true, 4, false, true>(a, B, s);
+            case 32: return launch_amp_t<32, 4, 3, true, 1, false, true>(a, B, s);
+            case 16: return launch_amp_t<16, 2, 4, false, 1, false, true>(a, B, s);
+            case 8:  return launch_amp_t<8, 4, 4, true, 1, false, true>(a, B, s);
+            default: set_error("amp_pair: unsupported channel count %d", c1.cin); return BVC_EINVAL;
+        }
+    }
+    if (bs) { set_error("amp_pair: a batch stride of its own belongs to a symmetric stage's view"); return BVC_EINVAL; }
     // streaming hops compute a few new rows behind a 64-row history: the 128 / 256-row tiles of the offline sweep would spend
     // most of their MFMAs on rows nobody reads, so short windows take the smallest tile (4 waves x 16 rows)
     const long long new_rows = L - a.row_begin;
@@ -1348,7 +1376,7 @@ int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, lo
     }
 }
 
-template <int CIN, int NTW, int MT, bool NSPLIT = false>
+template <int CIN, int NTW, int MT, bool NSPLIT = false, int SHIFT = 0>
 static int launch_one(const ConvArgs &a, int B, hipStream_t s) {
     constexpr int TT = (NSPLIT ? 1 : 4) * MT * 16;
     ConvArgs k = a;
@@ -1358,7 +1386,7 @@ static int launch_one(const ConvArgs &a, int B, hipStream_t s) {
     if (lds > 160 * 1024) { set_error("conv tile needs %zu B of LDS", lds); return BVC_EINVAL; }
     constexpr int NPW = NTW * (NSPLIT ? 4 : 1);            // column tiles per workgroup
     dim3 grid((unsigned)(k.tiles_per_batch * (long long)B), (unsigned)((a.ntiles + NPW - 1) / NPW));
-    auto kern = conv_mfma_kernel<CIN, NTW, MT, NSPLIT>;
+    auto kern = conv_mfma_kernel<CIN, NTW, MT, NSPLIT, SHIFT>;
     ProbeScope probe(PK_CONV, s);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, k);
     BVC_HIP_TRY(hipGetLastError());
@@ -1367,9 +1395,9 @@ static int launch_one(const ConvArgs &a, int B, hipStream_t s) {
 
 // Allow > 64 KiB of dynamic LDS for every instantiation (called once from bvc_model_create, so the
 // compute entry points stay free of non-stream API calls).
-template <int CIN, int NTW, int MT, bool NSPLIT = false>
+template <int CIN, int NTW, int MT, bool NSPLIT = false, int SHIFT = 0>
 static int allow_big_lds() {
-    BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_mfma_kernel<CIN, NTW, MT, NSPLIT>),
+    BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_mfma_kernel<CIN, NTW, MT, NSPLIT, SHIFT>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return BVC_OK;
 }
@@ -1402,6 +1430,7 @@ int conv_kernels_init() {
     if (!amp16_slots_all<4>()) return BVC_EHIP;
     if ((rc = allow_big_lds<128, 4, 2>())) return rc;
     if ((rc = allow_big_lds<80, 4, 2>())) return rc;
+    if ((rc = allow_big_lds<80, 4, 2, false, 3>())) return rc;
     if ((rc = allow_big_lds<64, 4, 2>())) return rc;
     if ((rc = allow_big_lds<32, 2, 4>())) return rc;
     if ((rc = allow_big_lds<16, 1, 4>())) return rc;
@@ -1411,18 +1440,22 @@ int conv_kernels_init() {
 
 int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *out, long long Lout, int B,
                      int epi, const float *res, const float *acc, float divisor, hipStream_t s, const ConvWindow *win,
-                     const long long *row_lim) {
+                     const long long *row_lim, long long in_bs, int shift) {
     if (B <= 0 || Lout <= 0) return BVC_OK;
     if (c.cout % 4) { set_error("conv_mfma: %d output columns (the epilogue stores 16-byte granules)", c.cout); return BVC_EINVAL; }
     ConvArgs a;
     a.in = in; a.Lin = Lin; a.out = out; a.Lout = Lout; a.res = res; a.acc = acc;
-    a.in_bs = win ? win->in_bs : Lin * c.cin;
+    a.in_bs = win ? win->in_bs : (in_bs ? in_bs : Lin * c.cin);
     a.out_bs = win ? win->out_bs : Lout * c.cout;
     a.row_begin = win ? win->row_begin : 0;
     a.wp = c.wp; a.bias = c.bias; a.act_a = c.act_a; a.act_ib = c.act_ib;
     a.divisor = divisor; a.epi = epi; a.ks = c.ks; a.dil = c.dil; a.cout = c.cout; a.ntiles = c.ntiles;
     a.tiles_per_batch = 0;
     a.row_lim = row_lim;
+    if (shift) {                                            // conv_pre of a pre_sym generator: the 7-tap window centred, offline
+        if (shift != 3 || c.cin != 80 || c.ks != 7 || c.dil != 1 || win || row_lim) { set_error("conv_mfma: a shifted window is conv_pre's (80 channels, 7 taps, shift 3)"); return BVC_EINVAL; }
+        return launch_one<80, 4, 2, false, 3>(a, B, s);
+    }
     // streaming hops: one or two new frames = at most 16 rows in front of the first two upsamplers; the row-split tiles (64 rows
     // and more per workgroup) would compute mostly rows nobody reads, so the waves split the columns instead
     if (win && Lout - a.row_begin <= 16) {
@@ -1449,7 +1482,8 @@ int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *
 // ------------------------------------------------------------------------------------------------
 // activation_post -> pad[6,0] -> conv_post (C -> 1) -> tanh -> [:length] -> / SCALING
 // (models.py:228-238, bvrnn_codec_model.py:71).  VALU kernel: C*ks = 56 MACs per sample.
-template <int C>
+// SHIFT: the window starts SHIFT rows later (post_sym pads [3, 3], models.py:230-233); rows behind the last read as zeros either way.
+template <int C, int SHIFT = 0>
 __global__ __launch_bounds__(256) void conv_post_kernel(const float *__restrict__ in, long long Lin, int ks,
                                                         const float *__restrict__ w, const float *__restrict__ bias,
                                                         const float *__restrict__ act_a,
@@ -1465,7 +1499,7 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float *__restrict_
     const float *inb = in + (long long)b * in_bs;
     for (int idx = tid; idx < (256 + halo) * C; idx += 256) {
         const int row = idx / C, c = idx - row * C;
-        const long long tg = t0 - halo + row;
+        const long long tg = t0 - halo + SHIFT + row;
         float v = 0.0f;
         if (tg >= 0 && tg < Lin) v = snakebeta(inb[tg * C + c], act_a[c], act_ib[c]);
         tile[idx] = v;
@@ -1515,11 +1549,13 @@ __global__ __launch_bounds__(256) void conv_post_aa_kernel(const float *__restri
 
 int launch_conv_post(const float *in, long long Lin, int C, int ks, const float *w, const float *bias,
                      const float *act_a, const float *act_ib, float div, float *wav, long long n_out, int B,
-                     hipStream_t s, const ConvWindow *win, const long long *n_rows, const float *aa_up, const float *aa_down) {
+                     hipStream_t s, const ConvWindow *win, const long long *n_rows, const float *aa_up, const float *aa_down,
+                     bool sym, long long in_bs) {
     if (B <= 0 || n_out <= 0) return BVC_OK;
     if (C != 8) { set_error("conv_post: unsupported channel count %d", C); return BVC_EINVAL; }
     const int tiles = (int)((n_out + 255) / 256);
     if (aa_up || aa_down) {
+        if (sym || in_bs) { set_error("conv_post: an anti-aliased activation_post stands in front of a causal conv_post, on a dense signal"); return BVC_EINVAL; }
         if (!aa_up || !aa_down || win || n_rows) { set_error("conv_post: an anti-aliased activation_post has no streaming window and no mixed lengths"); return BVC_EINVAL; }
         if (Lin + 512 > 0x7FFFFFFFll) { set_error("conv_post: %lld rows are beyond the anti-aliased kernel's row index", Lin); return BVC_EINVAL; }
         const size_t lds_aa = (size_t)(2 * (256 + ks - 1) + 10) * C * sizeof(float);
@@ -1531,8 +1567,15 @@ int launch_conv_post(const float *in, long long Lin, int C, int ks, const float 
     }
     const size_t lds = (size_t)(256 + ks - 1) * C * sizeof(float);
     ProbeScope probe(PK_POST, s);
+    if (sym) {
+        if (win || n_rows || ks != 7) { set_error("conv_post: a symmetric conv_post has 7 taps, no streaming window and no mixed lengths"); return BVC_EINVAL; }
+        hipLaunchKernelGGL((conv_post_kernel<8, 3>), dim3((unsigned)(tiles * (long long)B)), dim3(256), lds, s, in, Lin, ks,
+                           w, bias, act_a, act_ib, div, wav, n_out, tiles, in_bs ? in_bs : Lin * C, 0ll, n_rows);
+        BVC_HIP_TRY(hipGetLastError());
+        return BVC_OK;
+    }
     hipLaunchKernelGGL(conv_post_kernel<8>, dim3((unsigned)(tiles * (long long)B)), dim3(256), lds, s, in, Lin, ks,
-                       w, bias, act_a, act_ib, div, wav, n_out, tiles, win ? win->in_bs : Lin * C, win ? win->row_begin : 0, n_rows);
+                       w, bias, act_a, act_ib, div, wav, n_out, tiles, win ? win->in_bs : (in_bs ? in_bs : Lin * C), win ? win->row_begin : 0, n_rows);
     BVC_HIP_TRY(hipGetLastError());
     return BVC_OK;
 }

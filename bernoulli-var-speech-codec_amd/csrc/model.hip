@@ -316,8 +316,40 @@ int build_vocoder(bvc_model *m, const TensorMap &tm) {
         if (!t) return BVC_EMISSING;
         post_aa = t->h_data[0] != 0.0f;
     }
+    // symmetric paddings: optional tensors "layers_sym" (n_up values), "pre_sym" and "post_sym" (one value each); no keys of their own
+    m->stage_sym.assign(c.n_up, false);
+    if (tm.count("layers_sym")) {
+        const bvc_tensor *t = find(tm, "layers_sym", c.n_up);
+        if (!t) return BVC_EMISSING;
+        for (int i = 0; i < c.n_up; ++i) m->stage_sym[i] = t->h_data[i] != 0.0f;
+    }
+    for (const char *key : {"pre_sym", "post_sym"})
+        if (tm.count(key)) {
+            const bvc_tensor *t = find(tm, key, 1);
+            if (!t) return BVC_EMISSING;
+            (key[1] == 'r' ? m->pre_sym : m->post_sym) = t->h_data[0] != 0.0f;
+        }
+    m->symmetric = m->pre_sym || m->post_sym;
+    bool stages_sym = false;
+    for (int i = 0; i < c.n_up; ++i) {
+        stages_sym = stages_sym || m->stage_sym[i];
+        if (m->stage_sym[i] && stage_aa[i]) {
+            set_error("stage %d is symmetric and anti-aliased: filtered stages are implemented as causal stages only", i);
+            return BVC_EINVAL;
+        }
+    }
+    m->symmetric = m->symmetric || stages_sym;
+    if (m->post_sym && post_aa) { set_error("post_sym with antialias_post: a filtered activation_post is implemented in front of a causal conv_post only"); return BVC_EINVAL; }
+    if (stages_sym) {
+        for (int j = 0; j < c.n_resk; ++j)
+            if (c.res_kernels[j] % 2 == 0) { set_error("a symmetric stage needs odd resblock kernel sizes (got %d)", c.res_kernels[j]); return BVC_EINVAL; }
+        for (int i = 0; i < c.n_up; ++i)
+            if (m->stage_sym[i] && c.up_rates[i] % 2) { set_error("a symmetric upsampler needs an even rate (got %d)", c.up_rates[i]); return BVC_EINVAL; }
+        if (!m->fused_amp) { set_error("symmetric stages run in the fused AMP kernels only (BVC_UNFUSED_AMP is set)"); return BVC_EINVAL; }
+    }
     m->antialiased = post_aa;
     for (int i = 0; i < c.n_up; ++i) m->antialiased = m->antialiased || stage_aa[i];
+    m->noncausal = m->antialiased || m->symmetric;
     if (m->antialiased && !m->fused_amp) { set_error("anti-aliased activations run in the fused AMP kernels only (BVC_UNFUSED_AMP is set)"); return BVC_EINVAL; }
     const int c0 = c.upsample_initial_channel;
     if (!(w = find(tm, "conv_pre.weight", (int64_t)c0 * c.num_mels * 7))) return BVC_EMISSING;
@@ -433,9 +465,12 @@ namespace bvc {
 
 const char *const NOT_CAUSAL = "the model has anti-aliased activations: a filtered AMP block looks 30 rows ahead, so the generator is not causal";
 
-int64_t stage_len(const bvc_model *m, int64_t T, int stage) {    // length after upsampler `stage`
+const char *const NOT_CAUSAL_SYM = "the model has symmetric layers: a symmetric layer reads as many rows ahead as behind, so the generator is not causal";
+const char *not_causal(const bvc_model *m) { return m->antialiased ? NOT_CAUSAL : NOT_CAUSAL_SYM; }
+
+int64_t stage_len(const bvc_model *m, int64_t T, int stage) {    // length after upsampler `stage`: a symmetric one drops the u-row tail
     int64_t L = T;
-    for (int i = 0; i <= stage; ++i) L = (L + 1) * m->cfg.up_rates[i];
+    for (int i = 0; i <= stage; ++i) L = ((size_t)i < m->stage_sym.size() && m->stage_sym[i] ? L : L + 1) * m->cfg.up_rates[i];
     return L;
 }
 
@@ -476,7 +511,9 @@ void carve(const bvc_model *m, int B, int64_t T, char *base, Workspace *w) {
     w->part_gru = take(BT * 3 * H);
     size_t maxel = 0;
     for (int i = 0; i < c.n_up; ++i) {
-        const size_t e = (size_t)stage_len(m, T, i) * m->stage_ch[i];
+        int64_t Lc = T;                                         // the causal lengths: upper bounds of a symmetric generator's, whose
+        for (int k = 0; k <= i; ++k) Lc = (Lc + 1) * c.up_rates[k];     // stages work on views of the causal upsampler results
+        const size_t e = (size_t)Lc * m->stage_ch[i];
         if (e > maxel) maxel = e;
     }
     w->y0 = take((size_t)B * T * c.upsample_initial_channel);

@@ -607,7 +607,7 @@ int bvc_stream_codec_create_dir(const bvc_model *m, int32_t B, int32_t hop_sampl
     const bool enc = direction != BVC_STREAM_RECV, dec = direction != BVC_STREAM_SEND;
     if (!enc) hop_samples = 0;                               // a receive tick is given whole frames
     if (!m || !out || B <= 0 || (enc && hop_samples <= 0)) { set_error("bvc_stream_codec_create: bad arguments"); return BVC_EINVAL; }
-    if (dec && m->antialiased) { set_error("bvc_stream_codec_create: %s", NOT_CAUSAL); return BVC_EINVAL; }
+    if (dec && m->noncausal) { set_error("bvc_stream_codec_create: %s", not_causal(m)); return BVC_EINVAL; }
     const bvc_config &c = m->cfg;
     if (enc && hop_samples <= c.pad_left) { set_error("bvc_stream_codec_create: the hop must exceed the left reflect padding (%d samples)", c.pad_left); return BVC_EINVAL; }
     std::unique_ptr<bvc_stream_codec> st(new bvc_stream_codec());

@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from . import _abi, ragged, weights
-from .config import DEFAULT_CONFIG, NOT_CAUSAL, is_antialiased, load_config
+from .config import DEFAULT_CONFIG, is_causal, load_config, not_causal_message
 
 _ROOT = os.path.abspath(os.path.dirname(__file__))
 default_config = DEFAULT_CONFIG
@@ -469,7 +469,8 @@ class BVRNNCodecModel(_OnDevice):
     @torch.no_grad()
     def decode(self, codes, length, frames=None, lost=None, bitrate=None, return_codes=False):
         """Codes (batch, frames, z_dim) back to waveforms (batch, min(length, 256 * frames + 294)): coder decode from a
-        zero state, vocoder, output gain undone - bvrnn_codec_model.py:64-71.
+        zero state, vocoder, output gain undone - bvrnn_codec_model.py:64-71.  (A generator with symmetric stages makes
+        ``config.generator_length(conf, frames)`` samples instead of 256 * frames + 294: 256 * frames when every stage is symmetric.)
 
         Mixed-length batch: ``length`` (batch,) per row, and optionally ``frames`` (batch,) valid code frames per row (default
         min(frames, num_frames(length[b])), the frame count encode gives for that length).  Returns (batch, max n_b): row b equals
@@ -485,8 +486,8 @@ class BVRNNCodecModel(_OnDevice):
         if return_codes:
             raise ValueError("decode: return_codes belongs to concealment (pass lost)")
         if frames is not None or ragged.per_row(length, codes.shape[0], "length") is not None:
-            if is_antialiased(self.conf):
-                raise ValueError("decode: " + NOT_CAUSAL)
+            if not is_causal(self.conf):
+                raise ValueError("decode: " + not_causal_message(self.conf))
             return self._decode_ragged(codes, length, frames)
         eng = self.engine(codes)
         out_dev = codes.device
@@ -604,9 +605,9 @@ class BVRNNCodecModel(_OnDevice):
         frames = [int(c.shape[0]) for c in codes_list]
         eng = self.engine(codes_list[0])
         out_dev = codes_list[0].device
-        if is_antialiased(self.conf):                     # equal-length items only: plain batches of at most max_batch rows
+        if not is_causal(self.conf):                      # equal-length items only: plain batches of at most max_batch rows
             if len(set(frames)) > 1 or len(set(int(n) for n in lens)) > 1:
-                raise ValueError("decode_many: " + NOT_CAUSAL)
+                raise ValueError("decode_many: " + not_causal_message(self.conf))
             done = []
             for a in range(0, len(codes_list), max(int(max_batch), 1)):
                 c = torch.stack([_prep(ci, eng.device) for ci in codes_list[a:a + max(int(max_batch), 1)]])

@@ -27,7 +27,7 @@ import math
 import torch
 
 from . import _abi
-from .config import NOT_CAUSAL, is_antialiased
+from .config import is_causal, not_causal_message
 from .model import SCALING
 
 CONTEXT_FRAMES = 26      # ceil(6 + 1 + 15 + 1/8 + 120/64 + 1/64 + 120/128 + 1/128 + 120/256 + 6/256)
@@ -91,8 +91,8 @@ class VocoderStream:
     """Handle of the library's incremental generator state for `batch` parallel streams."""
 
     def __init__(self, engine, batch, max_frames_per_push):
-        if is_antialiased(engine.conf):
-            raise ValueError("VocoderStream: " + NOT_CAUSAL)
+        if not is_causal(engine.conf):
+            raise ValueError("VocoderStream: " + not_causal_message(engine.conf))
         self.eng = engine
         self.B = batch
         self.kmax = max_frames_per_push
@@ -133,8 +133,8 @@ class VocoderStream:
 
 class StreamingDecoder:
     def __init__(self, model, batch, device=None, incremental=True, max_frames_per_push=8):
-        if is_antialiased(model.conf):                         # (the context scheme counts on the same causality)
-            raise ValueError("StreamingDecoder: " + NOT_CAUSAL)
+        if not is_causal(model.conf):                          # (the context scheme counts on the same causality)
+            raise ValueError("StreamingDecoder: " + not_causal_message(model.conf))
         self.m = model
         self.B = batch
         eng = model.engine(None if device is None else torch.empty(0, device=device))
@@ -327,8 +327,8 @@ class StreamingCodec:
             raise ValueError("conceal: only a receive session has lost frames to conceal")
         if repair and direction != "recv":
             raise ValueError("repair: only a receive session has late packets to repair from")
-        if direction != "send" and is_antialiased(model.conf):
-            raise ValueError("StreamingCodec: " + NOT_CAUSAL)
+        if direction != "send" and not is_causal(model.conf):
+            raise ValueError("StreamingCodec: " + not_causal_message(model.conf))
         self.direction = direction
         eng = model.engine(None if device is None else torch.empty(0, device=device))
         if direction == "recv":

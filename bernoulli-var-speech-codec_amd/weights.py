@@ -13,7 +13,7 @@ reference convolves with.  The re-layout into MFMA fragment order happens inside
 import torch
 
 from . import melbank
-from .config import antialias_flags
+from .config import antialias_flags, symmetric_flags
 
 
 def expected_bvrnn_keys(conf):
@@ -94,6 +94,11 @@ def host_tensors(conf, vrnn_sd, gen_sd):
     if any(stages_aa) or post_aa:                           # the flags travel as tensors: bvc_config keeps its layout
         out["layers_antialias"] = torch.tensor([float(f) for f in stages_aa])
         out["antialias_post"] = torch.tensor([float(post_aa)])
+    stages_sym, pre_sym, post_sym = symmetric_flags(conf)
+    if any(stages_sym) or pre_sym or post_sym:              # likewise; a causal configuration carries none of the three
+        out["layers_sym"] = torch.tensor([float(f) for f in stages_sym])
+        out["pre_sym"] = torch.tensor([float(pre_sym)])
+        out["post_sym"] = torch.tensor([float(post_sym)])
     out["mel_basis"] = torch.from_numpy(melbank.slaney_mel_basis(conf["fs"], conf["winsize"], conf["num_mels"],
                                                                 conf["fmin"], conf["fmax"]))
     out["hann_window"] = torch.hann_window(conf["winsize"], dtype=torch.float32)     # meldataset.py:70

@@ -101,7 +101,15 @@ typedef struct bvc_config {
  * model.  What counts on the generator being causal returns BVC_EINVAL for it - bvc_vocoder_stream_create, bvc_stream_codec_create
  * (bvc_stream_codec_create_dir unless BVC_STREAM_SEND), bvc_decode_ragged, bvc_test_vocoder_layer with window != 0: a filtered
  * activation reads 5 rows ahead, an AMP block 30, so every output sample depends on later frames - about 53 ms of look-ahead when all
- * four stages and the post activation are filtered (30 rows at each of 8 / 64 / 128 / 256 rows per frame, and 5 samples). */
+ * four stages and the post activation are filtered (30 rows at each of 8 / 64 / 128 / 256 rows per frame, and 5 samples).
+ *
+ * Symmetric layers (vocoder_config.layers_sym / pre_sym / post_sym, models.py:35-44,151-155,209-213,230-233): three more optional tensors -
+ * "layers_sym", n_up values, non-zero = upsampler i is ConvTranspose1d(padding = (k-u)/2) and the stage's AMP blocks pad both sides;
+ * "pre_sym" and "post_sym", one value each, conv_pre / conv_post pad [3, 3] instead of [6, 0].  They add no weight tensors and bvc_config
+ * keeps its layout.  A symmetric upsampler makes L * rate rows instead of (L + 1) * rate: bvc_vocoder_length(m, T) follows.  A stage that
+ * is symmetric and anti-aliased, post_sym with antialias_post, an even resblock kernel size on a symmetric stage and a symmetric stage
+ * with BVC_UNFUSED_AMP set are BVC_EINVAL from bvc_model_create.  The same entry points as above work for such a model and the same
+ * ones return BVC_EINVAL (bvc_last_error() says "symmetric" unless the model is filtered too). */
 typedef struct bvc_tensor {
     const char  *name;
     const float *h_data;
