@@ -95,6 +95,11 @@ def generator_length(conf, T, stages=False):
     return out if stages else L
 
 
+GENERATOR_WIDTHS = (16, 32, 64, 128, 256, 512)     # vocoder_config.upsample_initial_channel (check_config in csrc/model.hip)
+FINAL_CHANNELS = (8, 16, 32)                       # channels in front of conv_post: the width halved once per upsampling stage
+WIDEST_SWITCHED_STAGE = 64                         # layers_sym / layers_antialias: stages of more channels have the causal kernels only
+
+
 def check_supported(conf):
     """The HIP path covers the snakebeta generator with causal or symmetric layers, and anti-aliased activations on causal stages;
     anything else fails loudly."""
@@ -119,6 +124,19 @@ def check_supported(conf):
     if v.get("post_sym", False) and v.get("antialias_post", False):
         bad.append("a filtered (anti-aliased) activation_post is implemented in front of a causal conv_post only: post_sym and "
                    "antialias_post are both set")
+    c0, n_up = v["upsample_initial_channel"], len(v["upsample_rates"])
+    if c0 not in GENERATOR_WIDTHS:
+        bad.append(f"vocoder_config.upsample_initial_channel must be one of {list(GENERATOR_WIDTHS)}, got {c0}")
+    elif (c0 >> n_up) not in FINAL_CHANNELS:
+        bad.append(f"vocoder_config.upsample_initial_channel = {c0} with {n_up} upsampling stages leaves {c0 >> n_up} channels in "
+                   f"front of conv_post: must be one of {list(FINAL_CHANNELS)}")
+    else:
+        for key, what in (("layers_sym", "symmetric layers"), ("layers_antialias", "anti-aliased activations")):
+            flags = v.get(key)
+            wide = [i for i in range(n_up) if flags is not None and len(flags) == n_up and flags[i] and (c0 >> (i + 1)) > WIDEST_SWITCHED_STAGE]
+            if wide:
+                bad.append(f"{what} ({key}) are implemented on stages of {WIDEST_SWITCHED_STAGE} channels at most: with "
+                           f"upsample_initial_channel = {c0}, stage {wide[0]} has {c0 >> (wide[0] + 1)}")
     for u, k in zip(v["upsample_rates"], v["upsample_kernel_sizes"]):
         if k != 2 * u:
             bad.append(f"transposed conv kernel {k} must be 2 x stride {u}")

@@ -1291,6 +1291,14 @@ int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, lo
     a.row_age = win ? win->row_age : nullptr;
     a.age_rate = win ? win->age_rate : 0;
     a.fu1 = c1.aa_up; a.fd1 = c1.aa_down; a.fu2 = c2.aa_up; a.fd2 = c2.aa_down;
+    // wide stages (C = 128 / 256) exist as causal, unfiltered pairs only; their rows go through 32-bit byte offsets (rows_load4)
+    const bool wide = c1.cin >= 128;
+    if (wide) {
+        if (c1.cin != 128 && c1.cin != 256) { set_error("amp_pair: unsupported channel count %d", c1.cin); return BVC_EINVAL; }
+        if (c1.aa_up || c2.aa_up || c1.aa_down || c2.aa_down) { set_error("amp_pair: anti-aliased activations are not implemented on a stage of %d channels (64 at most)", c1.cin); return BVC_EINVAL; }
+        if (sym) { set_error("amp_pair: symmetric layers are not implemented on a stage of %d channels (64 at most)", c1.cin); return BVC_EINVAL; }
+        if (L + 512 > 0x7FFFFFFFll / c1.cin / 4) { set_error("amp_pair: %lld rows of %d channels are beyond the kernel's row index", L, c1.cin); return BVC_EINVAL; }
+    }
     if (c1.aa_up || c2.aa_up) {
         // anti-aliased pair: the generic kernel with the filters around both activations, one tile shape per stage - the tallest whose
         // two LDS regions leave the stage's workgroups per CU (C = 64: 96 rows, 78 KiB at ks = 11; C = 32 / 16: 128 rows; C = 8: 256)
@@ -1323,6 +1331,30 @@ int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, lo
     // streaming hops compute a few new rows behind a 64-row history: the 128 / 256-row tiles of the offline sweep would spend
     // most of their MFMAs on rows nobody reads, so short windows take the smallest tile (4 waves x 16 rows)
     const long long new_rows = L - a.row_begin;
+    if (wide) {
+        // wide stages (generators of 256 / 512 initial channels): the generic pair with the waves along the columns (a conv's weights
+        // are 0.7 - 2.9 MB: a fragment is read once per workgroup) and the S2 tile in the S1 tile's LDS.  C = 256: 64 rows, 114 x 258
+        // floats = 117.6 KB at ks = 11, d = 5, one workgroup per CU: 32.9 ms for the stage at 64 x 430 frames; 96 rows (150.7 KB), the
+        // other compiled height, 39.0.  C = 128: 64 rows, 114 x 130 floats = 59 KB, two per CU: 7.69 ms as stage 0 of a 256-wide
+        // generator, 60.70 as stage 1 of a 512-wide one; 128 rows (92.6 KB, one per CU) 8.35 / 60.73.  BVC_AMP256_TR / BVC_AMP128_TR
+        // pick the other height (read per call: tests and tools/wide_generator_cost.py run both in one process;
+        // profiles/wide_generator_cost.md).  A streaming window of at most one 32-row tile takes that tile, like C = 64.
+        const bool short_win = win && new_rows <= 32 - (c1.ks - 1);
+        if (c1.cin == 256) {
+            if (short_win) return launch_amp_t<256, 2, 1, true, 4>(a, B, s);
+            const char *force = win ? nullptr : getenv("BVC_AMP256_TR");
+            const int tr = force ? atoi(force) : 64;
+            if (tr == 64) return launch_amp_t<256, 4, 1, true, 4>(a, B, s);
+            if (tr == 96) return launch_amp_t<256, 6, 1, true, 4>(a, B, s);
+            set_error("amp_pair: BVC_AMP256_TR=%s is not a compiled tile height", force); return BVC_EINVAL;
+        }
+        if (short_win) return launch_amp_t<128, 2, 2, true, 4>(a, B, s);
+        const char *force = win ? nullptr : getenv("BVC_AMP128_TR");
+        const int tr = force ? atoi(force) : 64;
+        if (tr == 64) return launch_amp_t<128, 4, 2, true, 4>(a, B, s);
+        if (tr == 128) return launch_amp_t<128, 8, 1, true, 4>(a, B, s);
+        set_error("amp_pair: BVC_AMP128_TR=%s is not a compiled tile height", force); return BVC_EINVAL;
+    }
     if (win && c1.cin == 64 && new_rows <= 32 - (c1.ks - 1)) return launch_amp_t<64, 2, 2, true, 4>(a, B, s);      // 32 rows, waves split the columns
     if (win && c1.cin == 64 && new_rows <= 2 * (64 - (c1.ks - 1))) return launch_amp_t<64, 1, 2, true>(a, B, s);
     static const int s32 = getenv("BVC_AMP32S") ? atoi(getenv("BVC_AMP32S")) : 3;       // (3 tiles of 64 rows against one of 256 for a two-frame hop: 1.53 -> 1.47 ms per tick at 256 streams)
@@ -1428,6 +1460,10 @@ int conv_kernels_init() {
     int rc;
     if (!amp8_slots_all<1, 4>() || !amp8_slots_all<2, 2>()) return BVC_EHIP;
     if (!amp16_slots_all<4>()) return BVC_EHIP;
+    if ((rc = allow_big_lds<512, 4, 1>())) return rc;
+    if ((rc = allow_big_lds<512, 4, 1, true>())) return rc;
+    if ((rc = allow_big_lds<256, 4, 2>())) return rc;
+    if ((rc = allow_big_lds<256, 4, 1, true>())) return rc;
     if ((rc = allow_big_lds<128, 4, 2>())) return rc;
     if ((rc = allow_big_lds<80, 4, 2>())) return rc;
     if ((rc = allow_big_lds<80, 4, 2, false, 3>())) return rc;
@@ -1460,6 +1496,8 @@ int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *
     // and more per workgroup) would compute mostly rows nobody reads, so the waves split the columns instead
     if (win && Lout - a.row_begin <= 16) {
         switch (c.cin) {
+            case 512: return launch_one<512, 4, 1, true>(a, B, s);
+            case 256: return launch_one<256, 4, 1, true>(a, B, s);
             case 128: return launch_one<128, 4, 1, true>(a, B, s);
             case 80:  return launch_one<80, 2, 1, true>(a, B, s);
             case 64:  return launch_one<64, 4, 1, true>(a, B, s);
@@ -1467,6 +1505,8 @@ int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *
         }
     }
     switch (c.cin) {
+        case 512: return launch_one<512, 4, 1>(a, B, s);     // ConvT 512->8x256: 64 rows (65 x 514 floats = 133.6 KB; 128 rows would need 265 KB)
+        case 256: return launch_one<256, 4, 2>(a, B, s);     // ConvT 256->8x128 (129 x 258 floats = 133.1 KB)
         case 128: return launch_one<128, 4, 2>(a, B, s);     // ConvT 128->8x64
         case 80:  return launch_one<80, 4, 2>(a, B, s);      // conv_pre 80->128
         case 64:  return launch_one<64, 4, 2>(a, B, s);      // AMP C=64, ConvT 64->8x32
@@ -1481,7 +1521,8 @@ int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *
 
 // ------------------------------------------------------------------------------------------------
 // activation_post -> pad[6,0] -> conv_post (C -> 1) -> tanh -> [:length] -> / SCALING
-// (models.py:228-238, bvrnn_codec_model.py:71).  VALU kernel: C*ks = 56 MACs per sample.
+// (models.py:228-238, bvrnn_codec_model.py:71).  VALU kernel: C*ks = 56 MACs per sample (C = 8; 112 / 224 behind a generator of
+// 256 / 512 initial channels, whose last stage has 16 / 32 channels).
 // SHIFT: the window starts SHIFT rows later (post_sym pads [3, 3], models.py:230-233); rows behind the last read as zeros either way.
 template <int C, int SHIFT = 0>
 __global__ __launch_bounds__(256) void conv_post_kernel(const float *__restrict__ in, long long Lin, int ks,
@@ -1552,7 +1593,7 @@ int launch_conv_post(const float *in, long long Lin, int C, int ks, const float 
                      hipStream_t s, const ConvWindow *win, const long long *n_rows, const float *aa_up, const float *aa_down,
                      bool sym, long long in_bs) {
     if (B <= 0 || n_out <= 0) return BVC_OK;
-    if (C != 8) { set_error("conv_post: unsupported channel count %d", C); return BVC_EINVAL; }
+    if (C != 8 && C != 16 && C != 32) { set_error("conv_post: unsupported channel count %d", C); return BVC_EINVAL; }
     const int tiles = (int)((n_out + 255) / 256);
     if (aa_up || aa_down) {
         if (sym || in_bs) { set_error("conv_post: an anti-aliased activation_post stands in front of a causal conv_post, on a dense signal"); return BVC_EINVAL; }
@@ -1560,7 +1601,12 @@ int launch_conv_post(const float *in, long long Lin, int C, int ks, const float 
         if (Lin + 512 > 0x7FFFFFFFll) { set_error("conv_post: %lld rows are beyond the anti-aliased kernel's row index", Lin); return BVC_EINVAL; }
         const size_t lds_aa = (size_t)(2 * (256 + ks - 1) + 10) * C * sizeof(float);
         ProbeScope probe(PK_POST, s);
-        hipLaunchKernelGGL(conv_post_aa_kernel<8>, dim3((unsigned)(tiles * (long long)B)), dim3(256), lds_aa, s, in, Lin, ks,
+        auto kern = C == 8 ? conv_post_aa_kernel<8> : C == 16 ? conv_post_aa_kernel<16> : conv_post_aa_kernel<32>;
+        if (C == 32) {                                         // (2 x 262 + 10) x 32 floats = 68 KB
+            static bool attr = false;
+            if (!attr) { BVC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_post_aa_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; }
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * (long long)B)), dim3(256), lds_aa, s, in, Lin, ks,
                            w, bias, act_a, act_ib, aa_up, aa_down, div, wav, n_out, tiles);
         BVC_HIP_TRY(hipGetLastError());
         return BVC_OK;
@@ -1569,12 +1615,14 @@ int launch_conv_post(const float *in, long long Lin, int C, int ks, const float 
     ProbeScope probe(PK_POST, s);
     if (sym) {
         if (win || n_rows || ks != 7) { set_error("conv_post: a symmetric conv_post has 7 taps, no streaming window and no mixed lengths"); return BVC_EINVAL; }
-        hipLaunchKernelGGL((conv_post_kernel<8, 3>), dim3((unsigned)(tiles * (long long)B)), dim3(256), lds, s, in, Lin, ks,
+        auto kern = C == 8 ? conv_post_kernel<8, 3> : C == 16 ? conv_post_kernel<16, 3> : conv_post_kernel<32, 3>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * (long long)B)), dim3(256), lds, s, in, Lin, ks,
                            w, bias, act_a, act_ib, div, wav, n_out, tiles, in_bs ? in_bs : Lin * C, 0ll, n_rows);
         BVC_HIP_TRY(hipGetLastError());
         return BVC_OK;
     }
-    hipLaunchKernelGGL(conv_post_kernel<8>, dim3((unsigned)(tiles * (long long)B)), dim3(256), lds, s, in, Lin, ks,
+    auto kern = C == 8 ? conv_post_kernel<8> : C == 16 ? conv_post_kernel<16> : conv_post_kernel<32>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * (long long)B)), dim3(256), lds, s, in, Lin, ks,
                        w, bias, act_a, act_ib, div, wav, n_out, tiles, win ? win->in_bs : (in_bs ? in_bs : Lin * C), win ? win->row_begin : 0, n_rows);
     BVC_HIP_TRY(hipGetLastError());
     return BVC_OK;

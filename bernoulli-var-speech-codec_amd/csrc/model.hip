@@ -347,6 +347,14 @@ int build_vocoder(bvc_model *m, const TensorMap &tm) {
             if (m->stage_sym[i] && c.up_rates[i] % 2) { set_error("a symmetric upsampler needs an even rate (got %d)", c.up_rates[i]); return BVC_EINVAL; }
         if (!m->fused_amp) { set_error("symmetric stages run in the fused AMP kernels only (BVC_UNFUSED_AMP is set)"); return BVC_EINVAL; }
     }
+    // wide stages (128 / 256 channels, generators of 256 / 512 initial channels) exist as causal, unfiltered, fused pairs only
+    for (int i = 0; i < c.n_up; ++i) {
+        const int C = c.upsample_initial_channel >> (i + 1);
+        if (C < 128) continue;
+        if (m->stage_sym[i]) { set_error("stage %d has %d channels: symmetric layers (layers_sym) are implemented on stages of 64 channels at most", i, C); return BVC_EINVAL; }
+        if (stage_aa[i]) { set_error("stage %d has %d channels: anti-aliased activations (layers_antialias) are implemented on stages of 64 channels at most", i, C); return BVC_EINVAL; }
+        if (!m->fused_amp) { set_error("stage %d has %d channels: wide stages run in the fused AMP kernels only (BVC_UNFUSED_AMP is set)", i, C); return BVC_EINVAL; }
+    }
     m->antialiased = post_aa;
     for (int i = 0; i < c.n_up; ++i) m->antialiased = m->antialiased || stage_aa[i];
     m->noncausal = m->antialiased || m->symmetric;
@@ -417,13 +425,13 @@ int check_config(const bvc_config *c) {
         set_error("num_mels/h_dim/z_dim must be multiples of 16 (num_mels <= 128)"); return BVC_EINVAL; }
     if (c->n_up < 1 || c->n_up > 8 || c->n_resk < 1 || c->n_resk > 4) { set_error("bad n_up / n_resk"); return BVC_EINVAL; }
     int ch = c->upsample_initial_channel;
-    if (ch != 128 && ch != 64 && ch != 32 && ch != 16) { set_error("unsupported upsample_initial_channel %d", ch); return BVC_EINVAL; }
+    if (ch != 512 && ch != 256 && ch != 128 && ch != 64 && ch != 32 && ch != 16) { set_error("unsupported upsample_initial_channel %d (16, 32, 64, 128, 256 or 512)", ch); return BVC_EINVAL; }
     for (int i = 0; i < c->n_up; ++i) {
         if (c->up_kernels[i] != 2 * c->up_rates[i]) { set_error("upsample kernel must be 2*rate"); return BVC_EINVAL; }
         ch /= 2;
         if (ch < 8) { set_error("too many upsampling stages for %d initial channels", c->upsample_initial_channel); return BVC_EINVAL; }
     }
-    if (ch != 8) { set_error("final channel count must be 8 (got %d)", ch); return BVC_EINVAL; }
+    if (ch != 8 && ch != 16 && ch != 32) { set_error("final channel count must be 8, 16 or 32 (got %d)", ch); return BVC_EINVAL; }
     if (c->num_mels != 80) { set_error("conv_pre kernel is built for num_mels=80"); return BVC_EINVAL; }
     return BVC_OK;
 }

@@ -64,7 +64,13 @@ enum {
 };
 
 /* Static description of the codec; mirrors the TOML keys the reference facade reads
- * (configs/config_varBitRate.toml:21-29,35-37,39-56; bvrnn_codec_model.py:27-36,49-59). */
+ * (configs/config_varBitRate.toml:21-29,35-37,39-56; bvrnn_codec_model.py:27-36,49-59).
+ * The generator's width: upsample_initial_channel is 16, 32, 64, 128, 256 or 512 and halves at every upsampling stage; every stage has
+ * at least 8 channels and conv_post reads 8, 16 or 32 (bvc_model_create returns BVC_EINVAL otherwise).  Stages of 128 and 256
+ * channels - the first one or two of a generator of 256 / 512 - run as causal, unfiltered, fused AMP pairs only: "layers_sym" or
+ * "layers_antialias" set on such a stage, or BVC_UNFUSED_AMP=1 with such a model, is BVC_EINVAL at creation; a stage of 256 (128)
+ * channels takes at most 2^31 / 1024 (2^31 / 512) - 512 rows per item.  Everything else - streaming, mixed lengths, concealment, the
+ * switches on the stages of 64 channels and fewer - works at every width. */
 typedef struct bvc_config {
     int32_t num_mels;          /* 80 */
     int32_t h_dim;             /* 1024 */
@@ -75,7 +81,7 @@ typedef struct bvc_config {
     int32_t pad_left;          /* mel_pad_left = 256 */
     int32_t sample_rate;       /* 22050 */
     float   fmin, fmax;        /* 0, 8000 */
-    int32_t upsample_initial_channel;      /* 128 */
+    int32_t upsample_initial_channel;      /* 128 (16 .. 512, powers of two) */
     int32_t n_up;                          /* 4 */
     int32_t up_rates[8];                   /* 8,8,2,2 */
     int32_t up_kernels[8];                 /* 16,16,4,4 (must be 2*rate) */
