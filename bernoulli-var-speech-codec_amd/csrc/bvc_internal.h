@@ -289,7 +289,7 @@ int launch_unpack_rows(const unsigned char *in, const unsigned char *present, co
 int launch_conceal_select(const unsigned char *present, long long kstride, const float *bits, float dflt, const int *row_off, int B,
                           long long k, float *sel, hipStream_t s);
 
-// ------------------------------------------------------------------ vocoder (k_vocoder.hip)
+// ------------------------------------------------------------------ vocoder (k_vocoder.hip; the AMP pairs: k_vocoder_amp.hip)
 struct ConvLayer {               // one causal conv as implicit GEMM on fp32 MFMA
     int cin;                     // input channels (multiple of 4)
     int cout;                    // real output columns
