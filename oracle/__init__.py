@@ -25,7 +25,9 @@ algorithm for the path (citations are relative to the reference checkout):
                      (``bvrnn.py:86-160``: sampler, prior, KLD) with the random numbers as inputs.
 * ``bigvgan.py``   - ``BigVGAN.forward`` (``third_party/BigVGAN/models.py:207-238``),
                      ``AMPBlock1.forward`` (``models.py:103-121``), ``SnakeBeta``
-                     (``third_party/BigVGAN/activations.py:107-120``), weight-norm fold.
+                     (``third_party/BigVGAN/activations.py:107-120``), ``Activation1d``
+                     (``third_party/BigVGAN/alias_free_torch/act.py:8-28``), weight-norm fold: every
+                     configuration the product loads (any width, causal / symmetric / anti-aliased stages).
 * ``codec.py``     - ``BVRNNCodecModel.encode/decode/forward``
                      (``bvrnn_codec_model.py:44-76``).
 

@@ -24,7 +24,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from bvcodec import config as bconfig, synth          # noqa: E402
-import antialias_oracle as aao                         # noqa: E402
+import vocoder_layers as vl                            # noqa: E402
 
 SEED = 1235
 
@@ -49,8 +49,8 @@ def main():
     conf = bconfig.load_config(os.path.join(a.ref, "configs", "config_varBitRate.toml"))
     rng = np.random.default_rng(79)
     mel = torch.from_numpy((-4.0 + 1.6 * rng.standard_normal((2, 80, 12))).astype(np.float32))
-    for tag, (layers, post) in aao.CONFIGS.items():
-        c = aao.with_antialias(conf, layers, post)
+    for tag, sw in vl.AA_CONFIGS.items():
+        c = vl.with_switches(conf, sw)
         sd = synth.generator_state_dict(c, seed=SEED)
         voc = BigVGAN(AttrDict(c["vocoder_config"]))
         voc.load_state_dict(sd)                                           # strict: the key layout is the reference's
@@ -70,7 +70,7 @@ def main():
         print(f"{tag}: wav rms {float(wav.pow(2).mean().sqrt()):.4f} max {float(wav.abs().max()):.4f}")
         path = os.path.join(HERE, f"g10_bigvgan_aa_{tag}.npz")
         np.savez_compressed(path, mel=mel.numpy(), wav=wav.numpy(), seed=np.int64(SEED),
-                            layers_antialias=np.asarray(layers), antialias_post=np.asarray(post),
+                            layers_antialias=np.asarray(sw["layers_antialias"]), antialias_post=np.asarray(sw["antialias_post"]),
                             **{k: v.numpy() for k, v in taps.items()})
         print(f"  wrote {os.path.basename(path)} ({os.path.getsize(path) / 1024:.0f} KiB)")
 

@@ -5,7 +5,7 @@ container only).
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_symmetric.py [--ref /root/reference]
 
-Three configurations of the shipped TOML (tests/symmetric_oracle.py CONFIGS): ``all`` (every switch on), ``mixed``
+Three configurations of the shipped TOML (tests/vocoder_layers.py SYM_CONFIGS): ``all`` (every switch on), ``mixed``
 (``layers_sym = [false, true, false, true]``, ``post_sym``) and ``with_aa`` (symmetric stages 0 and 2 and conv_pre, filtered
 stages 1 and 3 and activation_post).  B = 2, T = 12 frames; stored are the input, the untrimmed waveform, conv_pre and the four
 stage outputs (what the next upsampler, or ``activation_post``, receives), and the switches.  The weights are regenerated from the
@@ -24,7 +24,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from bvcodec import config as bconfig, synth          # noqa: E402
-import symmetric_oracle as symo                        # noqa: E402
+import vocoder_layers as vl                            # noqa: E402
 
 SEED = 1235
 
@@ -49,8 +49,8 @@ def main():
     conf = bconfig.load_config(os.path.join(a.ref, "configs", "config_varBitRate.toml"))
     rng = np.random.default_rng(79)
     mel = torch.from_numpy((-4.0 + 1.6 * rng.standard_normal((2, 80, 12))).astype(np.float32))
-    for tag, sw in symo.CONFIGS.items():
-        c = symo.with_switches(conf, tag)
+    for tag, sw in vl.SYM_CONFIGS.items():
+        c = vl.with_switches(conf, sw)
         bconfig.check_supported(c)
         sd = synth.generator_state_dict(c, seed=SEED)
         voc = BigVGAN(AttrDict(c["vocoder_config"]))
@@ -67,7 +67,7 @@ def main():
             wav = voc(mel, 10 ** 9)
         for h in hooks:
             h.remove()
-        lens = symo.sym_lengths(c["vocoder_config"], 12)
+        lens = vl.sym_lengths(c["vocoder_config"], 12)
         assert [taps[f"stage{i}"].shape[2] for i in range(4)] == lens and wav.shape == (2, 1, lens[-1]) and len(taps) == 5
         print(f"{tag}: stage lengths {lens}, wav rms {float(wav.pow(2).mean().sqrt()):.4f} max {float(wav.abs().max()):.4f}")
         path = os.path.join(HERE, f"g11_bigvgan_sym_{tag}.npz")

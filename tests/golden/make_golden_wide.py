@@ -28,7 +28,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from bvcodec import config as bconfig, synth          # noqa: E402
-import wide_generator as wg                            # noqa: E402
+import vocoder_layers as vl                            # noqa: E402
 
 SEED = 1235
 CASES = ((256, 2, 6), (512, 1, 6))                     # (width, B, T), in the order the inputs are drawn
@@ -55,7 +55,7 @@ def main():
     rng = np.random.default_rng(79)
     for width, B, T in CASES:
         mel = torch.from_numpy((-4.0 + 1.6 * rng.standard_normal((B, 80, T))).astype(np.float32))
-        c = wg.with_width(conf, width)
+        c = vl.with_switches(conf, width=width)
         bconfig.check_supported(c)
         sd = synth.generator_state_dict(c, seed=SEED)
         voc = BigVGAN(AttrDict(c["vocoder_config"]))
@@ -74,7 +74,7 @@ def main():
             h.remove()
         lens = bconfig.generator_length(c, T, stages=True)
         assert [taps[f"stage{i}"].shape[2] for i in range(4)] == lens and wav.shape == (B, 1, lens[-1]) and len(taps) == 5
-        assert [taps[f"stage{i}"].shape[1] for i in range(4)] == wg.stage_channels(c) and taps["conv_pre"].shape == (B, width, T)
+        assert [taps[f"stage{i}"].shape[1] for i in range(4)] == vl.stage_channels(c) and taps["conv_pre"].shape == (B, width, T)
         print(f"width {width}: stage lengths {lens}, wav rms {float(wav.pow(2).mean().sqrt()):.4f} max {float(wav.abs().max()):.4f}")
         path = os.path.join(HERE, f"g12_bigvgan_wide_{width}.npz")
         np.savez_compressed(path, mel=mel.numpy(), wav=wav.numpy(), seed=np.int64(SEED), width=np.int64(width),

@@ -1,4 +1,4 @@
-"""Anti-aliased activations without a GPU: the test oracle (tests/antialias_oracle.py) against the reference's own run
+"""Anti-aliased activations without a GPU: the oracle (oracle/bigvgan.py) against the reference's own run
 (tests/golden/g10_bigvgan_aa_*.npz, written by tests/golden/make_golden_antialias.py), the checkpoint key layouts, the reach of
 one filtered AMP pair - the halo the GPU kernel's tiles are cut with - and its conditioning in float32."""
 import os
@@ -7,7 +7,6 @@ import numpy as np
 import pytest
 import torch
 
-import antialias_oracle as aao
 import vocoder_layers as vl
 from conftest import load_golden
 from bvcodec import synth, weights
@@ -18,25 +17,25 @@ TAPS = ("conv_pre", "stage0", "stage1", "stage2", "stage3")
 
 @pytest.fixture(scope="module")
 def conf_all(conf_var):
-    return aao.with_antialias(conf_var, *aao.CONFIGS["all"])
+    return vl.with_switches(conf_var, vl.AA_CONFIGS["all"])
 
 
 # ----------------------------------------------------------------------------------------------- 1. the oracle is the reference
-@pytest.mark.parametrize("tag", sorted(aao.CONFIGS))
+@pytest.mark.parametrize("tag", sorted(vl.AA_CONFIGS))
 def test_oracle_equals_reference_fixture_bit_for_bit(conf_var, tag):
     """Waveform and every tap, float32, with the weight fold of the reference's forward pre-hook (torch._weight_norm: the oracle's own
-    fold_weight_norm gives weights one bit away, see antialias_oracle) and the fixture script's thread count, which decides
+    fold_weight_norm gives weights one bit away, see oracle/bigvgan.py) and the fixture script's thread count, which decides
     how the CPU convolutions split their sums."""
     g = load_golden(f"g10_bigvgan_aa_{tag}")
-    layers, post = aao.CONFIGS[tag]
-    assert list(g["layers_antialias"]) == layers and bool(g["antialias_post"]) == post
-    conf = aao.with_antialias(conf_var, layers, post)
+    sw = vl.AA_CONFIGS[tag]
+    assert list(g["layers_antialias"]) == sw["layers_antialias"] and bool(g["antialias_post"]) == sw["antialias_post"]
+    conf = vl.with_switches(conf_var, sw)
     sd = synth.generator_state_dict(conf, seed=int(g["seed"]))
     threads = torch.get_num_threads()
     torch.set_num_threads(8)
     try:
         taps = {}
-        wav = aao.forward(sd, conf["vocoder_config"], torch.from_numpy(g["mel"]), 10 ** 9, taps=taps, fold=aao.REFERENCE_FOLD)
+        wav = obig.forward(sd, conf["vocoder_config"], torch.from_numpy(g["mel"]), 10 ** 9, taps=taps, fold=obig.REFERENCE_FOLD)
     finally:
         torch.set_num_threads(threads)
     T = g["mel"].shape[2]
@@ -46,40 +45,51 @@ def test_oracle_equals_reference_fixture_bit_for_bit(conf_var, tag):
         assert np.array_equal(taps[k].numpy(), g[k]), (k, float(np.abs(taps[k].numpy() - g[k]).max()))
     assert float(np.sqrt((g["wav"] ** 2).mean())) > 0.05                  # a non-trivial signal
     # the oracle's own fold (the float64 truth's): the bar test_oracle_golden.py has for g5
-    wav2 = aao.forward(sd, conf["vocoder_config"], torch.from_numpy(g["mel"]), 10 ** 9)
+    wav2 = obig.forward(sd, conf["vocoder_config"], torch.from_numpy(g["mel"]), 10 ** 9)
     assert np.abs(wav2.numpy() - g["wav"]).max() < 2e-6
 
 
 def test_plain_stages_equal_the_plain_oracle(conf_var):
-    sd = synth.generator_state_dict(conf_var, 1235)
-    mel = torch.from_numpy(load_golden("g10_bigvgan_aa_all")["mel"])
-    assert torch.equal(aao.forward(sd, conf_var["vocoder_config"], mel, 10 ** 9), obig.forward(sd, conf_var["vocoder_config"], mel, 10 ** 9))
+    """The by-keys dispatch leaves a checkpoint of plain stages on the plain path: the shipped configuration's waveform and taps
+    against the reference's (g5), by the criterion of test_oracle_golden.py::test_bigvgan_stage_taps."""
+    g = load_golden("g5_bigvgan_taps")
+    sd = synth.generator_state_dict(conf_var, seed=int(g["seed"]))
+    assert not any(".act." in k or "filter" in k for k in sd)
+    taps = {}
+    w = obig.forward(sd, conf_var["vocoder_config"], torch.from_numpy(g["mel"]), 10 ** 9, taps=taps)
+    assert np.abs(w.numpy() - g["wav"]).max() < 2e-6
+    for i in range(4):
+        assert taps[f"up{i}"].shape[2] == g[f"up{i}"].shape[2]
+        assert np.abs(taps[f"up{i}"].numpy() - g[f"up{i}"]).max() < 1e-4
+        mean3 = (g[f"res{i}_0"] + g[f"res{i}_1"] + g[f"res{i}_2"]) / 3
+        assert np.abs(taps[f"stage{i}"].numpy() - mean3).max() < 1e-4
+    assert np.abs(taps["conv_pre"].numpy() - g["conv_pre"]).max() < 1e-5
 
 
 # ----------------------------------------------------------------------------------------------- 2. key layouts
 def test_config_accepts_the_switches_and_checks_the_list(tmp_path, conf_var):
     from bvcodec import config
-    for tag, (layers, post) in aao.CONFIGS.items():
-        c = aao.write_config(str(tmp_path / f"{tag}.toml"), layers, post)
-        assert config.antialias_flags(c) == (layers, post) and config.is_antialiased(c)
+    for tag, sw in vl.AA_CONFIGS.items():
+        c = vl.write_config(str(tmp_path / f"{tag}.toml"), switches=sw)
+        assert config.antialias_flags(c) == (sw["layers_antialias"], sw["antialias_post"]) and config.is_antialiased(c)
     assert config.antialias_flags(conf_var) == ([False] * 4, False) and not config.is_antialiased(conf_var)
-    bad = aao.with_antialias(conf_var, [True, False, True], False)
+    bad = vl.with_switches(conf_var, dict(layers_antialias=[True, False, True], antialias_post=False))
     with pytest.raises(ValueError, match="layers_antialias"):
         config.check_supported(bad)
-    sym = aao.with_antialias(conf_var, [True] * 4, True)
+    sym = vl.with_switches(conf_var, vl.AA_CONFIGS["all"])
     sym["vocoder_config"]["layers_sym"] = [True, False, False, False]
     with pytest.raises(ValueError, match="causal"):
         config.check_supported(sym)
-    snake = aao.with_antialias(conf_var, [True] * 4, True)
+    snake = vl.with_switches(conf_var, vl.AA_CONFIGS["all"])
     snake["vocoder_config"]["activation"] = "snake"
     with pytest.raises(ValueError, match="snakebeta"):
         config.check_supported(snake)
 
 
-@pytest.mark.parametrize("tag", sorted(aao.CONFIGS))
+@pytest.mark.parametrize("tag", sorted(vl.AA_CONFIGS))
 def test_checkpoint_keys_follow_the_config_both_ways(conf_var, tag):
-    layers, post = aao.CONFIGS[tag]
-    conf = aao.with_antialias(conf_var, layers, post)
+    layers, post = vl.AA_CONFIGS[tag]["layers_antialias"], vl.AA_CONFIGS[tag]["antialias_post"]
+    conf = vl.with_switches(conf_var, vl.AA_CONFIGS[tag])
     vr = synth.bvrnn_state_dict(conf_var, 3)
     g_aa, g_plain = synth.generator_state_dict(conf, 4), synth.generator_state_dict(conf_var, 4)
     ht = weights.host_tensors(conf, vr, g_aa)                              # loads under its own config
@@ -111,7 +121,7 @@ def test_synthetic_draws_of_the_shipped_configs_are_unchanged(conf_var):
     w = obig.forward(sd, conf_var["vocoder_config"], torch.from_numpy(g["mel"]), 8192)
     assert np.abs(w.numpy() - g["wav_8192"]).max() < 2e-6
     assert not any(".act." in k or "filter" in k for k in sd)
-    sd_aa = synth.generator_state_dict(aao.with_antialias(conf_var, *aao.CONFIGS["mixed"]), seed=int(g["seed"]))
+    sd_aa = synth.generator_state_dict(vl.with_switches(conf_var, vl.AA_CONFIGS["mixed"]), seed=int(g["seed"]))
     for k, v in sd.items():
         k2 = k if k in sd_aa else k.replace(".alpha", ".act.alpha").replace(".beta", ".act.beta")
         assert torch.equal(sd_aa[k2], v), k
@@ -126,26 +136,26 @@ def test_reach_of_one_filtered_pair(conf_all, ks, d):
     sd = synth.generator_state_dict(conf_all, 1235)
     L, t = 200, 120
     x = vl.make_input("n1", 1, C, L, L, 5).double()
-    base = aao.amp_pair(sd, pre, m, x, ks, d, dtype=torch.float64)
-    lo, hi = t - aao.halo(ks, d), t + 2 * aao.REACH
+    base = obig.amp_pair(sd, pre, m, x, ks, d, dtype=torch.float64)
+    lo, hi = t - vl.halo(ks, d), t + 2 * obig.REACH
     assert lo == t - (ks - 1) * (d + 1) - 10 and hi == t + 10
     for s in range(lo - 12, hi + 13):
         xp = x.clone()
         xp[:, :, s] += 0.5
-        changed = bool((aao.amp_pair(sd, pre, m, xp, ks, d, dtype=torch.float64)[:, :, t] != base[:, :, t]).any())
+        changed = bool((obig.amp_pair(sd, pre, m, xp, ks, d, dtype=torch.float64)[:, :, t] != base[:, :, t]).any())
         assert changed == (lo <= s <= hi), (s, lo, hi, changed)
 
 
 def test_reach_of_one_activation(conf_all):
     sd = {k: v.double() for k, v in synth.generator_state_dict(conf_all, 1235).items()}
     x = vl.make_input("n1", 1, 8, 60, 60, 6).double()
-    base = aao.activation(sd, "activation_post", x, torch.float64)
+    base = obig.activation(sd, "activation_post", x, torch.float64)
     assert base.shape == x.shape
     for s in range(30 - 9, 30 + 10):
         xp = x.clone()
         xp[:, :, s] += 0.5
-        changed = bool((aao.activation(sd, "activation_post", xp, torch.float64)[:, :, 30] != base[:, :, 30]).any())
-        assert changed == (abs(s - 30) <= aao.REACH), s
+        changed = bool((obig.activation(sd, "activation_post", xp, torch.float64)[:, :, 30] != base[:, :, 30]).any())
+        assert changed == (abs(s - 30) <= obig.REACH), s
 
 
 # ----------------------------------------------------------------------------------------------- 4. conditioning
@@ -158,8 +168,8 @@ def test_filtered_pair_is_well_conditioned_in_float32(conf_all, draw):
     i, j, m, C, ks, d, pre = pair
     for kind in ("n1", "n6"):
         x = vl.make_input(kind, 2, C, 300, 300, 11)
-        r64 = aao.amp_pair(sd, pre, m, x, ks, d, dtype=torch.float64)
-        r32 = aao.amp_pair(sd, pre, m, x, ks, d, dtype=torch.float32)
+        r64 = obig.amp_pair(sd, pre, m, x, ks, d, dtype=torch.float64)
+        r32 = obig.amp_pair(sd, pre, m, x, ks, d, dtype=torch.float32)
         e32, scale = float((r32.double() - r64).abs().max()), float(r64.abs().max())
         print(f"CONDITIONING draw={draw} input={kind} e32/scale={e32 / scale:.3e}")
         assert e32 <= 5e-6 * scale, (draw, kind, e32, scale)

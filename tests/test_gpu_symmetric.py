@@ -1,122 +1,42 @@
 """Symmetric layers on the GPU: every symmetric AMP pair, conv_pre, upsampler and conv_post one launch at a time against the
-float64 oracle (tests/symmetric_oracle.py) with the project's bar, vocoder_layers.compare: e_hip = max|hip - oracle64| <= 8 x
+float64 oracle (oracle/bigvgan.py) with the project's bar, vocoder_layers.compare: e_hip = max|hip - oracle64| <= 8 x
 max(e32, 2^-24 max|oracle64|); the three reference fixtures through BigVGAN.forward and the facade's decode; batch invariance; the
 refusals of everything that counts on a causal generator; and the tile cuts of a causal model beside the symmetric ones.
 Measured ratios: profiles/symmetric_parity.md.  Needs the MI355X: run with ``-m gpu``."""
 import ctypes
-import os
-import zlib
 
 import numpy as np
 import pytest
 import torch
 
-import symmetric_oracle as symo
+import gpu_generator as gg
 import vocoder_layers as vl
-from conftest import load_golden
+from gpu_generator import DEV, H_DIM, KIND_AMP, KIND_PRE, KIND_UP, amp_case, nan_like, seed_of, to_dev
+from oracle import bigvgan as obig
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-KIND_PRE, KIND_UP, KIND_AMP, KIND_POST = 0, 1, 2, 3
-H_DIM = 64                                   # a small coder: these tests are about the generator
 CAUSAL = "causal"                            # the shipped switches (all off), for the last test
 
 
-class Model:
-    """The product model of one configuration and one generator draw on the GPU."""
-
-    def __init__(self, directory, tag, draw):
-        from bvcodec import BVRNNCodecModel, _abi, config, synth
-        self.tag, self.draw = tag, draw
-        cfg = os.path.join(directory, f"{tag}.toml")
-        if tag == CAUSAL:
-            with open(cfg, "w") as f:
-                f.write(open(config.DEFAULT_CONFIG).read().replace("h_dim = 1024", f"h_dim = {H_DIM}"))
-            self.conf = config.load_config(cfg)
-        else:
-            self.conf = symo.write_config(cfg, tag, h_dim=H_DIM)
-        self.sd = vl.generator_draw(self.conf, draw)
-        self.vr = synth.bvrnn_state_dict(self.conf, 1234)
-        p1, p2 = os.path.join(directory, "bvrnn"), os.path.join(directory, f"bigvgan_{tag}_{draw}")
-        torch.save({"vrnn": self.vr}, p1)
-        torch.save({"generator": self.sd}, p2)
-        self.model = BVRNNCodecModel(cfg, p1, p2).to(DEV)
-        self.eng = self.model.engine(torch.empty(0, device=DEV))
-        self.lib, self.abi = _abi.load(), _abi
-
-    def layer_rc(self, kind, x, out, stage=0, block=0, iteration=0, epi=vl.CE_RES, acc=None, window=0, length=0, div=1.0):
-        info = (ctypes.c_int64 * 5)()
-        B, L = x.shape[0], x.shape[1]
-        rc = self.lib.bvc_test_vocoder_layer(self.eng.handle, kind, stage, block, iteration, self.abi.ptr(x), B, L, self.abi.ptr(out),
-                                             epi, self.abi.ptr(acc), window, 0, 0, length, div, info, self.eng.stream())
-        return rc, list(info)
-
-    def layer(self, *a, **k):
-        rc, info = self.layer_rc(*a, **k)
-        self.abi.check(rc)
-        return info
-
-    def planned_height(self, rows, B, ks):
-        out = (ctypes.c_int64 * 6)()
-        self.abi.check(self.lib.bvc_test_tile_plan(1, rows, B, ks, 0, out))
-        return int(out[0])
+def make_model(directory, tag, draw):
+    return gg.Model(directory, draw, tag, switches=None if tag == CAUSAL else vl.SYM_CONFIGS[tag], h_dim=H_DIM)
 
 
 @pytest.fixture(scope="module")
 def models(tmp_path_factory):
-    directory, cache = str(tmp_path_factory.mktemp("symmetric")), {}
-
-    def get(tag, draw="seed1235"):
-        if (tag, draw) not in cache:
-            cache[(tag, draw)] = Model(directory, tag, draw)
-        return cache[(tag, draw)]
-    yield get
-    for m in cache.values():
-        m.model.check_status()
+    """models(tag, draw): the product model of one of vl.SYM_CONFIGS (or the shipped switches) and one generator draw."""
+    directory = str(tmp_path_factory.mktemp("symmetric"))
+    get, close = gg.cached(lambda tag, draw: make_model(directory, tag, draw))
+    yield lambda tag, draw="seed1235": get(tag, draw)
+    close()
 
 
-def seed_of(*key):
-    return zlib.crc32(repr(key).encode())
-
-
-def to_dev(t):
-    return t.permute(0, 2, 1).contiguous().to(DEV)
-
-
-def nan_like(*shape):
-    return torch.full(shape, float("nan"), device=DEV)
+def check_fixture(mo, tag):
+    gg.check_fixture(mo, f"g11_bigvgan_sym_{tag}", tag, ("stage0", "stage1", "stage2", "stage3"), rms_bar=1e-4)
 
 
 # ----------------------------------------------------------------------------------------------- 1. symmetric AMP pairs
-def amp_case(mo, ledger, pair, B, L, kind, epi):
-    i, j, m, C, ks, d, pre = pair
-    TT = symo.sym_tile_rows(C, ks)
-    what = f"symmetric amp pair stage {i} block {j} iteration {m} (C={C} ks={ks} d={d}) epi={epi} B={B} L={L} input={kind}"
-    seed = seed_of(mo.draw, i, j, m, B, L, kind, epi)
-    x = vl.make_input(kind, B, C, L, TT, seed)
-    acc = vl.make_input("n1", B, C, L, TT, seed + 1) if epi >= vl.CE_RES_ACC else None
-
-    def oracle(dtype):
-        y = symo.amp_pair(mo.sd, pre, m, x, ks, d, dtype=dtype)
-        if epi >= vl.CE_RES_ACC:
-            y = acc.to(dtype) + y
-        if epi == vl.CE_RES_ACC_DIV:
-            y = y / 3
-        return vl.cl(y)
-    with torch.no_grad():
-        r64, r32 = oracle(torch.float64), oracle(torch.float32)
-    if acc is None:
-        out, acc_dev = nan_like(B, L, C), None
-    else:
-        out = to_dev(acc)                                            # the running sum IS the output buffer, as in the path
-        acc_dev = out
-    info = mo.layer(KIND_AMP, to_dev(x), out, i, j, m, epi, acc_dev)
-    tiles = B * -(-L // TT)
-    assert info == [L, C, tiles, (tiles + 7) // 8 * 8, TT], (what, info, "assumed tiles / rows per tile", tiles, TT)
-    ledger.add(f"amp{C}/symmetric", vl.compare(out.cpu().numpy(), r64, r32, what, tile_rows=TT))
-
-
 @pytest.mark.parametrize("stage", [0, 1, 2, 3])
 def test_symmetric_amp_pairs_against_float64(models, stage):
     """The nine (ks, d) pairs of the stage, each with one of the three epilogues (rotating, so that every (C, epilogue) occurs; the
@@ -129,11 +49,11 @@ def test_symmetric_amp_pairs_against_float64(models, stage):
     n = 0
     for q, pair in enumerate(p for p in vl.pairs(conf) if p[0] == stage):
         C, ks, d = pair[3:6]
-        TT = symo.sym_tile_rows(C, ks)
-        assert TT == symo.SYM_TILE_HEIGHT[C] - (ks - 1)
-        h = symo.reach(ks, d)
+        TT = vl.amp_tile_rows(C, ks, d, 10 ** 6, False, form="symmetric")[0]
+        assert TT == vl.SYM_TILE_HEIGHT[C] - (ks - 1)
+        h = vl.reach(ks, d)
         epi = (vl.CE_RES, vl.CE_RES_ACC, vl.CE_RES_ACC_DIV)[(q + stage) % 3]
-        for L in symo.amp_lengths(TT, ks, d):
+        for L in vl.sym_amp_lengths(TT, ks, d):
             n += 1
             draw = vl.DRAWS[n % 4]
             amp_case(models("all", draw), ledgers[draw], pair, 2 + (n // 4) % 2, L, "n6", epi)
@@ -147,12 +67,7 @@ def test_symmetric_amp_pairs_against_float64(models, stage):
 
 
 def test_every_channel_count_meets_every_epilogue(models):
-    conf = models("all").conf
-    seen = set()
-    for stage in range(4):
-        for q, pair in enumerate(p for p in vl.pairs(conf) if p[0] == stage):
-            seen.add((pair[3], (q + stage) % 3))
-    assert seen == {(C, e) for C in vl.CHANNELS for e in range(3)}
+    gg.every_channel_count_meets_every_epilogue(models("all").conf)
 
 
 # ----------------------------------------------------------------------------------------------- 2. conv_pre, upsamplers, conv_post
@@ -170,7 +85,7 @@ def test_symmetric_conv_pre_against_float64(models, draw):
         out = nan_like(B, L, 128)
         assert mo.layer(KIND_PRE, to_dev(x), out)[:2] == [L, 128]
         with torch.no_grad():
-            r64, r32 = vl.cl(symo.conv_pre(mo.sd, x, torch.float64)), vl.cl(symo.conv_pre(mo.sd, x, torch.float32))
+            r64, r32 = vl.cl(obig.conv_pre(mo.sd, x, torch.float64, sym=True)), vl.cl(obig.conv_pre(mo.sd, x, torch.float32, sym=True))
         ledger.add("conv_pre/symmetric", vl.compare(out.cpu().numpy(), r64, r32, f"symmetric conv_pre B={B} L={L}", tile_rows=tile))
     ledger.close()
 
@@ -190,7 +105,7 @@ def test_symmetric_upsamplers_against_float64(models, stage):
         out = nan_like(B, L * rate, cin // 2)
         assert mo.layer(KIND_UP, to_dev(x), out, stage)[:2] == [L * rate, cin // 2]
         with torch.no_grad():
-            r64, r32 = vl.cl(symo.upsample(mo.sd, v, stage, x, torch.float64)), vl.cl(symo.upsample(mo.sd, v, stage, x, torch.float32))
+            r64, r32 = vl.cl(obig.upsample(mo.sd, v, stage, x, torch.float64, sym=True)), vl.cl(obig.upsample(mo.sd, v, stage, x, torch.float32, sym=True))
         assert r64.shape == (B, L * rate, cin // 2)
         ledgers[draw].add(f"upsample{cin}/symmetric", vl.compare(out.cpu().numpy(), r64, r32, f"symmetric upsampler {stage} B={B} L={L}",
                                                                   tile_rows=tile * rate))
@@ -201,58 +116,12 @@ def test_symmetric_upsamplers_against_float64(models, stage):
 @pytest.mark.parametrize("draw", vl.DRAWS)
 def test_symmetric_conv_post_against_float64(models, draw):
     mo, ledger = models("all", draw), vl.Ledger(draw)
-    n = 0
-    for L in (1, 3, 4, 255, 256, 257, 600):
-        for length in sorted({L, max(1, L - 3), 10 ** 9}):
-            for kind in (("n6",) if L not in (4, 257) else ("n6", "row_first", "row_last", "row_tile2", "zeros")):
-                n += 1
-                B, div = 2 + n % 2, (1.0, 0.95)[n % 2]
-                x = vl.make_input(kind, B, 8, L, vl.POST_TILE_ROWS, seed_of(draw, "post", L, length, kind))
-                rows = min(L, length)
-                out = nan_like(B, rows)
-                info = mo.layer(KIND_POST, to_dev(x), out, length=length, div=div)
-                assert info[:2] == [rows, 1]
-                with torch.no_grad():
-                    r64 = symo.conv_post(mo.sd, x, length, torch.float64)[:, 0].numpy() / np.float64(np.float32(div))
-                    r32 = (symo.conv_post(mo.sd, x, length, torch.float32)[:, 0].numpy() / np.float32(div)).astype(np.float64)
-                ledger.add("conv_post/symmetric", vl.compare(out.cpu().numpy(), r64, r32,
-                                                             f"symmetric conv_post B={B} L={L} length={length} div={div} input={kind}",
-                                                             tile_rows=vl.POST_TILE_ROWS))
+    gg.conv_post_sweep(mo, ledger, "symmetric", (1, 3, 4, 255, 256, 257, 600), (4, 257), ("n6", "row_first", "row_last", "row_tile2", "zeros"))
     ledger.close()
 
 
 # ----------------------------------------------------------------------------------------------- 3. the reference's run
-def stage_tap(mo, mel_tm, i):
-    B, T = mel_tm.shape[0], mel_tm.shape[1]
-    ws, nws = mo.eng.workspace(B, T)
-    n = ctypes.c_int64()
-    mo.abi.check(mo.lib.bvc_test_vocoder_tap(mo.eng.handle, mo.abi.ptr(mel_tm), B, T, 2 + 2 * i, None, ctypes.byref(n), ws, nws, mo.eng.stream()))
-    out = nan_like(B, n.value)
-    mo.abi.check(mo.lib.bvc_test_vocoder_tap(mo.eng.handle, mo.abi.ptr(mel_tm), B, T, 2 + 2 * i, mo.abi.ptr(out), ctypes.byref(n), ws, nws,
-                                             mo.eng.stream()))
-    torch.cuda.synchronize()
-    return out
-
-
-def check_fixture(mo, tag):
-    g = load_golden(f"g11_bigvgan_sym_{tag}")
-    mel = torch.from_numpy(g["mel"]).to(DEV)
-    wav = mo.model.vocoder(mel, 10 ** 9).cpu().numpy()
-    assert wav.shape == g["wav"].shape
-    rms = float(np.sqrt(((wav - g["wav"]) ** 2).mean()))
-    print(f"FIXTURE {tag}: waveform rms error {rms:.3e} max {np.abs(wav - g['wav']).max():.3e}")
-    assert rms <= 1e-4
-    mel_tm = mel.permute(0, 2, 1).contiguous()
-    for i in range(4):
-        ref = g[f"stage{i}"]
-        got = stage_tap(mo, mel_tm, i).cpu().numpy().reshape(ref.shape[0], -1, ref.shape[1]).transpose(0, 2, 1)
-        assert got.shape == ref.shape
-        err, scale = float(np.abs(got - ref).max()), max(1.0, float(np.abs(ref).max()))
-        print(f"FIXTURE {tag}: stage{i} max error {err:.3e} (scale {scale:.3f})")
-        assert err <= 2e-5 * scale, (tag, i, err, scale)
-
-
-@pytest.mark.parametrize("tag", sorted(symo.CONFIGS))
+@pytest.mark.parametrize("tag", sorted(vl.SYM_CONFIGS))
 def test_reference_fixture_through_forward_and_decode(models, tag):
     """BigVGAN.forward against the reference's waveform (rms <= 1e-4) and stage taps (<= 2e-5), the bars test_gpu_parity.py has for
     g5.  The fixture starts at the mel, so the facade's decode is held against forward on the mel its own coder decodes, with the
@@ -264,7 +133,7 @@ def test_reference_fixture_through_forward_and_decode(models, tag):
     rng = np.random.default_rng(3)
     codes = torch.from_numpy(rng.integers(0, 2, size=(2, 12, 64)).astype(np.float32)).to(DEV)
     n = min(3000, config.generator_length(mo.conf, 12))
-    assert mo.eng.vocoder_length(12) == config.generator_length(mo.conf, 12) == symo.sym_lengths(mo.conf["vocoder_config"], 12)[-1]
+    assert mo.eng.vocoder_length(12) == config.generator_length(mo.conf, 12) == vl.sym_lengths(mo.conf["vocoder_config"], 12)[-1]
     wav = mo.model.decode(codes, 3000)
     mel, _ = mo.model.bvrnn.decode(codes, torch.zeros(1, 2, H_DIM, device=DEV))
     ref = mo.model.vocoder(mel, 3000, _scale_div=float(SCALING), _time_major=True)[:, 0]
@@ -320,7 +189,7 @@ def refusals(mo, word):
     assert mo.lib.bvc_vocoder_stream_create(mo.eng.handle, 2, 4, ctypes.byref(h)) == -1 and w in mo.lib.bvc_last_error()
     assert mo.lib.bvc_stream_codec_create(mo.eng.handle, 2, 441, 35.0, 0.95, 0.95, ctypes.byref(h)) == -1 and w in mo.lib.bvc_last_error()
     x = torch.zeros(2, 40, 64, device=DEV)
-    rc, _ = mo.layer_rc(KIND_AMP, x, torch.empty_like(x), 0, 0, 0, window=1)
+    rc, _ = mo.layer_rc(KIND_AMP, x, torch.empty_like(x), 0, 0, 0, window=(0, 0))
     assert rc == -1 and w in mo.lib.bvc_last_error()
     ws, nws = mo.eng.workspace(2, 12)
     frames = torch.tensor([12, 7], device=DEV)
@@ -352,7 +221,7 @@ def test_an_unfused_library_refuses_a_symmetric_stage(tmp_path, monkeypatch):
     from bvcodec import _abi
     monkeypatch.setenv("BVC_UNFUSED_AMP", "1")
     with pytest.raises(_abi.BvcError, match="symmetric stages run in the fused AMP kernels only"):
-        Model(str(tmp_path), "mixed", "seed1235")
+        make_model(str(tmp_path), "mixed", "seed1235")
 
 
 # ----------------------------------------------------------------------------------------------- 6. causal tile cuts
@@ -367,7 +236,7 @@ def test_a_causal_model_keeps_its_tile_cuts(models):
         pair = next(p for p in vl.pairs(mo.conf) if p[0] == stage and p[4] == 7 and p[5] == 3)
         i, j, m, C, ks, d, pre = pair
         B, L = 3, 700
-        TT, family = vl.amp_tile_rows(C, ks, d, L, False, height64=mo.planned_height(L, B, ks))
+        TT, family = vl.amp_tile_rows(C, ks, d, L, False, height=mo.planned_height(L, B, ks))
         families.append(family.split("/")[1] if C in (16, 8) else family)
         x = vl.make_input("n6", B, C, L, TT, seed_of("causal", stage))
         out = nan_like(B, L, C)

@@ -7,154 +7,34 @@ way; the whole chain at sizes with seams.  Every element, maximum norm: e_hip = 
 measured ratios in profiles/vocoder_layer_parity.md).  Every AMP case also asserts that the launch was cut into the tiles this file
 assumes.  Needs the MI355X: run with ``-m gpu``."""
 import contextlib
-import ctypes
-import os
-import zlib
 
 import numpy as np
 import pytest
 import torch
 
+import gpu_generator as gg
 import vocoder_layers as vl
+from gpu_generator import KIND_POST, KIND_PRE, KIND_UP, amp_case, nan_like, seed_of, to_dev
 from oracle import bigvgan as obig
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-SWITCHES = ("BVC_TILE_CUT", "BVC_AMP64_TR")
-KIND_PRE, KIND_UP, KIND_AMP, KIND_POST = 0, 1, 2, 3
-
-
-@contextlib.contextmanager
-def switches(**env):
-    old = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k in SWITCHES:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
-
-
-class Draw:
-    """One weight draw: the product model on the GPU (checkpoints written into a temporary directory) and its state dict."""
-
-    def __init__(self, conf, name, directory):
-        from bvcodec import BVRNNCodecModel, _abi, config, synth
-        self.name, self.conf, self.sd = name, conf, vl.generator_draw(conf, name)
-        p1 = os.path.join(directory, "bvrnn")
-        if not os.path.exists(p1):
-            torch.save({"vrnn": synth.bvrnn_state_dict(conf, 1234)}, p1)
-        p2 = os.path.join(directory, f"bigvgan_{name}")
-        torch.save({"generator": self.sd}, p2)
-        self.model = BVRNNCodecModel(config.DEFAULT_CONFIG, p1, p2).to(DEV)
-        self.eng = self.model.engine(torch.empty(0, device=DEV))
-        self.lib, self.abi = _abi.load(), _abi
-
-    def layer(self, kind, x, out, stage=0, block=0, iteration=0, epi=vl.CE_RES, acc=None, window=None, length=0, div=1.0):
-        """x (B, L, Cin), out: device tensors, channels-last.  Returns out_info."""
-        info = (ctypes.c_int64 * 5)()
-        rb, t0 = window if window else (0, 0)
-        B, L = x.shape[0], x.shape[1]
-        self.abi.check(self.lib.bvc_test_vocoder_layer(self.eng.handle, kind, stage, block, iteration, self.abi.ptr(x), B, L, self.abi.ptr(out),
-                                                       epi, self.abi.ptr(acc), 1 if window else 0, rb, t0, length, div, info, self.eng.stream()))
-        return list(info)
-
-    def planned_height(self, rows, B, ks):
-        out = (ctypes.c_int64 * 6)()
-        self.abi.check(self.lib.bvc_test_tile_plan(1, rows, B, ks, 0, out))
-        return int(out[0])
+DEV = gg.DEV
 
 
 @pytest.fixture(scope="module")
-def draws(conf_var, tmp_path_factory):
-    directory, cache = str(tmp_path_factory.mktemp("vocoder_layers")), {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = Draw(conf_var, name, directory)
-        return cache[name]
+def draws(tmp_path_factory):
+    """draws(name): the shipped model with the generator of one weight draw."""
+    directory = str(tmp_path_factory.mktemp("vocoder_layers"))
+    get, close = gg.cached(lambda name: gg.Model(directory, name))
     yield get
-    for d in cache.values():
-        d.model.check_status()
-
-
-def seed_of(*key):
-    return zlib.crc32(repr(key).encode())
-
-
-def to_dev(t):
-    """(B, C, L) CPU tensor -> contiguous channels-last device tensor (B, L, C)."""
-    return t.permute(0, 2, 1).contiguous().to(DEV)
-
-
-def nan_like(shape):
-    return torch.full(shape, float("nan"), device=DEV)
+    close()
 
 
 # ---------------------------------------------------------------------------------------------- one AMP pair
-def amp_case(dr, ledger, pair, B, L, kind, epi, variant, window=None):
-    """variant: dict(height64=int or 'plan', c8=bool, c16=bool) - the engine's options are set by the caller; height64 is forced here.
-    window: None, or (mode, row_begin, t_origin) with mode 'start' (history all zero, t_origin = -row_begin) or 'mid' (the buffer is
-    cut out of a longer signal).  L counts the buffer's rows (history included)."""
-    i, j, m, C, ks, d, pre = pair
-    rb = window[1] if window else 0
-    new_rows = L - rb
-    h64 = variant.get("height64", "plan")
-    height = dr.planned_height(new_rows, B, ks) if h64 == "plan" else h64
-    TT, family = vl.amp_tile_rows(C, ks, d, new_rows, window is not None, height64=height, c8=variant.get("c8", True), c16=variant.get("c16", True))
-    if C == 64 and not window and h64 == "plan":
-        family = "amp64/plan"
-    what = (f"amp pair stage {i} block {j} iteration {m} (C={C} ks={ks} d={d}) epi={epi} B={B} L={L} input={kind} variant={family}"
-            + (f" window={window}" if window else ""))
-    seed = seed_of(dr.name, i, j, m, B, L, kind, epi, family, window)
-    if window and window[0] == "mid":
-        t0 = window[2]
-        x_full = vl.make_input(kind, B, C, t0 + L, t0 + rb + TT, seed)
-        buf, x_ref, lo = x_full[:, :, t0:], x_full, t0 + rb
-    elif window:
-        t0 = -rb
-        x_new = vl.make_input(kind, B, C, new_rows, TT, seed)
-        buf, x_ref, lo = torch.cat([torch.zeros(B, C, rb), x_new], 2), x_new, 0
-    else:
-        t0 = 0
-        buf = x_ref = vl.make_input(kind, B, C, L, TT, seed)
-        lo = 0
-    acc = acc_ref = None
-    if epi >= vl.CE_RES_ACC:
-        acc = vl.make_input("n1", B, C, L, TT, seed + 1)
-        acc_ref = torch.zeros_like(x_ref)
-        acc_ref[:, :, lo:] = acc[:, :, rb:]
-    with torch.no_grad():
-        r64 = vl.cl(vl.oracle_pair(dr.sd, pair, x_ref, torch.float64, epi, acc_ref))[:, lo:]
-        r32 = vl.cl(vl.oracle_pair(dr.sd, pair, x_ref, torch.float32, epi, acc_ref))[:, lo:]
-    x_dev = to_dev(buf)
-    if acc is None:
-        out, acc_dev, before = nan_like((B, L, C)), None, None
-    else:
-        out = to_dev(acc)                                            # the running sum IS the output buffer, as in run_vocoder (w.XS)
-        acc_dev, before = out, out.clone()
-    env = {"BVC_AMP64_TR": str(h64)} if (C == 64 and h64 != "plan") else {}
-    with switches(**env):
-        info = dr.layer(KIND_AMP, x_dev, out, i, j, m, epi, acc_dev, (rb, t0) if window else None)
-    tiles = B * -(-new_rows // TT)
-    assert info[:2] == [L, C] and info[2] == tiles and info[4] == TT, (what, info, "assumed tiles / rows per tile", tiles, TT)
-    if "persistent" not in family and "full" not in family:
-        assert info[3] == (tiles + 7) // 8 * 8, (what, info)
-    got = out.cpu().numpy()
-    if rb:                                                           # history rows are nobody's to write
-        hist = got[:, :rb]
-        assert np.isnan(hist).all() if before is None else np.array_equal(hist, before.cpu().numpy()[:, :rb]), what + ": history rows written"
-    v = vl.compare(got[:, rb:], r64, r32, what, tile_rows=TT)
-    ledger.add(family, v)
-    return info
-
-
 def amp_variants(C):
     if C == 64:
-        return [dict(height64=h) for h in vl.AMP64_HEIGHTS] + [dict(height64="plan")]
+        return [dict(height=h) for h in vl.AMP_HEIGHTS[64]] + [dict()]             # each compiled height forced, and the planned one
     if C == 16:
         return [dict(c16=True), dict(c16=False)]
     if C == 8:
@@ -183,21 +63,19 @@ def test_amp_pairs_offline_against_float64(draws, conf_var, draw, stage):
     for pair in [p for p in vl.pairs(conf_var) if p[0] == stage]:
         C, ks, d = pair[3:6]
         for variant in amp_variants(C):
-            h64 = variant.get("height64", "plan")
-            TT = vl.amp_tile_rows(C, ks, d, 10 ** 6, False, height64=128 if h64 == "plan" else h64, c8=variant.get("c8", True),
-                                  c16=variant.get("c16", True))[0]
+            TT = vl.amp_tile_rows(C, ks, d, 10 ** 6, False, **variant)[0]
             with options(dr, variant):
                 for L in vl.lengths(TT, ks, d):
                     n += 1
-                    amp_case(dr, ledger, pair, vl.BATCHES[n % 4], L, "n1", vl.CE_RES, variant)
+                    amp_case(dr, ledger, pair, vl.BATCHES[n % 4], L, "n1", vl.CE_RES, **variant)
                 for kind in vl.INPUTS[1:]:
                     for L in (TT, 2 * TT + 1, 3 * TT + 17):
                         n += 1
-                        amp_case(dr, ledger, pair, vl.BATCHES[n % 4], L, kind, vl.CE_RES, variant)
+                        amp_case(dr, ledger, pair, vl.BATCHES[n % 4], L, kind, vl.CE_RES, **variant)
                 for epi in (vl.CE_RES_ACC, vl.CE_RES_ACC_DIV):
                     for L in (TT, 2 * TT + 1):
                         n += 1
-                        amp_case(dr, ledger, pair, vl.BATCHES[n % 4], L, "n1", epi, variant)
+                        amp_case(dr, ledger, pair, vl.BATCHES[n % 4], L, "n1", epi, **variant)
     ledger.close()
 
 
@@ -218,12 +96,12 @@ def test_amp_pairs_in_streaming_windows_against_float64(draws, conf_var, draw, s
                     for window in (("start", 64, -64), ("mid", 64, 0), ("mid", 64, 37), ("mid", deep, 5)):
                         n += 1
                         kind = ("n1", "n6", "row_first", "n1", "zeros", "row_tile2", "n1", "row_last")[n % 8]
-                        amp_case(dr, ledger, pair, vl.BATCHES[n % 4], window[1] + new, kind, vl.CE_RES, variant, window)
+                        amp_case(dr, ledger, pair, vl.BATCHES[n % 4], window[1] + new, kind, vl.CE_RES, window, **variant)
                 for new in (8, 400):
                     for epi in (vl.CE_RES_ACC, vl.CE_RES_ACC_DIV):
                         for window in (("start", 64, -64), ("mid", 64, 37)):
                             n += 1
-                            amp_case(dr, ledger, pair, vl.BATCHES[n % 4], 64 + new, "n1", epi, variant, window)
+                            amp_case(dr, ledger, pair, vl.BATCHES[n % 4], 64 + new, "n1", epi, window, **variant)
     ledger.close()
 
 
@@ -235,7 +113,7 @@ def test_persistent_kernels_walk_over_several_tiles_per_workgroup(draws, conf_va
     dr, ledger = draws("seed1235"), vl.Ledger("seed1235")
     pair = next(p for p in vl.pairs(conf_var) if p[0] == stage and p[1] == ks_index and p[2] == ks_index)
     B, L = (48, 12000) if stage == 2 else (64, 16000)         # (the C = 8 kernel fits four workgroups per CU: 1,024 of them)
-    info = amp_case(dr, ledger, pair, B, L, "n1", vl.CE_RES_ACC_DIV, dict())
+    info = amp_case(dr, ledger, pair, B, L, "n1", vl.CE_RES_ACC_DIV)
     print(f"persistent C={pair[3]} ks={pair[4]} d={pair[5]}: {info[2]} tiles on {info[3]} workgroups", flush=True)
     assert info[3] > 0 and info[2] >= 3 * info[3], info
     ledger.close()
@@ -260,7 +138,7 @@ def test_conv_pre_upsamplers_conv_post_against_float64(draws, conf_var, draw):
             n += 1
             B = vl.BATCHES[n % 4]
             x = vl.make_input(kind, B, 80, L, TT, seed_of(draw, "pre", L, kind))
-            out = nan_like((B, L, 128))
+            out = nan_like(B, L, 128)
             info = dr.layer(KIND_PRE, to_dev(x), out)
             assert info[:2] == [L, 128]
             ledger.add("conv_pre", vl.compare(out.cpu().numpy(), vl.cl(obig.conv_pre(dr.sd, x, torch.float64)), vl.cl(obig.conv_pre(dr.sd, x, torch.float32)),
@@ -275,7 +153,7 @@ def test_conv_pre_upsamplers_conv_post_against_float64(draws, conf_var, draw):
                 n += 1
                 B = vl.BATCHES[n % 4]
                 x = vl.make_input(kind, B, cin, L, TT - 1, seed_of(draw, "up", i, L, kind))
-                out = nan_like((B, rows * rate, cin // 2))
+                out = nan_like(B, rows * rate, cin // 2)
                 info = dr.layer(KIND_UP, to_dev(x), out, stage=i)
                 assert info[:2] == [rows * rate, cin // 2]
                 ledger.add(f"up{i}", vl.compare(out.cpu().numpy(), vl.cl(obig.upsample(dr.sd, vcfg, i, x, torch.float64)),
@@ -288,7 +166,7 @@ def test_conv_pre_upsamplers_conv_post_against_float64(draws, conf_var, draw):
                 B = vl.BATCHES[n % 4]
                 x = vl.make_input(kind, B, 8, L, TT, seed_of(draw, "post", L, kind))
                 n_out = min(length, L)
-                out = nan_like((B, n_out))
+                out = nan_like(B, n_out)
                 info = dr.layer(KIND_POST, to_dev(x), out, length=length, div=div)
                 assert info[:2] == [n_out, 1]
                 r64 = obig.conv_post(dr.sd, x, length, torch.float64)[:, 0].numpy() / np.float64(np.float32(div))
@@ -312,15 +190,8 @@ def test_whole_chain_taps_and_waveform_against_float64(draws, conf_var, draw, B,
     w64 = obig.forward(dr.sd, vcfg, mel, 10 ** 9, dtype=torch.float64, taps=t64)
     w32 = obig.forward(dr.sd, vcfg, mel, 10 ** 9, dtype=torch.float32, taps=t32)
     mel_cl = to_dev(mel)
-    ws, nws = dr.eng.workspace(B, T)
-    names = ["conv_pre"] + [f"{k}{i}" for i in range(4) for k in ("up", "stage")]
-    for which, nm in enumerate(names):
-        n = ctypes.c_int64()
-        dr.abi.check(dr.lib.bvc_test_vocoder_tap(dr.eng.handle, dr.abi.ptr(mel_cl), B, T, which, None, ctypes.byref(n), ws, nws, dr.eng.stream()))
-        out = nan_like((B, n.value))
-        dr.abi.check(dr.lib.bvc_test_vocoder_tap(dr.eng.handle, dr.abi.ptr(mel_cl), B, T, which, dr.abi.ptr(out), ctypes.byref(n), ws, nws,
-                                                 dr.eng.stream()))
-        torch.cuda.synchronize()
+    for which, nm in enumerate(gg.TAPS):
+        out = dr.tap(mel_cl, which)
         r64 = vl.cl(t64[nm])
         ledger.add(f"chain/{nm}", vl.compare(out.cpu().numpy().reshape(r64.shape), r64, vl.cl(t32[nm]), f"chain tap {nm} B={B} T={T}"))
     wav = dr.model.vocoder(mel.to(DEV), 10 ** 9)

@@ -3,29 +3,21 @@ at a time against the float64 oracle, offline and in streaming windows, with the
 max|hip - oracle64| <= 8 x max(e32, 2^-24 max|oracle64|); conv_pre, the upsamplers out of 512 / 256 / 128 / 64 channels and conv_post
 from 16 / 32 channels the same way; the reference's own run (tests/golden/g12_bigvgan_wide_*.npz); the whole chain with seams; the
 facade, mixed-length batches and the streaming classes with the assertions the shipped width is held to; and what stays refused.
-Every AMP case also asserts that the launch was cut into the tiles tests/wide_generator.py restates.  Measured ratios:
+Every AMP case also asserts that the launch was cut into the tiles tests/vocoder_layers.py restates.  Measured ratios:
 profiles/wide_generator_parity.md.  Needs the MI355X: run with ``-m gpu``."""
-import contextlib
 import ctypes
-import os
-import zlib
 
 import numpy as np
 import pytest
 import torch
 
-import symmetric_oracle as symo
+import gpu_generator as gg
 import vocoder_layers as vl
-import wide_generator as wg
-from conftest import load_golden
+from gpu_generator import DEV, H_DIM, KIND_AMP, KIND_POST, KIND_PRE, KIND_UP, amp_case, nan_like, seed_of, to_dev
 from oracle import bigvgan as obig
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-KIND_PRE, KIND_UP, KIND_AMP, KIND_POST = 0, 1, 2, 3
-H_DIM = 64                                   # a small coder: these tests are about the generator
-SWITCHES = ("BVC_AMP256_TR", "BVC_AMP128_TR")
 WIDE_STAGES = ((256, 0), (512, 0), (512, 1))                 # (width, stage): C = 128, 256, 128
 T_, F_ = True, False
 # symmetric and filtered narrow stages (C <= 64) behind the causal wide ones, per width
@@ -33,139 +25,20 @@ MIXED = {256: dict(layers_sym=[F_, T_, F_, T_], layers_antialias=[F_, F_, T_, F_
          512: dict(layers_sym=[F_, F_, T_, F_], layers_antialias=[F_, F_, F_, T_], antialias_post=True)}
 
 
-@contextlib.contextmanager
-def switches(**env):
-    old = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k in SWITCHES:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
-
-
-class Model:
-    """The product model of one width, one set of switches and one generator draw on the GPU."""
-
-    def __init__(self, directory, width, draw="seed1235", tag="causal", h_dim=H_DIM):
-        from bvcodec import BVRNNCodecModel, _abi, synth
-        self.width, self.draw, self.tag = width, draw, tag
-        cfg = os.path.join(directory, f"wide{width}_{tag}_{h_dim}.toml")
-        self.conf = wg.write_config(cfg, width, h_dim=h_dim, switches=None if tag == "causal" else MIXED[width])
-        self.sd = vl.generator_draw(self.conf, draw)
-        self.vr = synth.bvrnn_state_dict(self.conf, 1234)
-        p1, p2 = os.path.join(directory, f"bvrnn_{h_dim}"), os.path.join(directory, f"bigvgan_{width}_{tag}_{draw}")
-        torch.save({"vrnn": self.vr}, p1)
-        torch.save({"generator": self.sd}, p2)
-        self.model = BVRNNCodecModel(cfg, p1, p2).to(DEV)
-        self.eng = self.model.engine(torch.empty(0, device=DEV))
-        self.lib, self.abi = _abi.load(), _abi
-
-    def layer_rc(self, kind, x, out, stage=0, block=0, iteration=0, epi=vl.CE_RES, acc=None, window=None, length=0, div=1.0):
-        """x (B, L, Cin), out: device tensors, channels-last; window: None or (row_begin, t_origin).  Returns (rc, out_info)."""
-        info = (ctypes.c_int64 * 5)()
-        rb, t0 = window if window else (0, 0)
-        B, L = x.shape[0], x.shape[1]
-        rc = self.lib.bvc_test_vocoder_layer(self.eng.handle, kind, stage, block, iteration, self.abi.ptr(x), B, L, self.abi.ptr(out),
-                                             epi, self.abi.ptr(acc), 1 if window else 0, rb, t0, length, div, info, self.eng.stream())
-        return rc, list(info)
-
-    def layer(self, *a, **k):
-        rc, info = self.layer_rc(*a, **k)
-        self.abi.check(rc)
-        return info
-
-    def tap(self, mel_tm, which):
-        B, T = mel_tm.shape[0], mel_tm.shape[1]
-        ws, nws = self.eng.workspace(B, T)
-        n = ctypes.c_int64()
-        self.abi.check(self.lib.bvc_test_vocoder_tap(self.eng.handle, self.abi.ptr(mel_tm), B, T, which, None, ctypes.byref(n), ws, nws, self.eng.stream()))
-        out = nan_like(B, n.value)
-        self.abi.check(self.lib.bvc_test_vocoder_tap(self.eng.handle, self.abi.ptr(mel_tm), B, T, which, self.abi.ptr(out), ctypes.byref(n), ws, nws,
-                                                     self.eng.stream()))
-        torch.cuda.synchronize()
-        return out
+def make_model(directory, width, draw="seed1235", tag="causal", h_dim=H_DIM):
+    return gg.Model(directory, draw, f"wide{width}_{tag}_{h_dim}", width=width, switches=None if tag == "causal" else MIXED[width], h_dim=h_dim)
 
 
 @pytest.fixture(scope="module")
 def models(tmp_path_factory):
-    directory, cache = str(tmp_path_factory.mktemp("wide_generator")), {}
-
-    def get(width, draw="seed1235", tag="causal", h_dim=H_DIM):
-        key = (width, draw, tag, h_dim)
-        if key not in cache:
-            cache[key] = Model(directory, *key)
-        return cache[key]
-    yield get
-    for m in cache.values():
-        m.model.check_status()
-
-
-def seed_of(*key):
-    return zlib.crc32(repr(key).encode())
-
-
-def to_dev(t):
-    """(B, C, L) CPU tensor -> contiguous channels-last device tensor (B, L, C)."""
-    return t.permute(0, 2, 1).contiguous().to(DEV)
-
-
-def nan_like(*shape):
-    return torch.full(shape, float("nan"), device=DEV)
+    """models(width, draw, tag, h_dim): the product model of one width, one set of switches and one generator draw."""
+    directory = str(tmp_path_factory.mktemp("wide_generator"))
+    get, close = gg.cached(lambda *key: make_model(directory, *key))
+    yield lambda width, draw="seed1235", tag="causal", h_dim=H_DIM: get(width, draw, tag, h_dim)
+    close()
 
 
 # ----------------------------------------------------------------------------------------------- 1, 2. one AMP pair of a wide stage
-def amp_case(mo, ledger, pair, B, L, kind, epi, window=None, height=None):
-    """window: None, or (mode, row_begin, t_origin) with mode 'start' (history all zero, t_origin = -row_begin: global time 0 is the
-    first new row, inside the tile conv1 sweeps, and the S2 rows before it are zero) or 'mid' (the buffer is cut out of a longer
-    signal).  L counts the buffer's rows (history included).  height: a compiled tile height to force, or None for the default."""
-    i, j, m, C, ks, d, pre = pair
-    rb = window[1] if window else 0
-    new_rows = L - rb
-    TT, family = wg.amp_tile_rows(C, ks, d, new_rows, window is not None, height=height)
-    what = (f"amp pair width {mo.width} stage {i} block {j} iteration {m} (C={C} ks={ks} d={d}) epi={epi} B={B} L={L} input={kind} "
-            f"variant={family}" + (f" window={window}" if window else ""))
-    seed = seed_of(mo.draw, mo.width, i, j, m, B, L, kind, epi, family, window)
-    if window and window[0] == "mid":
-        t0 = window[2]
-        x_full = vl.make_input(kind, B, C, t0 + L, t0 + rb + TT, seed)
-        buf, x_ref, lo = x_full[:, :, t0:], x_full, t0 + rb
-    elif window:
-        t0 = -rb
-        x_new = vl.make_input(kind, B, C, new_rows, TT, seed)
-        buf, x_ref, lo = torch.cat([torch.zeros(B, C, rb), x_new], 2), x_new, 0
-    else:
-        t0 = 0
-        buf = x_ref = vl.make_input(kind, B, C, L, TT, seed)
-        lo = 0
-    acc = acc_ref = None
-    if epi >= vl.CE_RES_ACC:
-        acc = vl.make_input("n1", B, C, L, TT, seed + 1)
-        acc_ref = torch.zeros_like(x_ref)
-        acc_ref[:, :, lo:] = acc[:, :, rb:]
-    with torch.no_grad():
-        r64 = vl.cl(vl.oracle_pair(mo.sd, pair, x_ref, torch.float64, epi, acc_ref))[:, lo:]
-        r32 = vl.cl(vl.oracle_pair(mo.sd, pair, x_ref, torch.float32, epi, acc_ref))[:, lo:]
-    x_dev = to_dev(buf)
-    if acc is None:
-        out, acc_dev, before = nan_like(B, L, C), None, None
-    else:
-        out = to_dev(acc)                                            # the running sum IS the output buffer, as in run_vocoder (w.XS)
-        acc_dev, before = out, out.clone()
-    env = {f"BVC_AMP{C}_TR": str(height)} if height is not None else {}
-    with switches(**env):
-        info = mo.layer(KIND_AMP, x_dev, out, i, j, m, epi, acc_dev, (rb, t0) if window else None)
-    tiles = B * -(-new_rows // TT)
-    assert info == [L, C, tiles, (tiles + 7) // 8 * 8, TT], (what, info, "assumed tiles / rows per tile", tiles, TT)
-    got = out.cpu().numpy()
-    if rb:                                                           # history rows are nobody's to write
-        hist = got[:, :rb]
-        assert np.isnan(hist).all() if before is None else np.array_equal(hist, before.cpu().numpy()[:, :rb]), what + ": history rows written"
-    ledger.add(family, vl.compare(got[:, rb:], r64, r32, what, tile_rows=TT))
-
-
 def wide_pairs(mo, stage, block):
     return [p for p in vl.pairs(mo.conf) if p[0] == stage and p[1] == block]
 
@@ -182,9 +55,9 @@ def test_wide_amp_pairs_offline_against_float64(models, width, stage, draw, bloc
     mo, ledger = models(width, draw), vl.Ledger(draw)
     for pair in wide_pairs(mo, stage, block):
         C, ks, d = pair[3:6]
-        assert C in wg.WIDE_CHANNELS
-        TT = wg.amp_tile_rows(C, ks, d, 10 ** 6, False)[0]
-        assert TT == wg.AMP_HEIGHT[C] - (ks - 1)
+        assert C in vl.WIDE_CHANNELS
+        TT = vl.amp_tile_rows(C, ks, d, 10 ** 6, False)[0]
+        assert TT == vl.AMP_HEIGHT[C] - (ks - 1)
         for L in vl.lengths(TT, ks, d):
             amp_case(mo, ledger, pair, 3, L, "n1", vl.CE_RES)
         for B in (2, 5, 9):
@@ -194,7 +67,7 @@ def test_wide_amp_pairs_offline_against_float64(models, width, stage, draw, bloc
         for epi in (vl.CE_RES_ACC, vl.CE_RES_ACC_DIV):
             for L in (TT, 2 * TT + 1):
                 amp_case(mo, ledger, pair, 3, L, "n1", epi)
-        other = wg.AMP_HEIGHTS[C][1]
+        other = vl.AMP_HEIGHTS[C][1]
         for n, L in enumerate((other - (ks - 1), other - (ks - 1) + 1, 2 * (other - (ks - 1)) + 1)):
             amp_case(mo, ledger, pair, (3, 5, 2)[n], L, "n6", (vl.CE_RES, vl.CE_RES_ACC, vl.CE_RES_ACC_DIV)[n], height=other)
     ledger.close()
@@ -210,14 +83,14 @@ def test_wide_amp_pairs_in_streaming_windows_against_float64(models, width, stag
     for pair in [p for p in vl.pairs(mo.conf) if p[0] == stage]:
         C, ks, d = pair[3:6]
         families = set()
-        for new in wg.window_new_rows(ks):
+        for new in vl.wide_window_new_rows(ks):
             for window in (("start", 64, -64), ("mid", 64, 0), ("mid", 64, 37)):
                 n += 1
                 kind = ("n1", "n6", "row_first", "n1", "zeros", "row_tile2", "n1", "row_last")[n % 8]
                 epi = (vl.CE_RES, vl.CE_RES, vl.CE_RES_ACC, vl.CE_RES_ACC_DIV)[(n // 3) % 4]
                 amp_case(mo, ledger, pair, vl.BATCHES[n % 4], 64 + new, kind, epi, window)
-            families.add(wg.amp_tile_rows(C, ks, d, new, True)[1])
-        assert families == {f"amp{C}/window32", f"amp{C}/{wg.AMP_HEIGHT[C]}/window"}, families
+            families.add(vl.amp_tile_rows(C, ks, d, new, True)[1])
+        assert families == {f"amp{C}/window32", f"amp{C}/{vl.AMP_HEIGHT[C]}/window"}, families
     ledger.close()
 
 
@@ -226,17 +99,17 @@ def test_a_wide_pair_refuses_rows_beyond_its_index(models):
     buffers are never touched, so small ones do)."""
     for width, stage in WIDE_STAGES[1:]:
         mo = models(width)
-        C = wg.stage_channels(mo.conf)[stage]
+        C = vl.stage_channels(mo.conf)[stage]
         x = torch.zeros(1, 8, C, device=DEV)
         info = (ctypes.c_int64 * 5)()
-        L = wg.max_rows(C) + 1
+        L = vl.max_rows(C) + 1
         rc = mo.lib.bvc_test_vocoder_layer(mo.eng.handle, KIND_AMP, stage, 0, 0, mo.abi.ptr(x), 1, L, mo.abi.ptr(x), 1, None, 0, 0, 0, 0, 1.0,
                                            info, mo.eng.stream())
         assert rc == -1 and b"row index" in mo.lib.bvc_last_error(), (C, L, rc, mo.lib.bvc_last_error())
 
 
 # ----------------------------------------------------------------------------------------------- 3. conv_pre, upsamplers, conv_post
-@pytest.mark.parametrize("width", wg.WIDTHS)
+@pytest.mark.parametrize("width", vl.WIDTHS)
 def test_wide_conv_pre_and_upsamplers_against_float64(models, width):
     """conv_pre 80 -> width and every upsampler of the model (out of 256 / 128 / 64 / 32 channels, or 512 / 256 / 128 / 64) at
     L = 1, 6, 63, 64, 65, 129 input rows - both sides of the 64-row tiles of the 512-channel upsampler and of the 128-row ones."""
@@ -255,7 +128,7 @@ def test_wide_conv_pre_and_upsamplers_against_float64(models, width):
         ledgers[draw].add(f"conv_pre/{width}", vl.compare(out.cpu().numpy(), r64, r32, f"conv_pre width {width} B={B} L={L}", tile_rows=128))
         for i, rate in enumerate(vcfg["upsample_rates"]):
             cin = width >> i
-            tile = wg.conv_tile_rows(cin)
+            tile = vl.conv_tile_rows(cin)
             x = vl.make_input("n6" if (n + i) % 3 else "n1", B, cin, L, tile - 1, seed_of(draw, width, "up", i, L))
             out = nan_like(B, (L + 1) * rate, cin // 2)
             assert mo.layer(KIND_UP, to_dev(x), out, stage=i)[:2] == [(L + 1) * rate, cin // 2]
@@ -267,7 +140,7 @@ def test_wide_conv_pre_and_upsamplers_against_float64(models, width):
         ledger.close()
 
 
-@pytest.mark.parametrize("width", wg.WIDTHS)
+@pytest.mark.parametrize("width", vl.WIDTHS)
 def test_wide_conv_post_against_float64(models, width):
     """conv_post from 16 and 32 channels: L on both sides of the 256-sample tiles, ``length`` below, equal to and above L."""
     C = width >> 4
@@ -293,31 +166,17 @@ def test_wide_conv_post_against_float64(models, width):
 
 
 # ----------------------------------------------------------------------------------------------- 4. the reference's run
-@pytest.mark.parametrize("width", wg.WIDTHS)
+@pytest.mark.parametrize("width", vl.WIDTHS)
 def test_reference_fixture_taps_and_waveform(models, width):
     """bvc_test_vocoder_tap against the five stored taps (<= 2e-5) and BigVGAN.forward against the stored waveform (rms <= 1e-5):
     the bars test_gpu_parity.py holds the shipped width's fixtures g5 to."""
-    mo = models(width)
-    g = load_golden(f"g12_bigvgan_wide_{width}")
+    g = gg.check_fixture(models(width), f"g12_bigvgan_wide_{width}", f"width {width}", ("conv_pre", "stage0", "stage1", "stage2", "stage3"),
+                         rms_bar=1e-5, max_bar=1e-4)
     assert int(g["width"]) == width and int(g["seed"]) == 1235
-    mel = torch.from_numpy(g["mel"]).to(DEV)
-    wav = mo.model.vocoder(mel, 10 ** 9).cpu().numpy()
-    assert wav.shape == g["wav"].shape
-    rms = float(np.sqrt(((wav - g["wav"]) ** 2).mean()))
-    print(f"FIXTURE width {width}: waveform rms error {rms:.3e} max {np.abs(wav - g['wav']).max():.3e}")
-    assert rms <= 1e-5 and np.abs(wav - g["wav"]).max() < 1e-4
-    mel_tm = mel.permute(0, 2, 1).contiguous()
-    for nm, which in (("conv_pre", 0), ("stage0", 2), ("stage1", 4), ("stage2", 6), ("stage3", 8)):
-        ref = g[nm]
-        got = mo.tap(mel_tm, which).cpu().numpy().reshape(ref.shape[0], -1, ref.shape[1]).transpose(0, 2, 1)
-        assert got.shape == ref.shape
-        err, scale = float(np.abs(got - ref).max()), max(1.0, float(np.abs(ref).max()))
-        print(f"FIXTURE width {width}: {nm} max error {err:.3e} (scale {scale:.3f})")
-        assert err <= 2e-5 * scale, (width, nm, err, scale)
 
 
 # ----------------------------------------------------------------------------------------------- 5. the whole chain, with seams
-@pytest.mark.parametrize("width", wg.WIDTHS)
+@pytest.mark.parametrize("width", vl.WIDTHS)
 def test_wide_whole_chain_taps_and_waveform_against_float64(models, width):
     """All nine taps and the waveform at (B, T) = (3, 130): several tiles per item at every stage (the fixtures are below one)."""
     mo, ledger = models(width), vl.Ledger("seed1235")
@@ -329,8 +188,7 @@ def test_wide_whole_chain_taps_and_waveform_against_float64(models, width):
     w64 = obig.forward(mo.sd, vcfg, mel, 10 ** 9, dtype=torch.float64, taps=t64)
     w32 = obig.forward(mo.sd, vcfg, mel, 10 ** 9, dtype=torch.float32, taps=t32)
     mel_cl = to_dev(mel)
-    names = ["conv_pre"] + [f"{k}{i}" for i in range(4) for k in ("up", "stage")]
-    for which, nm in enumerate(names):
+    for which, nm in enumerate(gg.TAPS):
         r64 = vl.cl(t64[nm])
         out = mo.tap(mel_cl, which)
         ledger.add(f"chain{width}/{nm}", vl.compare(out.cpu().numpy().reshape(r64.shape), r64, vl.cl(t32[nm]), f"chain tap {nm} width {width} B={B} T={T}"))
@@ -341,7 +199,7 @@ def test_wide_whole_chain_taps_and_waveform_against_float64(models, width):
 
 
 # ----------------------------------------------------------------------------------------------- 6. facade
-@pytest.mark.parametrize("width", wg.WIDTHS)
+@pytest.mark.parametrize("width", vl.WIDTHS)
 def test_facade_encode_decode(models, tmp_path, width):
     """encode -> decode, B = 3, 1 s: the codes are the same coder's with the shipped generator (the generator does not enter encode);
     the waveform against the oracle's decode, rms < 1e-4 (the facade's bar); forward and forward_fused; lost frames: the filled codes
@@ -470,35 +328,35 @@ def test_switches_on_a_wide_stage_are_refused(tmp_path, conf_var, key):
     for width, stage in WIDE_STAGES:
         flags = [k == stage for k in range(4)]
         with pytest.raises(ValueError, match=key):
-            wg.write_config(str(tmp_path / f"{key}_{width}_{stage}.toml"), width, switches={key: flags})
+            vl.write_config(str(tmp_path / f"{key}_{width}_{stage}.toml"), width=width, switches={key: flags}, h_dim=H_DIM)
         # the library itself, handed the tensors such a checkpoint would carry
-        conf = symo.with_switches(wg.write_config(str(tmp_path / f"plain_{width}.toml"), width), {key: flags})
+        conf = vl.with_switches(vl.write_config(str(tmp_path / f"plain_{width}.toml"), width=width, h_dim=H_DIM), {key: flags})
         tensors = weights.host_tensors(conf, synth.bvrnn_state_dict(conf, 1234), synth.generator_state_dict(conf, 1235))
         with pytest.raises(_abi.BvcError, match=f"stage {stage} has {width >> (stage + 1)} channels") as e:
             _Engine(conf, tensors, torch.device(DEV))
         assert key in str(e.value)
-    assert config.check_supported(symo.with_switches(conf_var, {key: [True] * 4})) is None
+    assert config.check_supported(vl.with_switches(conf_var, {key: [True] * 4})) is None
 
 
 def test_an_unfused_library_refuses_a_wide_stage(tmp_path, monkeypatch):
     from bvcodec import _abi
     monkeypatch.setenv("BVC_UNFUSED_AMP", "1")
     with pytest.raises(_abi.BvcError, match="wide stages run in the fused AMP kernels only"):
-        Model(str(tmp_path), 256)
+        make_model(str(tmp_path), 256)
 
 
-@pytest.mark.parametrize("width", wg.WIDTHS)
+@pytest.mark.parametrize("width", vl.WIDTHS)
 def test_switches_on_the_narrow_stages_of_a_wide_generator(models, width):
     """Symmetric and filtered stages of 64 channels and fewer, a symmetric or filtered conv_post from 16 / 32 channels, behind
-    causal wide stages: the waveform and the stage taps against symmetric_oracle.forward in float64."""
+    causal wide stages: the waveform and the stage taps against the oracle in float64."""
     mo, ledger = models(width, tag="mixed"), vl.Ledger("seed1235")
     vcfg = mo.conf["vocoder_config"]
     B, T = 2, 40
     rng = np.random.default_rng(seed_of("mixed", width))
     mel = torch.from_numpy((-4 + 1.6 * rng.standard_normal((B, 80, T))).astype(np.float32))
     t64, t32 = {}, {}
-    w64 = symo.forward(mo.sd, vcfg, mel, 10 ** 9, dtype=torch.float64, taps=t64)
-    w32 = symo.forward(mo.sd, vcfg, mel, 10 ** 9, dtype=torch.float32, taps=t32)
+    w64 = obig.forward(mo.sd, vcfg, mel, 10 ** 9, dtype=torch.float64, taps=t64)
+    w32 = obig.forward(mo.sd, vcfg, mel, 10 ** 9, dtype=torch.float32, taps=t32)
     mel_cl = to_dev(mel)
     for i in range(4):
         r64 = vl.cl(t64[f"stage{i}"])

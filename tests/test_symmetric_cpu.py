@@ -1,11 +1,10 @@
-"""Symmetric layers without a GPU: the test oracle (tests/symmetric_oracle.py) against the reference's own run
+"""Symmetric layers without a GPU: the oracle (oracle/bigvgan.py) against the reference's own run
 (tests/golden/g11_bigvgan_sym_*.npz, written by tests/golden/make_golden_symmetric.py), the reach of one symmetric AMP pair - the
 halo the GPU kernel's tiles are cut with -, and what config and weights make of the three switches."""
 import numpy as np
 import pytest
 import torch
 
-import symmetric_oracle as symo
 import vocoder_layers as vl
 from conftest import load_golden
 from bvcodec import config, synth, weights
@@ -16,21 +15,21 @@ SWITCHES = ("layers_sym", "pre_sym", "post_sym", "layers_antialias", "antialias_
 
 
 # ----------------------------------------------------------------------------------------------- 1. the oracle is the reference
-@pytest.mark.parametrize("tag", sorted(symo.CONFIGS))
+@pytest.mark.parametrize("tag", sorted(vl.SYM_CONFIGS))
 def test_oracle_equals_reference_fixture_bit_for_bit(conf_var, tag):
     """Waveform and every tap, float32, with the weight fold of the reference's forward pre-hook and the fixture script's thread
     count (see test_antialias_cpu.py)."""
     g = load_golden(f"g11_bigvgan_sym_{tag}")
-    sw = symo.CONFIGS[tag]
+    sw = vl.SYM_CONFIGS[tag]
     for k in SWITCHES:
         assert g[k].tolist() == sw[k], k
-    conf = symo.with_switches(conf_var, tag)
+    conf = vl.with_switches(conf_var, vl.SYM_CONFIGS[tag])
     sd = synth.generator_state_dict(conf, seed=int(g["seed"]))
     threads = torch.get_num_threads()
     torch.set_num_threads(8)
     try:
         taps = {}
-        wav = symo.forward(sd, conf["vocoder_config"], torch.from_numpy(g["mel"]), 10 ** 9, taps=taps, fold=symo.REFERENCE_FOLD)
+        wav = obig.forward(sd, conf["vocoder_config"], torch.from_numpy(g["mel"]), 10 ** 9, taps=taps, fold=obig.REFERENCE_FOLD)
     finally:
         torch.set_num_threads(threads)
     assert wav.shape == g["wav"].shape
@@ -42,11 +41,16 @@ def test_oracle_equals_reference_fixture_bit_for_bit(conf_var, tag):
 
 
 def test_every_switch_off_equals_the_plain_oracle(conf_var):
+    """The five switches present and false (the shipped TOML) against a table without them (what a configuration from before the
+    switches holds): the same bits, waveform and every tap."""
+    v = conf_var["vocoder_config"]
+    assert all(k in v and not any(np.atleast_1d(v[k])) for k in SWITCHES)
+    bare = {k: f for k, f in v.items() if k not in SWITCHES}
     sd = synth.generator_state_dict(conf_var, 1235)
     mel = torch.from_numpy(load_golden("g11_bigvgan_sym_all")["mel"])
     taps, taps0 = {}, {}
-    wav = symo.forward(sd, conf_var["vocoder_config"], mel, 10 ** 9, taps=taps)
-    assert torch.equal(wav, obig.forward(sd, conf_var["vocoder_config"], mel, 10 ** 9, taps=taps0))
+    wav = obig.forward(sd, v, mel, 10 ** 9, taps=taps)
+    assert torch.equal(wav, obig.forward(sd, bare, mel, 10 ** 9, taps=taps0))
     assert sorted(taps) == sorted(taps0) and all(torch.equal(taps[k], taps0[k]) for k in taps)
 
 
@@ -55,18 +59,18 @@ def test_every_switch_off_equals_the_plain_oracle(conf_var):
 def test_reach_of_one_symmetric_pair(conf_var, ks, d):
     """Perturbing x[s] changes outputs up to (ks-1)(d+1)/2 rows away on each side, exactly the rows the two convs' taps reach,
     and no others."""
-    conf = symo.with_switches(conf_var, "all")
+    conf = vl.with_switches(conf_var, vl.SYM_CONFIGS["all"])
     i, j, m, C, _, _, pre = next(p for p in vl.pairs(conf) if p[3] == 8 and p[4] == ks and p[5] == d)
     sd = synth.generator_state_dict(conf, 1235)
-    h = symo.reach(ks, d)
+    h = vl.reach(ks, d)
     assert h == (ks - 1) * (d + 1) // 2 and 2 * h == (ks - 1) * (d + 1)
     L, s = 4 * h + 40, 2 * h + 17
     x = vl.make_input("n1", 1, C, L, L, 5).double()
-    base = symo.amp_pair(sd, pre, m, x, ks, d, dtype=torch.float64)
+    base = obig.amp_pair(sd, pre, m, x, ks, d, dtype=torch.float64, sym=True)
     assert base.shape == x.shape
     xp = x.clone()
     xp[:, :, s] += 0.5
-    changed = (symo.amp_pair(sd, pre, m, xp, ks, d, dtype=torch.float64) != base).any(dim=1)[0]
+    changed = (obig.amp_pair(sd, pre, m, xp, ks, d, dtype=torch.float64, sym=True) != base).any(dim=1)[0]
     # conv1's taps sit d rows apart and conv2's one row: the rows s + a d + b, |a|, |b| <= (ks-1)/2 (all of [s - h, s + h] where
     # d <= ks, and always both ends)
     p2 = (ks - 1) // 2
@@ -74,45 +78,45 @@ def test_reach_of_one_symmetric_pair(conf_var, ks, d):
     assert rows[0] == s - h and rows[-1] == s + h and (d > ks or rows == list(range(s - h, s + h + 1)))
     assert changed.nonzero().flatten().tolist() == rows, (ks, d, h)
     # and the causal form of the same pair reaches back only
-    base_c = symo.amp_pair(sd, pre, m, x, ks, d, dtype=torch.float64, sym=False)
-    changed_c = (symo.amp_pair(sd, pre, m, xp, ks, d, dtype=torch.float64, sym=False) != base_c).any(dim=1)[0]
+    base_c = obig.amp_pair(sd, pre, m, x, ks, d, dtype=torch.float64, sym=False)
+    changed_c = (obig.amp_pair(sd, pre, m, xp, ks, d, dtype=torch.float64, sym=False) != base_c).any(dim=1)[0]
     assert changed_c.nonzero().flatten().tolist() == [r + h for r in rows]
 
 
 def test_symmetric_upsampler_is_a_view_of_the_causal_one(conf_var):
     """ConvTranspose1d(padding = (k - u) / 2), k = 2u: rows [u/2, u/2 + L u) of the unpadded result - what the GPU path computes."""
-    conf = symo.with_switches(conf_var, "all")
+    conf = vl.with_switches(conf_var, vl.SYM_CONFIGS["all"])
     sd = synth.generator_state_dict(conf, 1235)
     v = conf["vocoder_config"]
     for i, u in enumerate(v["upsample_rates"]):
         x = vl.make_input("n1", 2, v["upsample_initial_channel"] >> i, 9, 9, 40 + i)
-        full = symo.upsample(sd, v, i, x, torch.float64, sym=False)     # (float32: the CPU sums the two taps in another order)
+        full = obig.upsample(sd, v, i, x, torch.float64, sym=False)     # (float32: the CPU sums the two taps in another order)
         assert full.shape[2] == 10 * u
-        assert torch.equal(symo.upsample(sd, v, i, x, torch.float64), full[:, :, u // 2:u // 2 + 9 * u])
+        assert torch.equal(obig.upsample(sd, v, i, x, torch.float64, sym=True), full[:, :, u // 2:u // 2 + 9 * u])
 
 
 # ----------------------------------------------------------------------------------------------- 3. configuration and weights
 def test_config_accepts_the_three_configurations(tmp_path, conf_var):
-    for tag, sw in symo.CONFIGS.items():
-        c = symo.write_config(str(tmp_path / f"{tag}.toml"), tag)
+    for tag, sw in vl.SYM_CONFIGS.items():
+        c = vl.write_config(str(tmp_path / f"{tag}.toml"), switches=sw)
         assert config.symmetric_flags(c) == (sw["layers_sym"], sw["pre_sym"], sw["post_sym"])
         assert config.antialias_flags(c) == (sw["layers_antialias"], sw["antialias_post"])
         assert not config.is_causal(c)
         assert "symmetric" in config.not_causal_message(c) or config.is_antialiased(c)
-    assert "symmetric" in config.not_causal_message(symo.with_switches(conf_var, "mixed"))
-    assert "anti-aliased" in config.not_causal_message(symo.with_switches(conf_var, "with_aa"))
+    assert "symmetric" in config.not_causal_message(vl.with_switches(conf_var, vl.SYM_CONFIGS["mixed"]))
+    assert "anti-aliased" in config.not_causal_message(vl.with_switches(conf_var, vl.SYM_CONFIGS["with_aa"]))
     assert config.symmetric_flags(conf_var) == ([False] * 4, False, False) and config.is_causal(conf_var)
-    only_aa = symo.with_switches(conf_var, dict(layers_antialias=[True, False, False, False]))
+    only_aa = vl.with_switches(conf_var, dict(layers_antialias=[True, False, False, False]))
     assert not config.is_causal(only_aa) and config.symmetric_flags(only_aa) == ([False] * 4, False, False)
 
 
-@pytest.mark.parametrize("tag", sorted(symo.CONFIGS))
+@pytest.mark.parametrize("tag", sorted(vl.SYM_CONFIGS))
 def test_generator_length_equals_the_fixture(conf_var, tag):
     g = load_golden(f"g11_bigvgan_sym_{tag}")
-    conf = symo.with_switches(conf_var, tag)
+    conf = vl.with_switches(conf_var, vl.SYM_CONFIGS[tag])
     T = g["mel"].shape[2]
     lens = config.generator_length(conf, T, stages=True)
-    assert lens == [g[f"stage{i}"].shape[2] for i in range(4)] == symo.sym_lengths(conf["vocoder_config"], T)
+    assert lens == [g[f"stage{i}"].shape[2] for i in range(4)] == vl.sym_lengths(conf["vocoder_config"], T)
     assert config.generator_length(conf, T) == g["wav"].shape[2] == lens[-1]
     expect = {"all": [96, 768, 1536, 3072], "mixed": [104, 832, 1666, 3332]}.get(tag)
     assert expect is None or lens == expect
@@ -121,37 +125,37 @@ def test_generator_length_equals_the_fixture(conf_var, tag):
 
 def test_config_refuses_what_is_not_built(conf_var):
     with pytest.raises(ValueError, match="layers_sym"):
-        config.check_supported(symo.with_switches(conf_var, dict(layers_sym=[True, False, True])))
-    even = symo.with_switches(conf_var, dict(layers_sym=[False, True, False, False]))
+        config.check_supported(vl.with_switches(conf_var, dict(layers_sym=[True, False, True])))
+    even = vl.with_switches(conf_var, dict(layers_sym=[False, True, False, False]))
     even["vocoder_config"]["resblock_kernel_sizes"] = [3, 8, 11]
     with pytest.raises(ValueError, match="odd"):
         config.check_supported(even)
     even["vocoder_config"]["layers_sym"] = [False] * 4                   # a causal generator may have even kernels
     config.check_supported(even)
-    both = symo.with_switches(conf_var, dict(layers_sym=[False, False, True, False], layers_antialias=[False, False, True, True]))
+    both = vl.with_switches(conf_var, dict(layers_sym=[False, False, True, False], layers_antialias=[False, False, True, True]))
     with pytest.raises(ValueError, match="causal"):
         config.check_supported(both)
-    post = symo.with_switches(conf_var, dict(post_sym=True, antialias_post=True))
+    post = vl.with_switches(conf_var, dict(post_sym=True, antialias_post=True))
     with pytest.raises(ValueError, match="causal"):
         config.check_supported(post)
     # what stays refused
-    snake = symo.with_switches(conf_var, "all")
+    snake = vl.with_switches(conf_var, vl.SYM_CONFIGS["all"])
     snake["vocoder_config"]["activation"] = "snake"
     with pytest.raises(ValueError, match="snakebeta"):
         config.check_supported(snake)
 
 
-@pytest.mark.parametrize("tag", sorted(symo.CONFIGS))
+@pytest.mark.parametrize("tag", sorted(vl.SYM_CONFIGS))
 def test_host_tensors_carry_the_flags(conf_var, tag):
-    sw = symo.CONFIGS[tag]
-    conf = symo.with_switches(conf_var, tag)
+    sw = vl.SYM_CONFIGS[tag]
+    conf = vl.with_switches(conf_var, vl.SYM_CONFIGS[tag])
     vr, gen = synth.bvrnn_state_dict(conf_var, 3), synth.generator_state_dict(conf, 4)
     ht = weights.host_tensors(conf, vr, gen)
     assert ht["layers_sym"].tolist() == [float(f) for f in sw["layers_sym"]]
     assert ht["pre_sym"].tolist() == [float(sw["pre_sym"])] and ht["post_sym"].tolist() == [float(sw["post_sym"])]
     assert ("layers_antialias" in ht) == (any(sw["layers_antialias"]) or sw["antialias_post"])
     # the switches add no keys: the same draws under the same names as the causal layout of the same filters
-    plain = synth.generator_state_dict(symo.with_switches(conf_var, dict(layers_antialias=sw["layers_antialias"],
+    plain = synth.generator_state_dict(vl.with_switches(conf_var, dict(layers_antialias=sw["layers_antialias"],
                                                                           antialias_post=sw["antialias_post"])), 4)
     assert list(plain) == list(gen) and all(torch.equal(plain[k], gen[k]) for k in gen)
 

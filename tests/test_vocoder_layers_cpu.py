@@ -85,7 +85,7 @@ def test_tile_geometry_table():
     """The restatement of the launchers' tile shapes (every GPU case also checks it against what the launch reports)."""
     assert vl.amp8_tile_rows(3, 1, 2) == 254 and vl.amp8_tile_rows(11, 3, 2) == 242 and vl.amp8_tile_rows(7, 5, 2) == 244
     assert vl.amp8_tile_rows(11, 5, 1) == 110
-    assert vl.amp_tile_rows(64, 7, 3, 1000, False, height64=96) == (90, "amp64/96")
+    assert vl.amp_tile_rows(64, 7, 3, 1000, False, height=96) == (90, "amp64/96")
     assert vl.amp_tile_rows(64, 7, 3, 26, True)[0] == 26 and vl.amp_tile_rows(64, 7, 3, 27, True)[0] == 58
     assert vl.amp_tile_rows(64, 7, 3, 116, True)[0] == 58 and vl.amp_tile_rows(64, 7, 3, 117, True)[0] == 122
     assert vl.amp_tile_rows(32, 11, 5, 162, True)[0] == 54 and vl.amp_tile_rows(32, 11, 5, 163, True)[0] == 246

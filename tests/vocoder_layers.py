@@ -1,6 +1,8 @@
-"""Shared by test_vocoder_layers_cpu.py and test_gpu_vocoder_layers.py: the weight draws, the inputs, the tile geometry of the
-generator's launchers (a restatement of k_vocoder.hip that every GPU case checks against what the launch reports) and the
-elementwise comparison with the float64 oracle."""
+"""Shared by every generator test (the four test_*_cpu.py / test_gpu_*.py pairs of the plain, anti-aliased, symmetric and wide
+generators), tests/golden/make_golden_*.py and the tools/*_cost.py scripts; imports no GPU code.  The named configurations and the
+TOML writer, the weight draws, the inputs and case lists, the tile geometry of the generator's launchers (a restatement of
+k_vocoder*.hip that every GPU case checks against what the launch reports) and the elementwise comparison with the float64 oracle
+(oracle/bigvgan.py)."""
 import collections
 
 import numpy as np
@@ -14,11 +16,65 @@ MARGIN = 8.0                         # e_hip <= MARGIN * max(e32, U * max|oracle
 NARROW_DRAWS = ("seed1235", "seed8", "seed100")
 DRAWS = NARROW_DRAWS + ("wide",)
 BATCHES = (2, 3, 5, 9)               # tile counts that are not multiples of 8 (the grids are padded to 8 and dealt per XCD)
-CHANNELS = (64, 32, 16, 8)           # per stage
+CHANNELS = (64, 32, 16, 8)           # per stage of the shipped width
+WIDTHS = (256, 512)                  # upsample_initial_channel of the wide generators (the shipped one has 128)
 KSIZES = (3, 7, 11)                  # per AMP block
 DILATIONS = (1, 3, 5)                # per iteration
-AMP64_HEIGHTS = (128, 112, 96, 80)
 CE_RES, CE_RES_ACC, CE_RES_ACC_DIV = 1, 2, 3
+
+
+# ---------------------------------------------------------------------------------------------- configurations
+def _c(layers_sym=(False,) * 4, pre_sym=False, post_sym=False, layers_antialias=(False,) * 4, antialias_post=False):
+    return dict(layers_sym=list(layers_sym), pre_sym=pre_sym, post_sym=post_sym, layers_antialias=list(layers_antialias),
+                antialias_post=antialias_post)
+
+
+T_, F_ = True, False
+AA_CONFIGS = {"all": _c(layers_antialias=[T_, T_, T_, T_], antialias_post=True), "mixed": _c(layers_antialias=[T_, F_, T_, F_])}
+SYM_CONFIGS = {
+    "all": _c([T_, T_, T_, T_], True, True),
+    # symmetric C = 32 and C = 8 stages around the causal persistent C = 16 kernel
+    "mixed": _c([F_, T_, F_, T_], False, True),
+    "with_aa": _c([T_, F_, T_, F_], True, False, [F_, T_, F_, T_], True),
+}
+
+
+def with_switches(conf, switches=None, width=None):
+    """A copy of the configuration with some of the five switches (a dict like the CONFIGS' entries, or a part of one) and / or
+    the generator's initial channel count set."""
+    v = dict(conf["vocoder_config"], **{k: (list(f) if isinstance(f, (list, tuple)) else bool(f)) for k, f in (switches or {}).items()})
+    if width is not None:
+        v["upsample_initial_channel"] = int(width)
+    return dict(conf, vocoder_config=v)
+
+
+def write_config(path, *, width=None, switches=None, h_dim=None):
+    """The shipped variable-rate TOML with another ``upsample_initial_channel``, the given switches set and, for cheap models,
+    another h_dim.  Returns the loaded config (config.load_config checks it)."""
+    from bvcodec import config
+    txt = open(config.DEFAULT_CONFIG).read()
+
+    def put(old, new):
+        nonlocal txt
+        assert txt.count(old) == 1, old
+        txt = txt.replace(old, new)
+    if width is not None:
+        put("upsample_initial_channel = 128", f"upsample_initial_channel = {int(width)}")
+    for key, value in (switches or {}).items():
+        if isinstance(value, (list, tuple)):
+            put(f"{key} = [false, false, false, false]", f"{key} = [" + ", ".join("true" if f else "false" for f in value) + "]")
+        else:
+            put(f"{key} = false", f"{key} = " + ("true" if value else "false"))
+    if h_dim is not None:
+        put("h_dim = 1024", f"h_dim = {h_dim}")
+    with open(path, "w") as f:
+        f.write(txt)
+    return config.load_config(path)
+
+
+def stage_channels(conf):
+    v = conf["vocoder_config"]
+    return [v["upsample_initial_channel"] >> (i + 1) for i in range(len(v["upsample_rates"]))]
 
 
 def generator_draw(conf, name):
@@ -47,16 +103,39 @@ def pairs(conf):
     return out
 
 
-# ---------------------------------------------------------------------------------------------- tile geometry (k_vocoder.hip)
+# ---------------------------------------------------------------------------------------------- tile geometry (k_vocoder*.hip)
+LDS_LIMIT = 160 * 1024
+WIDE_CHANNELS = (256, 128)                 # stages on the wide forms of the AMP-pair kernel
+# every compiled offline height (rows both convs of a tile sweep; BVC_AMP256_TR / BVC_AMP128_TR / BVC_AMP64_TR force one); the first
+# is the default of the wide ones, offline and in windows of more than one short tile - C = 64 takes the planned one
+AMP_HEIGHTS = {256: (64, 96), 128: (64, 128), 64: (128, 112, 96, 80)}
+AMP_HEIGHT = {C: AMP_HEIGHTS[C][0] for C in WIDE_CHANNELS}
+AMP_SHORT = 32                             # a streaming window of at most one such tile takes it
+AA_TILE_HEIGHT = {64: 96, 32: 128, 16: 128, 8: 256}       # launch_amp_pair's tile of a filtered stage
+SYM_TILE_HEIGHT = {64: 128, 32: 256, 16: 128, 8: 256}     # and of a symmetric one
+ROW_GUARD = 512                            # rows the host keeps between L and the 32-bit byte offset's end
+REACH = obig.REACH
+
+
 def amp8_tile_rows(ks, d, mt2):
     """Amp8Geom<KS, D, MT2>::TT: NP = 64 * MT2 row pairs, whole blocks of d pairs, two rows per pair."""
     npairs = 4 * mt2 * 16
     return 2 * (npairs // d) * d - (ks - 1)
 
 
-def amp_tile_rows(C, ks, d, new_rows, window, height64=128, c8=True, c16=True):
-    """Valid output rows per tile of the kernel launch_amp_pair picks.  height64: the offline C = 64 tile height (forced or planned);
-    c8 / c16: the model's vocoder_full_tiles / vocoder_c16_kernel options.  Returns (TT, family name)."""
+def amp_tile_rows(C, ks, d, new_rows, window, height=None, c8=True, c16=True, form="causal"):
+    """Valid output rows per tile of the kernel launch_amp_pair picks.  height: the offline tile height of C = 256, 128 and 64 (forced,
+    or for C = 64 planned; None: the default, 128 at C = 64); c8 / c16: the model's vocoder_full_tiles / vocoder_c16_kernel options;
+    form: 'causal', 'filtered' or 'symmetric', the stage's.  Returns (TT, family name)."""
+    if form == "filtered":     # conv1 runs on the tile's rows, 10 of which feed A2's reach, ks - 1 conv2's
+        return AA_TILE_HEIGHT[C] - (ks - 1) - 2 * REACH, f"amp{C}/filtered"
+    if form == "symmetric":    # conv2 spends ks - 1 of the tile's rows, (ks-1)/2 on each side
+        return SYM_TILE_HEIGHT[C] - (ks - 1), f"amp{C}/symmetric"
+    if C in WIDE_CHANNELS:
+        if window and new_rows <= AMP_SHORT - (ks - 1):
+            return AMP_SHORT - (ks - 1), f"amp{C}/window{AMP_SHORT}"
+        h = AMP_HEIGHT[C] if (window or height is None) else height
+        return h - (ks - 1), f"amp{C}/{h}" + ("/window" if window else "")
     if window and C == 64 and new_rows <= 32 - (ks - 1):
         return 32 - (ks - 1), "amp64/window32"
     if window and C == 64 and new_rows <= 2 * (64 - (ks - 1)):
@@ -68,7 +147,7 @@ def amp_tile_rows(C, ks, d, new_rows, window, height64=128, c8=True, c16=True):
             return amp8_tile_rows(ks, d, 1), "amp8/full<1,4>"
         return amp8_tile_rows(ks, d, 2), "amp8/full<2,2>" + ("/window" if window else "")
     if C == 64:
-        h = 128 if window else height64
+        h = 128 if (window or height is None) else height
         return h - (ks - 1), f"amp64/{h}" + ("/window" if window else "")
     if C == 32:
         return 256 - (ks - 1), "amp32/256" + ("/window" if window else "")
@@ -81,12 +160,34 @@ def amp_tile_rows(C, ks, d, new_rows, window, height64=128, c8=True, c16=True):
 
 def conv_tile_rows(cin):
     """launch_one's rows per workgroup for the row-split tiles of launch_conv_mfma (conv_pre and the upsamplers, offline)."""
-    return {128: 128, 80: 128, 64: 128, 32: 256, 16: 256, 8: 256}[cin]
+    return {512: 64, 256: 128, 128: 128, 80: 128, 64: 128, 32: 256, 16: 256, 8: 256}[cin]
 
 
 POST_TILE_ROWS = 256                 # conv_post_kernel: one output sample per thread
 
 
+def amp_lds_bytes(C, ks, d, height):
+    """amp_pair_kernel<C, ..., ALIAS = true>: the S1 rows (tile + conv1's halo); the S2 tile (height + ks - 1 rows) and the output
+    staging (height rows) re-use them."""
+    rows1 = height + (ks - 1) * d
+    assert rows1 >= height + ks - 1
+    return rows1 * (C + 2) * 4
+
+
+def conv_lds_bytes(cin, ks, d, rows):
+    return (rows + (ks - 1) * d) * (cin + 2) * 4
+
+
+def post_lds_bytes(C, ks, antialias=False):
+    return (2 * (256 + ks - 1) + 10 if antialias else 256 + ks - 1) * C * 4
+
+
+def max_rows(C):
+    """Rows per item the wide AMP pair accepts: rows_load4's byte offset is a 32-bit integer."""
+    return 0x7FFFFFFF // C // 4 - ROW_GUARD
+
+
+# ---------------------------------------------------------------------------------------------- the case lists
 def lengths(TT, ks, d):
     """Rows per item: the shortest signals, both halo depths, and the seams of the first tiles."""
     ls = {1, 2, ks - 1, (ks - 1) * d, (ks - 1) * d + 1, TT - 1, TT, TT + 1, 2 * TT, 2 * TT + 1, 3 * TT + 17}
@@ -96,6 +197,41 @@ def lengths(TT, ks, d):
 def window_new_rows(ks):
     return sorted({1, 8, 32 - (ks - 1), 32 - (ks - 1) + 1, 2 * (64 - (ks - 1)), 2 * (64 - (ks - 1)) + 1,
                    3 * (64 - (ks - 1)), 3 * (64 - (ks - 1)) + 1, 128, 129, 400})
+
+
+def wide_window_new_rows(ks):
+    """New rows of a streaming window: one row, one frame of stage 0, one short tile, one more, and past the tall tiles."""
+    return sorted({1, 8, AMP_SHORT - (ks - 1), AMP_SHORT - (ks - 1) + 1, 129})
+
+
+def halo(ks, d):
+    """An anti-aliased pair's out[t] reads x[t - halo .. t + 10] (test_antialias_cpu.py measures it)."""
+    return (ks - 1) * (d + 1) + 2 * REACH
+
+
+def aa_lengths(TT, ks, d):
+    """Rows per item: signals shorter than the filter's reach (both clamps at once), and both sides of every seam."""
+    return sorted({1, 2, 5, 6, 10, 11, (ks - 1) * d + 10, TT - 1, TT, TT + 1, 2 * TT + 1, 3 * TT + 17})
+
+
+def reach(ks, d):
+    """A symmetric pair's out[t] reads x[t - reach .. t + reach] (test_symmetric_cpu.py measures it)."""
+    return (ks - 1) * (d + 1) // 2
+
+
+def sym_amp_lengths(TT, ks, d):
+    """Rows per item: signals shorter than the reach on both sides at once, both sides of every seam, the last tile's end anywhere."""
+    p2, h = (ks - 1) // 2, reach(ks, d)
+    return sorted({1, 2, p2, p2 + 1, h, h + 1, 2 * h + 1, TT - 1, TT, TT + 1, 2 * TT + 1, 3 * TT + 17})
+
+
+def sym_lengths(cfg, T):
+    """Rows after every stage: L * u behind a symmetric upsampler, (L + 1) * u behind a causal one; the last is the waveform's."""
+    out, L = [], T
+    for u, s in zip(cfg["upsample_rates"], obig.flags(cfg)[0]):
+        L = L * u if s else (L + 1) * u
+        out.append(L)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- inputs, channels-first (B, C, L)
@@ -115,9 +251,9 @@ def make_input(kind, B, C, L, TT, seed):
 
 
 # ---------------------------------------------------------------------------------------------- oracle units with the epilogues
-def oracle_pair(sd, pair, x, dtype, epi=CE_RES, acc=None, n_blocks=3):
+def oracle_pair(sd, pair, x, dtype, epi=CE_RES, acc=None, n_blocks=3, sym=False):
     i, j, m, C, ks, d, pre = pair
-    y = obig.amp_pair(sd, pre, m, x, ks, d, dtype=dtype)
+    y = obig.amp_pair(sd, pre, m, x, ks, d, dtype=dtype, sym=sym)
     if epi >= CE_RES_ACC:
         y = acc.to(dtype) + y                                           # xs += resblock   (models.py:224)
     if epi == CE_RES_ACC_DIV:

@@ -22,16 +22,16 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np          # noqa: E402
 import torch                # noqa: E402
 
-import antialias_oracle as aao                                  # noqa: E402
+import vocoder_layers as vl                                     # noqa: E402
 from bvcodec import BVRNNCodecModel, _abi, synth                # noqa: E402
 
 DEV = "cuda:0"
 PK_CONV, PK_POST = 3, 6
 
 
-def make(directory, tag, layers, post):
+def make(directory, tag, switches):
     cfg = os.path.join(directory, f"{tag}.toml")
-    conf = aao.write_config(cfg, layers, post)
+    conf = vl.write_config(cfg, switches=switches)
     p1, p2 = os.path.join(directory, "bvrnn"), os.path.join(directory, f"bigvgan_{tag}")
     if not os.path.exists(p1):
         torch.save({"vrnn": synth.bvrnn_state_dict(conf, 1234)}, p1)
@@ -61,9 +61,9 @@ def main():
     assert torch.cuda.is_available(), "needs the MI355X"
     lib = _abi.load()
     d = tempfile.mkdtemp(prefix="bvc_aa_cost_")
-    models = {"plain": make(d, "plain", [False] * 4, False)}
-    for tag, (layers, post) in aao.CONFIGS.items():
-        models[tag] = make(d, tag, layers, post)
+    models = {"plain": make(d, "plain", None)}
+    for tag, sw in vl.AA_CONFIGS.items():
+        models[tag] = make(d, tag, sw)
     B, T = a.batch, a.frames
     rng = np.random.default_rng(0)
     info = (ctypes.c_int64 * 5)()

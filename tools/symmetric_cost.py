@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np          # noqa: E402
 import torch                # noqa: E402
 
-import symmetric_oracle as symo                                 # noqa: E402
+import vocoder_layers as vl                                     # noqa: E402
 from bvcodec import BVRNNCodecModel, _abi, config, synth        # noqa: E402
 
 DEV = "cuda:0"
@@ -32,7 +32,7 @@ def make(directory, tag):
             f.write(open(config.DEFAULT_CONFIG).read())
         conf = config.load_config(cfg)
     else:
-        conf = symo.write_config(cfg, tag)
+        conf = vl.write_config(cfg, switches=vl.SYM_CONFIGS[tag])
     p1, p2 = os.path.join(directory, "bvrnn"), os.path.join(directory, f"bigvgan_{tag}")
     if not os.path.exists(p1):
         torch.save({"vrnn": synth.bvrnn_state_dict(conf, 1234)}, p1)

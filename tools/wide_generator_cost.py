@@ -21,17 +21,17 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np          # noqa: E402
 import torch                # noqa: E402
 
-import wide_generator as wg                                     # noqa: E402
+import vocoder_layers as vl                                     # noqa: E402
 from bvcodec import BVRNNCodecModel, _abi, synth                # noqa: E402
 
 DEV = "cuda:0"
 PEAK_FP32_MFMA_TFLOPS = 157.3          # bench.py
-SWEEP = {256: ("BVC_AMP256_TR", wg.AMP_HEIGHTS[256]), 128: ("BVC_AMP128_TR", wg.AMP_HEIGHTS[128])}
+SWEEP = {256: ("BVC_AMP256_TR", vl.AMP_HEIGHTS[256]), 128: ("BVC_AMP128_TR", vl.AMP_HEIGHTS[128])}
 
 
 def make(directory, width):
     cfg = os.path.join(directory, f"wide{width}.toml")
-    conf = wg.write_config(cfg, width, h_dim=64)
+    conf = vl.write_config(cfg, width=width, h_dim=64)
     p1, p2 = os.path.join(directory, "bvrnn"), os.path.join(directory, f"bigvgan_{width}")
     if not os.path.exists(p1):
         torch.save({"vrnn": synth.bvrnn_state_dict(conf, 1234)}, p1)
@@ -112,7 +112,7 @@ def main():
             print(f"  width {width} {name}: {dt:.3f} ms, {fl / 1e9:.1f} GFLOP, {fl / dt / 1e9:.1f} TFLOP/s = {fl / dt / 1e9 / PEAK_FP32_MFMA_TFLOPS:.3f}", flush=True)
         print(f"  width {width} {groups[-1][0]} (whole call - last tap): {ms - cum[8]:.3f} ms", flush=True)
         if a.sweep:
-            for stage, C in enumerate(wg.stage_channels(conf)):
+            for stage, C in enumerate(vl.stage_channels(conf)):
                 if C not in SWEEP:
                     continue
                 key, heights = SWEEP[C]
