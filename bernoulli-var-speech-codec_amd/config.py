@@ -144,7 +144,7 @@ def check_supported(conf):
         bad.append("front-end kernel is specialised for winsize=1024, hopsize=256")
     if conf["mel_pad_left"] < 0 or conf["mel_pad_left"] > conf["winsize"] - conf["hopsize"]:
         bad.append("mel_pad_left out of range")
-    if conf["z_dim"] % 16 or conf["h_dim"] % 16 or conf["num_mels"] % 16:
-        bad.append("z_dim, h_dim and num_mels must be multiples of 16")
+    if any(conf[k] % 16 or conf[k] < 16 for k in ("z_dim", "h_dim", "num_mels")):
+        bad.append("z_dim, h_dim and num_mels must be positive multiples of 16")
     if bad:
         raise ValueError("unsupported configuration: " + "; ".join(bad))

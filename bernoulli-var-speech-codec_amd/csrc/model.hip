@@ -421,8 +421,8 @@ int check_config(const bvc_config *c) {
     if (!c) { set_error("null config"); return BVC_EINVAL; }
     if (c->n_fft != 1024 || c->hop != 256) { set_error("front-end kernel needs n_fft=1024, hop=256"); return BVC_EINVAL; }
     if (c->pad_left < 0 || c->pad_left > c->n_fft - c->hop) { set_error("pad_left out of range"); return BVC_EINVAL; }
-    if (c->num_mels % 16 || c->h_dim % 16 || c->z_dim % 16 || c->num_mels > 128) {
-        set_error("num_mels/h_dim/z_dim must be multiples of 16 (num_mels <= 128)"); return BVC_EINVAL; }
+    if (c->num_mels % 16 || c->h_dim % 16 || c->z_dim % 16 || c->num_mels > 128 || c->num_mels < 16 || c->h_dim < 16 || c->z_dim < 16) {
+        set_error("num_mels/h_dim/z_dim must be positive multiples of 16 (num_mels <= 128)"); return BVC_EINVAL; }
     if (c->n_up < 1 || c->n_up > 8 || c->n_resk < 1 || c->n_resk > 4) { set_error("bad n_up / n_resk"); return BVC_EINVAL; }
     int ch = c->upsample_initial_channel;
     if (ch != 512 && ch != 256 && ch != 128 && ch != 64 && ch != 32 && ch != 16) { set_error("unsupported upsample_initial_channel %d (16, 32, 64, 128, 256 or 512)", ch); return BVC_EINVAL; }

@@ -21,36 +21,88 @@ RANGE_HDIMS = (64, 128, 1024)
 TEACHER_FRAMES = (0, 1, 7, 23, 47)                      # of the (1024, 20, 48) case
 TIE = 1e-5                                              # the project's margin: a rounded argument this close to 0.5 may flip
 CAP_SHARE, CAP_ROWS, MIN_FRAMES = 1e-4, 2, 0.9
-Z = 64
+Z = 64                                                  # the shipped z_dim: the default of everything below that takes a z_dim
+
+# The size classes of tests/test_gpu_coder_sizes.py (profiles/coder_sizes.md): (class, h_dim, z_dim, ((B, T), ...)).  B 5 and 20: a row
+# tile that is not full and a partly filled second one; 80 rows x 4 frames: the interleaved chains, which exist at h_dim 1024 only.
+SMALL = ((5, 12), (20, 12))
+SIZE_CLASSES = (
+    ("one k-block", 16, 16, SMALL),
+    ("partial waves", 48, 48, SMALL), ("partial waves", 112, 96, SMALL),
+    ("Z > H", 64, 128, SMALL),
+    ("Z > 3H", 16, 64, SMALL),
+    ("table h_dim, other z", 128, 16, SMALL), ("table h_dim, other z", 256, 48, SMALL), ("table h_dim, other z", 512, 96, SMALL),
+    ("table h_dim, other z", 1024, 128, ((80, 4),)), ("table h_dim, other z", 1024, 16, SMALL),
+    ("no persistent kernel (h_dim)", 192, 64, SMALL), ("no persistent kernel (h_dim)", 384, 32, SMALL), ("no persistent kernel (h_dim)", 1040, 64, SMALL),
+    ("no persistent kernel (z_dim)", 64, 144, SMALL),
+)
+SIZE_DRAWS = ("default", "wide")
+SIZE_CASES = tuple((h, z, B, T) for _, h, z, shapes in SIZE_CLASSES for B, T in shapes)
+PINNED_SIZES = ((48, 48), (64, 128), (192, 64), (1024, 16))
+WIRE_SIZES = ((128, 16), (48, 48), (112, 96), (64, 128))
+REJECTED_SIZES = ((24, 64), (1024, 8), (1024, 0), (64, 24))      # h_dim = 24, z_dim = 8, z_dim = 0 (and a z_dim that is no multiple of 16)
 
 
-def seed_of(h_dim, draw):
-    """Checkpoint seed of a case.  1234 everywhere but one: at h 256 the float32 oracle's own sampled forward on the wide draw flips
-    two rounded arguments that lie within 1e-5 of 0.5 (test_bvrnn_draws_cpu.py holds the reference itself to the caps)."""
-    return 7 if (h_dim, draw) == (256, "wide") else 1234
+def class_of(h_dim, z_dim):
+    return next(c for c, h, z, _ in SIZE_CLASSES if (h, z) == (h_dim, z_dim))
 
 
-def conf_of(h_dim, var_bit=True):
+# what the library's own size rules say of a model (csrc/k_flow.hip flow_perh, csrc/model.hip build_flow, csrc/recurrence.hip)
+def flow_supported(h_dim, z_dim):
+    return (h_dim in (128, 256, 512, 1024) or h_dim < 128) and z_dim <= 128
+
+
+FORWARD_REFUSAL = "bvc_bvrnn_forward: z_dim > h_dim is not supported"
+FORWARD_NEEDS_Z = "bvc_bvrnn_forward: pass d_z for this z_dim"
+CONCEAL_REFUSAL = "bvc_bvrnn_decode_conceal: z_dim > 3 h_dim is not supported"
+
+
+def forward_runs(h_dim, z_dim):
+    return z_dim <= h_dim
+
+
+def forward_fallback_runs(h_dim, z_dim, num_mels=80):
+    """forward without the caller's z: the sample lives in a workspace buffer (recurrence.hip, run_forward)."""
+    return z_dim <= h_dim and (z_dim <= num_mels or 2 * z_dim <= h_dim)
+
+
+def conceal_runs(h_dim, z_dim):
+    return z_dim <= 3 * h_dim
+
+
+# (h_dim, draw, z_dim) -> checkpoint seed where 1234 does not do: the float32 oracle's OWN rounded outputs break a cap of the tie rule
+# there (test_bvrnn_draws_cpu.py / test_coder_sizes_cpu.py hold the reference itself to the caps)
+SEEDS = {(256, "wide", 64): 7}
+
+
+def seed_of(h_dim, draw, z_dim=Z):
+    """Checkpoint seed of a case.  1234 everywhere but the entries of SEEDS: at h 256 / z 64 the float32 oracle's own sampled forward
+    on the wide draw flips two rounded arguments that lie within 1e-5 of 0.5."""
+    return SEEDS.get((h_dim, draw, z_dim), 1234)
+
+
+def conf_of(h_dim, var_bit=True, z_dim=Z):
     conf = config.load_config(config.DEFAULT_CONFIG if var_bit else config.DEFAULT_CONFIG_64BIT)
     conf["h_dim"] = h_dim
+    conf["z_dim"] = z_dim
     return conf
 
 
-def state_dict(h_dim, draw, var_bit=True):
-    return synth.bvrnn_state_dict(conf_of(h_dim, var_bit), seed_of(h_dim, draw), gains=GAINS[draw])
+def state_dict(h_dim, draw, var_bit=True, z_dim=Z):
+    return synth.bvrnn_state_dict(conf_of(h_dim, var_bit, z_dim), seed_of(h_dim, draw, z_dim), gains=GAINS[draw])
 
 
-def inputs(B, T, seed=5):
-    """mel ~ N(-4, 1.6^2), bits per frame integers in 0..64."""
+def inputs(B, T, seed=5, z_dim=Z):
+    """mel ~ N(-4, 1.6^2), bits per frame integers in 0..z_dim."""
     rng = np.random.default_rng(seed)
     y = torch.from_numpy((-4.0 + 1.6 * rng.standard_normal((B, T, 80))).astype(np.float32))
-    bits = torch.from_numpy(rng.integers(0, 65, size=(B, T)).astype(np.float32))
+    bits = torch.from_numpy(rng.integers(0, z_dim + 1, size=(B, T)).astype(np.float32))
     return y, bits
 
 
-def bit_mask(bits):
-    """(B, T, Z) bool: position n of a frame carries a bit where bits > n."""
-    return bits[:, :, None] > torch.arange(Z, dtype=bits.dtype)[None, None, :]
+def bit_mask(bits, z_dim=Z):
+    """(B, T, z_dim) bool: position n of a frame carries a bit where bits > n."""
+    return bits[:, :, None] > torch.arange(z_dim, dtype=bits.dtype)[None, None, :]
 
 
 # ---------------------------------------------------------------------------------------------- the tie rule
@@ -116,18 +168,22 @@ def n64(t):
 
 
 # ---------------------------------------------------------------------------------------------- references of the free-running cases
+def reference(draw, h_dim, B, T, z_dim=Z):
+    return _reference(draw, h_dim, B, T, z_dim)
+
+
 @functools.lru_cache(maxsize=None)
-def reference(draw, h_dim, B, T):
+def _reference(draw, h_dim, B, T, z_dim):
     """The float64 and float32 oracles on one case: dict of dicts o64 / o32 with encode, decode (of the float64 oracle's codes), forward
     (p_use_gen 0.3, sampled, generator seed 77) and conceal (10 % loss plus a burst per row), the inputs, and the float32 oracle's own
     cuts against the float64 one.  Computed once; nobody changes it."""
     torch.set_num_threads(min(16, torch.get_num_threads()))
-    sd = state_dict(h_dim, draw)
-    y, bits = inputs(B, T)
+    sd = state_dict(h_dim, draw, z_dim=z_dim)
+    y, bits = inputs(B, T, z_dim=z_dim)
     h0 = torch.zeros(B, h_dim)
-    r, noise = obv.draw_randomness(T, B, Z, False, generator=torch.Generator().manual_seed(77))
+    r, noise = obv.draw_randomness(T, B, z_dim, False, generator=torch.Generator().manual_seed(77))
     present = co.loss_pattern(B, T, 0.1, seed=B + T, burst=min(6, T // 3))
-    res = dict(sd=sd, y=y, bits=bits, r=r, noise=noise, present=present, mask=bit_mask(bits))
+    res = dict(sd=sd, y=y, bits=bits, r=r, noise=noise, present=present, mask=bit_mask(bits, z_dim))
     enc64 = obv.encode(sd, y, bits, h0, dtype=torch.float64)
     codes = enc64["codes"].float()
     res["codes"] = codes
@@ -140,19 +196,20 @@ def reference(draw, h_dim, B, T):
     return res
 
 
-def cuts_of(ref, codes, z, codes_out, who):
-    """The three tie cuts of one implementation's rounded outputs against the float64 oracle of `ref`."""
+def cuts_of(ref, codes, z, codes_out, who, z_dim=None):
+    """The three tie cuts of one implementation's rounded outputs against the float64 oracle of `ref` (z_dim: the width `ref` must have)."""
     o = ref["o64"]
     mask = ref["mask"].numpy()
+    assert z_dim is None or mask.shape[2] == z_dim == np.shape(codes)[2]
     lost = (~ref["present"])[:, :, None].numpy() & mask
     return dict(encode=Cut(f"{who} encode codes", codes, o["encode"]["codes"], o["encode"]["prob"], mask),
                 forward=Cut(f"{who} forward z", z, o["forward"]["z"], o["forward"]["arg"], mask),
                 conceal=Cut(f"{who} conceal codes_out", codes_out, o["conceal"]["codes_out"], o["conceal"]["prior"], lost))
 
 
-def regime(draw, h_dim, B, T):
+def regime(draw, h_dim, B, T, z_dim=Z):
     """What the float64 oracle reaches on a case: the figures of the draws' table."""
-    ref = reference(draw, h_dim, B, T)
+    ref = reference(draw, h_dim, B, T, z_dim)
     e64, f64, f32 = ref["o64"]["encode"], ref["o64"]["forward"], ref["o32"]["forward"]
     e, q = f64["prob"], f64["prior"]
     beyond = lambda p: (p < 1e-3) | (p > 1 - 1e-3)
@@ -168,33 +225,45 @@ LOGIT_TABLE = (0.0, 1e-4, 0.5, 6.9, 6.92, 16.6, 17.4, 25.0, 87.0, 89.0, 104.0, 1
 assert len(LOGIT_TABLE) == 32
 
 
-def logit_tables():
-    """(enc.4.bias, prior.4.bias) float32 (64,): the table with both signs (0 twice), in two different orders so that the (e, q) pairs
-    cover the KLD clamp on, off and mixed."""
+def logit_tables(z_dim=Z):
+    """(enc.4.bias, prior.4.bias) float32 (z_dim,): the table with both signs (0 twice), in two different orders so that the (e, q)
+    pairs cover the KLD clamp on, off and mixed.  z_dim <= 64: the first z_dim entries of the 64-entry tables; beyond 64 the tables
+    followed by permutations of themselves (one more per 64 entries), cut at z_dim: the 64 leading values are the same for every z_dim."""
     t = np.array([s * v for v in LOGIT_TABLE for s in (1.0, -1.0)], dtype=np.float32)
     rng = np.random.default_rng(11)
-    return torch.from_numpy(t[rng.permutation(Z)]), torch.from_numpy(t[rng.permutation(Z)])
+    be, bq = t[rng.permutation(Z)], t[rng.permutation(Z)]
+    more = np.random.default_rng(12)
+    while be.size < z_dim:
+        be, bq = np.concatenate([be, be[:Z][more.permutation(Z)]]), np.concatenate([bq, bq[:Z][more.permutation(Z)]])
+    return torch.from_numpy(be[:z_dim].copy()), torch.from_numpy(bq[:z_dim].copy())
 
 
 def pin_logits(sd):
     sd = dict(sd)
-    be, bq = logit_tables()
-    assert tuple(sd["enc.4.bias"].shape) == (Z,)
+    be, bq = logit_tables(sd["enc.4.bias"].shape[0])
     sd["enc.4.weight"], sd["prior.4.weight"] = torch.zeros_like(sd["enc.4.weight"]), torch.zeros_like(sd["prior.4.weight"])
     sd["enc.4.bias"], sd["prior.4.bias"] = be, bq
     return sd
 
 
-PINNED_BITS = (0.0, 1.0, 34.5, 63.0, 64.0, 1000.0)
+PINNED_BITS = (0.0, 1.0, 34.5, 63.0, 64.0, 1000.0)      # of the shipped z_dim
 
 
-def pinned_bits(B, T):
-    return torch.tensor([[PINNED_BITS[(b + 2 * t) % len(PINNED_BITS)] for t in range(T)] for b in range(B)], dtype=torch.float32)
+def pinned_bit_values(z_dim=Z):
+    """No bit, one, a count that is no integer, all but one, all, far more than all.  (0, 1, z/2 + 0.5, z - 1, z, 1000); at 64 the
+    fractional count stays the 34.5 the shipped size's tests have always used."""
+    return PINNED_BITS if z_dim == Z else (0.0, 1.0, z_dim / 2 + 0.5, z_dim - 1.0, float(z_dim), 1000.0)
 
 
-def pinned_noise(B, T, seed=3):
+def pinned_bits(B, T, z_dim=Z):
+    v = pinned_bit_values(z_dim)
+    return torch.tensor([[v[(b + 2 * t) % len(v)] for t in range(T)] for b in range(B)], dtype=torch.float32)
+
+
+def pinned_noise(B, T, seed=3, z_dim=Z):
     """Uniform samples for the sampled forward with every rounded argument u - 0.5 + sigmoid(enc bias) at least 1e-3 from 0.5."""
-    e = torch.sigmoid(logit_tables()[0].double())
+    Z = z_dim
+    e = torch.sigmoid(logit_tables(Z)[0].double())
     u = torch.rand(B, T, Z, generator=torch.Generator().manual_seed(seed))
     d = u.double() - 1.0 + e[None, None, :]
     u = torch.where(d.abs() < 2e-3, torch.where(u < 0.5, u + 4e-3, u - 4e-3), u)
@@ -202,12 +271,13 @@ def pinned_noise(B, T, seed=3):
     return u
 
 
-def pinned_logits_reference(B, T, bits, noise, dtype):
+def pinned_logits_reference(B, T, bits, noise, dtype, z_dim=Z):
     """Closed forms of the pinned-logits checkpoint in `dtype`: prob, prior (Z,), codes (B,T,Z), z greedy / sampled, kld_frames (T,),
     generated (B,T,Z) = masked round(prior).  bits None: a fixed-rate model (no mask)."""
-    be, bq = (b.to(dtype) for b in logit_tables())
+    Z = z_dim
+    be, bq = (b.to(dtype) for b in logit_tables(Z))
     e, q = torch.sigmoid(be), torch.sigmoid(bq)
-    mask = torch.ones(B, T, Z, dtype=torch.bool) if bits is None else bit_mask(bits)
+    mask = torch.ones(B, T, Z, dtype=torch.bool) if bits is None else bit_mask(bits, Z)
     half = torch.full((B, T, Z), 0.5, dtype=dtype)
     eb = e[None, None, :].expand(B, T, Z)
     out = dict(prob=e, prior=q, mask=mask)

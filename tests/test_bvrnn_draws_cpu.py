@@ -52,6 +52,49 @@ def test_float32_oracle_meets_the_tie_caps(draw, h_dim, B, T):
         cut.check()
 
 
+def test_reference_through_the_sized_signature_is_the_reference_as_it_was():
+    """reference(..., z_dim=64) is the four-argument reference, and that one is what the harness computed before it took a z_dim:
+    the shipped config's sizes, checkpoint seed 1234, inputs from generator 5 with bit counts in 0..64."""
+    from bvcodec import config
+    draw, h_dim, B, T = "default", 1024, 20, 48
+    new = bd.reference(draw, h_dim, B, T, z_dim=64)
+    assert new is bd.reference(draw, h_dim, B, T)
+    conf = config.load_config(config.DEFAULT_CONFIG)
+    assert conf["z_dim"] == 64 == bd.Z and bd.seed_of(h_dim, draw) == 1234 == bd.seed_of(h_dim, draw, 64)
+    conf["h_dim"] = h_dim
+    sd = synth.bvrnn_state_dict(conf, 1234, gains=None)
+    rng = np.random.default_rng(5)
+    y = torch.from_numpy((-4.0 + 1.6 * rng.standard_normal((B, T, 80))).astype(np.float32))
+    bits = torch.from_numpy(rng.integers(0, 65, size=(B, T)).astype(np.float32))
+    assert torch.equal(new["y"], y) and torch.equal(new["bits"], bits)
+    for k in sd:
+        assert torch.equal(new["sd"][k], sd[k]), k
+    old = obv.encode(sd, y, bits, torch.zeros(B, h_dim), dtype=torch.float64)
+    assert torch.equal(new["o64"]["encode"]["codes"], old["codes"]) and torch.equal(new["o64"]["encode"]["prob"], old["prob"])
+    assert torch.equal(new["mask"], bits[:, :, None] > torch.arange(64, dtype=torch.float32)[None, None, :])
+
+
+def test_logit_tables_keep_their_64_leading_values():
+    t = np.array([s * v for v in bd.LOGIT_TABLE for s in (1.0, -1.0)], dtype=np.float32)
+    rng = np.random.default_rng(11)
+    be, bq = torch.from_numpy(t[rng.permutation(64)]), torch.from_numpy(t[rng.permutation(64)])
+    a, b = bd.logit_tables()
+    assert torch.equal(a, be) and torch.equal(b, bq)                # the 64-wide tables as they were
+    for z in (16, 48, 64, 96, 128, 144):
+        e, q = bd.logit_tables(z)
+        n = min(z, 64)
+        assert e.shape == q.shape == (z,) and torch.equal(e[:n], be[:n]) and torch.equal(q[:n], bq[:n])
+        for i in range(64, z, 64):                                  # beyond 64: permutations of the 64-entry tables
+            m = min(64, z - i)
+            assert set(e[i:i + m].tolist()) <= set(be.tolist()) and set(q[i:i + m].tolist()) <= set(bq.tolist())
+            if m == 64:
+                assert sorted(e[i:i + 64].tolist()) == sorted(be.tolist()) and not torch.equal(e[i:i + 64], be)
+        assert bd.pinned_bit_values(z)[3:5] == (z - 1.0, float(z)) and bd.pinned_bit_values(z)[:2] == (0.0, 1.0)
+        assert z / 2 < bd.pinned_bit_values(z)[2] < z - 1 and bd.pinned_bit_values(z)[2] % 1 == 0.5
+    assert bd.pinned_bit_values(64) == bd.PINNED_BITS == (0.0, 1.0, 34.5, 63.0, 64.0, 1000.0)
+    assert bd.pinned_bit_values(48)[2] == 24.5
+
+
 def test_teacher_forced_float32_oracle_meets_the_tie_caps():
     h_dim, B, T = bd.SHAPES[0]
     for draw in bd.DRAWS:

@@ -72,34 +72,50 @@ def on_leg(model, leg, fn):
 @pytest.mark.parametrize("h_dim", [128, 1024])
 def test_pinned_logits(h_dim, var_bit, B, leg):
     """enc.4.weight = prior.4.weight = 0: the logits are the bias tables whatever the mel and the states are."""
-    model = make_model(var_bit, h_dim, pinned="logits")[0]
+    pinned_logits_case(h_dim, bd.Z, var_bit, B, leg)
+
+
+def pinned_logits_case(h_dim, z_dim, var_bit, B, leg, ledger_name="pinned", forward=True, conceal=True):
+    """The body of test_pinned_logits at a model size.  forward / conceal False: that entry point refuses this size (z_dim > h_dim,
+    z_dim > 3 h_dim; tests/test_gpu_coder_sizes.py pins the refusals) and is left out."""
+    Z = z_dim
+    model = make_model(var_bit, h_dim, pinned="logits", z_dim=Z)[0]
     T = 3
-    y, _ = bd.inputs(B, T, seed=B)
-    bits = bd.pinned_bits(B, T) if var_bit else None
-    noise = bd.pinned_noise(B, T)
+    y, _ = bd.inputs(B, T, seed=B, z_dim=Z)
+    bits = bd.pinned_bits(B, T, Z) if var_bit else None
+    noise = bd.pinned_noise(B, T, z_dim=Z)
     r = torch.tensor([0.1, 0.9, 0.2])                              # h2, h, h2 with p_use_gen 0.3
-    c64 = bd.pinned_logits_reference(B, T, bits, noise, torch.float64)
-    c32 = bd.pinned_logits_reference(B, T, bits, noise, torch.float32)
+    c64 = bd.pinned_logits_reference(B, T, bits, noise, torch.float64, Z)
+    c32 = bd.pinned_logits_reference(B, T, bits, noise, torch.float32, Z)
     present = torch.tensor([[(b + t) % 3 != 0 for t in range(T)] for b in range(B)])
     rng = np.random.default_rng(B)
-    recv = torch.from_numpy(rng.integers(0, 2, size=(B, T, 64)).astype(np.float32))
+    recv = torch.from_numpy(rng.integers(0, 2, size=(B, T, Z)).astype(np.float32))
     h0 = torch.from_numpy((0.3 * rng.standard_normal((1, B, h_dim))).astype(np.float32)).to(DEV)
     yd, bd_, nd, rd, pd = y.to(DEV), None if bits is None else bits.to(DEV), noise.to(DEV), recv.to(DEV), present.to(DEV)
 
+    names = ["codes", "prob"] + (["gz", "gprob", "gprior", "gkld", "sz", "sprob", "sprior", "skld"] if forward else []) + (["filled", "prior"] if conceal else [])
+
     def fn():
         codes, _, prob = model.bvrnn.encode(yd, bd_, h0, return_prob=True)
-        _, _, g = model.bvrnn(yd, 0.3, True, bd_, r=r, return_all=True)
-        _, _, s = model.bvrnn(yd, 0.3, False, bd_, r=r, noise=nd, return_all=True)
-        _, _, filled, prior = model.bvrnn.decode(rd, h0, present=pd, bits=bd_, return_codes=True)
-        return (codes, prob, g["z"], g["prob"], g["prior"], g["kld_frames"], s["z"], s["prob"], s["prior"], s["kld_frames"], filled, prior)
+        out = [codes, prob]
+        if forward:
+            _, _, g = model.bvrnn(yd, 0.3, True, bd_, r=r, return_all=True)
+            _, _, s = model.bvrnn(yd, 0.3, False, bd_, r=r, noise=nd, return_all=True)
+            out += [g["z"], g["prob"], g["prior"], g["kld_frames"], s["z"], s["prob"], s["prior"], s["kld_frames"]]
+        if conceal:
+            _, _, filled, prior = model.bvrnn.decode(rd, h0, present=pd, bits=bd_, return_codes=True)
+            out += [filled, prior]
+        return tuple(out)
 
-    out = [o.cpu() for o in on_leg(model, leg, fn)]
-    codes, prob, gz, gprob, gprior, gkld, sz, sprob, sprior, skld, filled, prior = out
-    case = Case("pinned", f"pinned logits h {h_dim} {'var' if var_bit else 'fix'} B {B}")
+    o = dict(zip(names, (t.cpu() for t in on_leg(model, leg, fn))))
+    codes, prob = o["codes"], o["prob"]
+    case = Case(ledger_name, f"pinned logits h {h_dim}{'' if Z == bd.Z else f' z {Z}'} {'var' if var_bit else 'fix'} B {B}")
     label = f"{leg[0]} fold {leg[1]}"
-    be, bq = bd.logit_tables()
-    full = lambda v: v[None, None, :].expand(B, T, 64)
-    for fam, tensors, table, key in (("prob", (prob, gprob, sprob), be, "prob"), ("prior", (gprior, sprior, prior), bq, "prior")):
+    be, bq = bd.logit_tables(Z)
+    full = lambda v: v[None, None, :].expand(B, T, Z)
+    probs = (prob,) + ((o["gprob"], o["sprob"]) if forward else ())
+    priors = ((o["gprior"], o["sprior"]) if forward else ()) + ((o["prior"],) if conceal else ())
+    for fam, tensors, table, key in (("prob", probs, be, "prob"), ("prior", priors, bq, "prior")):
         order = torch.argsort(table, stable=True)
         for tns in tensors:
             assert bool(torch.isfinite(tns).all()) and bool((tns >= 0).all()) and bool((tns <= 1).all()), fam
@@ -108,16 +124,19 @@ def test_pinned_logits(h_dim, var_bit, B, leg):
             case.cmp(fam, tns, full(c64[key]), full(c32[key]), label)
     # codes: the sign of the logit, 0 at logit 0 (half to even), 0.5 where the frame carries no bit
     assert torch.equal(codes.double(), c64["codes"]), int((codes.double() != c64["codes"]).sum())
-    case.cmp("z", gz, c64["z_greedy"], c32["z_greedy"], label + " greedy")
-    case.cmp("z", sz, c64["z_sampled"], c32["z_sampled"], label + " sampled")
-    assert bool(((c64["arg"] - 0.5).abs() >= 1e-3).all())
-    assert torch.equal(torch.round(gz).double()[c64["mask"]], torch.round(c64["z_greedy"])[c64["mask"]])
-    assert torch.equal(torch.round(sz).double()[c64["mask"]], torch.round(c64["z_sampled"])[c64["mask"]])
-    assert bool((gz[~c64["mask"]] == 0.5).all()) and bool((sz[~c64["mask"]] == 0.5).all())
-    case.cmp("kld_frames", gkld, c64["kld_frames"], c32["kld_frames"], label + " greedy")
-    case.cmp("kld_frames", skld, c64["kld_frames"], c32["kld_frames"], label + " sampled")
-    want = torch.where(present[:, :, None], recv.double(), c64["generated"])
-    assert torch.equal(filled.double(), want), int((filled.double() != want).sum())
+    if forward:
+        gz, sz, gkld, skld = o["gz"], o["sz"], o["gkld"], o["skld"]
+        case.cmp("z", gz, c64["z_greedy"], c32["z_greedy"], label + " greedy")
+        case.cmp("z", sz, c64["z_sampled"], c32["z_sampled"], label + " sampled")
+        assert bool(((c64["arg"] - 0.5).abs() >= 1e-3).all())
+        assert torch.equal(torch.round(gz).double()[c64["mask"]], torch.round(c64["z_greedy"])[c64["mask"]])
+        assert torch.equal(torch.round(sz).double()[c64["mask"]], torch.round(c64["z_sampled"])[c64["mask"]])
+        assert bool((gz[~c64["mask"]] == 0.5).all()) and bool((sz[~c64["mask"]] == 0.5).all())
+        case.cmp("kld_frames", gkld, c64["kld_frames"], c32["kld_frames"], label + " greedy")
+        case.cmp("kld_frames", skld, c64["kld_frames"], c32["kld_frames"], label + " sampled")
+    if conceal:
+        want = torch.where(present[:, :, None], recv.double(), c64["generated"])
+        assert torch.equal(o["filled"].double(), want), int((o["filled"].double() != want).sum())
     model.check_status()
     case.close()
 
@@ -128,12 +147,17 @@ def test_pinned_logits(h_dim, var_bit, B, leg):
 @pytest.mark.parametrize("h_dim", [128, 1024])
 def test_pinned_gates(h_dim, B, leg):
     """rnn.weight_ih_l0 = rnn.weight_hh_l0 = 0: r, z and both halves of n are bias tables over {-30 ... 30}, the state follows from h0."""
-    model = make_model(True, h_dim, pinned="gates")[0]
+    pinned_gates_case(h_dim, bd.Z, B, leg)
+
+
+def pinned_gates_case(h_dim, z_dim, B, leg, ledger_name="pinned"):
+    """The body of test_pinned_gates at a model size."""
+    model = make_model(True, h_dim, pinned="gates", z_dim=z_dim)[0]
     T = 3
-    y, bits = bd.inputs(B, T, seed=B)
+    y, bits = bd.inputs(B, T, seed=B, z_dim=z_dim)
     h0 = bd.pinned_h0(B, h_dim)
     rng = np.random.default_rng(B)
-    z = torch.from_numpy(rng.integers(0, 2, size=(B, T, 64)).astype(np.float32)).to(DEV)
+    z = torch.from_numpy(rng.integers(0, 2, size=(B, T, z_dim)).astype(np.float32)).to(DEV)
     yd, bd_, hd = y.to(DEV), bits.to(DEV), h0[None].to(DEV)
 
     def fn():
@@ -146,7 +170,7 @@ def test_pinned_gates(h_dim, B, leg):
 
     e1, d1, all_h, e3, d3 = (o.cpu() for o in on_leg(model, leg, fn))
     h64, h32 = bd.pinned_gates_reference(h0, T, torch.float64), bd.pinned_gates_reference(h0, T, torch.float32)
-    case = Case("pinned", f"pinned gates h {h_dim} B {B}")
+    case = Case(ledger_name, f"pinned gates h {h_dim}{'' if z_dim == bd.Z else f' z {z_dim}'} B {B}")
     label = f"{leg[0]} fold {leg[1]}"
     assert torch.equal(all_h[:, 0], h0)
     case.cmp("h_T", e1, h64[0], h32[0], label + " encode T 1")

@@ -86,7 +86,7 @@ def test_finish_plan_refuses_what_the_library_refuses():
         finish_plan(0, 5, -1, 441)
 
 
-@pytest.mark.parametrize("z", [64, 26, 8, 70])
+@pytest.mark.parametrize("z", [64, 26, 8, 70, 16, 48, 96, 128, 144])
 def test_packet_layout_against_packbits(z):
     """A frame on the wire: ceil(z / 8) bytes for every row; a row with nbits active bits uses the first ceil(nbits / 8) of them, bit i
     in byte i // 8 at position i % 8 - numpy's little bit order - and everything behind nbits is 0."""
