@@ -30,7 +30,7 @@ struct ProbeScope {
     ~ProbeScope();
 };
 
-// ------------------------------------------------------------------ skinny / recurrent GEMM (k_gemm.hip)
+// ------------------------------------------------------------------ skinny / recurrent GEMM (k_gemm.hip; shared device helpers: k_gemm.h)
 // Per-call dynamic state, resident in device memory.  The recurrent-step kernels are captured ONCE
 // into a hipGraph and replayed for every frame, so nothing that changes per call or per frame may be a
 // kernel argument: caller tensors are reached through this descriptor and the frame index `t` is a
@@ -158,8 +158,13 @@ inline TilePlan tile_plan(long long rows, long long column_blocks, const int *he
 }
 // The batched GEMM's cut: one launch of `height`-row tiles (tail_height 0), or full_blocks row blocks of 128 followed by a second
 // launch of tail_height-row tiles for the rows of the last, partly filled round.  cost100: the model's cost in hundredths of a row.
+// A pure function of its arguments (k_gemm_batched.hip): no_tail / no_quarter take the two-launch cut or its quarter tiles out.
 struct GemmCut { int height; int full_blocks; int tail_height; long long tiles, rounds, cost100; };
-GemmCut gemm_batched_cut(int M, int N, int force_height = 0, bool legacy = false);
+GemmCut gemm_batched_cut(int M, int N, int force_height = 0, bool legacy = false, bool no_tail = false, bool no_quarter = false);
+// The environment switches of the batched GEMM, read by gemm_switches() alone (which says when): BVC_NO_LDS_GEMM, BVC_NO_GEMM_TAIL,
+// BVC_NO_GEMM_QUARTER, BVC_TILE_TRACE, BVC_TILE_CUT=legacy, BVC_GEMM_BM (its text, or null)
+struct GemmSwitches { bool no_lds, no_tail, no_quarter, trace, legacy; const char *gemm_bm; };
+GemmSwitches gemm_switches();
 // The offline C = 64 AMP pair's cut: rows per workgroup tile (a compiled TR) for L output rows x B items
 TilePlan amp_pair_cut(long long L, int B, int ks, int force_height = 0, bool legacy = false);
 // what the last launch_gemm_batched / offline C = 64 launch_amp_pair of this process chose (tests)
@@ -168,12 +173,14 @@ void tile_trace(const char *what, long long rows, long long cols, int height, in
 extern GemmCut g_last_gemm_cut;
 extern TilePlan g_last_amp_cut;
 
+// ------------------------------------------------------------------ batched GEMM (k_gemm_batched.hip)
 // batched GEMM over all frames: y = act(x @ w^T + bias), M large.  out_mode (GemmOut) says where the rows go:
-// see out_index() in k_gemm.hip.  frames_T = frames per utterance, mt16 = utterances rounded up to 16.
+// see out_index() in k_gemm_batched.hip.  frames_T = frames per utterance, mt16 = utterances rounded up to 16.
 enum GemmOut { GO_NATURAL = 0, GO_FRAME_MAJOR_ROWS = 1, GO_PACKED_FRAMES = 2, GO_PACKED_FROM_UTT = 3 };
 int launch_gemm_batched(const float *x, long long ldx, const float *w, long long ldw, const float *bias,
                         int M, int N, int K, int act, float *y, long long ldy, hipStream_t s,
                         int out_mode = GO_NATURAL, long long frames_T = 0, int mt16 = 0);
+// ------------------------------------------------------------------ row-wise utilities (k_rows.hip)
 // yn = (y - mean) / std over rows of length n (bvrnn.py:173)
 int launch_normalize_rows(const float *y, const float *mean, const float *stdv, long long rows, int n,
                           float *out, hipStream_t s);

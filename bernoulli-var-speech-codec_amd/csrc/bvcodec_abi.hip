@@ -402,7 +402,8 @@ int bvc_test_tile_plan(int32_t kind, int64_t rows, int32_t column_blocks, int32_
     const bool last = mode == -1, legacy = mode == 1;
     const int force = mode >= 16 ? mode : 0;
     if (kind == 0) {
-        const GemmCut c = last ? g_last_gemm_cut : gemm_batched_cut((int)rows, column_blocks * 128, force, legacy);
+        const GemmSwitches sw = gemm_switches();
+        const GemmCut c = last ? g_last_gemm_cut : gemm_batched_cut((int)rows, column_blocks * 128, force, legacy, sw.no_tail, sw.no_quarter);
         out[0] = c.height; out[1] = c.full_blocks; out[2] = c.tail_height; out[3] = c.tiles; out[4] = c.rounds; out[5] = c.cost100;
         return BVC_OK;
     }

@@ -28,11 +28,10 @@
 //
 // Measured form of the hand-off: MI355X_MICROARCH.md (valid forms: sc1 stores, sc1 loads, data-tagged
 // granules), tools/persist_bench.hip (3.3-3.8 us per 1024x1024 layer against 4.25 launch-per-layer).
-#include "bvc_internal.h"
+#include "k_gemm.h"             // f32x4, mfma16, elu1, sigmoid1: one definition for every kernel that computes a layer
 
 namespace bvc {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -102,12 +101,6 @@ namespace {
 //       that way, the linear layers' epilogue is not bound by its instruction count
 //   resident rounds of the GRU stream, other request orders, fences in the chain kernels: r04
 constexpr int AUX_SC1 = 16;
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float elu1(float v) { return v > 0.0f ? v : expf(v) - 1.0f; }
-__device__ __forceinline__ float sigmoid1(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // the status word lives in host-mapped pinned memory (the host reads it without synchronising): a plain system-scope store
 __device__ __forceinline__ void flow_report(unsigned *status, unsigned code) {

@@ -12,7 +12,8 @@ and run
 Each .s is read together with the .remarks next to it (same path, other suffix).  A side may be several files (a source that
 was split).  Kernels are matched by demangled name.  For every matched kernel the resource figures of the remarks must be equal
 and the instruction streams - what is left of the function's text when comments, labels, directives and blank lines are
-stripped and the function's number is taken out of its local labels - are compared as text.  A kernel whose stream differs is
+stripped and the function's number is taken out of its local labels (and the file-wide one out of a long branch's `.Lpost_getpc`
+anchor, which follows the order in which the file's kernels are emitted) - are compared as text.  A kernel whose stream differs is
 listed with its instruction counts per class on both sides.  --dropped names kernels (a substring of the demangled name) that
 the branch removes on purpose; any other missing or added kernel is a failure.  Exit status 0: nothing differs.
 """
@@ -69,7 +70,9 @@ def read_streams(path):
         code = line.split(";")[0].strip()
         if not code or code.startswith(".") or code.endswith(":"):
             continue
-        cur.append(re.sub(r"\.L(BB|JTI|tmp)\d+_", r".L\1_", re.sub(r"\s+", " ", code)))
+        code = re.sub(r"\.L(BB|JTI|tmp)\d+_", r".L\1_", re.sub(r"\s+", " ", code))
+        # the anchor label of a long branch is numbered through the whole file, in the order the kernels are emitted
+        cur.append(re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", code))
     return out
 
 
