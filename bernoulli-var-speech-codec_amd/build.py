@@ -9,8 +9,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libbvcodec_hip.so")
-SOURCES = ["bvcodec_abi.hip", "model.hip", "recurrence.hip", "generator.hip", "stream_codec.hip", "k_gemm.hip", "k_gemm_batched.hip", "k_rows.hip", "k_flow.hip", "k_frontend.hip", "k_vocoder.hip", "k_vocoder_amp.hip"]
-HEADERS = ["bvc_internal.h", "bvc_host.h", "k_gemm.h", "k_vocoder.h", os.path.join("..", "..", "include", "bvcodec.h")]
+SOURCES = ["bvcodec_abi.hip", "model.hip", "recurrence.hip", "generator.hip", "stream_codec.hip", "k_gemm.hip", "k_gemm_batched.hip", "k_rows.hip", "k_flow.hip", "k_flow_support.hip", "k_frontend.hip", "k_vocoder.hip", "k_vocoder_amp.hip"]
+HEADERS = ["bvc_internal.h", "bvc_host.h", "k_gemm.h", "k_flow_handoff.h", "k_flow_layers.h", "k_flow_gru.h", "k_vocoder.h", os.path.join("..", "..", "include", "bvcodec.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 
@@ -32,7 +32,7 @@ def build(force=False, verbose=True):
         if force or _stale(o, [s] + hdrs):
             extra = (["-mllvm", "-amdgpu-kernarg-preload-count=16"]
                      if (src == "k_gemm.hip" and os.environ.get("BVC_KERNARG_PRELOAD", "0") == "1") else [])
-            if src == "k_flow.hip" and os.environ.get("BVC_FLOW_WAVES"):       # experiments: register budget of the persistent kernel
+            if src == "k_flow.hip" and os.environ.get("BVC_FLOW_WAVES"):       # experiments: register budget of the persistent kernel (bvrnn_flow_kernel is in that file)
                 extra = extra + ["-DBVC_FLOW_WAVES_PER_SIMD=" + os.environ["BVC_FLOW_WAVES"]]
             cmd = [hipcc] + FLAGS + extra + ["-c", s, "-o", o]
             if verbose:

@@ -67,7 +67,7 @@ struct bvc_model {
     unsigned amp_kernels = bvc::AMPK_ALL;   // stage-specific generator kernels in use (options vocoder_full_tiles / vocoder_c16_kernel)
     bool precomp_pz = true;     // decode: the phi_z halves of dec.0 and of the GRU input product are batched over all frames
     int mtw = 1;                // 16-row tiles per workgroup in the recurrent kernels (BVC_MTW = 1 | 2 | 4)
-    // persistent recurrence (k_flow.hip): hop tables of encode / decode, resident in device memory
+    // persistent recurrence (k_flow.hip, its device code in k_flow_handoff.h / k_flow_layers.h / k_flow_gru.h): hop tables of encode / decode, resident in device memory
     // recurrence schedule: RS_PERSISTENT one launch per call (k_flow.hip), RS_LAYERS one launch per layer (hipGraph replay),
     // RS_AUTO (default) persistent while calls come one at a time, layers while calls of several streams overlap
     int recurrence = 2;         // BVC_RECURRENCE=persistent|layers|auto, bvc_model_set_option("recurrence")
@@ -223,6 +223,10 @@ inline int flow_grid_tiles(const bvc_model *m) {          // feature tiles cover
     const int H = m->cfg.h_dim, X = m->cfg.num_mels, Z = m->cfg.z_dim;
     return ((H > X ? (H > Z ? H : Z) : (X > Z ? X : Z)) / 16 + 7) / 8 * 8;
 }
+// The environment switches of the persistent recurrence, read by flow_switches() alone (recurrence.hip, which says when): BVC_FLOW_HOTW,
+// BVC_FLOW_FILL, BVC_FLOW_TICKETS, BVC_FLOW_NO_CHAINS; with `probing` also BVC_PROBE_WG and BVC_PROBE_WAVE (0 / 0 otherwise)
+struct FlowSwitches { bool hot_w, fill, no_chains; int tickets, probe_wg, probe_wave; };
+FlowSwitches flow_switches(bool probing = false);
 int flow_chains_static(const bvc_model *m, int B);      // 0: not usable; else utterance groups per workgroup
 
 int run_encode(const bvc_model *m, const Workspace &w, void *ws_base, const float *d_mel, const float *d_bits, const float *d_h0, int B,

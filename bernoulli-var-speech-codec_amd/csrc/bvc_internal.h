@@ -192,12 +192,12 @@ int launch_copy_rows(const float *src, long long lds, float *dst, long long ldd,
 // natural [rows][n] (row stride ld) <-> fragment-packed [rows/16][n/16][64][4]; dir 0: pack, 1: unpack
 int launch_repack_rows(const float *src, float *dst, long long ld_natural, int rows, int n, int dir, hipStream_t s);
 
-// ------------------------------------------------------------------ persistent recurrence (k_flow.hip)
+// ------------------------------------------------------------------ persistent recurrence (k_flow.hip, k_flow_support.hip)
 // All frames of BVRNN.encode / BVRNN.decode in one launch; layers are chained by "poisoned buffer" dataflow
-// (see k_flow.hip).  Activations live in the flow region of the workspace: FlowBuf id, frame parity ->
+// (see k_flow_handoff.h).  Activations live in the flow region of the workspace: FlowBuf id, frame parity ->
 // flow + (id * 2 + parity) * slot_bytes, each a fragment-packed [MT16][dim] matrix.
 constexpr unsigned FLOW_POISON = 0xFFFFDEADu;      // a NaN bit pattern no layer may publish as data
-constexpr int FLOW_STAMPS = 6;                     // stamp kinds per layer and frame (k_flow.hip: flow_stamp)
+constexpr int FLOW_STAMPS = 6;                     // stamp kinds per layer and frame (k_flow_layers.h: flow_stamp)
 enum FlowEpi { FE_ELU = 0, FE_CODE = 1, FE_MEL = 2, FE_GRU = 3, FE_ELU_KEEP = 4, FE_CODE_SEL = 5 };   // FE_ELU_KEEP: ELU, and the result also goes to FlowArgs::keep
                                                                                      // FE_CODE_SEL: FE_CODE of the concealing decoder (CS_SELECT)
 enum FlowBuf { FB_H = 0, FB_E1, FB_E2, FB_ZC, FB_Q1, FB_Q2, FB_Q3, FB_D1, FB_D2, FB_D3, FB_DN, FB_G1, FB_G2, FB_G3, FB_COUNT };
@@ -241,8 +241,30 @@ struct FlowArgs {
     // filled codes (may be codes_in itself), `prob` the prior's probabilities
     const float *codes_in;
 };
+// The persistent kernels' dynamic LDS, defined once: the kernel takes its regions' offsets from here (in floats; NW waves per workgroup,
+// a wave's partial 16 x 16 tile is 256 floats), the launch table its bytes per form, the census kernel the filler form's bytes.
+enum FlowForm { FF_PLAIN = 0, FF_FILL = 1, FF_CHAINS = 2, FF_CHAINS_FOLDED = 3 };      // chains: several utterance groups per workgroup (FlowArgs::MG > 1)
+template <int NW>
+struct FlowLds {
+    static constexpr int partials = 0;                          // [2][NW][256] layer partials, slot = hop & 1
+    static constexpr int gru = partials + 2 * NW * 256;         // [NW][6][256] GRU partials
+    static constexpr int plain_end = gru + NW * 6 * 256;
+    static constexpr int chain = plain_end;                     // chains: [2][4][NW][256] partial tiles of a group of chains
+    static constexpr int chain_end = chain + 2 * 4 * NW * 256;
+    // Filler kernels: the waves' operand stashes lie over the GRU partials - the stashes are dead from the last quantum (layer 9) to the
+    // next frame's first layer, whose operand, h(t+1), exists only after wave 0 has read the partials
+    static constexpr int stash = gru;                           // [NW][8][256], a wave's blocks at stride PERH * 256
+    static constexpr int park = stash + NW * 8 * 256;           // [NW][8][256] the first layer's parked weights (BVC_FLOW_PARKL)
+    static constexpr int flag = park + NW * 8 * 256;            // hop count of wave 0's last publishing store (BVC_FLOW_PARTNER_WAIT), 16 bytes
+    static constexpr int fill_end = flag + 4;
+    static constexpr size_t bytes(int form) { return sizeof(float) * (form == FF_PLAIN ? plain_end : form == FF_FILL ? fill_end : chain_end); }
+};
+static_assert(FlowLds<8>::bytes(FF_PLAIN) == 64 * 1024 && FlowLds<8>::bytes(FF_CHAINS) == 128 * 1024 && FlowLds<8>::bytes(FF_CHAINS_FOLDED) == 128 * 1024 &&
+              FlowLds<8>::bytes(FF_FILL) == 144 * 1024 + 16, "64 / 128 / 144 KiB (+ the flag) of a compute unit's 160");
 int flow_kernels_init();
+int flow_census_init();       // (k_flow_support.hip; called by flow_kernels_init)
 int flow_perh(int h_dim);
+int launch_flow_set_args(const FlowArgs &a, FlowArgs *d_args, hipStream_t s);         // the device copy of the arguments alone (k_flow_support.hip)
 int launch_flow(const FlowArgs &a, FlowArgs *d_args, int perh, bool encode, bool fill, hipStream_t s, bool args_resident = false,
                 bool conceal = false);
 // sentinel fill of the flow region + initial state into its first buffer + the device copy of the arguments, in one kernel

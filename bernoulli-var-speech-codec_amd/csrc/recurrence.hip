@@ -460,7 +460,8 @@ int run_flow(const bvc_model *m, const Workspace &w, bool encode, int chains, co
     a.mean = m->mean_mel; a.stdv = m->std_mel;
     a.var_bit = m->cfg.var_bit;
     a.status = m->d_status;
-    { static const bool hot = getenv("BVC_FLOW_HOTW") != nullptr; a.dbg_hot_w = hot ? 1 : 0; }
+    const FlowSwitches sw = flow_switches(g_kprobe.enabled);
+    a.dbg_hot_w = sw.hot_w ? 1 : 0;
     a.spin_limit = m->flow_spin_limit;
     a.dbg_withhold = m->flow_debug_withhold;
     if (g_kprobe.enabled) {                    // bench instrumentation: per-layer entry / exit stamps of workgroup 0
@@ -470,8 +471,8 @@ int run_flow(const bvc_model *m, const Workspace &w, bool encode, int chains, co
         BVC_HIP_TRY(hipMemsetAsync(g_kprobe.dev, 0, need * sizeof(unsigned long long), s));
         g_kprobe.T = T; g_kprobe.nodes = nodes;
         a.probe = g_kprobe.dev; a.probe_nodes = nodes; a.probe_first = encode ? 1 : 7;
-        a.probe_wg = getenv("BVC_PROBE_WG") ? atoi(getenv("BVC_PROBE_WG")) : 0;
-        a.probe_wave = getenv("BVC_PROBE_WAVE") ? atoi(getenv("BVC_PROBE_WAVE")) & 7 : 0;
+        a.probe_wg = sw.probe_wg;
+        a.probe_wave = sw.probe_wave;
     }
     // the flow region filled with the sentinel, h(-1) in its first buffer (FB_H, parity 0, at the start of the region) and the device copy
     // of the arguments: one kernel (a misaligned initial state takes the three separate ones)
@@ -490,15 +491,14 @@ int run_flow(const bvc_model *m, const Workspace &w, bool encode, int chains, co
         int dev = 0;
         BVC_HIP_TRY(hipGetDevice(&dev));
         dev &= 15;
-        static const int tickets = (getenv("BVC_FLOW_TICKETS") && atoi(getenv("BVC_FLOW_TICKETS")) == 2) ? 2 : 1;
+        const int tickets = sw.tickets;
         hipEvent_t &ev = g_flow_ev[dev][g_flow_n[dev] % tickets];        // the launch `tickets` launches ago must have finished
         if (!ev) BVC_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         if (g_flow_n[dev] >= (unsigned long long)tickets) BVC_HIP_TRY(hipStreamWaitEvent(s, ev, 0));
         for (auto &f : g_fence[dev])
             if (f.pending) { BVC_HIP_TRY(hipStreamWaitEvent(s, f.ev, 0)); f.pending = false; }
         ProbeScope probe(PK_LINEAR, s);
-        static const bool fill = !(getenv("BVC_FLOW_FILL") && getenv("BVC_FLOW_FILL")[0] == '0');
-        if ((rc = launch_flow(a, w.flow_args, m->flow_perh, encode, fill && !m->flow_debug_nofill && a.MG == 1, s, fused_prepare, conceal))) return rc;
+        if ((rc = launch_flow(a, w.flow_args, m->flow_perh, encode, sw.fill && !m->flow_debug_nofill && a.MG == 1, s, fused_prepare, conceal))) return rc;
         BVC_HIP_TRY(hipEventRecord(ev, s));
         ++g_flow_n[dev];
     }
@@ -688,6 +688,24 @@ thread_local bool g_stream_tick = false;
 thread_local bool g_tick_flow = false;
 std::mutex g_flow_mu;
 
+// ---- the switches of the persistent recurrence (host only), all read here and nowhere else:
+//   once per process    BVC_FLOW_HOTW        experiments: every weight request hits the same blocks (wrong results; FlowArgs::dbg_hot_w)
+//                       BVC_FLOW_FILL=0      the plain kernels instead of the filler form
+//                       BVC_FLOW_TICKETS=2   two persistent launches may be in flight per device instead of one
+//                       BVC_FLOW_NO_CHAINS   batches beyond one chain per workgroup take the launch-per-layer schedule
+//   at every call that stamps (probing)      BVC_PROBE_WG / BVC_PROBE_WAVE: which workgroup / wave records the stamps (default 0 / 0)
+FlowSwitches flow_switches(bool probing) {
+    static const bool hot_w = getenv("BVC_FLOW_HOTW") != nullptr, fill = !(getenv("BVC_FLOW_FILL") && getenv("BVC_FLOW_FILL")[0] == '0'),
+                      no_chains = getenv("BVC_FLOW_NO_CHAINS") != nullptr;
+    static const int tickets = (getenv("BVC_FLOW_TICKETS") && atoi(getenv("BVC_FLOW_TICKETS")) == 2) ? 2 : 1;
+    FlowSwitches sw = {hot_w, fill, no_chains, tickets, 0, 0};
+    if (probing) {
+        sw.probe_wg = getenv("BVC_PROBE_WG") ? atoi(getenv("BVC_PROBE_WG")) : 0;
+        sw.probe_wave = getenv("BVC_PROBE_WAVE") ? atoi(getenv("BVC_PROBE_WAVE")) & 7 : 0;
+    }
+    return sw;
+}
+
 // The persistent kernel needs every one of its workgroups resident (they wait for each other) and a workgroup takes a whole
 // compute unit (8 waves x 256 VGPRs): utterance groups x feature tiles must not exceed the device's CU count (256 on MI355X:
 // up to 64 utterances at h_dim 1024).  Anything else takes the launch-per-layer schedule.
@@ -700,8 +718,7 @@ int flow_chains_static(const bvc_model *m, int B) {      // 0: not usable; else 
     if (slots <= 0) return 0;
     const int mg = (mt + slots - 1) / slots;
     if (mg <= 1) return 1;
-    static const bool no_multi = getenv("BVC_FLOW_NO_CHAINS") != nullptr;
-    if (no_multi || m->flow_perh != 8 || mg > FLOW_MAX_CHAINS) return 0;
+    if (flow_switches().no_chains || m->flow_perh != 8 || mg > FLOW_MAX_CHAINS) return 0;
     return mg;
 }
 

@@ -1,4 +1,5 @@
-"""Builds variant libraries of the persistent recurrence (k_flow.hip with extra -D switches) next to the product library, and
+"""Builds variant libraries of the persistent recurrence (k_flow.hip, which holds the kernel and includes its device code from
+k_flow_handoff.h / k_flow_layers.h / k_flow_gru.h, with extra -D switches) next to the product library, and
 times them against each other on the GPU box.
 
     python tools/flow_variants.py build base: depth2:-DBVC_GRU_DEPTH=2 "g2diag:-DBVC_CHAIN_G=2 -DBVC_FLOW_DIAG=1"     (here: cross-compiles)

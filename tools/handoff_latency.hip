@@ -1,5 +1,5 @@
 // What does a hand-off between two workgroups cost on an MI355X?  The persistent recurrence kernel publishes a 1 KiB block with
-// system-scope (sc1) buffer stores and its consumers poll / fetch it with sc1 buffer loads (k_flow.hip: flow_publish, flow_wait, flow_issue);
+// system-scope (sc1) buffer stores and its consumers poll / fetch it with sc1 buffer loads (k_flow_layers.h: flow_publish; k_flow_handoff.h: flow_wait, flow_issue);
 // the L2s of the eight XCDs are not coherent with each other, so both go through the fabric.  Here workgroup A (XCD 0) and workgroup B
 // (on XCD x) play ping-pong with exactly those instructions:  A stores block i, B polls its last dword (32 bytes per poll), fetches the
 // block, stores its own block i; A polls and fetches that.  One round = two hand-offs.  Workgroups land on XCD (blockIdx % 8).
