@@ -83,6 +83,17 @@ SIGNATURES = {
     "bvc_decode_ragged": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _f, _vp, _vp, _sz, _vp]),
     "bvc_resample_poly": (ctypes.c_int, [_vp, _i32, _i64, _vp, _i32, _i32, _i32, _i64, _vp, _i64, _vp]),
     "bvc_peak_normalize": (ctypes.c_int, [_vp, _i32, _i64, _vp]),
+    "bvc_resampler_create": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_vp)]),
+    "bvc_resampler_destroy": (None, [_vp]),
+    "bvc_resampler_set_taps": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), _i32]),
+    "bvc_resampler_open": (ctypes.c_int, [_vp, _i32, _i32]),
+    "bvc_resampler_close": (ctypes.c_int, [_vp, _i32]),
+    "bvc_resampler_end": (ctypes.c_int, [_vp, _i32, _i32]),
+    "bvc_resampler_push": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i64, ctypes.POINTER(_i32), _vp]),
+    "bvc_resampler_flush": (ctypes.c_int, [_vp, _i32, _vp, ctypes.POINTER(_i32), _vp]),
+    "bvc_resampler_count": (_i64, [_i32, _i32, _i64]),
+    "bvc_resampler_lag": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    "bvc_resampler_taps": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(ctypes.c_double), _i32]),
     "bvc_pack_codes": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _vp, _vp]),
     "bvc_unpack_codes": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _vp, _vp]),
     "bvc_probe_begin": (ctypes.c_int, [_i32, _i32, _i32]),

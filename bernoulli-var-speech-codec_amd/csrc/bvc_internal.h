@@ -306,6 +306,25 @@ int launch_ragged_mask(float *codes, const long long *lens, int B, long long L, 
 int launch_resample_poly(const float *x, int B, long long Lin, const double *h, int ntaps, int up, int down,
                          long long n_pre_remove, float *y, long long n_out, hipStream_t s);
 int launch_peak_normalize(float *x, int B, long long L, hipStream_t s);
+
+// ---- streaming resampler (k_resample_stream.hip; its host side, bvc_resampler_*, is resampler.hip)
+// Outputs that N inputs of a row complete: E(N) = max(0, ceil(N up / down) - n_pre_remove); the lag-delayed stream
+// zeros(n_pre_remove) ++ y has ceil(N up / down) of its samples then.  The one copy, for the host's counts and the kernel's.
+__host__ __device__ inline long long rs_ceil_mul(long long n, int up, int down) { return (n * up + down - 1) / down; }
+__host__ __device__ inline long long rs_count(long long n, int up, int down, int n_pre_remove, bool delayed) {
+    const long long c = rs_ceil_mul(n, up, down);
+    return delayed ? c : (c > n_pre_remove ? c - n_pre_remove : 0);
+}
+struct RsRow { long long n; int run, start, valid, pad_; };     // device state of a row: inputs so far; running; where it starts in the
+                                                                // next chunk; how many of that chunk's samples are its (-1: all)
+const int RS_LIST = 64;                                         // row changes per launch: they travel as a kernel argument
+struct RsUpdate { int row, run, start, valid, reset, pad_[3]; };
+struct RsUpdateList { int n; int pad_[3]; RsUpdate e[RS_LIST]; };
+struct RsFilter { const double *h; int ntaps, up, down, n_pre_remove, H; };      // H = ceil(ntaps / up) inputs of history per row
+struct RsCall { const void *x; long long xs; void *y; long long ys, yoff; int n_in, n_fill, fmt_in, fmt_out, delayed, flush_row; };
+int launch_rs_update(const RsUpdateList &l, RsRow *ctl, float *hist, int H, hipStream_t s);
+int launch_rs_push(const RsFilter &f, const RsCall &c, RsRow *ctl, float *hist, int B, hipStream_t s);
+
 int launch_pack_codes(const float *codes, long long frames, int z, int nbits, unsigned char *out, hipStream_t s);
 int launch_unpack_codes(const unsigned char *in, long long frames, int z, int nbits, float *codes, hipStream_t s);
 // the same wire format with every row's own bit count (directed streaming sessions): packets (B, kstride, nbytes) with nbytes = ceil(z / 8)

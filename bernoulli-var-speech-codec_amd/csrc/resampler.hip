@@ -1,0 +1,326 @@
+// bvc_resampler_* (include/bvcodec.h): the host side of the streaming resampler - the filter design, the rows' book and the two
+// launches of a push.  Host only; the kernels are in k_resample_stream.hip.
+#include <cmath>
+
+#include "bvc_internal.h"
+
+using namespace bvc;
+
+namespace {
+
+// ---- the filter: bvcodec.preprocess.design(rate_out, rate_in), i.e. what scipy.signal.resample_poly(x, rate_out, rate_in) designs
+struct Geometry { int up, down, half_len, n_pre_pad, n_pre_remove, ntaps, H; };
+
+int gcd_i(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
+
+bool geometry(int rate_in, int rate_out, Geometry *g) {
+    if (rate_in <= 0 || rate_out <= 0) return false;
+    const int d = gcd_i(rate_in, rate_out);
+    g->up = rate_out / d; g->down = rate_in / d;
+    const int max_rate = g->up > g->down ? g->up : g->down;
+    if (max_rate > (1 << 20)) return false;                  // (coprime rates of millions: 20 * max_rate taps)
+    g->half_len = 10 * max_rate;
+    g->n_pre_pad = g->down - g->half_len % g->down;
+    g->n_pre_remove = (g->half_len + g->n_pre_pad) / g->down;
+    g->ntaps = g->n_pre_pad + 2 * g->half_len + 1;
+    g->H = (g->ntaps + g->up - 1) / g->up;
+    return true;
+}
+
+// numpy's i0 on [0, 8] (Clenshaw's Chebyshev series, the coefficients of Cephes' i0 as numpy.i0 carries them), in numpy's order
+const double I0A[30] = {
+    -4.4153416464793395e-18, 3.3307945188222384e-17, -2.431279846547955e-16, 1.715391285555133e-15, -1.1685332877993451e-14,
+    7.676185498604936e-14, -4.856446783111929e-13, 2.95505266312964e-12, -1.726826291441556e-11, 9.675809035373237e-11,
+    -5.189795601635263e-10, 2.6598237246823866e-09, -1.300025009986248e-08, 6.046995022541919e-08, -2.670793853940612e-07,
+    1.1173875391201037e-06, -4.4167383584587505e-06, 1.6448448070728896e-05, -5.754195010082104e-05, 0.00018850288509584165,
+    -0.0005763755745385824, 0.0016394756169413357, -0.004324309995050576, 0.010546460394594998, -0.02373741480589947,
+    0.04930528423967071, -0.09490109704804764, 0.17162090152220877, -0.3046826723431984, 0.6767952744094761};
+
+double i0_small(double x) {
+#pragma clang fp contract(off)
+    const double y = x / 2.0 - 2.0;
+    double b0 = I0A[0], b1 = 0.0, b2 = 0.0;
+    for (int i = 1; i < 30; ++i) { b2 = b1; b1 = b0; b0 = y * b1 - b2 + I0A[i]; }
+    return std::exp(x) * (0.5 * (b0 - b2));
+}
+
+// numpy's add.reduce over a contiguous float64 array (pairwise, blocks of 128 with eight partial sums)
+double pairwise_sum(const double *a, long long n) {
+#pragma clang fp contract(off)
+    if (n < 8) {
+        double res = 0.0;
+        for (long long i = 0; i < n; ++i) res += a[i];
+        return res;
+    }
+    if (n <= 128) {
+        double r[8];
+        for (int j = 0; j < 8; ++j) r[j] = a[j];
+        long long i = 8;
+        for (; i < n - (n % 8); i += 8)
+            for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) res += a[i];
+        return res;
+    }
+    long long n2 = n / 2;
+    n2 -= n2 % 8;
+    return pairwise_sum(a, n2) + pairwise_sum(a + n2, n - n2);
+}
+
+// h (g.ntaps doubles): n_pre_pad zeros, then firwin(2 half_len + 1, 1 / max_rate, window=("kaiser", 5.0)) * up, as preprocess.design
+// computes it in numpy float64, operation for operation.  Equal rates: the unit impulse (preprocess.resample_poly copies there).
+void design_taps(const Geometry &g, double *h) {
+#pragma clang fp contract(off)
+    const int numtaps = 2 * g.half_len + 1;
+    double *w = h + g.n_pre_pad;
+    for (int i = 0; i < g.n_pre_pad; ++i) h[i] = 0.0;
+    if (g.up == 1 && g.down == 1) {
+        for (int i = 0; i < numtaps; ++i) w[i] = i == g.half_len ? 1.0 : 0.0;
+        return;
+    }
+    const double pi = 3.141592653589793;
+    const double cutoff = 1.0 / (double)(g.up > g.down ? g.up : g.down);
+    const double alpha = (numtaps - 1) / 2.0, beta = 5.0, i0_beta = i0_small(beta);
+    for (int i = 0; i < numtaps; ++i) {
+        const double m = (double)i - alpha;
+        const double cm = cutoff * m;
+        const double y = pi * (cm == 0.0 ? 1.0e-20 : cm);
+        const double sinc = std::sin(y) / y;
+        const double q = ((double)i - alpha) / alpha;
+        const double kaiser = i0_small(std::fabs(beta * std::sqrt(1.0 - q * q))) / i0_beta;
+        w[i] = cutoff * sinc * kaiser;
+    }
+    const double sum = pairwise_sum(w, numtaps);
+    for (int i = 0; i < numtaps; ++i) w[i] = w[i] / sum * (double)g.up;
+}
+
+enum { ROW_IDLE = 0, ROW_RUNNING = 1, ROW_ENDED = 2 };
+const int FMT_MASK = 15;
+
+}  // namespace
+
+struct bvc_resampler {
+    int B = 0, max_in = 0, fmt_in = 0, fmt_out = 0;
+    bool delayed = false;
+    Geometry g{};
+    double *d_h = nullptr;
+    float *d_hist = nullptr;
+    RsRow *d_ctl = nullptr;
+    // the book: what the device holds for a row once the pending changes have been sent
+    struct Row { int state = ROW_IDLE; long long n = 0; int start = 0, valid = -1; bool dirty = false, reset = false; };
+    std::vector<Row> rows;
+    int n_dirty = 0;
+    ~bvc_resampler() {
+        if (d_h) (void)hipFree(d_h);
+        if (d_hist) (void)hipFree(d_hist);
+        if (d_ctl) (void)hipFree(d_ctl);
+    }
+};
+
+namespace {
+
+int row_arg(const bvc_resampler *r, int row, const char *fn) {
+    if (!r) { set_error("%s: null resampler", fn); return BVC_EINVAL; }
+    if (row < 0 || row >= r->B) { set_error("%s: row %d outside 0..%d", fn, row, r->B - 1); return BVC_EINVAL; }
+    return BVC_OK;
+}
+
+void mark(bvc_resampler *r, bvc_resampler::Row &w) {
+    if (!w.dirty) { w.dirty = true; ++r->n_dirty; }
+}
+
+// the changed rows -> device, RS_LIST rows per launch, ahead of the push or flush on its stream
+int send_changes(bvc_resampler *r, hipStream_t s) {
+    RsUpdateList l;
+    l.n = 0;
+    for (int b = 0; b < r->B && r->n_dirty > 0; ++b) {
+        bvc_resampler::Row &w = r->rows[b];
+        if (!w.dirty) continue;
+        l.e[l.n++] = RsUpdate{b, w.state == ROW_RUNNING ? 1 : 0, w.start, w.valid, w.reset ? 1 : 0, {0, 0, 0}};
+        w.dirty = w.reset = false;
+        --r->n_dirty;
+        if (l.n == RS_LIST) {
+            if (int rc = launch_rs_update(l, r->d_ctl, r->d_hist, r->g.H, s)) return rc;
+            l.n = 0;
+        }
+    }
+    r->n_dirty = 0;
+    return launch_rs_update(l, r->d_ctl, r->d_hist, r->g.H, s);
+}
+
+RsFilter filter_of(const bvc_resampler *r) { return RsFilter{r->d_h, r->g.ntaps, r->g.up, r->g.down, r->g.n_pre_remove, r->g.H}; }
+
+}  // namespace
+
+extern "C" {
+
+int64_t bvc_resampler_count(int32_t rate_in, int32_t rate_out, int64_t n_inputs) {
+    Geometry g;
+    if (!geometry(rate_in, rate_out, &g) || n_inputs < 0) { set_error("bvc_resampler_count: rates must be positive, n_inputs not negative"); return BVC_EINVAL; }
+    return rs_count(n_inputs, g.up, g.down, g.n_pre_remove, false);
+}
+
+int bvc_resampler_lag(int32_t rate_in, int32_t rate_out, int32_t *n_pre_remove, int32_t *history) {
+    Geometry g;
+    if (!geometry(rate_in, rate_out, &g)) { set_error("bvc_resampler_lag: rates must be positive"); return BVC_EINVAL; }
+    if (n_pre_remove) *n_pre_remove = g.n_pre_remove;
+    if (history) *history = g.H;
+    return BVC_OK;
+}
+
+int bvc_resampler_taps(int32_t rate_in, int32_t rate_out, double *h_taps, int32_t capacity) {
+    Geometry g;
+    if (!geometry(rate_in, rate_out, &g)) { set_error("bvc_resampler_taps: rates must be positive"); return BVC_EINVAL; }
+    if (h_taps && capacity >= g.ntaps) design_taps(g, h_taps);
+    return g.ntaps;
+}
+
+int bvc_resampler_create(int32_t B, int32_t rate_in, int32_t rate_out, int32_t max_in, int32_t fmt_in, int32_t fmt_out, bvc_resampler **out) {
+    Geometry g;
+    const int fo = fmt_out & FMT_MASK;
+    if (!out || B <= 0 || max_in <= 0 || !geometry(rate_in, rate_out, &g) || (fmt_in != BVC_PCM_F32 && fmt_in != BVC_PCM_S16) ||
+        (fo != BVC_PCM_F32 && fo != BVC_PCM_S16) || (fmt_out & ~(FMT_MASK | BVC_PCM_DELAYED))) {
+        set_error("bvc_resampler_create: B, max_in and both rates must be positive, the formats BVC_PCM_F32 or BVC_PCM_S16");
+        return BVC_EINVAL;
+    }
+    if ((size_t)(g.H + (long long)max_in) * sizeof(float) > 64 * 1024) {
+        set_error("bvc_resampler_create: history %d + max_in %d samples do not fit the 64 KiB of LDS a push stages them in", g.H, (int)max_in);
+        return BVC_EINVAL;
+    }
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+        (void)hipGetLastError();
+        set_error("bvc_resampler_create: no HIP device");
+        return BVC_ENODEVICE;
+    }
+    bvc_resampler *r = new (std::nothrow) bvc_resampler;
+    if (!r) { set_error("bvc_resampler_create: out of host memory"); return BVC_ENOMEM; }
+    r->B = B; r->max_in = max_in; r->fmt_in = fmt_in; r->fmt_out = fo; r->delayed = (fmt_out & BVC_PCM_DELAYED) != 0;
+    r->g = g;
+    r->rows.resize(B);
+    std::vector<double> h(g.ntaps);
+    design_taps(g, h.data());
+    const size_t hist_bytes = (size_t)B * g.H * sizeof(float), ctl_bytes = (size_t)B * sizeof(RsRow);
+    std::vector<RsRow> ctl(B, RsRow{0, 0, 0, -1, 0});
+    bool ok = hipMalloc(reinterpret_cast<void **>(&r->d_h), (size_t)g.ntaps * sizeof(double)) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void **>(&r->d_hist), hist_bytes) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void **>(&r->d_ctl), ctl_bytes) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        delete r;
+        set_error("bvc_resampler_create: device allocation failed");
+        return BVC_ENOMEM;
+    }
+    hipError_t e = hipMemcpy(r->d_h, h.data(), (size_t)g.ntaps * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(r->d_hist, 0, hist_bytes);
+    if (e == hipSuccess) e = hipMemcpy(r->d_ctl, ctl.data(), ctl_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        delete r;
+        set_error("bvc_resampler_create: %s", hipGetErrorString(e));
+        return BVC_EHIP;
+    }
+    *out = r;
+    return BVC_OK;
+}
+
+void bvc_resampler_destroy(bvc_resampler *r) { delete r; }
+
+int bvc_resampler_set_taps(bvc_resampler *r, const double *h_taps, int32_t ntaps) {
+    if (!r || !h_taps || ntaps != r->g.ntaps) {
+        set_error("bvc_resampler_set_taps: null argument, or not the %d taps of the design", r ? r->g.ntaps : 0);
+        return BVC_EINVAL;
+    }
+    BVC_HIP_TRY(hipMemcpy(r->d_h, h_taps, (size_t)ntaps * sizeof(double), hipMemcpyHostToDevice));
+    return BVC_OK;
+}
+
+int bvc_resampler_open(bvc_resampler *r, int32_t row, int32_t offset_in_next_push) {
+    if (int rc = row_arg(r, row, "bvc_resampler_open")) return rc;
+    bvc_resampler::Row &w = r->rows[row];
+    if (w.state == ROW_RUNNING) { set_error("bvc_resampler_open: row %d is running", (int)row); return BVC_EINVAL; }
+    if (offset_in_next_push < 0 || offset_in_next_push > r->max_in) {
+        set_error("bvc_resampler_open: offset %d outside 0..%d", (int)offset_in_next_push, r->max_in);
+        return BVC_EINVAL;
+    }
+    w.state = ROW_RUNNING; w.n = 0; w.start = offset_in_next_push; w.valid = -1; w.reset = true;
+    mark(r, w);
+    return BVC_OK;
+}
+
+int bvc_resampler_close(bvc_resampler *r, int32_t row) {
+    if (int rc = row_arg(r, row, "bvc_resampler_close")) return rc;
+    bvc_resampler::Row &w = r->rows[row];
+    if (w.state == ROW_IDLE) return BVC_OK;
+    w.state = ROW_IDLE; w.start = 0; w.valid = -1;
+    mark(r, w);
+    return BVC_OK;
+}
+
+int bvc_resampler_end(bvc_resampler *r, int32_t row, int32_t n_valid_in_next_push) {
+    if (int rc = row_arg(r, row, "bvc_resampler_end")) return rc;
+    bvc_resampler::Row &w = r->rows[row];
+    if (w.state != ROW_RUNNING) { set_error("bvc_resampler_end: row %d is not running", (int)row); return BVC_EINVAL; }
+    if (n_valid_in_next_push < w.start || n_valid_in_next_push > r->max_in) {
+        set_error("bvc_resampler_end: %d samples outside %d..%d", (int)n_valid_in_next_push, w.start, r->max_in);
+        return BVC_EINVAL;
+    }
+    w.valid = n_valid_in_next_push;
+    mark(r, w);
+    return BVC_OK;
+}
+
+int bvc_resampler_push(bvc_resampler *r, const void *d_x, int64_t x_row_stride, int32_t n_in, void *d_y, int64_t y_row_stride,
+                       int64_t y_offset, int32_t *h_counts, void *stream) {
+    if (!r || !d_x || !d_y) { set_error("bvc_resampler_push: null argument"); return BVC_EINVAL; }
+    if (n_in < 0 || n_in > r->max_in) { set_error("bvc_resampler_push: n_in %d outside 0..%d (max_in)", (int)n_in, r->max_in); return BVC_EINVAL; }
+    const int n_fill = (int)rs_ceil_mul(n_in, r->g.up, r->g.down);
+    if (x_row_stride < n_in || y_row_stride < n_fill || y_offset < 0) {
+        set_error("bvc_resampler_push: a row of d_x holds n_in = %d samples, a row of d_y ceil(n_in up / down) = %d behind y_offset >= 0", (int)n_in, n_fill);
+        return BVC_EINVAL;
+    }
+    for (int b = 0; b < r->B; ++b) {
+        const bvc_resampler::Row &w = r->rows[b];
+        if (w.state == ROW_RUNNING && (w.start > n_in || w.valid > n_in)) {
+            set_error("bvc_resampler_push: row %d starts at %d / ends at %d of a chunk of %d", b, w.start, w.valid, (int)n_in);
+            return BVC_EINVAL;
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (r->n_dirty > 0) { if (int rc = send_changes(r, s)) return rc; }
+    const RsCall c{d_x, x_row_stride, d_y, y_row_stride, y_offset, n_in, n_fill, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, -1};
+    if (int rc = launch_rs_push(filter_of(r), c, r->d_ctl, r->d_hist, r->B, s)) return rc;
+    for (int b = 0; b < r->B; ++b) {
+        bvc_resampler::Row &w = r->rows[b];
+        int count = 0;
+        if (w.state == ROW_RUNNING) {
+            const int end = w.valid >= 0 ? w.valid : n_in;
+            const long long n1 = w.n + (end - w.start);
+            count = (int)(rs_count(n1, r->g.up, r->g.down, r->g.n_pre_remove, r->delayed) -
+                          rs_count(w.n, r->g.up, r->g.down, r->g.n_pre_remove, r->delayed));
+            w.n = n1; w.start = 0;
+            if (w.valid >= 0) { w.state = ROW_ENDED; w.valid = -1; }
+        }
+        if (h_counts) h_counts[b] = count;
+    }
+    return BVC_OK;
+}
+
+int bvc_resampler_flush(bvc_resampler *r, int32_t row, void *d_y_row, int32_t *count, void *stream) {
+    if (int rc = row_arg(r, row, "bvc_resampler_flush")) return rc;
+    bvc_resampler::Row &w = r->rows[row];
+    if (w.state == ROW_IDLE) { set_error("bvc_resampler_flush: row %d is idle", (int)row); return BVC_EINVAL; }
+    const long long done = rs_count(w.n, r->g.up, r->g.down, r->g.n_pre_remove, r->delayed);
+    const long long all = rs_ceil_mul(w.n, r->g.up, r->g.down) + (r->delayed ? r->g.n_pre_remove : 0);
+    const int n = (int)(all - done);                         // <= n_pre_remove
+    if (n > 0 && !d_y_row) { set_error("bvc_resampler_flush: null d_y_row for %d samples", n); return BVC_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if (r->n_dirty > 0) { if (int rc = send_changes(r, s)) return rc; }       // (a row opened since the last push is reset first)
+    w.state = ROW_IDLE; w.start = 0; w.valid = -1;           // the kernel leaves the device's copy of the row idle
+    const RsCall c{nullptr, 0, d_y_row, 0, 0, 0, n, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, row};
+    if (int rc = launch_rs_push(filter_of(r), c, r->d_ctl, r->d_hist, r->B, s)) return rc;
+    if (count) *count = n;
+    return BVC_OK;
+}
+
+}  // extern "C"

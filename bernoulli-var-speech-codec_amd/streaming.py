@@ -270,6 +270,163 @@ def repair_plan(ticks, window, requests):
     return taken, passes
 
 
+PCM_FORMATS = {"f32": 0, "s16": 1}                              # BVC_PCM_F32 / BVC_PCM_S16
+PCM_DTYPES = {"f32": torch.float32, "s16": torch.int16}
+PCM_DELAYED = 16                                                # BVC_PCM_DELAYED
+
+
+def pcm_s16_to_f32(x):
+    """What a resampler does with s16 input: x / 32768 in float32 (exact)."""
+    return x.to(torch.float32) / 32768.0
+
+
+def pcm_f32_to_s16(y):
+    """What a resampler does with s16 output: clamp(rint(y * 32768), -32768, 32767) of the float32 it would have stored; NaN gives 0."""
+    q = torch.clamp(torch.round(y.to(torch.float32) * 32768.0), -32768.0, 32767.0)
+    return torch.nan_to_num(q, nan=0.0).to(torch.int16)
+
+
+def resampler_count(rate_in, rate_out, n_inputs):
+    """E(N) = max(0, ceil(N up / down) - n_pre_remove): the outputs of ``resample_poly(x, rate_out, rate_in)`` that the first N inputs
+    complete.  The library's arithmetic (``bvc_resampler_count``); no device."""
+    n = _abi.load().bvc_resampler_count(int(rate_in), int(rate_out), int(n_inputs))
+    if n < 0:
+        raise ValueError("resampler_count: rates must be positive, n_inputs not negative")
+    return int(n)
+
+
+def resampler_lag(rate_in, rate_out):
+    """(n_pre_remove, history) of the filter between two rates: the lag in output samples, and the inputs a row keeps.  No device."""
+    a, b = ctypes.c_int32(), ctypes.c_int32()
+    if _abi.load().bvc_resampler_lag(int(rate_in), int(rate_out), ctypes.byref(a), ctypes.byref(b)) != 0:
+        raise ValueError("resampler_lag: rates must be positive")
+    return a.value, b.value
+
+
+def client_hop(hop, client_rate, fs=22050):
+    """The internal samples of a hop of client samples; ValueError where that is no whole number."""
+    if int(client_rate) <= 0 or int(hop) <= 0:
+        raise ValueError(f"client_rate {client_rate} and hop {hop} must be positive")
+    if hop * fs % client_rate:
+        raise ValueError(f"a hop of {hop} samples at {client_rate} Hz is {hop * fs / client_rate:g} samples at {fs} Hz: not a whole number")
+    return hop * fs // client_rate
+
+
+def client_finish_plan(n_client, hop, fs, fs_internal=22050):
+    """Where the internal stream of a rate-converting send session ends: ``(len_S, push, n_last)``.
+
+    The stream has ``n_client`` client samples in all, pushed ``hop`` at a time from its push 0 on.  Its internal stream S =
+    zeros(lag) ++ resample_poly(x, fs_internal, fs) has ``len_S = lag + ceil(n_client * fs_internal / fs)`` samples, of which every push
+    writes hop22 = hop * fs_internal / fs.  The session's ``finish`` takes the internal ``n_last`` (0 .. hop22) in front of push ``push``
+    of the stream: the push that holds the client's last sample where the flushed tail still fits its hop, else the next one (the tail
+    spills: at most ``lag`` samples).  Pure host arithmetic."""
+    hop22 = client_hop(hop, fs, fs_internal)
+    lag = resampler_lag(fs, fs_internal)[0]
+    if n_client < 0:
+        raise ValueError("client_finish_plan: n_client must not be negative")
+    len_s = lag + -(-n_client * fs_internal // fs)
+    last = max(0, -(-n_client // hop) - 1)                      # the push that holds the client's last sample
+    tail = len_s - last * hop22
+    return (len_s, last, tail) if tail <= hop22 else (len_s, last + 1, tail - hop22)
+
+
+class StreamResampler:
+    """``batch`` independent rows resampled from ``rate_in`` to ``rate_out`` a chunk at a time (``bvc_resampler_*``): what a row has
+    got is a bit-exact prefix of ``preprocess.resample_poly(row, rate_out, rate_in)`` on its own signal, whatever the chunking.
+
+    Rows start idle.  ``open(row, offset)`` resets a row and starts it at sample ``offset`` of the next chunk, ``close(row)`` idles it,
+    ``end(row, n_valid)`` ends its stream with the first ``n_valid`` samples of the next chunk, ``flush(row)`` returns the rest.  ``push(x)``
+    with x (batch, n <= max_in) returns ``(y (batch, ceil(n up / down)) view, counts (batch,) int64 CPU tensor)``; row b's samples are
+    ``y[b, :counts[b]]``, zeros behind them; an idle row's input is never read.  The counts are host arithmetic (``resampler_count``): a
+    push does not synchronise.  ``fmt_in`` / ``fmt_out``: "f32" or "s16".  ``delayed=True``: the row's output is zeros(lag) followed by
+    the resampled signal, ``ceil(N up / down)`` samples after N inputs - a fixed hop in, a fixed hop out."""
+
+    def __init__(self, batch, rate_in, rate_out, max_in, fmt_in="f32", fmt_out="f32", delayed=False, device=None):
+        from . import preprocess
+        if fmt_in not in PCM_FORMATS or fmt_out not in PCM_FORMATS:
+            raise ValueError(f"sample formats are {sorted(PCM_FORMATS)}")
+        if int(rate_in) <= 0 or int(rate_out) <= 0:
+            raise ValueError("StreamResampler: rates must be positive")
+        self.lib = _abi.load()
+        self.dev = torch.device("cuda" if device is None else device)
+        if self.dev.index is None:
+            self.dev = torch.device("cuda", torch.cuda.current_device())
+        self.B, self.rate_in, self.rate_out, self.max_in = batch, int(rate_in), int(rate_out), int(max_in)
+        self.fmt_in, self.fmt_out, self.delayed = fmt_in, fmt_out, bool(delayed)
+        self.up, self.down, taps, self.lag = preprocess.design(rate_out, rate_in)
+        self.max_out = -(-self.max_in * self.up // self.down)
+        self.running = set()
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.dev):
+            rc = self.lib.bvc_resampler_create(batch, self.rate_in, self.rate_out, self.max_in, PCM_FORMATS[fmt_in],
+                                               PCM_FORMATS[fmt_out] | (PCM_DELAYED if delayed else 0), ctypes.byref(h))
+            self._call(rc)
+            self.handle = h
+            if self.up != self.down:        # the offline call's taps are numpy's: hand them in, whatever the C library's exp and sin round to
+                taps = taps.astype("float64")
+                self._call(self.lib.bvc_resampler_set_taps(h, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(taps)))
+        self._counts = (ctypes.c_int32 * batch)()
+        self._out = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self.lib.bvc_resampler_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def _call(self, rc):
+        if rc == -1:                                           # BVC_EINVAL: a misuse, the object is untouched
+            msg = self.lib.bvc_last_error()
+            raise ValueError(msg.decode() if msg else "bvcodec: invalid argument")
+        _abi.check(rc)
+
+    def open(self, row, offset=0):
+        self._call(self.lib.bvc_resampler_open(self.handle, int(row), int(offset)))
+        self.running.add(int(row))
+
+    def close(self, row):
+        self._call(self.lib.bvc_resampler_close(self.handle, int(row)))
+        self.running.discard(int(row))
+
+    def end(self, row, n_valid):
+        self._call(self.lib.bvc_resampler_end(self.handle, int(row), int(n_valid)))
+
+    def push_raw(self, x_ptr, x_row_stride, n_in, y_ptr, y_row_stride, y_offset, stream):
+        """The C call on raw device addresses (strides and offset in elements); returns the rows' counts as a list."""
+        self._call(self.lib.bvc_resampler_push(self.handle, ctypes.c_void_p(x_ptr), int(x_row_stride), int(n_in), ctypes.c_void_p(y_ptr),
+                                               int(y_row_stride), int(y_offset), self._counts, ctypes.c_void_p(stream)))
+        return list(self._counts)
+
+    def flush_raw(self, row, y_ptr, stream):
+        n = ctypes.c_int32()
+        self._call(self.lib.bvc_resampler_flush(self.handle, int(row), ctypes.c_void_p(y_ptr), ctypes.byref(n), ctypes.c_void_p(stream)))
+        self.running.discard(int(row))
+        return n.value
+
+    @torch.no_grad()
+    def push(self, x):
+        if x.dim() != 2 or x.shape[0] != self.B or x.shape[1] > self.max_in or x.dtype != PCM_DTYPES[self.fmt_in]:
+            raise ValueError(f"StreamResampler.push: expected a {PCM_DTYPES[self.fmt_in]} tensor ({self.B}, n <= {self.max_in})")
+        x = x.to(self.dev).contiguous()
+        n = x.shape[1]
+        if self._out is None:
+            self._out = torch.empty(self.B, max(1, self.max_out), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
+        with torch.cuda.device(self.dev):
+            counts = self.push_raw(x.data_ptr() if n else self._out.data_ptr(), max(n, 1), n, self._out.data_ptr(), self._out.shape[1], 0,
+                                   torch.cuda.current_stream(self.dev).cuda_stream)
+        return self._out[:, :-(-n * self.up // self.down)], torch.tensor(counts, dtype=torch.int64)
+
+    @torch.no_grad()
+    def flush(self, row):
+        """The rest of the row's outputs (at most ``lag`` samples, a new tensor); the row is idle afterwards."""
+        y = torch.empty(max(1, self.lag), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
+        with torch.cuda.device(self.dev):
+            n = self.flush_raw(row, y.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream)
+        return y[:n]
+
+
 class StreamingCodec:
     """BASELINE configs[4]: `batch` parallel streams, a fixed hop of new samples per tick, encode + decode of the frames
     each hop completes in ONE library call (``bvc_stream_codec_tick``: one persistent launch per recurrence where that
@@ -313,12 +470,41 @@ class StreamingCodec:
     state in front of its earliest late frame - with the bit counts those frames had, generating again what is still lost - and
     continues from a state that is bit for bit that of a session which got the packet in time: its ``filled_codes`` equal that
     session's from this push on, its samples once the generator's history has flushed (``CONTEXT_FRAMES`` later).  What was
-    returned before is not touched.  ``set_conceal`` and ``set_repair`` empty the window."""
+    returned before is not touched.  ``set_conceal`` and ``set_repair`` empty the window.
+
+    ``client_rate=fs`` (8000 .. 48000 Hz; None or the model's own 22050: the session as above), ``sample_format="f32"`` or ``"s16"``:
+    the session speaks the client's rate and format on both sides.  ``hop`` then counts client samples and must be a whole number of
+    internal ones (``hop * 22050 % fs == 0``, else ``ValueError``: 480 samples at 48 kHz would be 220.5; 20 ms hops of the six usual
+    rates pass).  One ``StreamResampler`` sits in front of the session's input buffer (send, duplex) and one behind its output buffer
+    (recv, duplex), both on the session's stream, writing into and reading from the session's own buffers.  Send side: with ``lag`` =
+    ``self.lag`` (``n_pre_remove`` of ``design(22050, fs)``: 14 samples at 16 kHz, 11 at 48 kHz) a slot's internal stream is S =
+    zeros(lag) ++ resample_poly(x, 22050, fs) - the offline resampling of the client's signal, ``lag`` samples late because the filter
+    looks that far ahead; ``open`` returns the session's delay as before, in internal samples, and the stream is ``lag`` later than
+    that.  The slot's packets and codes equal ``model.encode(S[None], bitrate)`` on the frames the session emits, bit for bit, and
+    ``finish(slot, n_last)`` (``n_last`` in client samples) ends the slot with all ``num_frames(len(S))`` of them.  Receive side: after
+    N internal samples of a stream the client has ``resample_poly(wav22[:N], fs, 22050)[:E(N)]`` (``resampler_count``), ``wav22`` what
+    the same session without ``client_rate`` returns; the last ``lag'`` (11 .. 22) client samples of a stream stay inside - receive
+    sessions have no ``finish``.  ``push_packets`` then returns ``(wav (batch, n_max) view, counts (batch,) int64 CPU tensor)`` - row
+    b's samples are ``wav[b, :counts[b]]`` - and a duplex ``push`` ``(codes, wav, counts)``; a send ``push`` returns what it returned
+    before.  ``"s16"`` takes and returns int16 tensors (in: x / 32768; out: clamp(rint(y * 32768)) of the float32 result, NaN 0).
+    Concealment, repair, ``set_bitrate`` and ``late`` act on the inner session unchanged; ``close`` also idles the row's resamplers."""
 
     DIRECTIONS = {"duplex": 0, "send": 1, "recv": 2}
     CONCEAL = {"none": 0, "prior": 1}
 
-    def __init__(self, model, batch, bitrate, hop=441, device=None, open_all=True, direction="duplex", conceal="none", repair=0):
+    def __init__(self, model, batch, bitrate, hop=441, device=None, open_all=True, direction="duplex", conceal="none", repair=0,
+                 client_rate=None, sample_format="f32"):
+        if sample_format not in PCM_FORMATS:
+            raise ValueError(f"sample_format must be one of {sorted(PCM_FORMATS)}")
+        if client_rate is None and sample_format != "f32":
+            raise ValueError("sample_format: a session without client_rate speaks float32")
+        fs = model.conf["fs"]
+        if client_rate is not None and (client_rate != int(client_rate) or client_rate <= 0):
+            raise ValueError(f"client_rate must be a positive number of Hz, not {client_rate}")
+        converting = client_rate is not None and (int(client_rate) != fs or sample_format != "f32")
+        self.client_rate, self.sample_format, self.client_hop = (int(client_rate) if converting else None), sample_format, hop
+        if converting and direction != "recv":
+            hop = client_hop(hop, int(client_rate), fs)         # ValueError before anything is created
         if direction not in self.DIRECTIONS:
             raise ValueError(f"direction must be one of {sorted(self.DIRECTIONS)}")
         if conceal not in self.CONCEAL:
@@ -361,6 +547,9 @@ class StreamingCodec:
             self._present = torch.as_tensor(_DeviceView(pr.value, (batch, self.kmax), "|u1"), device=self.dev)
         self.frames = 0
         self._model = model
+        self._rs_in = self._rs_out = None
+        if converting:
+            self._client_setup(fs, open_all)
         if not open_all:
             for b in range(batch):
                 self.close(b)
@@ -379,6 +568,95 @@ class StreamingCodec:
         except Exception:
             pass
 
+    def _client_setup(self, fs, open_all):
+        """The resamplers of a rate-converting session: one in front of d_in (delayed: a fixed hop in, a fixed hop out), one behind
+        d_wav, both on the session's stream, writing into / reading from the session's own buffers."""
+        rate, fmt, B = self.client_rate, self.sample_format, self.B
+        self._n_push = 0                                       # pushes so far
+        self._open_push = [0] * B                              # the push that took a slot's first client samples
+        self._ending = {}                                      # slot -> (internal n_last, spills) of a finish the next push carries out
+        self._carry = {}                                       # slot -> (from, count): the part of a flushed tail that goes into the next push
+        self._out_wait, self._out_drain = set(), set()         # slots whose samples have yet to start / are about to end on the wav side
+        if self.direction != "recv":
+            self._rs_in = StreamResampler(B, rate, fs, self.client_hop, fmt, "f32", delayed=True, device=self.dev)
+            self.lag = self._rs_in.lag
+            self._tail = torch.zeros(B, max(1, self.lag), device=self.dev)
+            self.hop, self._hop_in = self.client_hop, self.hop  # ``hop`` counts client samples from here on
+        if self.direction != "send":
+            self._rs_out = StreamResampler(B, fs, rate, self.kmax * self.spf, "f32", fmt, device=self.dev)
+            self._cwav = torch.zeros(B, max(1, self._rs_out.max_out), dtype=PCM_DTYPES[fmt], device=self.dev)
+        if open_all:
+            for b in range(B):
+                self._client_open(b)
+
+    def _client_open(self, slot):
+        if self._rs_in is not None:
+            self._rs_in.close(slot)
+            self._rs_in.open(slot, 0)
+            self._open_push[slot] = self._n_push
+            self._ending.pop(slot, None)
+            self._carry.pop(slot, None)
+        if self._rs_out is not None:
+            self._rs_out.close(slot)
+            self._out_wait.add(slot)
+            self._out_drain.discard(slot)
+
+    def _client_close(self, slot):
+        if self._rs_in is not None:
+            self._rs_in.close(slot)
+            self._ending.pop(slot, None)
+            self._carry.pop(slot, None)
+        if self._rs_out is not None:
+            self._rs_out.close(slot)
+            self._out_wait.discard(slot)
+            self._out_drain.discard(slot)
+
+    def _client_in(self, x):
+        """A hop of client samples -> d_in, inside the session's stream: one resampler push for all rows, and for a row that ends the
+        flush of its last ``lag`` samples - straight into d_in where they fit the hop, else through a buffer into this hop and the next."""
+        if tuple(x.shape) != (self.B, self.hop) or x.dtype != PCM_DTYPES[self.sample_format]:
+            raise ValueError(f"push: expected a {PCM_DTYPES[self.sample_format]} tensor ({self.B}, {self.hop})")
+        x = x.to(self.dev).contiguous()
+        rs, hop22, s = self._rs_in, self._hop_in, self.stream.cuda_stream
+        counts = rs.push_raw(x.data_ptr(), self.hop, self.hop, self._in.data_ptr(), hop22, 0, s)
+        for slot, (frm, n) in list(self._carry.items()):       # the rest of a tail that spilled: the row is idle, its hop zeros
+            self._in[slot, :n].copy_(self._tail[slot, frm:frm + n], non_blocking=True)
+            self._slot_call(self.eng.lib.bvc_stream_codec_finish(self.handle, slot, n))
+            self._out_drain.add(slot)
+            del self._carry[slot]
+        for slot, (n22, spills) in list(self._ending.items()):
+            e = counts[slot]                                   # what the row's last client samples completed
+            if not spills:
+                rs.flush_raw(slot, self._in.data_ptr() + 4 * (slot * hop22 + e), s)
+                self._slot_call(self.eng.lib.bvc_stream_codec_finish(self.handle, slot, n22))
+                self._out_drain.add(slot)
+            else:
+                rs.flush_raw(slot, self._tail.data_ptr() + 4 * slot * self._tail.shape[1], s)
+                self._in[slot, e:].copy_(self._tail[slot, :hop22 - e], non_blocking=True)
+                self._carry[slot] = (hop22 - e, n22)
+            del self._ending[slot]
+        self._n_push += 1
+
+    def _client_out(self, k):
+        """The tick's k frames of d_wav -> client samples: (wav (B, n_max) view, counts (B,) int64 CPU tensor)."""
+        rs = self._rs_out
+        for slot in list(self._out_wait):                      # a row's resampler starts with its stream's frame 0
+            first, count, frame0 = self.slot_frames(slot)
+            if count > 0 and frame0 == 0:
+                rs.open(slot, self.spf * first)
+                self._out_wait.discard(slot)
+        for slot in list(self._out_drain):                     # ... and ends with its last one (the last lag' samples stay inside)
+            if self.slot_state(slot) == "idle":
+                first, count, _ = self.slot_frames(slot)
+                if slot in rs.running:
+                    rs.end(slot, self.spf * (first + max(0, count)))
+                    rs.running.discard(slot)
+                self._out_drain.discard(slot)
+                self._out_wait.discard(slot)                   # (a stream that ended before its frame 0 came out)
+        n = k * self.spf
+        counts = rs.push_raw(self._wav_ptr, n, n, self._cwav.data_ptr(), self._cwav.shape[1], 0, self.stream.cuda_stream)
+        return self._cwav[:, :-(-n * rs.up // rs.down)], torch.tensor(counts, dtype=torch.int64)
+
     def _slot_call(self, rc):
         if rc == -1:                                           # BVC_EINVAL: a misuse of the slot calls, the session is untouched
             msg = self.eng.lib.bvc_last_error()
@@ -386,15 +664,20 @@ class StreamingCodec:
         _abi.check(rc)
 
     def open(self, slot, bitrate):
-        """Start a new stream in idle row `slot` from the next push on; returns its delay in samples."""
+        """Start a new stream in idle row `slot` from the next push on; returns its delay in (internal) samples.  A rate-converting
+        send side delays the stream by ``lag`` more: its filter looks that far ahead (``self.lag`` internal samples)."""
         d = ctypes.c_int32()
         self._slot_call(self.eng.lib.bvc_stream_codec_open(self.handle, int(slot), float(self._model.bits_per_frame(bitrate)),
                                                            ctypes.byref(d)))
+        if self.client_rate is not None:
+            self._client_open(int(slot))
         return d.value
 
     def close(self, slot):
         """The row is idle from the next push on (ask ``slot_frames`` first)."""
         self._slot_call(self.eng.lib.bvc_stream_codec_close(self.handle, int(slot)))
+        if self.client_rate is not None:
+            self._client_close(int(slot))
 
     def set_bitrate(self, slot, bitrate):
         """Bits per frame of an open slot from the next push on (variable-bitrate models only)."""
@@ -410,8 +693,26 @@ class StreamingCodec:
 
     def finish(self, slot, n_last=None):
         """The stream in `slot` ends with the first `n_last` samples of the next push's row (None: the whole hop; 0: it ended with
-        the last push).  The slot drains from that push on and is idle once its last frame is out."""
+        the last push).  The slot drains from that push on and is idle once its last frame is out.  On a rate-converting session `n_last`
+        counts client samples; the stream's internal signal S = zeros(lag) ++ resample_poly(x, 22050, client_rate) ends ``lag`` samples
+        later, so the drain starts with the next push, or the one after it where the flushed tail does not fit the hop
+        (``client_finish_plan``); the slot ends with all ``num_frames(len(S))`` frames."""
+        if self._rs_in is not None:
+            return self._client_finish(int(slot), self.hop if n_last is None else int(n_last))
         self._slot_call(self.eng.lib.bvc_stream_codec_finish(self.handle, int(slot), int(self.hop if n_last is None else n_last)))
+
+    def _client_finish(self, slot, n_last):
+        if not 0 <= slot < self.B or self.slot_state(slot) != "running" or slot in self._ending or slot in self._carry:
+            raise ValueError(f"finish: slot {slot} is not a running stream")
+        if not 0 <= n_last <= self.hop:
+            raise ValueError(f"finish: n_last {n_last} outside 0..{self.hop}")
+        push = self._n_push - self._open_push[slot]            # the coming push, counted from the stream's first
+        c = self._model.conf
+        len_s, at, n22 = client_finish_plan(push * self.hop + n_last, self.hop, self.client_rate, c["fs"])
+        if len_s <= c["winsize"] - c["hopsize"] - c["mel_pad_left"]:
+            raise ValueError(f"finish: a stream of {len_s} internal samples is too short for the right reflect padding")
+        self._rs_in.end(slot, n_last)
+        self._ending[slot] = (n22, at > push)
 
     def set_conceal(self, mode):
         """What the next pushes do with a lost frame: "none" (a frame of no bits) or "prior" (generated from the prior net).
@@ -470,8 +771,12 @@ class StreamingCodec:
             else:
                 self._present[:, :k].copy_(present.to(self.dev).ne(0).to(torch.uint8).reshape(self.B, k), non_blocking=True)
             self._slot_call(self.eng.lib.bvc_stream_codec_tick_recv(self.handle, k, ctypes.c_void_p(self.stream.cuda_stream)))
+            if self._rs_out is not None:
+                out = self._client_out(k)
         cur.wait_stream(self.stream)
         self.frames += k
+        if self._rs_out is not None:
+            return out
         return torch.as_tensor(_DeviceView(self._wav_ptr, (self.B, k * self.spf)), device=self.dev)
 
     @torch.no_grad()
@@ -483,13 +788,25 @@ class StreamingCodec:
         cur = torch.cuda.current_stream(self.dev)
         self.stream.wait_stream(cur)
         k = ctypes.c_int32()
+        out = None
         with torch.cuda.stream(self.stream), torch.cuda.device(self.dev):
-            self._in.copy_(x.to(self.dev, torch.float32), non_blocking=True)
+            if self._rs_in is not None:
+                self._client_in(x)
+            else:
+                self._in.copy_(x.to(self.dev, torch.float32), non_blocking=True)
             _abi.check(self.eng.lib.bvc_stream_codec_tick(self.handle, ctypes.byref(k), ctypes.c_void_p(self.stream.cuda_stream)))
+            if self._rs_out is not None and k.value > 0:
+                out = self._client_out(k.value)
         cur.wait_stream(self.stream)
         k = k.value
         self.frames += k
         send = self.direction == "send"
+        if self._rs_out is not None:                           # a rate-converting duplex session: (codes, wav, counts)
+            codes = torch.as_tensor(_DeviceView(self._codes_ptr, (self.B, k, self.z)), device=self.dev) if k else \
+                torch.empty(self.B, 0, self.z, device=self.dev)
+            if out is None:
+                out = (torch.empty(self.B, 0, dtype=PCM_DTYPES[self.sample_format], device=self.dev), torch.zeros(self.B, dtype=torch.int64))
+            return codes, out[0], out[1]
         if k == 0:
             first = torch.empty(self.B, 0, self.bytes_per_frame, dtype=torch.uint8, device=self.dev) if send else \
                 torch.empty(self.B, 0, self.z, device=self.dev)

@@ -12,7 +12,7 @@
  *  - every pointer named d_* is DEVICE memory owned by the caller, contiguous float32;
  *    every pointer named h_* is HOST memory;
  *  - the compute entry points (bvc_stft_logmel, bvc_bvrnn_*, bvc_bigvgan, bvc_encode, bvc_decode, bvc_decode_conceal,
- *    bvc_encode_ragged, bvc_decode_ragged, bvc_vocoder_stream_push, bvc_pack/unpack_codes, bvc_resample_poly, bvc_peak_normalize) are
+ *    bvc_encode_ragged, bvc_decode_ragged, bvc_vocoder_stream_push, bvc_pack/unpack_codes, bvc_resample_poly, bvc_peak_normalize, bvc_resampler_push / flush) are
  *    asynchronous on `stream` and use only the caller-provided workspace.  They do not allocate or
  *    synchronise, with these exceptions: the first calls per process create a handful of HIP events (the
  *    persistent launches' ticket, the end-of-call mark of the "auto" schedule, one per bvc_flow_fence slot in
@@ -51,7 +51,8 @@ extern "C" {
                              *    still 3 (new symbols only, nothing existing changed): + bvc_encode_ragged, bvc_decode_ragged;
                              *    + bvc_stream_codec_open / close / set_bits / slot_frames;
                              *    + bvc_stream_codec_create_dir / packets / tick_recv / finish / slot_state;
-                             *    + bvc_bvrnn_decode_conceal, bvc_decode_conceal, bvc_stream_codec_set_conceal */
+                             *    + bvc_bvrnn_decode_conceal, bvc_decode_conceal, bvc_stream_codec_set_conceal;
+                             *    + bvc_resampler_* */
 
 enum {
     BVC_OK = 0,
@@ -458,6 +459,55 @@ int bvc_forward(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, fl
 int bvc_resample_poly(const float *d_x, int32_t B, int64_t L_in, const double *d_h, int32_t ntaps, int32_t up,
                       int32_t down, int64_t n_pre_remove, float *d_y, int64_t n_out, void *stream);
 int bvc_peak_normalize(float *d_x, int32_t B, int64_t L, void *stream);
+
+/* Streaming resampler (not in the reference): bvc_resample_poly a chunk at a time, for B rows with lives of their own - what puts a
+ * streaming session in front of a client that speaks 8 .. 48 kHz, float32 or s16.  The filter is the one scipy.signal.resample_poly(x,
+ * rate_out, rate_in) designs (up = rate_out / gcd, down = rate_in / gcd, Kaiser beta 5, n_pre_remove = the lag in output samples), and
+ * one output is the sum bvc_resample_poly forms, term for term in float64.  So the outputs a row has got are a BIT-EXACT PREFIX of
+ * bvc_resample_poly on that row's own signal, however it was cut into chunks:
+ *  - output m needs the inputs up to floor((m + n_pre_remove) * down / up); after N inputs exactly
+ *    E(N) = max(0, ceil(N * up / down) - n_pre_remove) outputs are complete (bvc_resampler_count: host arithmetic, 64 bit, no device);
+ *  - a push of n_in inputs gives a row E(N + n_in) - E(N) outputs; a flush gives the rest up to ceil(N * up / down), with zeros for the
+ *    inputs behind the end - what bvc_resample_poly's clamp at the signal's end amounts to.
+ * State per row, in device memory owned by the object: the last `history` = ceil(ntaps / up) inputs and the input count.
+ *  - create: every row idle.  max_in: the longest chunk; history + max_in float32 must fit 64 KiB (BVC_EINVAL otherwise).  fmt_in /
+ *    fmt_out: BVC_PCM_F32, or BVC_PCM_S16 (in: x / 32768, exact; out: clamp(rintf(y * 32768), -32768, 32767) of the float32 value the
+ *    f32 path would have stored, NaN gives 0 - the s16 result is a function of the f32 result).  fmt_out | BVC_PCM_DELAYED: the row's
+ *    output stream is zeros(n_pre_remove) followed by the outputs, of which ceil(N * up / down) samples are complete after N inputs - a
+ *    chunk with n_in * up % down == 0 then gives EVERY running row exactly n_in * up / down samples, the first chunk included (a
+ *    session's input side: a fixed hop in, a fixed hop out); a flush gives the last n_pre_remove.  The library designs the filter
+ *    itself, in float64, restating numpy's firwin / kaiser / i0 operation for operation (bvc_resampler_taps gives the taps, no device);
+ *    the two agree to the last bit where exp, sin and sqrt of the two C libraries do.  A caller whose reference is a numpy design hands
+ *    its own taps in (set_taps: host memory, the design's ntaps, before the first push; it copies synchronously).
+ *  - open (reset + run), close (idle) and end are host bookkeeping between two pushes: they neither launch, allocate nor synchronise.
+ *    The next push carries them to the device on its own stream, ahead of its own work (one small launch per 64 changed rows).  open:
+ *    history zero, N = 0, and the row's first sample is sample offset_in_next_push of the next chunk (a stream that starts inside a
+ *    chunk).  end: the row's stream ends with the first n_valid_in_next_push samples of the next chunk; what lies behind them is not
+ *    read, the row takes nothing after that push and waits for its flush (or close, or open).
+ *  - push: the same n_in for every row; row b reads d_x + b * x_row_stride (elements of the input format) and writes its outputs from
+ *    d_y + b * y_row_stride + y_offset (elements of the output format) on; the positions behind them up to ceil(n_in * up / down) are
+ *    written as zeros, so a row of d_y holds at least that many behind y_offset.  An idle (or ended) row's input is NEVER read - NaN,
+ *    Inf, uninitialised memory there reach nothing - and its output is zeros.  One launch over all rows; no allocation, no
+ *    synchronisation; capturable.  h_counts (B, host, may be NULL): the rows' output counts, from E by arithmetic.
+ *  - flush: the rest of a running or ended row, *count <= n_pre_remove samples, to d_y_row (one launch); the row is idle afterwards.
+ *  - lag: n_pre_remove and history of a pair of rates (no device).
+ * BVC_EINVAL with the object untouched: a row out of range, open on a running row, end on one that is not, flush of an idle one,
+ * n_in > max_in, a row that starts or ends behind n_in, rates <= 0.  One in-flight push per object. */
+typedef struct bvc_resampler bvc_resampler;
+enum { BVC_PCM_F32 = 0, BVC_PCM_S16 = 1, BVC_PCM_DELAYED = 16 };
+int  bvc_resampler_create(int32_t B, int32_t rate_in, int32_t rate_out, int32_t max_in, int32_t fmt_in, int32_t fmt_out,
+                          bvc_resampler **out);
+void bvc_resampler_destroy(bvc_resampler *r);
+int  bvc_resampler_set_taps(bvc_resampler *r, const double *h_taps, int32_t ntaps);
+int  bvc_resampler_open(bvc_resampler *r, int32_t row, int32_t offset_in_next_push);
+int  bvc_resampler_close(bvc_resampler *r, int32_t row);
+int  bvc_resampler_end(bvc_resampler *r, int32_t row, int32_t n_valid_in_next_push);
+int  bvc_resampler_push(bvc_resampler *r, const void *d_x, int64_t x_row_stride, int32_t n_in, void *d_y, int64_t y_row_stride,
+                        int64_t y_offset, int32_t *h_counts, void *stream);
+int  bvc_resampler_flush(bvc_resampler *r, int32_t row, void *d_y_row, int32_t *count, void *stream);
+int64_t bvc_resampler_count(int32_t rate_in, int32_t rate_out, int64_t n_inputs);
+int  bvc_resampler_lag(int32_t rate_in, int32_t rate_out, int32_t *n_pre_remove, int32_t *history);
+int  bvc_resampler_taps(int32_t rate_in, int32_t rate_out, double *h_taps, int32_t capacity);   /* returns ntaps; writes if capacity >= ntaps */
 
 /* Wire format for the codes (new: the reference keeps them as float32 {0,1,0.5}, bvrnn.py:191-196, and
  * defines no bit stream).  A frame is ceil(nbits/8) bytes, bit i at byte i/8 position i%8 (LSB first);
