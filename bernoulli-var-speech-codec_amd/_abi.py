@@ -78,6 +78,13 @@ SIGNATURES = {
     "bvc_stream_codec_late": (ctypes.c_int, [_vp, _i32, _i64, _vp, ctypes.POINTER(_i32)]),
     "bvc_encode": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _f, _vp, _vp, _sz, _vp]),
     "bvc_decode": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i64, _f, _vp, _vp, _sz, _vp]),
+    "bvc_vbr_workspace_bytes": (_sz, [_vp, _i32, _i64, _i32]),
+    "bvc_bvrnn_encode_vbr": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_i32), _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _sz, _vp]),
+    "bvc_encode_vbr": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _vp, ctypes.POINTER(_i32), _i32, _vp, _vp, _vp, _sz, _vp]),
+    "bvc_pack_codes_vbr": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "bvc_unpack_codes_vbr": (ctypes.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "bvc_test_vbr_select": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "bvc_forward": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _f, _i64, _f, _vp, _vp, _vp, _sz, _vp]),
     "bvc_encode_ragged": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _f, _vp, _f, _vp, _vp, _sz, _vp]),
     "bvc_decode_ragged": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _f, _vp, _vp, _sz, _vp]),

@@ -235,6 +235,18 @@ int run_decode(const bvc_model *m, const Workspace &w, void *ws_base, const floa
                float *d_mel, float *d_hT, hipStream_t s);
 int run_decode_conceal(const bvc_model *m, const Workspace &w, void *ws_base, const float *d_codes, const float *d_sel, const float *d_h0,
                        int B, int64_t T, float *d_mel, float *d_hT, float *d_codes_out, float *d_prior, hipStream_t s);
+// ---- closed-loop rate selection (bvc_bvrnn_encode_vbr): its workspace is the frame buffers of the K * B candidate rows, whose size depends
+// on (B, K) alone, FOLLOWED by the ordinary workspace of (B, T) - so every address a captured step holds is a function of (base, B, K)
+struct VbrWorkspace {
+    float *zraw, *zc, *hrep, *pz[3], *d[3], *melk, *dnk, *pzsel, *dnsel;
+    VbrCall *call;
+    size_t floats;              // the frame buffers in front of `call` (cleared at the start of a call: padded rows hold zeros)
+    size_t total;               // bytes in front of the ordinary workspace
+};
+void carve_vbr(const bvc_model *m, int B, int K, char *base, VbrWorkspace *v);
+int run_encode_vbr(const bvc_model *m, const Workspace &w, const VbrWorkspace &v, void *ws_base, const float *d_mel, const float *d_tau,
+                   const int *h_ladder, int K, const float *d_h0, int B, int64_t T, float *d_codes, float *d_bits, float *d_all_h,
+                   float *d_hT, float *d_prob, float *d_dist, float *d_dec, hipStream_t s);
 int run_forward(const bvc_model *m, const Workspace &w, const float *d_mel, const float *d_bits, const uint8_t *h_use_gen, bool update_h,
                 bool update_h2, const float *d_noise, int B, int64_t T, float *d_dec, float *d_kld, float *d_z, float *d_prob,
                 float *d_prior, hipStream_t s);

@@ -337,6 +337,46 @@ int launch_unpack_rows(const unsigned char *in, const unsigned char *present, co
 int launch_conceal_select(const unsigned char *present, long long kstride, const float *bits, float dflt, const int *row_off, int B,
                           long long k, float *sel, hipStream_t s);
 
+// ------------------------------------------------------------------ closed-loop rate selection (k_vbr.hip)
+// bvc_bvrnn_encode_vbr: per frame the encoder tries the rungs of a ladder of bit counts - the K masked copies of the frame's code
+// run phi_z and dec as K * B rows (candidate row k * B + b) of the recurrent-layer GEMM - and keeps the first rung whose decoded mel
+// lies within the frame's target: D_k = mean_j |d^k_j - y_j| <= tau, else the last rung.
+constexpr int VBR_MAX_RUNGS = 8;
+// The caller's tensors and the ladder of one call, resident in the call's workspace: like the CallDesc they are no kernel arguments,
+// because the step is captured once and replayed.  The frame counter and T are the CallDesc's.
+struct VbrCall {
+    const float *y;                  // (B,T,X) the mel the call encodes
+    const float *tau;                // (B,T) distortion targets
+    float *codes;                    // (B,T,Z) the chosen rung's code
+    float *bits;                     // (B,T) its bit count
+    float *dist;                     // (B,T,K) D of every rung, or null
+    float *dec;                      // (B,T,X) the chosen rung's decoded mel, or null
+    int *choice;                     // (B,T) the chosen rung, or null (the test hook)
+    int ladder[VBR_MAX_RUNGS];       // bit counts, ascending
+};
+// One frame's buffers (workspace-static; fragment-packed unless stated) and sizes: the arguments of the two kernels.
+struct VbrStep {
+    const CallDesc *desc;            // null: a stand-alone launch on (B, 1, .) tensors (the test hook)
+    const VbrCall *call;
+    int B, K, Z, H, X;
+    const float *zraw;               // [mt16(B)][Z] round(p) of the frame, no mask
+    const float *hbuf; long long MH; // the GRU state ping-pong: h_t = hbuf + (t & 1) * MH, [mt16(B)][H]
+    float *zc;                       // [mt16(K B)][Z] the K masked copies
+    float *hrep;                     // [mt16(K B)][H] h_t, K times
+    const float *melk;               // natural [K B][X] dec.6 of the candidates
+    const float *dnk;                // [mt16(K B)][X] ... normalised (may be null)
+    const float *pzk;                // [mt16(K B)][H] phi_z of the candidates (may be null)
+    float *pzsel;                    // [mt16(B)][H] the chosen rows of pzk
+    float *dnsel;                    // [mt16(B)][X] the chosen rows of dnk
+};
+int launch_vbr_set_call(VbrCall *d, const VbrCall &v, hipStream_t s);
+int launch_vbr_candidates(const VbrStep &a, int tstep, hipStream_t s);
+int launch_vbr_select(const VbrStep &a, int tstep, hipStream_t s);
+// the wire format with a per-frame bit count: a frame is 1 + ceil(z / 8) bytes - its bit count n, ceil(n / 8) bytes of bits in
+// launch_pack_codes order, zeros; sizes (frames) = 1 + ceil(n / 8)
+int launch_pack_codes_vbr(const float *codes, const float *bits, long long frames, int z, unsigned char *out, int *sizes, hipStream_t s);
+int launch_unpack_codes_vbr(const unsigned char *in, long long frames, int z, float *codes, float *bits, hipStream_t s);
+
 // ------------------------------------------------------------------ vocoder (k_vocoder.hip; the AMP pairs: k_vocoder_amp.hip)
 struct ConvLayer {               // one causal conv as implicit GEMM on fp32 MFMA
     int cin;                     // input channels (multiple of 4)

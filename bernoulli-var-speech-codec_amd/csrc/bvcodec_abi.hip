@@ -67,6 +67,28 @@ int enter(const bvc_model *m, int B, const int64_t *L, int64_t *T, void *d_ws, s
 }
 const char *const BAD_LENGTH = "null argument or non-positive length";
 
+// the checks of a closed-loop call that need no tensor, in the order in which they are reported; on success the two workspaces are carved
+int enter_vbr(const bvc_model *m, int B, int64_t T, const int32_t *h_ladder, int K, void *d_ws, size_t ws_bytes, Workspace *w,
+              VbrWorkspace *v, const char *fn) {
+    if (!m) { set_error("null model"); return BVC_EINVAL; }
+    if (int rc = sticky_status(m)) return rc;
+    if (B <= 0 || T <= 0) { set_error("B and T must be positive (B=%d, T=%lld)", B, (long long)T); return BVC_EINVAL; }
+    if (!m->cfg.var_bit) { set_error("%s: a fixed-rate model (var_bit = 0) has no bit mask to choose", fn); return BVC_EINVAL; }
+    if (!h_ladder || K < 1 || K > VBR_MAX_RUNGS) { set_error("%s: the ladder takes 1 to %d rungs (K=%d)", fn, VBR_MAX_RUNGS, K); return BVC_EINVAL; }
+    for (int k = 0; k < K; ++k)
+        if (h_ladder[k] < 0 || h_ladder[k] > m->cfg.z_dim || (k && h_ladder[k] <= h_ladder[k - 1])) {
+            set_error("%s: rung %d = %d: bit counts in [0, %d], strictly ascending", fn, k, h_ladder[k], m->cfg.z_dim);
+            return BVC_EINVAL;
+        }
+    carve_vbr(m, B, K, static_cast<char *>(d_ws), v);
+    carve(m, B, T, static_cast<char *>(d_ws) + v->total, w);
+    if (!d_ws || ws_bytes < v->total + w->total) {
+        set_error("%s: workspace too small: %zu bytes given, %zu needed (bvc_vbr_workspace_bytes)", fn, ws_bytes, v->total + w->total);
+        return BVC_EINVAL;
+    }
+    return BVC_OK;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -175,6 +197,43 @@ int bvc_encode(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, flo
     if ((rc = launch_stft_logmel(m->fe, d_wav, B, L, T, m->cfg.pad_left, scale, w.mel, s))) return rc;
     if ((rc = launch_fill(w.bits, bits_per_frame, (long long)B * T, s))) return rc;
     return run_encode(m, w, d_ws, w.mel, w.bits, nullptr, B, T, d_codes, nullptr, nullptr, nullptr, s);
+}
+
+// ---- closed-loop rate selection: the workspace is the candidates' frame buffers followed by the ordinary workspace (carve_vbr)
+size_t bvc_vbr_workspace_bytes(const bvc_model *m, int32_t B, int64_t T, int32_t K) {
+    if (!m || B <= 0 || T <= 0 || K < 1 || K > VBR_MAX_RUNGS) return 0;
+    Workspace w;
+    VbrWorkspace v;
+    carve(m, B, T, nullptr, &w);
+    carve_vbr(m, B, K, nullptr, &v);
+    return v.total + w.total;
+}
+
+int bvc_bvrnn_encode_vbr(const bvc_model *m, const float *d_mel, const float *d_target, const int32_t *h_ladder, int32_t K,
+                         const float *d_h0, int32_t B, int64_t T, float *d_codes, float *d_bits, float *d_all_h, float *d_hT,
+                         float *d_prob, float *d_dist, float *d_dec, void *d_ws, size_t ws_bytes, void *stream) {
+    Workspace w;
+    VbrWorkspace v;
+    if (int rc = enter_vbr(m, B, T, h_ladder, K, d_ws, ws_bytes, &w, &v, "bvc_bvrnn_encode_vbr")) return rc;
+    if (!d_mel || !d_target || !d_codes || !d_bits) { set_error("null argument"); return BVC_EINVAL; }
+    return run_encode_vbr(m, w, v, d_ws, d_mel, d_target, h_ladder, K, d_h0, B, T, d_codes, d_bits, d_all_h, d_hT, d_prob, d_dist, d_dec,
+                          (hipStream_t)stream);
+}
+
+int bvc_encode_vbr(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale, const float *d_target,
+                   const int32_t *h_ladder, int32_t K, float *d_codes, float *d_bits, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!m) { set_error("null model"); return BVC_EINVAL; }
+    const int64_t T = bvc_num_frames(m, L);
+    if (T <= 0) { set_error("input too short for reflect padding (L=%lld)", (long long)L); return BVC_EINVAL; }
+    Workspace w;
+    VbrWorkspace v;
+    int rc = enter_vbr(m, B, T, h_ladder, K, d_ws, ws_bytes, &w, &v, "bvc_encode_vbr");
+    if (rc) return rc;
+    if (!d_wav || !d_target || !d_codes || !d_bits) { set_error("null argument"); return BVC_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = launch_stft_logmel(m->fe, d_wav, B, L, T, m->cfg.pad_left, scale, w.mel, s))) return rc;
+    return run_encode_vbr(m, w, v, d_ws, w.mel, d_target, h_ladder, K, nullptr, B, T, d_codes, d_bits, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, s);
 }
 
 int bvc_forward(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale, float bits_per_frame, int64_t length,
@@ -306,6 +365,48 @@ int bvc_unpack_codes(const uint8_t *d_bytes, int32_t B, int64_t T, int32_t z_dim
         return BVC_EINVAL;
     }
     return launch_unpack_codes(d_bytes, (long long)B * T, z_dim, nbits, d_codes, (hipStream_t)stream);
+}
+
+int bvc_pack_codes_vbr(const float *d_codes, const float *d_bits, int32_t B, int64_t T, int32_t z_dim, uint8_t *d_bytes, int32_t *d_sizes,
+                       void *stream) {
+    if (!d_codes || !d_bits || !d_bytes || B <= 0 || T <= 0 || z_dim <= 0 || z_dim > 255) {
+        set_error("bvc_pack_codes_vbr: bad arguments (the bit count of a frame is one byte: z_dim <= 255)");
+        return BVC_EINVAL;
+    }
+    return launch_pack_codes_vbr(d_codes, d_bits, (long long)B * T, z_dim, d_bytes, d_sizes, (hipStream_t)stream);
+}
+
+int bvc_unpack_codes_vbr(const uint8_t *d_bytes, int32_t B, int64_t T, int32_t z_dim, float *d_codes, float *d_bits, void *stream) {
+    if (!d_bytes || !d_codes || B <= 0 || T <= 0 || z_dim <= 0 || z_dim > 255) {
+        set_error("bvc_unpack_codes_vbr: bad arguments (the bit count of a frame is one byte: z_dim <= 255)");
+        return BVC_EINVAL;
+    }
+    return launch_unpack_codes_vbr(d_bytes, (long long)B * T, z_dim, d_codes, d_bits, (hipStream_t)stream);
+}
+
+int bvc_test_vbr_select(const float *d_melhat, const float *d_y, const float *d_tau, const int32_t *h_ladder, int32_t K, int32_t B,
+                        int32_t num_mels, float *d_dist, int32_t *d_choice, float *d_bits, void *stream) {
+    // test helper (allocates + synchronises): the select kernel alone, on one frame
+    if (!d_melhat || !d_y || !d_tau || !h_ladder || !d_dist || !d_choice || !d_bits || B <= 0 || num_mels <= 0 || K < 1 || K > VBR_MAX_RUNGS) {
+        set_error("bvc_test_vbr_select: bad arguments");
+        return BVC_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    VbrCall c;
+    memset(&c, 0, sizeof(c));
+    c.y = d_y; c.tau = d_tau; c.dist = d_dist; c.bits = d_bits; c.choice = d_choice;
+    for (int k = 0; k < K; ++k) c.ladder[k] = h_ladder[k];
+    VbrCall *dc = nullptr;
+    BVC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dc), sizeof(VbrCall)));
+    int rc = launch_vbr_set_call(dc, c, s);
+    VbrStep a;
+    memset(&a, 0, sizeof(a));
+    a.call = dc; a.B = B; a.K = K; a.X = num_mels; a.melk = d_melhat;
+    if (!rc) rc = launch_vbr_select(a, 0, s);
+    const hipError_t e = hipStreamSynchronize(s);
+    (void)hipFree(dc);
+    if (!rc && e != hipSuccess) { set_error("bvc_test_vbr_select: %s", hipGetErrorString(e)); rc = BVC_EHIP; }
+    return rc;
 }
 
 int bvc_kprobe_enable(int32_t on) {

@@ -8,12 +8,14 @@ namespace {
 
 // One operation of a step: a kernel on the main or the side branch, or an event record / wait that
 // forks and joins the two branches (they become graph dependencies under stream capture).
-enum { OP_KERNEL = 0, OP_RECORD = 1, OP_WAIT = 2 };
+enum { OP_KERNEL = 0, OP_RECORD = 1, OP_WAIT = 2, OP_VBR_CANDIDATES = 3, OP_VBR_SELECT = 4 };   // _VBR_*: the two kernels of k_vbr.hip (v)
 enum { BR_MAIN = 0, BR_SIDE = 1 };
-struct StepNode { int op; int branch; int event; GemmParams p; int epi; };
-enum { STEP_ENCODE = 0, STEP_DECODE = 1, STEP_DECODE_PRE = 2, STEP_CONCEAL = 3 };   // _PRE: phi_z halves of dec.0 / GRU arrive pre-computed
+struct StepNode { int op; int branch; int event; GemmParams p; int epi; VbrStep v; };
+enum { STEP_ENCODE = 0, STEP_DECODE = 1, STEP_DECODE_PRE = 2, STEP_CONCEAL = 3, STEP_ENCODE_VBR = 4 };   // _PRE: phi_z halves of dec.0 / GRU arrive pre-computed
                                                                   // _CONCEAL: the concealing decoder - the encode step with the prior net in the encoder's place
-enum { STEP_KIND_MASK = 0xF, STEP_FOLD = 0x10 };                  // | STEP_FOLD: the folded hop (step_fold below)
+                                                                  // _VBR: the encode step with K candidate rungs per frame (build_vbr_step)
+enum { STEP_KIND_MASK = 0xF, STEP_FOLD = 0x10, STEP_RUNGS_SHIFT = 8 };   // | STEP_FOLD: the folded hop (step_fold below); | K << STEP_RUNGS_SHIFT: the rungs of a
+                                                                  // _VBR step (part of the graph-cache key: the candidate launches have K * B rows)
 constexpr int64_t SMALL_T_FRAMES = 4;          // up to this many frames per call the all-frame MLPs run frame by frame on the recurrent-layer kernel
 enum { EV_START = 0, EV_DEC0H = 1, EV_PZ = 2, EV_GATES = 3, EV_COUNT = 4 };
 
@@ -24,6 +26,8 @@ enum { EV_START = 0, EV_DEC0H = 1, EV_PZ = 2, EV_GATES = 3, EV_COUNT = 4 };
 //   encode (bvrnn.py:187-206): enc -> sigmoid/round/mask -> phi_z -> dec -> phi_x(norm) -> GRU
 //   decode (bvrnn.py:222-227): [phi_z batched over all frames beforehand] dec -> phi_x(norm) -> GRU
 //   conceal (bvc_bvrnn_decode_conceal): prior -> sigmoid/round/mask, SELECTED against the received codes -> phi_z -> ... as encode
+//   closed-loop rates (bvc_bvrnn_encode_vbr): enc -> sigmoid/round -> K masked candidates -> phi_z -> dec on K * B rows -> select -> ... as encode
+//     (build_vbr_step below; never folded: dec.6 must exist to be measured)
 // Side branch: the halves of the split dot products that do not depend on the current frame's chain -
 // dec.0[:, H:] h, W_hh h + b_hh, W_ih[:, H:] phi_z + b_ih - run concurrently with the chain (which is
 // latency-bound), so the GRU kernel on the critical path only streams W_ih[:, :H].
@@ -184,6 +188,90 @@ std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, 
     return plan;
 }
 
+// One frame of bvc_bvrnn_encode_vbr: STEP_ENCODE with the rate chosen inside the frame.  Main branch only, and always the unfolded
+// layer list - dec.6 must exist to be measured, so `encode_fold` does not apply here:
+//   enc.0-4 at B rows (the phi_x half pre-computed: encode_prologue), the code written WITHOUT a mask to a scratch matrix
+//   candidates: the K masked copies and h_t K times over, candidate row k * B + b
+//   phi_z.0-4, dec.0-6 at K * B rows in one launch each (the kernels' results do not depend on the row count); dec.0 sums its h half
+//     before its phi_z half, as build_step does
+//   select: D of every rung, the first within the target, the frame's outputs, the chosen rows gathered back into B-row operands
+//   phi_x.0-4 and the GRU at B rows, as build_step does
+std::vector<StepNode> build_vbr_step(const bvc_model *m, const Workspace &w, const VbrWorkspace &vw, int B, int nrungs) {
+    const int H = m->cfg.h_dim, Z = m->cfg.z_dim, X = m->cfg.num_mels;
+    const int KB = nrungs * B;
+    std::vector<StepNode> plan;
+    const long long MH = (long long)((B + 15) / 16) * 16 * H;
+    const DynPtr h_cur = dp_parity(w.hbuf, H, MH, 0, 1);
+    const DynPtr h_next = dp_parity(w.hbuf + MH, H, -MH, 0, 1);
+    float *e1 = w.step[0], *e2 = w.step[1], *g1 = w.step[9], *g2 = w.step[10], *g3 = w.step[11];
+    auto S = [&](float *p, int ld) { return dp_static(p, ld, 1); };
+    int node = 0;
+    auto K = [&](GemmParams p, int epi) {
+        p.desc = w.desc; p.node = node++;
+        p.probe = g_kprobe.enabled ? g_kprobe.dev : nullptr;
+        finish(p);
+        plan.push_back(StepNode{OP_KERNEL, BR_MAIN, -1, p, epi});
+    };
+    VbrStep v;
+    memset(&v, 0, sizeof(v));
+    v.desc = w.desc; v.call = vw.call;
+    v.B = B; v.K = nrungs; v.Z = Z; v.H = H; v.X = X;
+    v.zraw = vw.zraw; v.hbuf = w.hbuf; v.MH = MH;
+    v.zc = vw.zc; v.hrep = vw.hrep;
+    v.melk = vw.melk; v.dnk = vw.dnk; v.pzk = vw.pz[2];
+    v.pzsel = vw.pzsel; v.dnsel = vw.dnsel;
+    auto V = [&](int op) { GemmParams z; memset(&z, 0, sizeof(z)); plan.push_back(StepNode{op, BR_MAIN, -1, z, 0, v}); };
+    {
+        GemmParams p = half_params(m->enc[0], H / 16, h_cur, H, B, S(e1, H), false);
+        p.aux = dp_frame(DS_PARTD, H);
+        K(p, EPI_ELU);
+    }
+    K(lin_params(m->enc[1], S(e1, H), B, S(e2, H)), EPI_ELU);
+    {
+        GemmParams p = lin_params(m->enc[2], S(e2, H), B, S(vw.zraw, Z));     // var_bit off: the mask is the candidates' business
+        p.y3 = dp_frame(DS_PROB, Z);
+        K(p, EPI_CODE);
+    }
+    V(OP_VBR_CANDIDATES);
+    K(lin_params(m->phi_z[0], S(vw.zc, Z), KB, S(vw.pz[0], H)), EPI_ELU);
+    K(lin_params(m->phi_z[1], S(vw.pz[0], H), KB, S(vw.pz[1], H)), EPI_ELU);
+    K(lin_params(m->phi_z[2], S(vw.pz[1], H), KB, S(vw.pz[2], H)), EPI_ELU);
+    {
+        GemmParams p = lin_params(m->dec[0], S(vw.hrep, H), KB, S(vw.d[0], H));
+        p.nseg = 2;
+        p.seg[0] = mkseg(S(vw.hrep, H), m->dec[0].wp + (size_t)(H / 16) * 256, 2 * H / 16, H, 0);
+        p.seg[1] = mkseg(S(vw.pz[2], H), m->dec[0].wp, 2 * H / 16, H, 0);
+        K(p, EPI_ELU);
+    }
+    K(lin_params(m->dec[1], S(vw.d[0], H), KB, S(vw.d[1], H)), EPI_ELU);
+    K(lin_params(m->dec[2], S(vw.d[1], H), KB, S(vw.d[2], H)), EPI_ELU);
+    {
+        GemmParams p = lin_params(m->dec[3], S(vw.d[2], H), KB, dp_static(vw.melk, X));      // natural rows: the select kernel reads them band by band
+        p.y2 = S(vw.dnk, X); p.mean = m->mean_mel; p.stdv = m->std_mel;
+        K(p, EPI_MEL);
+    }
+    V(OP_VBR_SELECT);
+    K(lin_params(m->phi_x[0], S(vw.dnsel, X), B, S(g1, H)), EPI_ELU);
+    K(lin_params(m->phi_x[1], S(g1, H), B, S(g2, H)), EPI_ELU);
+    K(lin_params(m->phi_x[2], S(g2, H), B, S(g3, H)), EPI_ELU);
+    {
+        GemmParams p;
+        memset(&p, 0, sizeof(p));
+        p.M = B; p.N = H; p.gate_rows = H;
+        p.y = h_next;
+        p.y2 = dp_frame(DS_ALLH, H, 1);
+        p.aux = h_cur;
+        p.nseg = 3;
+        p.gate_il = 1;
+        p.seg[0] = mkseg(S(vw.pzsel, H), m->w_ih_il + (size_t)(H / 16) * 3 * 256, 2 * H / 16, H, 0);
+        p.seg[1] = mkseg(S(g3, H), m->w_ih_il, 2 * H / 16, H, 0);
+        p.seg[2] = mkseg(h_cur, m->w_hh_il, H / 16, H, 1);
+        p.bias0 = m->b_ih; p.bias1 = m->b_hh;
+        K(p, EPI_GRU);
+    }
+    return plan;
+}
+
 int count_kernels(const std::vector<StepNode> &plan) {
     int n = 0;
     for (const StepNode &s : plan) n += (s.op == OP_KERNEL);
@@ -203,6 +291,10 @@ int launch_steps(const bvc_model *m, const std::vector<StepNode> &plan, const Wo
                 GemmParams p = n.p;
                 p.tstep = k;
                 if ((rc = launch_gemm_skinny(p, n.epi, st, m->mtw))) return rc;
+            } else if (n.op == OP_VBR_CANDIDATES) {
+                if ((rc = launch_vbr_candidates(n.v, k, st))) return rc;
+            } else if (n.op == OP_VBR_SELECT) {
+                if ((rc = launch_vbr_select(n.v, k, st))) return rc;
             } else if (side) {
                 if (n.op == OP_RECORD) BVC_HIP_TRY(hipEventRecord(m->cap_events[n.event], st));
                 else                   BVC_HIP_TRY(hipStreamWaitEvent(st, m->cap_events[n.event], 0));
@@ -746,6 +838,60 @@ int run_encode(const bvc_model *m, const Workspace &w, void *ws_base, const floa
             else d.p[DS_MEL] = d_melhat;
         }
         return run_layers(m, w, ws_base, d, kind, d_h0, B, T, d_hT, fold ? d_melhat : nullptr, s);
+    });
+}
+
+void carve_vbr(const bvc_model *m, int B, int K, char *base, VbrWorkspace *v) {
+    const int H = m->cfg.h_dim, Z = m->cfg.z_dim, X = m->cfg.num_mels;
+    size_t off = 0;
+    auto take = [&](size_t nfloats) {
+        float *p = reinterpret_cast<float *>(base + off);
+        off += (nfloats * sizeof(float) + 255) / 256 * 256;
+        return p;
+    };
+    const size_t mb = (size_t)((B + 15) / 16) * 16, mk = (size_t)((K * B + 15) / 16) * 16;
+    v->zraw = take(mb * Z);
+    v->zc = take(mk * Z);
+    v->hrep = take(mk * H);
+    for (int i = 0; i < 3; ++i) v->pz[i] = take(mk * H);
+    for (int i = 0; i < 3; ++i) v->d[i] = take(mk * H);
+    v->melk = take(mk * X);
+    v->dnk = take(mk * X);
+    v->pzsel = take(mb * H);
+    v->dnsel = take(mb * X);
+    v->floats = off / sizeof(float);
+    v->call = reinterpret_cast<VbrCall *>(take((sizeof(VbrCall) + 3) / 4));
+    v->total = off;
+}
+
+// BVRNN.encode with the bits of every frame chosen inside the frame (build_vbr_step).  Always the launch-per-layer schedule, whatever
+// `recurrence` says: the persistent kernel has no candidate rows.  h_ladder: K ascending bit counts, checked by the caller.
+int run_encode_vbr(const bvc_model *m, const Workspace &w, const VbrWorkspace &v, void *ws_base, const float *d_mel, const float *d_tau,
+                   const int *h_ladder, int K, const float *d_h0, int B, int64_t T, float *d_codes, float *d_bits, float *d_all_h,
+                   float *d_hT, float *d_prob, float *d_dist, float *d_dec, hipStream_t s) {
+    return end_call(s, [&]() -> int {
+        const int H = m->cfg.h_dim;
+        const long long MH = (long long)((B + 15) / 16) * 16 * H;
+        int rc;
+        if ((rc = launch_normalize_rows(d_mel, m->mean_mel, m->std_mel, (long long)B * T, m->cfg.num_mels, w.yn, s))) return rc;
+        if ((rc = encode_prologue(m, w, B, T, s))) return rc;
+        if ((rc = launch_fill(v.zraw, 0.0f, (long long)v.floats, s))) return rc;      // rows of a fragment behind the last candidate read as zeros
+        VbrCall c;
+        memset(&c, 0, sizeof(c));
+        c.y = d_mel; c.tau = d_tau; c.codes = d_codes; c.bits = d_bits; c.dist = d_dist; c.dec = d_dec;
+        for (int k = 0; k < K; ++k) c.ladder[k] = h_ladder[k];
+        if ((rc = launch_vbr_set_call(v.call, c, s))) return rc;
+        CallDesc d;
+        memset(&d, 0, sizeof(d));
+        d.p[DS_PARTD] = w.part_dec0; d.p[DS_PROB] = d_prob; d.p[DS_ALLH] = d_all_h;
+        d.T = T;
+        if ((rc = d_h0 ? launch_repack_rows(d_h0, w.hbuf, H, B, H, 0, s) : launch_fill(w.hbuf, 0.0f, MH, s))) return rc;
+        if (d_all_h && (rc = launch_repack_rows(w.hbuf, d_all_h, (long long)T * H, B, H, 1, s))) return rc;      // all_h[:, 0] = h0
+        const std::vector<StepNode> plan = build_vbr_step(m, w, v, B, K);
+        if ((rc = begin_call(m, w, d, count_kernels(plan), s))) return rc;
+        if ((rc = run_recurrence(m, w, ws_base, B, T, STEP_ENCODE_VBR | (K << STEP_RUNGS_SHIFT), plan, s))) return rc;
+        if (d_hT && (rc = launch_repack_rows(w.hbuf + (T & 1) * MH, d_hT, H, B, H, 1, s))) return rc;
+        return BVC_OK;
     });
 }
 

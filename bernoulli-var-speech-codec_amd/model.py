@@ -98,6 +98,16 @@ class _Engine:
             ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
         return ctypes.c_void_p(ws.data_ptr()), ws.numel()
 
+    def vbr_workspace(self, B, T, K):
+        """Scratch of a closed-loop call (bvc_vbr_workspace_bytes): the current stream's buffer, grown if need be."""
+        need = self.lib.bvc_vbr_workspace_bytes(self.handle, B, T, K)
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            self._ws[key] = None
+            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ctypes.c_void_p(ws.data_ptr()), ws.numel()
+
     def stream(self):
         return _abi.current_stream(self.device)
 
@@ -144,6 +154,36 @@ def _trimmed(total, length):
 
 def _prep(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+_MAX_RUNGS = 8                   # VBR_MAX_RUNGS of the library
+
+
+def _check_ladder(ladder, z_dim, var_bit):
+    """The ladder of a closed-loop call as a ctypes int32 array, or ValueError: 1 to 8 integer bit counts in [0, z_dim], strictly
+    ascending, on a variable-rate model."""
+    if not var_bit:
+        raise ValueError("encode_vbr: a fixed-rate model (var_bit = false) has no bit mask to choose")
+    rungs = [int(n) for n in ladder]
+    if any(float(a) != float(b) for a, b in zip(rungs, ladder)):
+        raise ValueError(f"encode_vbr: the rungs must be integer bit counts, got {list(ladder)}")
+    if not 1 <= len(rungs) <= _MAX_RUNGS:
+        raise ValueError(f"encode_vbr: the ladder takes 1 to {_MAX_RUNGS} rungs, got {len(rungs)}: {rungs}")
+    if any(n < 0 or n > z_dim for n in rungs) or any(b <= a for a, b in zip(rungs, rungs[1:])):
+        raise ValueError(f"encode_vbr: the rungs must lie in [0, {z_dim}] and ascend strictly, got {rungs}")
+    return (ctypes.c_int32 * len(rungs))(*rungs), len(rungs)
+
+
+def _broadcast_target(target, B, T, device):
+    """A scalar, (B,) or (B,T) distortion target as a contiguous float32 (B,T) tensor on ``device``."""
+    t = torch.as_tensor(target, dtype=torch.float32).detach()
+    if t.dim() == 0:
+        t = t.reshape(1, 1)
+    elif tuple(t.shape) == (B,) and t.dim() == 1:
+        t = t.reshape(B, 1)
+    elif tuple(t.shape) != (B, T):
+        raise ValueError(f"encode_vbr: target must be a scalar, ({B},) or ({B}, {T}), got {tuple(t.shape)}")
+    return t.to(device).expand(B, T).contiguous()
 
 
 class _OnDevice(nn.Module):
@@ -271,6 +311,42 @@ class BVRNN(_OnDevice):
         if return_prob:
             return codes.to(out_dev), all_h.to(out_dev), eng.deliver(prob, out_dev)
         return codes.to(out_dev), eng.deliver(all_h, out_dev)
+
+    @torch.no_grad()
+    def encode_vbr(self, y, ladder, target, h, return_all=False):
+        """``encode`` with the bits of every frame chosen inside the frame (``bvc_bvrnn_encode_vbr``): y (B,T,x_dim), ``ladder`` up to 8
+        ascending bit counts, ``target`` a scalar, (B,) or (B,T) bound on the mean absolute log-mel error of the frame as the receiver
+        will decode it, h (1,B,h_dim).  A frame gets the first rung of the ladder that meets its target, the last one if none does.
+        Returns (codes (B,T,z), bits (B,T), all_h (B,T,h)); ``return_all=True`` adds a dict with prob (B,T,z), dist (B,T,K) - the error
+        of every rung -, dec (B,T,x_dim) - the chosen rung's decoded mel - and h_next (1,B,h_dim)."""
+        lad, K = _check_ladder(ladder, self.z_dim, self.varBit)
+        if y.dim() != 3:
+            raise ValueError("encode_vbr: y must be (B, T, num_mels)")
+        B, T, _ = y.shape
+        tau = _broadcast_target(target, B, T, "cpu")
+        eng = self.engine(y)
+        out_dev = y.device
+        y = _prep(y, eng.device)
+        tau = tau.to(eng.device)
+        h0 = _prep(h.reshape(B, self.h_dim), eng.device)
+        codes = torch.empty(B, T, self.z_dim, device=eng.device)
+        bits = torch.empty(B, T, device=eng.device)
+        all_h = torch.empty(B, T, self.h_dim, device=eng.device)
+        extra = {}
+        if return_all:
+            extra = {"prob": torch.empty(B, T, self.z_dim, device=eng.device), "dist": torch.empty(B, T, K, device=eng.device),
+                     "dec": torch.empty(B, T, self.x_dim, device=eng.device), "h_next": torch.empty(B, self.h_dim, device=eng.device)}
+        ws, nws = eng.vbr_workspace(B, T, K)
+        with torch.cuda.device(eng.device):
+            _abi.check(eng.lib.bvc_bvrnn_encode_vbr(
+                eng.handle, _abi.ptr(y), _abi.ptr(tau), lad, K, _abi.ptr(h0), B, T, _abi.ptr(codes), _abi.ptr(bits), _abi.ptr(all_h),
+                _abi.ptr(extra.get("h_next")), _abi.ptr(extra.get("prob")), _abi.ptr(extra.get("dist")), _abi.ptr(extra.get("dec")),
+                ws, nws, eng.stream()))
+        out = (codes.to(out_dev), bits.to(out_dev), eng.deliver(all_h, out_dev))
+        if return_all:
+            extra["h_next"] = extra["h_next"].unsqueeze(0)
+            return out + ({k: v.to(out_dev) for k, v in extra.items()},)
+        return out
 
     @torch.no_grad()
     def encode_stateful(self, y, varBitrate, h):
@@ -435,6 +511,42 @@ class BVRNNCodecModel(_OnDevice):
         with torch.cuda.device(eng.device):
             _abi.check(eng.lib.bvc_encode(eng.handle, _abi.ptr(x), B, L, float(SCALING), self.bits_per_frame(bitrate),
                                           _abi.ptr(codes), ws, nws, eng.stream()))
+        return eng.deliver(codes, out_dev)
+
+    @torch.no_grad()
+    def encode_vbr(self, x, target, bitrates=(1500, 3000, 6000), return_bits=True, lengths=None):
+        """Closed-loop variable-rate ``encode`` (``bvc_encode_vbr``): every frame gets the lowest of ``bitrates`` at which the mel the
+        receiver will decode lies within ``target`` - the mean absolute error over the bands of the natural-log mel; a scalar, (batch,)
+        or (batch, frames) - of the input's, the highest where none does.  ``bitrates`` [bit/s] become bits per frame as in ``encode``
+        (saturating at z_dim) and must still ascend strictly after that.  Returns (codes, bits (batch, frames)); ``decode`` takes the
+        codes as they are, ``pack_vbr`` puts them on the wire.  Equal-length batches only."""
+        if lengths is not None:
+            raise ValueError("encode_vbr: mixed-length batches (lengths=) are not supported")
+        z = self.conf["z_dim"]
+        rungs = [int(min(z, max(0.0, self.bits_per_frame(r)))) for r in bitrates]
+        lad, K = _check_ladder(rungs, z, self.conf["var_bit"])
+        if x.dim() != 2:
+            raise RuntimeError("expected a (batch, length) waveform")
+        B, L = x.shape
+        c = self.conf
+        pr = c["winsize"] - c["mel_pad_left"] - c["hopsize"]          # bvc_num_frames
+        T = 0 if (L <= c["mel_pad_left"] or L <= pr) else (L + c["mel_pad_left"] + pr - c["winsize"]) // c["hopsize"] + 1
+        if T <= 0:
+            raise RuntimeError(f"Argument #4: Padding size should be less than the corresponding input dimension "
+                               f"(length {L} is too short for the reflect padding of the STFT front-end)")
+        tau = _broadcast_target(target, B, T, "cpu")
+        eng = self.engine(x)
+        out_dev = x.device
+        x = _prep(x, eng.device)
+        tau = tau.to(eng.device)
+        codes = torch.empty(B, T, z, device=eng.device)
+        bits = torch.empty(B, T, device=eng.device)
+        ws, nws = eng.vbr_workspace(B, T, K)
+        with torch.cuda.device(eng.device):
+            _abi.check(eng.lib.bvc_encode_vbr(eng.handle, _abi.ptr(x), B, L, float(SCALING), _abi.ptr(tau), lad, K, _abi.ptr(codes),
+                                              _abi.ptr(bits), ws, nws, eng.stream()))
+        if return_bits:
+            return codes.to(out_dev), eng.deliver(bits, out_dev)
         return eng.deliver(codes, out_dev)
 
     @torch.no_grad()
@@ -683,3 +795,40 @@ class BVRNNCodecModel(_OnDevice):
             _abi.check(eng.lib.bvc_unpack_codes(ctypes.c_void_p(packed.data_ptr()) if packed.numel() else None, B, T, Z,
                                                 n, _abi.ptr(codes), eng.stream()))
         return codes.to(out_dev)
+
+    @torch.no_grad()
+    def pack_vbr(self, codes, bits):
+        """codes (B,T,z_dim) and bits (B,T) from encode_vbr -> (bytes uint8 (B,T,1 + ceil(z_dim/8)), sizes int32 (B,T)): a frame is its
+        bit count n, ceil(n/8) bytes of bits, zeros; sizes = 1 + ceil(n/8) are the bytes of the frame worth sending."""
+        if codes.dim() != 3 or tuple(bits.shape) != tuple(codes.shape[:2]) or codes.shape[2] != self.conf["z_dim"]:
+            raise ValueError("pack_vbr: codes (B, T, z_dim) with bits (B, T)")
+        eng = self.engine(codes)
+        out_dev = codes.device
+        codes = _prep(codes, eng.device)
+        bits = _prep(bits, eng.device)
+        B, T, Z = codes.shape
+        out = torch.empty(B, T, 1 + (Z + 7) // 8, dtype=torch.uint8, device=eng.device)
+        sizes = torch.empty(B, T, dtype=torch.int32, device=eng.device)
+        if sizes.numel():
+            with torch.cuda.device(eng.device):
+                _abi.check(eng.lib.bvc_pack_codes_vbr(_abi.ptr(codes), _abi.ptr(bits), B, T, Z, ctypes.c_void_p(out.data_ptr()),
+                                                      ctypes.c_void_p(sizes.data_ptr()), eng.stream()))
+        return out.to(out_dev), sizes.to(out_dev)
+
+    @torch.no_grad()
+    def unpack_vbr(self, packed):
+        """Inverse of pack_vbr(): uint8 (B,T,1 + ceil(z_dim/8)) -> (codes (B,T,z_dim) with 0.5 behind each frame's bits, bits (B,T))."""
+        Z = self.conf["z_dim"]
+        if packed.dim() != 3 or packed.shape[2] != 1 + (Z + 7) // 8 or packed.dtype != torch.uint8:
+            raise ValueError(f"unpack_vbr: uint8 (B, T, {1 + (Z + 7) // 8}) expected")
+        eng = self.engine(packed)
+        out_dev = packed.device
+        packed = packed.to(eng.device).contiguous()
+        B, T, _ = packed.shape
+        codes = torch.empty(B, T, Z, device=eng.device)
+        bits = torch.empty(B, T, device=eng.device)
+        if bits.numel():
+            with torch.cuda.device(eng.device):
+                _abi.check(eng.lib.bvc_unpack_codes_vbr(ctypes.c_void_p(packed.data_ptr()), B, T, Z, _abi.ptr(codes), _abi.ptr(bits),
+                                                        eng.stream()))
+        return codes.to(out_dev), bits.to(out_dev)

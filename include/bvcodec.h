@@ -452,6 +452,30 @@ int bvc_decode_ragged(const bvc_model *m, const float *d_codes, const int64_t *d
 int bvc_forward(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale, float bits_per_frame, int64_t length,
                 float out_scale_div, float *d_codes, float *d_wav_out, void *d_ws, size_t ws_bytes, void *stream);
 
+/* Closed-loop variable-rate encoding (new: the reference takes the bits of every frame from its caller, bvrnn.py:163-194).  The caller
+ * states a distortion target per frame and a ladder of bit counts; the encoder, which runs the decoder on every frame anyway
+ * (bvrnn.py:198-204), spends the fewest bits of the ladder that meet the target.  Per utterance b and frame t at state h_t:
+ *   p = sigmoid(enc([phi_x(norm(y_t)), h_t])), z = round(p)                                  - the plain encoder;
+ *   for every rung k: z^k = z on positions < n_k and 0.5 behind them, d^k = dec([phi_z(z^k), h_t]),
+ *                     D_k = mean_j |d^k_j - y_{t,j}| over the num_mels bands, in float32, summed in an order that depends on the row alone;
+ *   k* = the first k with D_k <= target[b, t], the last rung if there is none (so a NaN or -inf target gives the last rung, +inf rung 0);
+ *   codes[b, t] = z^{k*}, bits[b, t] = n_{k*}, and the recurrence goes on with rung k*: h_{t+1} = GRU([phi_x(norm(d^{k*})), phi_z(z^{k*})], h_t).
+ * With K = 1 the result is bvc_bvrnn_encode at n_0 bits, bit for bit.  The codes need no side information: bvc_bvrnn_decode, the
+ * concealing decoder and the streaming receiver take them unchanged.
+ *   d_mel (B,T,num_mels); d_target (B,T) in the units of the natural-log mel; h_ladder: K HOST int32, 1 <= K <= 8, each in [0, z_dim],
+ *   strictly ascending; d_h0 (B,h_dim) or NULL.  Outputs: d_codes (B,T,z_dim), d_bits (B,T) float; optional (may be NULL) d_all_h
+ *   (B,T,h_dim) the state BEFORE each frame, d_hT (B,h_dim), d_prob (B,T,z_dim), d_dist (B,T,K) = D, d_dec (B,T,num_mels) = d^{k*}.
+ * The candidates run as K * B rows of the recurrent-layer kernels, on the launch-per-layer schedule whatever the `recurrence` option says
+ * and on the unfolded layer list (`encode_fold` does not apply: dec.6 must exist to be measured).  Workspace: bvc_vbr_workspace_bytes(m, B,
+ * T, K) - NOT bvc_workspace_bytes.  BVC_EINVAL: a fixed-rate model (var_bit = 0: there is no mask), a bad ladder, a short workspace.
+ * bvc_encode_vbr: the front-end of bvc_encode (scale, log-mel, zero state) followed by the above; d_target (B, bvc_num_frames(L)). */
+size_t bvc_vbr_workspace_bytes(const bvc_model *m, int32_t B, int64_t T, int32_t K);
+int bvc_bvrnn_encode_vbr(const bvc_model *m, const float *d_mel, const float *d_target, const int32_t *h_ladder, int32_t K,
+                         const float *d_h0, int32_t B, int64_t T, float *d_codes, float *d_bits, float *d_all_h, float *d_hT,
+                         float *d_prob, float *d_dist, float *d_dec, void *d_ws, size_t ws_bytes, void *stream);
+int bvc_encode_vbr(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale, const float *d_target,
+                   const int32_t *h_ladder, int32_t K, float *d_codes, float *d_bits, void *d_ws, size_t ws_bytes, void *stream);
+
 /* Pre-processing of the reference's example.py:15-17.
  * bvc_resample_poly: y = upfirdn(h, x, up, down)[n_pre_remove : n_pre_remove + n_out] with zero padding, i.e.
  * scipy.signal.resample_poly once the caller has designed / padded the filter h (float64, device memory) as
@@ -518,7 +542,20 @@ int bvc_pack_codes(const float *d_codes, int32_t B, int64_t T, int32_t z_dim, in
 int bvc_unpack_codes(const uint8_t *d_bytes, int32_t B, int64_t T, int32_t z_dim, int32_t nbits, float *d_codes,
                      void *stream);
 
+/* The wire format with a bit count PER FRAME (the codes of bvc_bvrnn_encode_vbr).  A frame has a fixed stride of 1 + ceil(z_dim/8)
+ * bytes: byte 0 is the frame's bit count n, the next ceil(n/8) bytes are its bits in bvc_pack_codes order, the rest of the stride is
+ * zero.  d_bytes (B, T, 1 + ceil(z_dim/8)); d_bits (B,T) float; d_sizes (B,T) int32 (may be NULL) = 1 + ceil(n/8), the bytes worth
+ * sending.  Unpack reads a header above z_dim as z_dim - no read leaves the frame's stride, whatever the bytes hold -, writes 0.5 at
+ * positions >= n and n to d_bits (may be NULL).  z_dim <= 255. */
+int bvc_pack_codes_vbr(const float *d_codes, const float *d_bits, int32_t B, int64_t T, int32_t z_dim, uint8_t *d_bytes,
+                       int32_t *d_sizes, void *stream);
+int bvc_unpack_codes_vbr(const uint8_t *d_bytes, int32_t B, int64_t T, int32_t z_dim, float *d_codes, float *d_bits, void *stream);
+
 /* ---- building blocks exported for the parity tests (tests/ only; same kernels the path uses) */
+/* The select kernel of bvc_bvrnn_encode_vbr alone, on one frame (allocates, synchronises): d_melhat (K, B, num_mels) the decoded mel of
+ * every rung, d_y (B, num_mels), d_tau (B), h_ladder K host int32 -> d_dist (B, K) = D, d_choice (B) int32 = k*, d_bits (B) = n_{k*}. */
+int bvc_test_vbr_select(const float *d_melhat, const float *d_y, const float *d_tau, const int32_t *h_ladder, int32_t K, int32_t B,
+                        int32_t num_mels, float *d_dist, int32_t *d_choice, float *d_bits, void *stream);
 /* y[M,N] = act(x[M,K] @ w[N,K]^T + bias), act: 0 none, 1 ELU.  Recurrent-step kernel. */
 int bvc_test_linear(const float *d_x, const float *d_w, const float *d_bias, int32_t M, int32_t N,
                     int32_t K, int32_t act, float *d_y, void *stream);
