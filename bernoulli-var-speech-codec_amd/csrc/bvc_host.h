@@ -1,5 +1,5 @@
-// Host side of libbvcodec_hip.so, shared by its sources model.hip, recurrence.hip, generator.hip, stream_codec.hip and
-// bvcodec_abi.hip: the model, the workspace layout, the GEMM parameter helpers, the drivers of the offline paths and the state that
+// Host side of libbvcodec_hip.so, shared by its sources model.hip, recurrence.hip, step_plan.hip, flow_launch.hip, generator.hip,
+// stream_codec.hip and bvcodec_abi.hip (what only the three sources of the recurrence share is in recurrence.h): the model, the workspace layout, the GEMM parameter helpers, the drivers of the offline paths and the state that
 // crosses a file boundary.  Host only.  What more than one source uses lives in namespace bvc, next to the launchers of
 // bvc_internal.h; everything else is local to its file.
 #pragma once
@@ -138,7 +138,7 @@ namespace bvc {
 extern thread_local bool g_capturing;     // no event probes while THIS thread captures a stream (captures are thread-local)
 extern thread_local bool g_stream_tick;   // inside bvc_stream_codec_tick: a launch-per-layer recurrence is launched eagerly (the tick itself is the graph)
 extern thread_local bool g_tick_flow;     // ... of a tick that is NOT a graph: its recurrences may take the persistent kernel
-extern std::mutex g_flow_mu;              // persistent launches and the residency census, one at a time per process (recurrence.hip)
+extern std::mutex g_flow_mu;              // persistent launches and the residency census, one at a time per process (flow_launch.hip)
 // the two tick flags for a scope (a tick's body, a replay pass): no path out of it leaves them set
 struct TickFlags {
     explicit TickFlags(bool flow) { g_stream_tick = true; g_tick_flow = flow; }
@@ -223,7 +223,7 @@ inline int flow_grid_tiles(const bvc_model *m) {          // feature tiles cover
     const int H = m->cfg.h_dim, X = m->cfg.num_mels, Z = m->cfg.z_dim;
     return ((H > X ? (H > Z ? H : Z) : (X > Z ? X : Z)) / 16 + 7) / 8 * 8;
 }
-// The environment switches of the persistent recurrence, read by flow_switches() alone (recurrence.hip, which says when): BVC_FLOW_HOTW,
+// The environment switches of the persistent recurrence, read by flow_switches() alone (flow_launch.hip, which says when): BVC_FLOW_HOTW,
 // BVC_FLOW_FILL, BVC_FLOW_TICKETS, BVC_FLOW_NO_CHAINS; with `probing` also BVC_PROBE_WG and BVC_PROBE_WAVE (0 / 0 otherwise)
 struct FlowSwitches { bool hot_w, fill, no_chains; int tickets, probe_wg, probe_wave; };
 FlowSwitches flow_switches(bool probing = false);
