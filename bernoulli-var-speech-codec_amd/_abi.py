@@ -82,6 +82,15 @@ SIGNATURES = {
     "bvc_bvrnn_encode_vbr": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_i32), _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _sz, _vp]),
     "bvc_encode_vbr": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _vp, ctypes.POINTER(_i32), _i32, _vp, _vp, _vp, _sz, _vp]),
+    "bvc_bvrnn_encode_vbr_capped": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_i32), _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _sz, _vp, _i32, _i32, _vp, _vp]),
+    "bvc_encode_vbr_capped": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _vp, ctypes.POINTER(_i32), _i32, _vp, _vp, _vp, _sz, _vp, _i32, _i32]),
+    "bvc_test_vbr_select_capped": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "bvc_stream_codec_create_vbr": (ctypes.c_int, [_vp, _i32, _i32, ctypes.POINTER(_i32), _i32, _f, _i32, _i32, _f, _f, _f, _i32,
+                                                   ctypes.POINTER(_vp)]),
+    "bvc_stream_codec_set_target": (ctypes.c_int, [_vp, _i32, _f]),
+    "bvc_stream_codec_sizes": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "bvc_stream_codec_bits": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "bvc_pack_codes_vbr": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "bvc_unpack_codes_vbr": (ctypes.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "bvc_test_vbr_select": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -240,13 +240,14 @@ int run_decode_conceal(const bvc_model *m, const Workspace &w, void *ws_base, co
 struct VbrWorkspace {
     float *zraw, *zc, *hrep, *pz[3], *d[3], *melk, *dnk, *pzsel, *dnsel;
     VbrCall *call;
+    int *tok;                   // (B) the buckets of a capped call, behind `call`
     size_t floats;              // the frame buffers in front of `call` (cleared at the start of a call: padded rows hold zeros)
     size_t total;               // bytes in front of the ordinary workspace
 };
 void carve_vbr(const bvc_model *m, int B, int K, char *base, VbrWorkspace *v);
 int run_encode_vbr(const bvc_model *m, const Workspace &w, const VbrWorkspace &v, void *ws_base, const float *d_mel, const float *d_tau,
                    const int *h_ladder, int K, const float *d_h0, int B, int64_t T, float *d_codes, float *d_bits, float *d_all_h,
-                   float *d_hT, float *d_prob, float *d_dist, float *d_dec, hipStream_t s);
+                   float *d_hT, float *d_prob, float *d_dist, float *d_dec, hipStream_t s, const VbrCap *cap = nullptr);
 int run_forward(const bvc_model *m, const Workspace &w, const float *d_mel, const float *d_bits, const uint8_t *h_use_gen, bool update_h,
                 bool update_h2, const float *d_noise, int B, int64_t T, float *d_dec, float *d_kld, float *d_z, float *d_prob,
                 float *d_prior, hipStream_t s);

@@ -353,7 +353,14 @@ struct VbrCall {
     float *dec;                      // (B,T,X) the chosen rung's decoded mel, or null
     int *choice;                     // (B,T) the chosen rung, or null (the test hook)
     int ladder[VBR_MAX_RUNGS];       // bit counts, ascending
+    // the rate cap (bvc_bvrnn_encode_vbr_capped): an integer token bucket per row in q8 (1/256 bit).  Per frame, behind today's choice
+    // k_target: tok = min(burst, tok + rate); a = the largest k with ladder[k] * 256 <= tok (0 if none); k* = min(k_target, a);
+    // tok = max(0, tok - ladder[k*] * 256).  capped == 0: none of it runs.
+    int capped, rate_q8, burst_q8;
+    int *tok;                        // (B) the rows' buckets, carried from frame to frame (and from call to call by the caller)
 };
+// the cap of one call as the host passes it on: tok0 (B) or null = full buckets, tokT (B) or null; tok0 == tokT is fine
+struct VbrCap { int capped, rate_q8, burst_q8; const int *tok0; int *tokT; };
 // One frame's buffers (workspace-static; fragment-packed unless stated) and sizes: the arguments of the two kernels.
 struct VbrStep {
     const CallDesc *desc;            // null: a stand-alone launch on (B, 1, .) tensors (the test hook)
@@ -376,6 +383,15 @@ int launch_vbr_select(const VbrStep &a, int tstep, hipStream_t s);
 // launch_pack_codes order, zeros; sizes (frames) = 1 + ceil(n / 8)
 int launch_pack_codes_vbr(const float *codes, const float *bits, long long frames, int z, unsigned char *out, int *sizes, hipStream_t s);
 int launch_unpack_codes_vbr(const unsigned char *in, long long frames, int z, float *codes, float *bits, hipStream_t s);
+// dst[b] = src ? src[b] : fill, b < B (the buckets of a capped call; dst == src: nothing)
+int launch_vbr_tok(int *dst, const int *src, int fill, int B, hipStream_t s);
+// that wire inside a streaming tick (bvc_stream_codec_create_vbr): codes (B, k, z), bits (B, k); frame j of row b at
+// (b * kstride + j) * (1 + ceil(z / 8)) of the packet buffer, sizes / bits_out (B, kstride) (each may be null; so may `out`).  Unpack: a
+// frame that is not present, or of an idle row (row_off[b] < 0), is a frame of no bits
+int launch_pack_rows_vbr(const float *codes, const float *bits, int B, int k, int z, int kstride, unsigned char *out, int *sizes,
+                         float *bits_out, hipStream_t s);
+int launch_unpack_rows_vbr(const unsigned char *in, const unsigned char *present, const int *row_off, int B, int k, int z, int kstride,
+                           float *codes, float *bits_out, hipStream_t s);
 
 // ------------------------------------------------------------------ vocoder (k_vocoder.hip; the AMP pairs: k_vocoder_amp.hip)
 struct ConvLayer {               // one causal conv as implicit GEMM on fp32 MFMA

@@ -209,31 +209,76 @@ size_t bvc_vbr_workspace_bytes(const bvc_model *m, int32_t B, int64_t T, int32_t
     return v.total + w.total;
 }
 
-int bvc_bvrnn_encode_vbr(const bvc_model *m, const float *d_mel, const float *d_target, const int32_t *h_ladder, int32_t K,
-                         const float *d_h0, int32_t B, int64_t T, float *d_codes, float *d_bits, float *d_all_h, float *d_hT,
-                         float *d_prob, float *d_dist, float *d_dec, void *d_ws, size_t ws_bytes, void *stream) {
-    Workspace w;
-    VbrWorkspace v;
-    if (int rc = enter_vbr(m, B, T, h_ladder, K, d_ws, ws_bytes, &w, &v, "bvc_bvrnn_encode_vbr")) return rc;
-    if (!d_mel || !d_target || !d_codes || !d_bits) { set_error("null argument"); return BVC_EINVAL; }
-    return run_encode_vbr(m, w, v, d_ws, d_mel, d_target, h_ladder, K, d_h0, B, T, d_codes, d_bits, d_all_h, d_hT, d_prob, d_dist, d_dec,
-                          (hipStream_t)stream);
+// the cap's own checks, behind enter_vbr's: 0 with *cap filled in
+static int enter_cap(const char *fn, const int32_t *h_ladder, int32_t rate_q8, int32_t burst_q8, const int32_t *d_tok0, int32_t *d_tokT,
+                     VbrCap *cap) {
+    if (rate_q8 < 0 || burst_q8 < 0) { set_error("%s: rate_q8 = %d, burst_q8 = %d: neither may be negative", fn, (int)rate_q8, (int)burst_q8); return BVC_EINVAL; }
+    if ((long long)burst_q8 < (long long)h_ladder[0] * 256) {
+        set_error("%s: a bucket of %d/256 bits never holds rung 0 (%d bits)", fn, (int)burst_q8, (int)h_ladder[0]);
+        return BVC_EINVAL;
+    }
+    *cap = VbrCap{1, rate_q8, burst_q8, d_tok0, d_tokT};
+    return BVC_OK;
 }
 
-int bvc_encode_vbr(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale, const float *d_target,
-                   const int32_t *h_ladder, int32_t K, float *d_codes, float *d_bits, void *d_ws, size_t ws_bytes, void *stream) {
+static int encode_vbr_mel(const char *fn, const bvc_model *m, const float *d_mel, const float *d_target, const int32_t *h_ladder, int32_t K,
+                          const float *d_h0, int32_t B, int64_t T, float *d_codes, float *d_bits, float *d_all_h, float *d_hT, float *d_prob,
+                          float *d_dist, float *d_dec, void *d_ws, size_t ws_bytes, void *stream, bool capped, int32_t rate_q8, int32_t burst_q8,
+                          const int32_t *d_tok0, int32_t *d_tokT) {
+    Workspace w;
+    VbrWorkspace v;
+    VbrCap cap{0, 0, 0, nullptr, nullptr};
+    if (int rc = enter_vbr(m, B, T, h_ladder, K, d_ws, ws_bytes, &w, &v, fn)) return rc;
+    if (!d_mel || !d_target || !d_codes || !d_bits) { set_error("null argument"); return BVC_EINVAL; }
+    if (capped) if (int rc = enter_cap(fn, h_ladder, rate_q8, burst_q8, d_tok0, d_tokT, &cap)) return rc;
+    return run_encode_vbr(m, w, v, d_ws, d_mel, d_target, h_ladder, K, d_h0, B, T, d_codes, d_bits, d_all_h, d_hT, d_prob, d_dist, d_dec,
+                          (hipStream_t)stream, &cap);
+}
+
+static int encode_vbr_wav(const char *fn, const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale, const float *d_target,
+                          const int32_t *h_ladder, int32_t K, float *d_codes, float *d_bits, void *d_ws, size_t ws_bytes, void *stream,
+                          bool capped, int32_t rate_q8, int32_t burst_q8) {
     if (!m) { set_error("null model"); return BVC_EINVAL; }
     const int64_t T = bvc_num_frames(m, L);
     if (T <= 0) { set_error("input too short for reflect padding (L=%lld)", (long long)L); return BVC_EINVAL; }
     Workspace w;
     VbrWorkspace v;
-    int rc = enter_vbr(m, B, T, h_ladder, K, d_ws, ws_bytes, &w, &v, "bvc_encode_vbr");
+    VbrCap cap{0, 0, 0, nullptr, nullptr};
+    int rc = enter_vbr(m, B, T, h_ladder, K, d_ws, ws_bytes, &w, &v, fn);
     if (rc) return rc;
     if (!d_wav || !d_target || !d_codes || !d_bits) { set_error("null argument"); return BVC_EINVAL; }
+    if (capped && (rc = enter_cap(fn, h_ladder, rate_q8, burst_q8, nullptr, nullptr, &cap))) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = launch_stft_logmel(m->fe, d_wav, B, L, T, m->cfg.pad_left, scale, w.mel, s))) return rc;
     return run_encode_vbr(m, w, v, d_ws, w.mel, d_target, h_ladder, K, nullptr, B, T, d_codes, d_bits, nullptr, nullptr, nullptr, nullptr,
-                          nullptr, s);
+                          nullptr, s, &cap);
+}
+
+int bvc_bvrnn_encode_vbr(const bvc_model *m, const float *d_mel, const float *d_target, const int32_t *h_ladder, int32_t K,
+                         const float *d_h0, int32_t B, int64_t T, float *d_codes, float *d_bits, float *d_all_h, float *d_hT,
+                         float *d_prob, float *d_dist, float *d_dec, void *d_ws, size_t ws_bytes, void *stream) {
+    return encode_vbr_mel("bvc_bvrnn_encode_vbr", m, d_mel, d_target, h_ladder, K, d_h0, B, T, d_codes, d_bits, d_all_h, d_hT, d_prob, d_dist,
+                          d_dec, d_ws, ws_bytes, stream, false, 0, 0, nullptr, nullptr);
+}
+
+int bvc_bvrnn_encode_vbr_capped(const bvc_model *m, const float *d_mel, const float *d_target, const int32_t *h_ladder, int32_t K,
+                                const float *d_h0, int32_t B, int64_t T, float *d_codes, float *d_bits, float *d_all_h, float *d_hT,
+                                float *d_prob, float *d_dist, float *d_dec, void *d_ws, size_t ws_bytes, void *stream, int32_t rate_q8,
+                                int32_t burst_q8, const int32_t *d_tok0, int32_t *d_tokT) {
+    return encode_vbr_mel("bvc_bvrnn_encode_vbr_capped", m, d_mel, d_target, h_ladder, K, d_h0, B, T, d_codes, d_bits, d_all_h, d_hT, d_prob,
+                          d_dist, d_dec, d_ws, ws_bytes, stream, true, rate_q8, burst_q8, d_tok0, d_tokT);
+}
+
+int bvc_encode_vbr(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale, const float *d_target,
+                   const int32_t *h_ladder, int32_t K, float *d_codes, float *d_bits, void *d_ws, size_t ws_bytes, void *stream) {
+    return encode_vbr_wav("bvc_encode_vbr", m, d_wav, B, L, scale, d_target, h_ladder, K, d_codes, d_bits, d_ws, ws_bytes, stream, false, 0, 0);
+}
+
+int bvc_encode_vbr_capped(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale, const float *d_target,
+                          const int32_t *h_ladder, int32_t K, float *d_codes, float *d_bits, void *d_ws, size_t ws_bytes, void *stream,
+                          int32_t rate_q8, int32_t burst_q8) {
+    return encode_vbr_wav("bvc_encode_vbr_capped", m, d_wav, B, L, scale, d_target, h_ladder, K, d_codes, d_bits, d_ws, ws_bytes, stream, true,
+                          rate_q8, burst_q8);
 }
 
 int bvc_forward(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale, float bits_per_frame, int64_t length,
@@ -384,11 +429,12 @@ int bvc_unpack_codes_vbr(const uint8_t *d_bytes, int32_t B, int64_t T, int32_t z
     return launch_unpack_codes_vbr(d_bytes, (long long)B * T, z_dim, d_codes, d_bits, (hipStream_t)stream);
 }
 
-int bvc_test_vbr_select(const float *d_melhat, const float *d_y, const float *d_tau, const int32_t *h_ladder, int32_t K, int32_t B,
-                        int32_t num_mels, float *d_dist, int32_t *d_choice, float *d_bits, void *stream) {
-    // test helper (allocates + synchronises): the select kernel alone, on one frame
+// test helpers (allocate + synchronise): the select kernel alone, on one frame; d_tok != null: under the cap, the (B) buckets in place
+static int test_vbr_select(const char *fn, const float *d_melhat, const float *d_y, const float *d_tau, const int32_t *h_ladder, int32_t K,
+                           int32_t B, int32_t num_mels, float *d_dist, int32_t *d_choice, float *d_bits, void *stream, int32_t rate_q8,
+                           int32_t burst_q8, int32_t *d_tok) {
     if (!d_melhat || !d_y || !d_tau || !h_ladder || !d_dist || !d_choice || !d_bits || B <= 0 || num_mels <= 0 || K < 1 || K > VBR_MAX_RUNGS) {
-        set_error("bvc_test_vbr_select: bad arguments");
+        set_error("%s: bad arguments", fn);
         return BVC_EINVAL;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -396,6 +442,7 @@ int bvc_test_vbr_select(const float *d_melhat, const float *d_y, const float *d_
     memset(&c, 0, sizeof(c));
     c.y = d_y; c.tau = d_tau; c.dist = d_dist; c.bits = d_bits; c.choice = d_choice;
     for (int k = 0; k < K; ++k) c.ladder[k] = h_ladder[k];
+    if (d_tok) { c.capped = 1; c.rate_q8 = rate_q8; c.burst_q8 = burst_q8; c.tok = d_tok; }
     VbrCall *dc = nullptr;
     BVC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dc), sizeof(VbrCall)));
     int rc = launch_vbr_set_call(dc, c, s);
@@ -405,8 +452,21 @@ int bvc_test_vbr_select(const float *d_melhat, const float *d_y, const float *d_
     if (!rc) rc = launch_vbr_select(a, 0, s);
     const hipError_t e = hipStreamSynchronize(s);
     (void)hipFree(dc);
-    if (!rc && e != hipSuccess) { set_error("bvc_test_vbr_select: %s", hipGetErrorString(e)); rc = BVC_EHIP; }
+    if (!rc && e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); rc = BVC_EHIP; }
     return rc;
+}
+
+int bvc_test_vbr_select(const float *d_melhat, const float *d_y, const float *d_tau, const int32_t *h_ladder, int32_t K, int32_t B,
+                        int32_t num_mels, float *d_dist, int32_t *d_choice, float *d_bits, void *stream) {
+    return test_vbr_select("bvc_test_vbr_select", d_melhat, d_y, d_tau, h_ladder, K, B, num_mels, d_dist, d_choice, d_bits, stream, 0, 0, nullptr);
+}
+
+int bvc_test_vbr_select_capped(const float *d_melhat, const float *d_y, const float *d_tau, const int32_t *h_ladder, int32_t K, int32_t B,
+                               int32_t num_mels, float *d_dist, int32_t *d_choice, float *d_bits, void *stream, int32_t rate_q8,
+                               int32_t burst_q8, int32_t *d_tok) {
+    if (!d_tok || rate_q8 < 0 || burst_q8 < 0) { set_error("bvc_test_vbr_select_capped: bad arguments"); return BVC_EINVAL; }
+    return test_vbr_select("bvc_test_vbr_select_capped", d_melhat, d_y, d_tau, h_ladder, K, B, num_mels, d_dist, d_choice, d_bits, stream,
+                           rate_q8, burst_q8, d_tok);
 }
 
 int bvc_kprobe_enable(int32_t on) {

@@ -75,6 +75,16 @@ __global__ __launch_bounds__(64) void vbr_select_kernel(VbrStep a, int tstep) {
         if (c.dist && lane == 0) c.dist[bt * a.K + k] = D;
         if (!found && D <= tau) { choice = k; found = true; }       // (a NaN on either side compares false)
     }
+    if (c.capped) {
+        // the row's token bucket, in q8 integers (every lane computes the same numbers, lane 0 keeps them): never more than it holds
+        long long tok = (long long)c.tok[b] + c.rate_q8;
+        if (tok > c.burst_q8) tok = c.burst_q8;
+        int afford = 0;
+        for (int k = 1; k < a.K; ++k) if ((long long)c.ladder[k] * 256 <= tok) afford = k;
+        if (afford < choice) choice = afford;
+        tok -= (long long)c.ladder[choice] * 256;
+        if (lane == 0) c.tok[b] = tok > 0 ? (int)tok : 0;
+    }
     const int n = c.ladder[choice];
     const int row = choice * a.B + b;
     if (lane == 0) {
@@ -136,6 +146,57 @@ __global__ void unpack_codes_vbr_kernel(const unsigned char *__restrict__ in, lo
     }
 }
 
+// the rows' buckets into or out of the call's workspace: dst[b] = src ? src[b] : fill
+__global__ void vbr_tok_kernel(int *__restrict__ dst, const int *__restrict__ src, int fill, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) dst[b] = src ? src[b] : fill;
+}
+
+// ---- the same wire inside a streaming tick (bvc_stream_codec_create_vbr): codes (B, k, z) and bits (B, k) of the tick, frame j of row b
+// at (b * kstride + j) * stride of the packet buffer; sizes and the bit counts as floats at b * kstride + j.  One thread per byte.
+__global__ void sc_pack_rows_vbr_kernel(const float *__restrict__ codes, const float *__restrict__ bits, int B, int k, int z, int stride, int kstride,
+                                        unsigned char *__restrict__ out, int *__restrict__ sizes, float *__restrict__ bits_out) {
+    const long long total = (long long)B * k * stride;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long f = i / stride;
+        const int y = (int)(i - f * stride);
+        const int b = (int)(f / k), j = (int)(f - (long long)b * k);
+        const long long pf = (long long)b * kstride + j;
+        const int n = vbr_nbits(bits[f], z);
+        unsigned v = 0;
+        if (y == 0) {
+            v = (unsigned)n;
+            if (sizes) sizes[pf] = 1 + ((n + 7) >> 3);
+            if (bits_out) bits_out[pf] = (float)n;
+        } else {
+            for (int q = 0; q < 8; ++q) {
+                const int bit = (y - 1) * 8 + q;
+                if (bit < n && codes[f * z + bit] > 0.75f) v |= 1u << q;
+            }
+        }
+        if (out) out[pf * stride + y] = (unsigned char)v;
+    }
+}
+
+// one thread per code position.  A frame that did not arrive (present == 0) has no header: it is a frame of no bits, and so is every
+// frame of an idle row (row_off[b] < 0).  A header above z reads as z, so no read leaves the frame's stride.
+__global__ void sc_unpack_rows_vbr_kernel(const unsigned char *__restrict__ in, const unsigned char *__restrict__ present,
+                                          const int *__restrict__ row_off, int B, int k, int z, int stride, int kstride,
+                                          float *__restrict__ codes, float *__restrict__ bits_out) {
+    const long long total = (long long)B * k * z;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long f = i / z;
+        const int bit = (int)(i - f * z);
+        const int b = (int)(f / k), j = (int)(f - (long long)b * k);
+        const long long pf = (long long)b * kstride + j;
+        const unsigned char *fr = in + pf * stride;
+        int n = 0;
+        if (row_off[b] >= 0 && present[pf] != 0) { const int h = fr[0]; n = h > z ? z : h; }
+        codes[i] = bit < n ? (float)((fr[1 + (bit >> 3)] >> (bit & 7)) & 1u) : 0.5f;
+        if (bits_out && bit == 0) bits_out[pf] = (float)n;
+    }
+}
+
 int vbr_step_ok(const VbrStep &a) {
     if (a.B <= 0 || a.K < 1 || a.K > VBR_MAX_RUNGS || a.X <= 0 || (a.Z & 15) || (a.H & 15) || (a.dnk && (a.X & 15))) {
         set_error("vbr: B=%d K=%d Z=%d H=%d X=%d: 1..%d rungs, packed rows in multiples of 16", a.B, a.K, a.Z, a.H, a.X, VBR_MAX_RUNGS);
@@ -148,6 +209,35 @@ int vbr_step_ok(const VbrStep &a) {
 
 int launch_vbr_set_call(VbrCall *d, const VbrCall &v, hipStream_t s) {
     hipLaunchKernelGGL(vbr_set_call_kernel, dim3(1), dim3(64), 0, s, d, v);
+    BVC_HIP_TRY(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_vbr_tok(int *dst, const int *src, int fill, int B, hipStream_t s) {
+    if (B <= 0 || !dst || dst == src) return BVC_OK;
+    hipLaunchKernelGGL(vbr_tok_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, dst, src, fill, B);
+    BVC_HIP_TRY(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_pack_rows_vbr(const float *codes, const float *bits, int B, int k, int z, int kstride, unsigned char *out, int *sizes,
+                         float *bits_out, hipStream_t s) {
+    const int stride = 1 + (z + 7) / 8;
+    const long long total = (long long)B * k * stride;
+    if (total <= 0) return BVC_OK;
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(sc_pack_rows_vbr_kernel, dim3(grid), dim3(256), 0, s, codes, bits, B, k, z, stride, kstride, out, sizes, bits_out);
+    BVC_HIP_TRY(hipGetLastError());
+    return BVC_OK;
+}
+
+int launch_unpack_rows_vbr(const unsigned char *in, const unsigned char *present, const int *row_off, int B, int k, int z, int kstride,
+                           float *codes, float *bits_out, hipStream_t s) {
+    const int stride = 1 + (z + 7) / 8;
+    const long long total = (long long)B * k * z;
+    if (total <= 0) return BVC_OK;
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(sc_unpack_rows_vbr_kernel, dim3(grid), dim3(256), 0, s, in, present, row_off, B, k, z, stride, kstride, codes, bits_out);
     BVC_HIP_TRY(hipGetLastError());
     return BVC_OK;
 }

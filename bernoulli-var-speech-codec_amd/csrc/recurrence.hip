@@ -181,16 +181,19 @@ void carve_vbr(const bvc_model *m, int B, int K, char *base, VbrWorkspace *v) {
     v->dnsel = take(mb * X);
     v->floats = off / sizeof(float);
     v->call = reinterpret_cast<VbrCall *>(take((sizeof(VbrCall) + 3) / 4));
+    v->tok = reinterpret_cast<int *>(take((size_t)B));
     v->total = off;
 }
 
 // BVRNN.encode with the bits of every frame chosen inside the frame (build_vbr_step).  Always the launch-per-layer schedule, whatever
-// `recurrence` says: the persistent kernel has no candidate rows.  h_ladder: K ascending bit counts, checked by the caller.
+// `recurrence` says: the persistent kernel has no candidate rows.  h_ladder: K ascending bit counts, checked by the caller.  cap (null
+// or capped == 0: none): the token bucket of the selection, the rows' buckets from cap->tok0 (null: full) and back to cap->tokT.
 int run_encode_vbr(const bvc_model *m, const Workspace &w, const VbrWorkspace &v, void *ws_base, const float *d_mel, const float *d_tau,
                    const int *h_ladder, int K, const float *d_h0, int B, int64_t T, float *d_codes, float *d_bits, float *d_all_h,
-                   float *d_hT, float *d_prob, float *d_dist, float *d_dec, hipStream_t s) {
+                   float *d_hT, float *d_prob, float *d_dist, float *d_dec, hipStream_t s, const VbrCap *cap) {
     return end_call(s, [&]() -> int {
         int rc;
+        const bool capped = cap && cap->capped;
         if ((rc = launch_normalize_rows(d_mel, m->mean_mel, m->std_mel, (long long)B * T, m->cfg.num_mels, w.yn, s))) return rc;
         if ((rc = encode_prologue(m, w, B, T, s))) return rc;
         if ((rc = launch_fill(v.zraw, 0.0f, (long long)v.floats, s))) return rc;      // rows of a fragment behind the last candidate read as zeros
@@ -198,11 +201,17 @@ int run_encode_vbr(const bvc_model *m, const Workspace &w, const VbrWorkspace &v
         memset(&c, 0, sizeof(c));
         c.y = d_mel; c.tau = d_tau; c.codes = d_codes; c.bits = d_bits; c.dist = d_dist; c.dec = d_dec;
         for (int k = 0; k < K; ++k) c.ladder[k] = h_ladder[k];
+        if (capped) {
+            c.capped = 1; c.rate_q8 = cap->rate_q8; c.burst_q8 = cap->burst_q8; c.tok = v.tok;
+            if ((rc = launch_vbr_tok(v.tok, cap->tok0, cap->burst_q8, B, s))) return rc;
+        }
         if ((rc = launch_vbr_set_call(v.call, c, s))) return rc;
         CallDesc d;
         memset(&d, 0, sizeof(d));
         d.p[DS_PARTD] = w.part_dec0; d.p[DS_PROB] = d_prob; d.p[DS_ALLH] = d_all_h;
-        return run_layers(m, w, ws_base, d, build_vbr_step(m, w, v, B, K), STEP_ENCODE_VBR | (K << STEP_RUNGS_SHIFT), d_h0, B, T, d_hT, nullptr, s);
+        if ((rc = run_layers(m, w, ws_base, d, build_vbr_step(m, w, v, B, K), STEP_ENCODE_VBR | (K << STEP_RUNGS_SHIFT), d_h0, B, T, d_hT, nullptr, s)))
+            return rc;
+        return capped ? launch_vbr_tok(cap->tokT, v.tok, 0, B, s) : BVC_OK;
     });
 }
 

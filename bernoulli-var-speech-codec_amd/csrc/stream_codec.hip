@@ -108,6 +108,11 @@ __global__ __launch_bounds__(256) void sc_slot_start_kernel(SlotRowList l, const
     }
 }
 
+// ... and in a session that chooses its own rates under a cap (bvc_stream_codec_create_vbr) those rows' buckets are full again
+__global__ void sc_tok_start_kernel(SlotRowList l, int *__restrict__ tok, int full) {
+    if ((int)threadIdx.x < l.n) tok[l.row[threadIdx.x]] = full;
+}
+
 // end of a stream (bvc_stream_codec_finish), after the append of the tick that takes its last hop: of that hop only the first n_last
 // samples (SlotUpdate::off) are the stream's.  Directly behind them the right reflect padding of the front-end (meldataset.py:72-81):
 // with e = the index one behind the last sample, d[e + i] = d[e - 2 - i], i = 0 .. rpad - 1; zeros from there to the end of the row (the
@@ -266,6 +271,17 @@ struct bvc_stream_codec {
     };
     RepairWindow rep;
     bool tick_retained(const RepairWindow::RingTick &t) const { return t.valid && t.f0 + t.k > frames - rep.w; }
+    // sessions that choose their own rates and / or speak the wire with a bit count per frame (bvc_stream_codec_create_vbr).  SEND and
+    // DUPLEX: a slot's `bits` and `bitsbuf` hold the slot's TARGET (the (B, k) layouts are what run_encode_vbr reads as tau), the tick's
+    // bit counts go to vbits (B, k), and from there to last_bits / sizes (B, kmax); tok (B) are the rows' buckets.  RECV: the unpack reads
+    // each frame's header, `bits` stays the count a lost frame is concealed with.
+    bool vbr = false;
+    bool choosing() const { return vbr && dir != BVC_STREAM_RECV; }
+    int K = 0, ladder[VBR_MAX_RUNGS] = {};
+    int rate_q8 = 0, burst_q8 = -1;     // burst_q8 < 0: no cap
+    char *vws = nullptr;                // the candidates' frame buffers (carve_vbr), apart from the ordinary workspace `ws`
+    float *vbits = nullptr, *last_bits = nullptr;
+    int *sizes = nullptr, *tok = nullptr;
     bool use_graph = true;
     bool tick_flow = true;      // the ticks' recurrences on the persistent kernel where it is available (BVC_STREAM_FLOW=0: never)
     ~bvc_stream_codec() {
@@ -359,6 +375,7 @@ int stream_start_rows(bvc_stream_codec *st, int64_t f_begin, int k, hipStream_t 
         sc_slot_start_kernel<<<dim3(gx, (unsigned)n_ten + 1, (unsigned)l.n), 256, 0, s>>>(
             l, v ? v->d_tab : nullptr, n_ten, v && v->slide ? v->cursor : 0, st->sbuf, st->cap, enc ? c.pad_left : 0, st->h_enc, st->h_dec,
             c.h_dim, st->age);
+        if (st->choosing() && st->burst_q8 >= 0) sc_tok_start_kernel<<<1, SC_LIST, 0, s>>>(l, st->tok, st->burst_q8);
     });
 }
 
@@ -394,6 +411,19 @@ int decode_frames(bvc_stream_codec *st, int B, int k, float *codes, const float 
     return run_decode(st->m, w, st->ws, codes, h, B, k, st->melhat, h, s);
 }
 
+// the encode half of a tick of a session that chooses its own rates: every row's rungs tried inside the frame against the row's target
+// (its (B, k) layout in bitsbuf) and bucket, state h_enc to h_enc; then one launch for the wire (a send session: a duplex one has no
+// packet buffer), the bytes worth sending and the bit counts of the tick
+int encode_frames_vbr(bvc_stream_codec *st, const Workspace &w, int k, hipStream_t s) {
+    const bvc_model *m = st->m;
+    VbrWorkspace v;
+    carve_vbr(m, st->B, st->K, st->vws, &v);
+    const VbrCap cap{st->burst_q8 >= 0, st->rate_q8, st->burst_q8, st->tok, st->tok};
+    if (int rc = run_encode_vbr(m, w, v, st->ws, st->mel, st->bits_of(k), st->ladder, st->K, st->h_enc, st->B, k, st->codes, st->vbits, nullptr,
+                                st->h_enc, nullptr, nullptr, nullptr, s, &cap)) return rc;
+    return launch_pack_rows_vbr(st->codes, st->vbits, st->B, k, m->cfg.z_dim, st->kmax, st->packets, st->sizes, st->last_bits, s);
+}
+
 // the launches of one tick with k new frames (k > 0), in stream order
 int stream_tick_body(bvc_stream_codec *st, int k, hipStream_t s) {
     const bvc_model *m = st->m;
@@ -403,7 +433,10 @@ int stream_tick_body(bvc_stream_codec *st, int k, hipStream_t s) {
     if ((rc = check_ws(m, B, k, st->ws, st->ws_bytes, &w))) return rc;
     if (st->dir == BVC_STREAM_RECV) {
         // the wire -> codes: every row's own bit count, 0.5 for what did not arrive and for idle rows
-        if ((rc = launch_unpack_rows(st->packets, st->present, st->tick_bits(k), st->row_off, B, k, m->cfg.z_dim, st->kmax, st->codes, s))) return rc;
+        // (the wire with a bit count per frame: the count is the frame's header, a frame that is not there is a frame of no bits)
+        if (st->vbr) rc = launch_unpack_rows_vbr(st->packets, st->present, st->row_off, B, k, m->cfg.z_dim, st->kmax, st->codes, st->last_bits, s);
+        else rc = launch_unpack_rows(st->packets, st->present, st->tick_bits(k), st->row_off, B, k, m->cfg.z_dim, st->kmax, st->codes, s);
+        if (rc) return rc;
         // lost frames of open rows are generated with the row's bit count (all z bits on a fixed-rate model); idle rows keep their 0.5
         if (st->conceal && (rc = launch_conceal_select(st->present, st->kmax, st->tick_bits(k), (float)m->cfg.z_dim, st->row_off, B, k, w.bits, s))) return rc;
     } else {
@@ -414,9 +447,14 @@ int stream_tick_body(bvc_stream_codec *st, int k, hipStream_t s) {
         sc_shift_kernel<<<dim3((unsigned)((keep + 255) / 256), B), 256, 0, s>>>(st->sbuf, st->cap, 256 * k, st->stmp, st->cap, keep);
         sc_shift_kernel<<<dim3((unsigned)((keep + 255) / 256), B), 256, 0, s>>>(st->stmp, st->cap, 0, st->sbuf, st->cap, keep);
         BVC_HIP_TRY(hipGetLastError());
-        if ((rc = run_encode(m, w, st->ws, st->mel, st->tick_bits(k), st->h_enc, B, k, st->codes, nullptr, st->h_enc, nullptr, s))) return rc;
-        if (st->dir == BVC_STREAM_SEND)                      // codes -> the wire, and that is the tick
-            return launch_pack_rows(st->codes, st->tick_bits(k), B, k, m->cfg.z_dim, st->kmax, st->packets, s);
+        if (st->choosing()) {
+            if ((rc = encode_frames_vbr(st, w, k, s))) return rc;
+            if (st->dir == BVC_STREAM_SEND) return BVC_OK;
+        } else {
+            if ((rc = run_encode(m, w, st->ws, st->mel, st->tick_bits(k), st->h_enc, B, k, st->codes, nullptr, st->h_enc, nullptr, s))) return rc;
+            if (st->dir == BVC_STREAM_SEND)                  // codes -> the wire, and that is the tick
+                return launch_pack_rows(st->codes, st->tick_bits(k), B, k, m->cfg.z_dim, st->kmax, st->packets, s);
+        }
     }
     if ((rc = decode_frames(st, B, k, st->codes, w.bits, st->h_dec, s))) return rc;
     return bvc_vocoder_stream_push(st->voc, st->melhat, k, st->out_div, st->wav, s);
@@ -599,8 +637,47 @@ int bvc_stream_codec_create(const bvc_model *m, int32_t B, int32_t hop_samples, 
     return bvc_stream_codec_create_dir(m, B, hop_samples, bits_per_frame, scale, out_scale_div, BVC_STREAM_DUPLEX, out);
 }
 
+// what bvc_stream_codec_create_vbr adds to a session (checked by it); null: the fixed wire, rates set by the caller
+struct VbrSession { const int32_t *ladder; int K; float target; int rate_q8, burst_q8; };
+static int stream_codec_create(const bvc_model *m, int32_t B, int32_t hop_samples, float bits_per_frame, float scale, float out_scale_div,
+                               int32_t direction, const VbrSession *vs, bvc_stream_codec **out);
+
 int bvc_stream_codec_create_dir(const bvc_model *m, int32_t B, int32_t hop_samples, float bits_per_frame, float scale,
                                 float out_scale_div, int32_t direction, bvc_stream_codec **out) {
+    return stream_codec_create(m, B, hop_samples, bits_per_frame, scale, out_scale_div, direction, nullptr, out);
+}
+
+int bvc_stream_codec_create_vbr(const bvc_model *m, int32_t B, int32_t hop_samples, const int32_t *h_ladder, int32_t K, float target,
+                                int32_t rate_q8, int32_t burst_q8, float bits_per_frame, float scale, float out_scale_div, int32_t direction,
+                                bvc_stream_codec **out) {
+    const char *fn = "bvc_stream_codec_create_vbr";
+    if (!m || !out) { set_error("%s: bad arguments", fn); return BVC_EINVAL; }
+    if (!m->cfg.var_bit) { set_error("%s: a fixed-rate model (var_bit = 0) has no bit mask to choose", fn); return BVC_EINVAL; }
+    if (m->cfg.z_dim > 255) { set_error("%s: the bit count of a frame is one byte: z_dim <= 255", fn); return BVC_EINVAL; }
+    VbrSession vs{h_ladder, K, target, rate_q8, burst_q8};
+    if (direction == BVC_STREAM_RECV) {
+        if (h_ladder || K != 0) { set_error("%s: a receive session takes no ladder (NULL, 0)", fn); return BVC_EINVAL; }
+        if (!(bits_per_frame >= 0.0f)) { set_error("%s: bits per frame must not be negative", fn); return BVC_EINVAL; }
+        vs.burst_q8 = -1;
+    } else {
+        if (!h_ladder || K < 1 || K > VBR_MAX_RUNGS) { set_error("%s: the ladder takes 1 to %d rungs (K=%d)", fn, VBR_MAX_RUNGS, (int)K); return BVC_EINVAL; }
+        for (int k = 0; k < K; ++k)
+            if (h_ladder[k] < 0 || h_ladder[k] > m->cfg.z_dim || (k && h_ladder[k] <= h_ladder[k - 1])) {
+                set_error("%s: rung %d = %d: bit counts in [0, %d], strictly ascending", fn, k, (int)h_ladder[k], m->cfg.z_dim);
+                return BVC_EINVAL;
+            }
+        if (burst_q8 >= 0 && (rate_q8 < 0 || (long long)burst_q8 < (long long)h_ladder[0] * 256)) {
+            set_error("%s: rate_q8 = %d must not be negative, and a bucket of %d/256 bits must hold rung 0 (%d bits)", fn, (int)rate_q8, (int)burst_q8, (int)h_ladder[0]);
+            return BVC_EINVAL;
+        }
+        if (burst_q8 < 0) vs.burst_q8 = -1;
+        bits_per_frame = target;                             // what a slot's `bits` holds in such a session
+    }
+    return stream_codec_create(m, B, hop_samples, bits_per_frame, scale, out_scale_div, direction, &vs, out);
+}
+
+static int stream_codec_create(const bvc_model *m, int32_t B, int32_t hop_samples, float bits_per_frame, float scale, float out_scale_div,
+                               int32_t direction, const VbrSession *vs, bvc_stream_codec **out) {
     if (direction != BVC_STREAM_DUPLEX && direction != BVC_STREAM_SEND && direction != BVC_STREAM_RECV) {
         set_error("bvc_stream_codec_create_dir: direction %d is none of BVC_STREAM_DUPLEX / _SEND / _RECV", (int)direction); return BVC_EINVAL;
     }
@@ -613,6 +690,13 @@ int bvc_stream_codec_create_dir(const bvc_model *m, int32_t B, int32_t hop_sampl
     std::unique_ptr<bvc_stream_codec> st(new bvc_stream_codec());
     st->m = m; st->B = B; st->hop = hop_samples; st->bits = bits_per_frame; st->scale = scale; st->out_div = out_scale_div;
     st->dir = direction; st->bpf = (c.z_dim + 7) / 8;
+    size_t vws_bytes = 0;
+    if (vs) {
+        st->vbr = true; st->bpf = 1 + (c.z_dim + 7) / 8;     // a frame's bit count in front of its bytes
+        st->K = enc ? vs->K : 0; st->rate_q8 = vs->rate_q8; st->burst_q8 = vs->burst_q8;
+        for (int k = 0; k < st->K; ++k) st->ladder[k] = vs->ladder[k];
+        if (enc) { VbrWorkspace v; carve_vbr(m, B, st->K, nullptr, &v); vws_bytes = v.total; }
+    }
     // a receive tick takes up to 7 frames: whatever one tick of a send session emits (its own limit, the size of the graph table)
     st->kmax = enc ? (hop_samples + c.hop - 1) / c.hop + 1 : 7;
     if (st->kmax > 7) { set_error("bvc_stream_codec_create: hop too long (%d frames per tick)", st->kmax); return BVC_EINVAL; }
@@ -638,6 +722,9 @@ int bvc_stream_codec_create_dir(const bvc_model *m, int32_t B, int32_t hop_sampl
                  o_melhat = pl.take(two * B * st->kmax * c.num_mels * 4), o_wav = pl.take(two * B * st->kmax * spf * 4),
                  o_he = pl.take(one * B * c.h_dim * 4), o_hd = pl.take(two * B * c.h_dim * 4), o_ws = pl.take(st->ws_bytes),
                  o_pk = pl.take(wire * B * st->kmax * st->bpf), o_pr = pl.take(wire * B * st->kmax);
+    const size_t vb = vs ? 1 : 0;
+    const size_t o_vws = pl.take(vws_bytes), o_vbits = pl.take(vb * B * st->kmax * 4), o_lbits = pl.take(vb * B * st->kmax * 4),
+                 o_sizes = pl.take(vb * B * st->kmax * 4), o_tok = pl.take(vb * B * 4);
     if (hipMalloc(reinterpret_cast<void **>(&st->pool), pl.bytes) != hipSuccess) {
         (void)hipGetLastError();
         set_error("bvc_stream_codec_create: cannot allocate %zu bytes", pl.bytes);
@@ -653,16 +740,22 @@ int bvc_stream_codec_create_dir(const bvc_model *m, int32_t B, int32_t hop_sampl
     }
     if (dec) { st->melhat = pl.at<float>(p, o_melhat); st->wav = pl.at<float>(p, o_wav); st->h_dec = pl.at<float>(p, o_hd); }
     if (wire) { st->packets = pl.at<uint8_t>(p, o_pk); st->present = pl.at<uint8_t>(p, o_pr); }
+    if (vs) {
+        st->vws = p + o_vws; st->vbits = pl.at<float>(p, o_vbits); st->last_bits = pl.at<float>(p, o_lbits);
+        st->sizes = pl.at<int>(p, o_sizes); st->tok = pl.at<int>(p, o_tok);
+    }
     st->row_off = pl.at<int>(p, o_rowoff); st->age = pl.at<int>(p, o_age);          // zero: every slot open, delay 0, age 0
     st->slots.assign(B, bvc_stream_codec::Slot());
     for (auto &sl : st->slots) sl.bits = bits_per_frame;
     int rc;
     if ((rc = launch_fill(st->bitsbuf, bits_per_frame, (long long)B * (st->kmax * (st->kmax + 1) / 2), nullptr))) return rc;
+    if (st->choosing() && st->burst_q8 >= 0 && (rc = launch_vbr_tok(st->tok, nullptr, st->burst_q8, B, nullptr))) return rc;   // full buckets
     st->fill = c.pad_left;                                   // room for the left reflect padding of frame 0
     StreamDev init{st->fill, {0, 0, 0}};
     BVC_HIP_TRY(hipMemcpy(st->d_state, &init, sizeof(init), hipMemcpyHostToDevice));
     { const char *ng = getenv("BVC_STREAM_NO_GRAPH"); st->use_graph = !(ng && ng[0] == '1'); }
     { const char *tf = getenv("BVC_STREAM_FLOW"); st->tick_flow = !(tf && tf[0] == '0'); }
+    if (st->choosing()) st->tick_flow = false;               // the candidates are not in the persistent kernel: launch-per-layer ticks
     // ticks that are launched eagerly (persistent recurrence) let the generator's windows slide through their buffers instead of moving
     // every history back after every hop (56 us of a 1.5 ms tick at 256 streams); BVC_STREAM_SLIDE=0: never
     const char *sl = getenv("BVC_STREAM_SLIDE");
@@ -700,7 +793,8 @@ int bvc_stream_codec_open(bvc_stream_codec *st, int32_t slot, float bits_per_fra
     if (int rc = slot_arg(st, slot, "bvc_stream_codec_open")) return rc;
     bvc_stream_codec::Slot &sl = st->slots[slot];
     if (sl.open) { set_error("bvc_stream_codec_open: slot %d is open", (int)slot); return BVC_EINVAL; }
-    if (!(bits_per_frame >= 0.0f)) { set_error("bvc_stream_codec_open: bits per frame must not be negative"); return BVC_EINVAL; }
+    if (st->choosing()) bits_per_frame = st->bits;          // the session's default target (the argument is ignored); the bucket fills at frame 0
+    else if (!(bits_per_frame >= 0.0f)) { set_error("bvc_stream_codec_open: bits per frame must not be negative"); return BVC_EINVAL; }
     if (st->dir == BVC_STREAM_RECV) { sl.delay = 0; sl.frame0 = st->frames; }     // frame-aligned: frame 0 is the first frame of the next tick
     else join_plan(st->ticks * st->hop, st->hop, st->m->cfg, &sl.delay, &sl.frame0, nullptr);
     sl.open = true; sl.started = false; sl.bits = bits_per_frame;
@@ -752,11 +846,34 @@ int bvc_stream_codec_slot_state(bvc_stream_codec *st, int32_t slot, int32_t *sta
 int bvc_stream_codec_set_bits(bvc_stream_codec *st, int32_t slot, float bits_per_frame) {
     if (int rc = slot_arg(st, slot, "bvc_stream_codec_set_bits")) return rc;
     if (!st->m->cfg.var_bit) { set_error("bvc_stream_codec_set_bits: the model has a fixed bitrate (var_bit = 0)"); return BVC_EINVAL; }
+    if (st->choosing()) { set_error("bvc_stream_codec_set_bits: the session chooses its own rates (bvc_stream_codec_set_target)"); return BVC_EINVAL; }
     bvc_stream_codec::Slot &sl = st->slots[slot];
     if (!sl.open) { set_error("bvc_stream_codec_set_bits: slot %d is idle", (int)slot); return BVC_EINVAL; }
     if (!(bits_per_frame >= 0.0f)) { set_error("bvc_stream_codec_set_bits: bits per frame must not be negative"); return BVC_EINVAL; }
     sl.bits = bits_per_frame;
     slot_mark(st, sl, SC_SET_BITS);
+    return BVC_OK;
+}
+
+int bvc_stream_codec_set_target(bvc_stream_codec *st, int32_t slot, float target) {
+    if (int rc = slot_arg(st, slot, "bvc_stream_codec_set_target")) return rc;
+    if (!st->choosing()) { set_error("bvc_stream_codec_set_target: not a session that chooses its own rates (bvc_stream_codec_create_vbr, SEND or DUPLEX)"); return BVC_EINVAL; }
+    bvc_stream_codec::Slot &sl = st->slots[slot];
+    if (!sl.open) { set_error("bvc_stream_codec_set_target: slot %d is idle", (int)slot); return BVC_EINVAL; }
+    sl.bits = target;                                        // (any float: +inf is rung 0, -inf or a NaN the top rung)
+    slot_mark(st, sl, SC_SET_BITS);
+    return BVC_OK;
+}
+
+int bvc_stream_codec_sizes(bvc_stream_codec *st, int32_t **d_sizes) {
+    if (!st || !st->vbr) { set_error("bvc_stream_codec_sizes: not a session of bvc_stream_codec_create_vbr"); return BVC_EINVAL; }
+    if (d_sizes) *d_sizes = st->sizes;
+    return BVC_OK;
+}
+
+int bvc_stream_codec_bits(bvc_stream_codec *st, float **d_bits) {
+    if (!st || !st->vbr) { set_error("bvc_stream_codec_bits: not a session of bvc_stream_codec_create_vbr"); return BVC_EINVAL; }
+    if (d_bits) *d_bits = st->last_bits;
     return BVC_OK;
 }
 
@@ -827,6 +944,7 @@ int bvc_stream_codec_set_conceal(bvc_stream_codec *st, int32_t mode) {
 int bvc_stream_codec_set_repair(bvc_stream_codec *st, int32_t window_frames) {
     if (!st) { set_error("null stream codec"); return BVC_EINVAL; }
     if (st->dir != BVC_STREAM_RECV) { set_error("bvc_stream_codec_set_repair: not a receive session"); return BVC_EINVAL; }
+    if (st->vbr) { set_error("bvc_stream_codec_set_repair: the window's ring has the fixed wire's packet width (not a bvc_stream_codec_create_vbr session)"); return BVC_EINVAL; }
     if (window_frames < 0 || window_frames > 64) { set_error("bvc_stream_codec_set_repair: window of %d frames outside 0..64", (int)window_frames); return BVC_EINVAL; }
     if (window_frames > 0 && st->bpf > SC_LATE_BYTES) { set_error("bvc_stream_codec_set_repair: frames of %d bytes (at most %d)", st->bpf, SC_LATE_BYTES); return BVC_EINVAL; }
     if (window_frames == st->rep.w) { st->rep.clear(); return BVC_OK; }
@@ -868,6 +986,7 @@ int bvc_stream_codec_late(bvc_stream_codec *st, int32_t slot, int64_t stream_fra
     if (taken) *taken = 0;
     if (int rc = slot_arg(st, slot, "bvc_stream_codec_late")) return rc;
     if (st->dir != BVC_STREAM_RECV) { set_error("bvc_stream_codec_late: not a receive session"); return BVC_EINVAL; }
+    if (st->vbr) { set_error("bvc_stream_codec_late: no repair window on the wire with a bit count per frame"); return BVC_EINVAL; }
     if (!packet) { set_error("bvc_stream_codec_late: null packet"); return BVC_EINVAL; }
     const bvc_stream_codec::Slot &sl = st->slots[slot];
     if (st->rep.w <= 0 || !sl.open || !sl.started || stream_frame < 0) return BVC_OK;      // no window, or no running stream of which this is a frame

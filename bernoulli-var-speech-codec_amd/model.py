@@ -174,6 +174,40 @@ def _check_ladder(ladder, z_dim, var_bit):
     return (ctypes.c_int32 * len(rungs))(*rungs), len(rungs)
 
 
+_Q8 = 256                        # the token bucket of a capped closed-loop call counts 1/256 bit
+_I32_MAX = 2 ** 31 - 1
+
+
+def _check_cap_q8(rungs, rate_q8, burst_q8):
+    """The bucket of a capped closed-loop call as two ints, or ValueError (what the library refuses with BVC_EINVAL): neither negative,
+    both int32, and a full bucket holds rung 0."""
+    if rate_q8 is None or burst_q8 is None:
+        raise ValueError("encode_vbr: a rate cap takes both rate_q8 and burst_q8")
+    if int(rate_q8) != rate_q8 or int(burst_q8) != burst_q8:
+        raise ValueError(f"encode_vbr: rate_q8 and burst_q8 are integers (1/256 bit), got {rate_q8!r}, {burst_q8!r}")
+    rate_q8, burst_q8 = int(rate_q8), int(burst_q8)
+    if rate_q8 < 0 or burst_q8 < 0 or rate_q8 > _I32_MAX or burst_q8 > _I32_MAX:
+        raise ValueError(f"encode_vbr: rate_q8 = {rate_q8} and burst_q8 = {burst_q8} must lie in [0, 2^31)")
+    if burst_q8 < int(rungs[0]) * _Q8:
+        raise ValueError(f"encode_vbr: a bucket of {burst_q8 / _Q8:g} bits never holds rung 0 ({int(rungs[0])} bits)")
+    return rate_q8, burst_q8
+
+
+def cap_q8(conf, rungs, rate_cap, burst):
+    """``rate_cap`` [bit/s] and ``burst`` [bits] of a capped closed-loop call as (rate_q8, burst_q8), None without a cap; ValueError as
+    ``_check_cap_q8``.  rate_q8 = round(rate_cap * hopsize / fs * 256), burst_q8 = round(burst * 256), the default burst four times the
+    top rung."""
+    if rate_cap is None:
+        if burst is not None:
+            raise ValueError("encode_vbr: burst without rate_cap")
+        return None
+    if not (rate_cap >= 0) or (burst is not None and not (burst >= 0)) or rate_cap == float("inf") or burst == float("inf"):
+        raise ValueError(f"encode_vbr: rate_cap = {rate_cap} and burst = {burst} must be finite and not negative")
+    if burst is None:
+        burst = 4 * int(rungs[-1])
+    return _check_cap_q8(rungs, round(rate_cap * conf["hopsize"] / conf["fs"] * _Q8), round(burst * _Q8))
+
+
 def _broadcast_target(target, B, T, device):
     """A scalar, (B,) or (B,T) distortion target as a contiguous float32 (B,T) tensor on ``device``."""
     t = torch.as_tensor(target, dtype=torch.float32).detach()
@@ -313,13 +347,23 @@ class BVRNN(_OnDevice):
         return codes.to(out_dev), eng.deliver(all_h, out_dev)
 
     @torch.no_grad()
-    def encode_vbr(self, y, ladder, target, h, return_all=False):
+    def encode_vbr(self, y, ladder, target, h, return_all=False, rate_q8=None, burst_q8=None, tok=None):
         """``encode`` with the bits of every frame chosen inside the frame (``bvc_bvrnn_encode_vbr``): y (B,T,x_dim), ``ladder`` up to 8
         ascending bit counts, ``target`` a scalar, (B,) or (B,T) bound on the mean absolute log-mel error of the frame as the receiver
         will decode it, h (1,B,h_dim).  A frame gets the first rung of the ladder that meets its target, the last one if none does.
         Returns (codes (B,T,z), bits (B,T), all_h (B,T,h)); ``return_all=True`` adds a dict with prob (B,T,z), dist (B,T,K) - the error
-        of every rung -, dec (B,T,x_dim) - the chosen rung's decoded mel - and h_next (1,B,h_dim)."""
+        of every rung -, dec (B,T,x_dim) - the chosen rung's decoded mel - and h_next (1,B,h_dim).
+
+        ``rate_q8`` and ``burst_q8`` (ints, 1/256 bit; both or neither) put a token bucket per row under the choice
+        (``bvc_bvrnn_encode_vbr_capped``): per frame tok = min(burst_q8, tok + rate_q8), the frame gets the lower of its rung and the
+        highest rung with ladder[k] * 256 <= tok (rung 0 if none), tok = max(0, tok - 256 bits).  ``tok`` (B,) int32: the buckets in
+        front of the first frame (None: full); the dict then carries ``tok_next`` (B,) int32, which the next chunk takes as ``tok``."""
         lad, K = _check_ladder(ladder, self.z_dim, self.varBit)
+        capped = rate_q8 is not None or burst_q8 is not None
+        if capped:
+            rate_q8, burst_q8 = _check_cap_q8(list(lad), rate_q8, burst_q8)
+        elif tok is not None:
+            raise ValueError("encode_vbr: tok without rate_q8 and burst_q8")
         if y.dim() != 3:
             raise ValueError("encode_vbr: y must be (B, T, num_mels)")
         B, T, _ = y.shape
@@ -337,13 +381,27 @@ class BVRNN(_OnDevice):
             extra = {"prob": torch.empty(B, T, self.z_dim, device=eng.device), "dist": torch.empty(B, T, K, device=eng.device),
                      "dec": torch.empty(B, T, self.x_dim, device=eng.device), "h_next": torch.empty(B, self.h_dim, device=eng.device)}
         ws, nws = eng.vbr_workspace(B, T, K)
-        with torch.cuda.device(eng.device):
-            _abi.check(eng.lib.bvc_bvrnn_encode_vbr(
-                eng.handle, _abi.ptr(y), _abi.ptr(tau), lad, K, _abi.ptr(h0), B, T, _abi.ptr(codes), _abi.ptr(bits), _abi.ptr(all_h),
+        args = (eng.handle, _abi.ptr(y), _abi.ptr(tau), lad, K, _abi.ptr(h0), B, T, _abi.ptr(codes), _abi.ptr(bits), _abi.ptr(all_h),
                 _abi.ptr(extra.get("h_next")), _abi.ptr(extra.get("prob")), _abi.ptr(extra.get("dist")), _abi.ptr(extra.get("dec")),
-                ws, nws, eng.stream()))
+                ws, nws, eng.stream())
+        tok_next = None
+        with torch.cuda.device(eng.device):
+            if capped:
+                tok0 = None
+                if tok is not None:
+                    tok0 = torch.as_tensor(tok).detach().to(device=eng.device, dtype=torch.int32).contiguous()
+                    if tuple(tok0.shape) != (B,):
+                        raise ValueError(f"encode_vbr: tok must be ({B},), got {tuple(tok0.shape)}")
+                tok_next = torch.empty(B, dtype=torch.int32, device=eng.device)
+                _abi.check(eng.lib.bvc_bvrnn_encode_vbr_capped(
+                    *args, rate_q8, burst_q8, ctypes.c_void_p(tok0.data_ptr()) if tok0 is not None else None,
+                    ctypes.c_void_p(tok_next.data_ptr())))
+            else:
+                _abi.check(eng.lib.bvc_bvrnn_encode_vbr(*args))
         out = (codes.to(out_dev), bits.to(out_dev), eng.deliver(all_h, out_dev))
         if return_all:
+            if capped:
+                extra["tok_next"] = tok_next
             extra["h_next"] = extra["h_next"].unsqueeze(0)
             return out + ({k: v.to(out_dev) for k, v in extra.items()},)
         return out
@@ -514,17 +572,23 @@ class BVRNNCodecModel(_OnDevice):
         return eng.deliver(codes, out_dev)
 
     @torch.no_grad()
-    def encode_vbr(self, x, target, bitrates=(1500, 3000, 6000), return_bits=True, lengths=None):
+    def encode_vbr(self, x, target, bitrates=(1500, 3000, 6000), return_bits=True, lengths=None, rate_cap=None, burst=None):
         """Closed-loop variable-rate ``encode`` (``bvc_encode_vbr``): every frame gets the lowest of ``bitrates`` at which the mel the
         receiver will decode lies within ``target`` - the mean absolute error over the bands of the natural-log mel; a scalar, (batch,)
         or (batch, frames) - of the input's, the highest where none does.  ``bitrates`` [bit/s] become bits per frame as in ``encode``
         (saturating at z_dim) and must still ascend strictly after that.  Returns (codes, bits (batch, frames)); ``decode`` takes the
-        codes as they are, ``pack_vbr`` puts them on the wire.  Equal-length batches only."""
+        codes as they are, ``pack_vbr`` puts them on the wire.  Equal-length batches only.
+
+        ``rate_cap`` [bit/s] caps the rate of every row for good (``bvc_encode_vbr_capped``): a token bucket that gains
+        ``rate_cap * hopsize / fs`` bits per frame, holds at most ``burst`` bits (default: four times the top rung) and starts full; a
+        frame never gets a rung the bucket does not hold.  If the lowest rung is within the rate, any L consecutive frames of a row
+        carry at most ``burst + L * rate_cap * hopsize / fs`` bits.  ``target=-inf`` then spends whatever the bucket allows."""
         if lengths is not None:
             raise ValueError("encode_vbr: mixed-length batches (lengths=) are not supported")
         z = self.conf["z_dim"]
         rungs = [int(min(z, max(0.0, self.bits_per_frame(r)))) for r in bitrates]
         lad, K = _check_ladder(rungs, z, self.conf["var_bit"])
+        cap = cap_q8(self.conf, rungs, rate_cap, burst)
         if x.dim() != 2:
             raise RuntimeError("expected a (batch, length) waveform")
         B, L = x.shape
@@ -543,8 +607,8 @@ class BVRNNCodecModel(_OnDevice):
         bits = torch.empty(B, T, device=eng.device)
         ws, nws = eng.vbr_workspace(B, T, K)
         with torch.cuda.device(eng.device):
-            _abi.check(eng.lib.bvc_encode_vbr(eng.handle, _abi.ptr(x), B, L, float(SCALING), _abi.ptr(tau), lad, K, _abi.ptr(codes),
-                                              _abi.ptr(bits), ws, nws, eng.stream()))
+            args = (eng.handle, _abi.ptr(x), B, L, float(SCALING), _abi.ptr(tau), lad, K, _abi.ptr(codes), _abi.ptr(bits), ws, nws, eng.stream())
+            _abi.check(eng.lib.bvc_encode_vbr(*args) if cap is None else eng.lib.bvc_encode_vbr_capped(*args, *cap))
         if return_bits:
             return codes.to(out_dev), eng.deliver(bits, out_dev)
         return eng.deliver(codes, out_dev)

@@ -487,13 +487,25 @@ class StreamingCodec:
     sessions have no ``finish``.  ``push_packets`` then returns ``(wav (batch, n_max) view, counts (batch,) int64 CPU tensor)`` - row
     b's samples are ``wav[b, :counts[b]]`` - and a duplex ``push`` ``(codes, wav, counts)``; a send ``push`` returns what it returned
     before.  ``"s16"`` takes and returns int16 tensors (in: x / 32768; out: clamp(rint(y * 32768)) of the float32 result, NaN 0).
-    Concealment, repair, ``set_bitrate`` and ``late`` act on the inner session unchanged; ``close`` also idles the row's resamplers."""
+    Concealment, repair, ``set_bitrate`` and ``late`` act on the inner session unchanged; ``close`` also idles the row's resamplers.
+
+    ``vbr=dict(bitrates=(1500, 3000, 6000), target=0.35, rate_cap=None, burst=None)`` (send and duplex sessions; ``bitrate`` is then
+    ignored): the session chooses every frame's rate itself, as ``model.encode_vbr(x, target, bitrates, rate_cap=, burst=)`` does -
+    the lowest of ``bitrates`` at which the decoded mel lies within the slot's ``target``, under the slot's own token bucket where
+    ``rate_cap`` [bit/s] is given.  ``open(slot, target=None)`` starts a stream with that (None: the session's) target, zero state
+    and a full bucket, ``set_target(slot, target)`` changes it from the next push on; ``set_bitrate`` is refused.  ``push`` returns
+    what it returns without ``vbr``, the packets on the wire of ``model.pack_vbr``: ``bytes_per_frame = 1 + ceil(z_dim / 8)``, byte 0
+    the frame's bit count.  ``last_bits`` (batch, k) float and ``last_sizes`` (batch, k) int32 - the bytes of each frame worth sending -
+    are views valid until the next push.  Every stream equals ``model.encode_vbr`` of its own signal alone, bit for bit.  On a receive
+    session ``vbr=True`` selects that wire: every present frame says how many bits it holds, ``bitrate`` is the count a lost frame is
+    concealed with (``conceal="prior"``), ``last_bits`` what the last push read.  Not with ``repair``, not on a fixed-rate model."""
 
     DIRECTIONS = {"duplex": 0, "send": 1, "recv": 2}
     CONCEAL = {"none": 0, "prior": 1}
 
     def __init__(self, model, batch, bitrate, hop=441, device=None, open_all=True, direction="duplex", conceal="none", repair=0,
-                 client_rate=None, sample_format="f32"):
+                 client_rate=None, sample_format="f32", vbr=None):
+        self.vbr = self._check_vbr(model, direction, repair, vbr)     # ValueError before anything is created
         if sample_format not in PCM_FORMATS:
             raise ValueError(f"sample_format must be one of {sorted(PCM_FORMATS)}")
         if client_rate is None and sample_format != "f32":
@@ -526,7 +538,13 @@ class StreamingCodec:
         self.stream = torch.cuda.Stream(self.dev)          # a tick may be captured into a hipGraph: not possible on the default stream
         h = ctypes.c_void_p()
         with torch.cuda.device(self.dev):
-            if direction == "duplex":
+            if self.vbr is not None:
+                v = self.vbr
+                lad = (ctypes.c_int32 * len(v["ladder"]))(*v["ladder"]) if v["ladder"] else None
+                _abi.check(eng.lib.bvc_stream_codec_create_vbr(
+                    eng.handle, batch, hop, lad, len(v["ladder"]), float(v["target"]), v["rate_q8"], v["burst_q8"],
+                    float(model.bits_per_frame(bitrate)), float(SCALING), float(SCALING), self.DIRECTIONS[direction], ctypes.byref(h)))
+            elif direction == "duplex":
                 _abi.check(eng.lib.bvc_stream_codec_create(eng.handle, batch, hop, float(model.bits_per_frame(bitrate)), float(SCALING),
                                                            float(SCALING), ctypes.byref(h)))
             else:
@@ -545,6 +563,13 @@ class StreamingCodec:
         if pp.value:                                           # (batch, kmax, bytes_per_frame) / (batch, kmax) whatever a tick's frame count
             self._packets = torch.as_tensor(_DeviceView(pp.value, (batch, self.kmax, bpf.value), "|u1"), device=self.dev)
             self._present = torch.as_tensor(_DeviceView(pr.value, (batch, self.kmax), "|u1"), device=self.dev)
+        self._sizes_ptr = self._bits_ptr = None
+        self._last_k = 0
+        if self.vbr is not None:
+            ps, pb = ctypes.c_void_p(), ctypes.c_void_p()
+            _abi.check(eng.lib.bvc_stream_codec_sizes(h, ctypes.byref(ps)))
+            _abi.check(eng.lib.bvc_stream_codec_bits(h, ctypes.byref(pb)))
+            self._sizes_ptr, self._bits_ptr = ps.value, pb.value
         self.frames = 0
         self._model = model
         self._rs_in = self._rs_out = None
@@ -559,6 +584,55 @@ class StreamingCodec:
         self.repair = 0
         if repair:
             self.set_repair(repair)
+
+    VBR_KEYS = ("bitrates", "target", "rate_cap", "burst")
+
+    @classmethod
+    def _check_vbr(cls, model, direction, repair, vbr):
+        """The ``vbr`` keyword as what bvc_stream_codec_create_vbr takes - dict(ladder, target, rate_q8, burst_q8), burst_q8 = -1
+        without a cap - or None for a session without it; ValueError for what the library would refuse."""
+        if vbr is None or vbr is False:
+            return None
+        from .model import _check_ladder, cap_q8
+        conf = model.conf
+        if not conf["var_bit"]:
+            raise ValueError("vbr: a fixed-rate model (var_bit = false) has no bit mask to choose")
+        if direction == "recv":
+            if vbr is not True:
+                raise ValueError("vbr: a receive session takes vbr=True (the wire with a bit count per frame); the sender chooses the rates")
+            if repair:
+                raise ValueError("vbr: no repair window on the wire with a bit count per frame")
+            return dict(ladder=[], target=0.0, rate_q8=0, burst_q8=-1)
+        if not isinstance(vbr, dict):
+            raise ValueError("vbr: a send or duplex session takes dict(bitrates=, target=, rate_cap=, burst=)")
+        unknown = sorted(set(vbr) - set(cls.VBR_KEYS))
+        if unknown:
+            raise ValueError(f"vbr: unknown keys {unknown}; known: {list(cls.VBR_KEYS)}")
+        z = conf["z_dim"]
+        rungs = [int(min(z, max(0.0, model.bits_per_frame(r)))) for r in vbr.get("bitrates", (1500, 3000, 6000))]
+        _check_ladder(rungs, z, True)
+        target = float(vbr.get("target", 0.35))
+        cap = cap_q8(conf, rungs, vbr.get("rate_cap"), vbr.get("burst"))
+        return dict(ladder=rungs, target=target, rate_q8=cap[0] if cap else 0, burst_q8=cap[1] if cap else -1)
+
+    @property
+    def last_bits(self):
+        """vbr sessions: the bit count of every frame of the last push, (batch, k) float; a view valid until the next push."""
+        return self._vbr_view(self._bits_ptr, "<f4")
+
+    @property
+    def last_sizes(self):
+        """vbr sessions: 1 + ceil(bits / 8) of every frame of the last push - the bytes worth sending - (batch, k) int32; a view."""
+        return self._vbr_view(self._sizes_ptr, "<i4")
+
+    def _vbr_view(self, ptr, typestr):
+        if not ptr:
+            raise ValueError("last_bits / last_sizes: not a vbr session")
+        return torch.as_tensor(_DeviceView(ptr, (self.B, self.kmax), typestr), device=self.dev)[:, :self._last_k]
+
+    def set_target(self, slot, target):
+        """vbr send / duplex sessions: the distortion target of an open slot from the next push on."""
+        self._slot_call(self.eng.lib.bvc_stream_codec_set_target(self.handle, int(slot), float(target)))
 
     def __del__(self):
         try:
@@ -663,12 +737,20 @@ class StreamingCodec:
             raise ValueError(msg.decode() if msg else "bvcodec: invalid argument")
         _abi.check(rc)
 
-    def open(self, slot, bitrate):
+    def open(self, slot, bitrate=None, target=None):
         """Start a new stream in idle row `slot` from the next push on; returns its delay in (internal) samples.  A rate-converting
-        send side delays the stream by ``lag`` more: its filter looks that far ahead (``self.lag`` internal samples)."""
+        send side delays the stream by ``lag`` more: its filter looks that far ahead (``self.lag`` internal samples).  A vbr send or
+        duplex session takes ``target`` (None: the session's) instead of ``bitrate``."""
+        choosing = self.vbr is not None and self.direction != "recv"
+        if choosing and bitrate is not None:
+            raise ValueError("open: a vbr session chooses its own rates (open(slot, target=...))")
+        if not choosing and (bitrate is None or target is not None):
+            raise ValueError("open: open(slot, bitrate)" if bitrate is None else "open: target belongs to a vbr send or duplex session")
         d = ctypes.c_int32()
-        self._slot_call(self.eng.lib.bvc_stream_codec_open(self.handle, int(slot), float(self._model.bits_per_frame(bitrate)),
+        self._slot_call(self.eng.lib.bvc_stream_codec_open(self.handle, int(slot), 0.0 if choosing else float(self._model.bits_per_frame(bitrate)),
                                                            ctypes.byref(d)))
+        if choosing and target is not None:
+            self.set_target(slot, target)
         if self.client_rate is not None:
             self._client_open(int(slot))
         return d.value
@@ -775,6 +857,7 @@ class StreamingCodec:
                 out = self._client_out(k)
         cur.wait_stream(self.stream)
         self.frames += k
+        self._last_k = k
         if self._rs_out is not None:
             return out
         return torch.as_tensor(_DeviceView(self._wav_ptr, (self.B, k * self.spf)), device=self.dev)
@@ -800,6 +883,7 @@ class StreamingCodec:
         cur.wait_stream(self.stream)
         k = k.value
         self.frames += k
+        self._last_k = k
         send = self.direction == "send"
         if self._rs_out is not None:                           # a rate-converting duplex session: (codes, wav, counts)
             codes = torch.as_tensor(_DeviceView(self._codes_ptr, (self.B, k, self.z)), device=self.dev) if k else \

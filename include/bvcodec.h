@@ -408,6 +408,34 @@ int  bvc_stream_codec_set_conceal(bvc_stream_codec *st, int32_t mode);
 int  bvc_stream_codec_set_repair(bvc_stream_codec *st, int32_t window_frames);
 int  bvc_stream_codec_late(bvc_stream_codec *st, int32_t slot, int64_t stream_frame, const uint8_t *packet, int32_t *taken);
 
+/* Sessions that choose their own rates (SEND, DUPLEX) and that read a bit count per frame (RECV): the closed-loop selection of
+ * bvc_bvrnn_encode_vbr(_capped), see there, tick by tick.  The kind of session is decided at creation: its packet buffer has fixed
+ * addresses and bvc_stream_codec_packets reports bytes_per_frame = 1 + ceil(z_dim / 8).  A frame has the layout of bvc_pack_codes_vbr -
+ * byte 0 its bit count n, then the bits LSB first, then zeros - frame j of row b at (b * max_frames_per_tick + j) * bytes_per_frame as
+ * ever; d_sizes (B, max_frames_per_tick) int32 holds 1 + ceil(n / 8), the bytes worth sending, d_bits (same shape, float) holds n.
+ *   h_ladder, K: SEND and DUPLEX 1..8 strictly ascending rungs in [0, z_dim]; RECV: NULL, 0.   target: what every slot opens with.
+ *   rate_q8, burst_q8: the cap of bvc_bvrnn_encode_vbr_capped, one bucket per row; burst_q8 < 0: no cap.
+ *   bits_per_frame: RECV only - the count a lost frame is concealed with (open / set_bits change it per slot); else ignored.
+ *  - A SEND tick runs the front-end as ever, then the selection on the tick's (B, k) frames with the carried h_enc, each row's carried
+ *    bucket and each row's current target, then one pack launch into d_packets / d_sizes / d_bits; d_codes as ever.  Always on the
+ *    launch-per-layer schedule (the candidate rows are not in the persistent kernel); BVC_STREAM_NO_GRAPH=1 gives the same bits.  A stream
+ *    equals bvc_encode_vbr(_capped) of its own signal alone, bit for bit.
+ *  - A DUPLEX tick is the same followed by the decoder half on the chosen codes (which need no side information); no packet buffer.
+ *  - A RECV tick reads n from each present frame's header (above z_dim: z_dim); a frame that is not present has no header and is a frame
+ *    of no bits, or with set_conceal(1) generated from the prior at the slot's bits_per_frame.  Behind the unpack the tick is the
+ *    receive tick of bvc_stream_codec_create_dir.
+ *  - Slots: open on SEND / DUPLEX starts the stream with the session's target, zero state and a full bucket (its bits_per_frame is
+ *    ignored); bvc_stream_codec_set_target changes a slot's target from the next tick on; close, finish, slot_frames, slot_state, draining
+ *    and idle rows as ever.
+ *  - BVC_EINVAL: a fixed-rate model; a bad ladder; burst_q8 >= 0 with rate_q8 < 0 or burst_q8 < ladder[0] * 256; set_bits on SEND /
+ *    DUPLEX; set_target on RECV or on a session of the other constructors; set_repair and late (the ring has the fixed wire's width). */
+int  bvc_stream_codec_create_vbr(const bvc_model *m, int32_t B, int32_t hop_samples, const int32_t *h_ladder, int32_t K, float target,
+                                 int32_t rate_q8, int32_t burst_q8, float bits_per_frame, float scale, float out_scale_div,
+                                 int32_t direction, bvc_stream_codec **out);
+int  bvc_stream_codec_set_target(bvc_stream_codec *st, int32_t slot, float target);
+int  bvc_stream_codec_sizes(bvc_stream_codec *st, int32_t **d_sizes);
+int  bvc_stream_codec_bits(bvc_stream_codec *st, float **d_bits);
+
 /* BVRNNCodecModel.encode (bvrnn_codec_model.py:44-62): scale, log-mel, bits/frame =
  * bits_per_frame for every (b,t), zero initial state, BVRNN.encode.  d_wav (B,L) -> d_codes. */
 int bvc_encode(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale,
@@ -475,6 +503,26 @@ int bvc_bvrnn_encode_vbr(const bvc_model *m, const float *d_mel, const float *d_
                          float *d_prob, float *d_dist, float *d_dec, void *d_ws, size_t ws_bytes, void *stream);
 int bvc_encode_vbr(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale, const float *d_target,
                    const int32_t *h_ladder, int32_t K, float *d_codes, float *d_bits, void *d_ws, size_t ws_bytes, void *stream);
+/* The same with a hard cap on the rate: an integer token bucket per row inside the selection.  Units are q8 (1/256 bit) in int32;
+ * rate_q8 >= 0 and burst_q8 >= 0 are the same for every row, the state is tok[b].  For row b at frame t, once k_target - the choice of
+ * the rule above - is known:
+ *   1. tok = min(burst_q8, tok + rate_q8)
+ *   2. a = the largest k with ladder[k] * 256 <= tok, 0 if there is none
+ *   3. k* = min(k_target, a): codes, bits, the decoded mel and the recurrence all go on with k*
+ *   4. tok = max(0, tok - ladder[k*] * 256)
+ * Integers only, so the result is exact on every schedule.  If ladder[0] * 256 <= rate_q8, every window of L consecutive frames of a row
+ * holds 256 * sum(bits) <= burst_q8 + L * rate_q8.  A target of -inf spends whatever the bucket allows (a rate target).
+ *   d_tok0 (B) int32 or NULL = a full bucket (burst_q8) in every row; d_tokT (B) or NULL: the state behind the last frame.  A sequence
+ *   cut into calls carries d_tokT into d_tok0 as it carries d_hT into d_h0; the result does not depend on where the cut is.
+ * BVC_EINVAL: a negative parameter; burst_q8 < ladder[0] * 256 (such a bucket never holds rung 0).  bvc_encode_vbr_capped: behind the
+ * front-end of bvc_encode_vbr, zero state, full buckets.  The uncapped entries run none of this. */
+int bvc_bvrnn_encode_vbr_capped(const bvc_model *m, const float *d_mel, const float *d_target, const int32_t *h_ladder, int32_t K,
+                                const float *d_h0, int32_t B, int64_t T, float *d_codes, float *d_bits, float *d_all_h, float *d_hT,
+                                float *d_prob, float *d_dist, float *d_dec, void *d_ws, size_t ws_bytes, void *stream, int32_t rate_q8,
+                                int32_t burst_q8, const int32_t *d_tok0, int32_t *d_tokT);
+int bvc_encode_vbr_capped(const bvc_model *m, const float *d_wav, int32_t B, int64_t L, float scale, const float *d_target,
+                          const int32_t *h_ladder, int32_t K, float *d_codes, float *d_bits, void *d_ws, size_t ws_bytes, void *stream,
+                          int32_t rate_q8, int32_t burst_q8);
 
 /* Pre-processing of the reference's example.py:15-17.
  * bvc_resample_poly: y = upfirdn(h, x, up, down)[n_pre_remove : n_pre_remove + n_out] with zero padding, i.e.
@@ -556,6 +604,10 @@ int bvc_unpack_codes_vbr(const uint8_t *d_bytes, int32_t B, int64_t T, int32_t z
  * every rung, d_y (B, num_mels), d_tau (B), h_ladder K host int32 -> d_dist (B, K) = D, d_choice (B) int32 = k*, d_bits (B) = n_{k*}. */
 int bvc_test_vbr_select(const float *d_melhat, const float *d_y, const float *d_tau, const int32_t *h_ladder, int32_t K, int32_t B,
                         int32_t num_mels, float *d_dist, int32_t *d_choice, float *d_bits, void *stream);
+/* ... under the cap of bvc_bvrnn_encode_vbr_capped: d_tok (B) int32, the buckets in front of the frame in, behind it out */
+int bvc_test_vbr_select_capped(const float *d_melhat, const float *d_y, const float *d_tau, const int32_t *h_ladder, int32_t K, int32_t B,
+                               int32_t num_mels, float *d_dist, int32_t *d_choice, float *d_bits, void *stream, int32_t rate_q8,
+                               int32_t burst_q8, int32_t *d_tok);
 /* y[M,N] = act(x[M,K] @ w[N,K]^T + bias), act: 0 none, 1 ELU.  Recurrent-step kernel. */
 int bvc_test_linear(const float *d_x, const float *d_w, const float *d_bias, int32_t M, int32_t N,
                     int32_t K, int32_t act, float *d_y, void *stream);
