@@ -159,6 +159,32 @@ def check(rc):
         raise BvcError(f"bvcodec error {rc}: {msg.decode() if msg else ''}")
 
 
+def check_arg(rc):
+    """``check`` for calls that can be misused: BVC_EINVAL (-1; the object is untouched) is a ValueError with the library's message."""
+    if rc == -1:
+        msg = load().bvc_last_error()
+        raise ValueError(msg.decode() if msg else "bvcodec: invalid argument")
+    check(rc)
+
+
+class Handle(ctypes.c_void_p):
+    """A handle the library created, destroyed with ``destroy`` when the last reference goes: ``ctypes.byref(h)`` for the create call,
+    ``h`` itself for every other.  ``keep``: what the destroy call still needs alive (the engine the object was created on).  A create
+    call that failed leaves it null, and nothing is destroyed; at interpreter shutdown, when the library may be gone, errors are dropped."""
+
+    def __init__(self, destroy, *keep):
+        super().__init__()
+        self._destroy, self._keep = destroy, keep
+
+    def __del__(self):
+        try:
+            if self:
+                self._destroy(self)
+                self.value = None
+        except Exception:
+            pass
+
+
 def ptr(t):
     """Device (or host) pointer of a contiguous float32 tensor, or None."""
     if t is None:

@@ -1,0 +1,143 @@
+"""The client-rate side of a ``StreamingCodec`` session: the resamplers in front of and behind the session's own buffers."""
+import weakref
+
+import torch
+
+from .resampling import PCM_DTYPES, StreamResampler
+from .stream_plans import client_finish_plan
+
+
+class _ClientRate:
+    """What ``StreamingCodec(client_rate=fs, sample_format=...)`` adds to a session (8000 .. 48000 Hz; None or the model's own 22050:
+    no adapter), ``sample_format="f32"`` or ``"s16"``: the session speaks the client's rate and format on both sides.  ``hop`` then
+    counts client samples and must be a whole number of internal ones (``hop * 22050 % fs == 0``, else ``ValueError``: 480 samples at
+    48 kHz would be 220.5; 20 ms hops of the six usual rates pass).  One ``StreamResampler`` sits in front of the session's input
+    buffer (send, duplex) and one behind its output buffer (recv, duplex), both on the session's stream, writing into and reading from
+    the session's own buffers.  Send side: with ``lag`` = ``self.lag`` (``n_pre_remove`` of ``design(22050, fs)``: 14 samples at
+    16 kHz, 11 at 48 kHz) a slot's internal stream is S = zeros(lag) ++ resample_poly(x, 22050, fs) - the offline resampling of the
+    client's signal, ``lag`` samples late because the filter looks that far ahead; ``open`` returns the session's delay as before, in
+    internal samples, and the stream is ``lag`` later than that.  The slot's packets and codes equal ``model.encode(S[None],
+    bitrate)`` on the frames the session emits, bit for bit, and ``finish(slot, n_last)`` (``n_last`` in client samples) ends the slot
+    with all ``num_frames(len(S))`` of them.  Receive side: after N internal samples of a stream the client has
+    ``resample_poly(wav22[:N], fs, 22050)[:E(N)]`` (``resampler_count``), ``wav22`` what the same session without ``client_rate``
+    returns; the last ``lag'`` (11 .. 22) client samples of a stream stay inside - receive sessions have no ``finish``.
+    ``push_packets`` then returns ``(wav (batch, n_max) view, counts (batch,) int64 CPU tensor)`` - row b's samples are
+    ``wav[b, :counts[b]]`` - and a duplex ``push`` ``(codes, wav, counts)``; a send ``push`` returns what it returned before.
+    ``"s16"`` takes and returns int16 tensors (in: x / 32768; out: clamp(rint(y * 32768)) of the float32 result, NaN 0).
+    Concealment, repair, ``set_bitrate`` and ``late`` act on the inner session unchanged; ``close`` also idles the row's resamplers.
+
+    The session calls ``opened`` / ``closed`` behind its own open / close, ``finish`` in place of its own, ``feed`` in place of the
+    copy into d_in and ``drain`` behind the tick.  Of the session the adapter uses ``_finish``, ``slot_frames`` and ``slot_state``,
+    the d_in view, the address of d_wav, the stream, ``spf`` and ``kmax``."""
+
+    def __init__(self, session, conf, rate, fmt, hop, hop_in, open_all):
+        sc = self.sc = weakref.proxy(session)                  # (the session owns the adapter: no cycle)
+        self.conf, self.rate, self.fmt, self.hop, self.hop_in = conf, rate, fmt, hop, hop_in
+        self.B, self.dev, self.spf, self.stream, self.d_in, self.wav_ptr = sc.B, sc.dev, sc.spf, sc.stream, sc._in, sc._wav_ptr
+        self.n_push = 0                                        # pushes so far
+        self.open_push = [0] * self.B                          # the push that took a slot's first client samples
+        self.ending = {}                                       # slot -> (internal n_last, spills) of a finish the next push carries out
+        self.carry = {}                                        # slot -> (from, count): the part of a flushed tail that goes into the next push
+        self.out_wait, self.out_drain = set(), set()           # slots whose samples have yet to start / are about to end on the wav side
+        self.rs_in = self.rs_out = None
+        if sc.direction != "recv":                             # in front of d_in (delayed: a fixed hop in, a fixed hop out)
+            self.rs_in = StreamResampler(self.B, rate, conf["fs"], hop, fmt, "f32", delayed=True, device=self.dev)
+            self.lag = self.rs_in.lag
+            self.tail = torch.zeros(self.B, max(1, self.lag), device=self.dev)
+        if sc.direction != "send":                             # behind d_wav
+            self.rs_out = StreamResampler(self.B, conf["fs"], rate, sc.kmax * self.spf, "f32", fmt, device=self.dev)
+            self.cwav = torch.zeros(self.B, max(1, self.rs_out.max_out), dtype=PCM_DTYPES[fmt], device=self.dev)
+        if open_all:
+            for b in range(self.B):
+                self.opened(b)
+
+    def opened(self, slot):
+        if self.rs_in is not None:
+            self.rs_in.close(slot)
+            self.rs_in.open(slot, 0)
+            self.open_push[slot] = self.n_push
+            self.ending.pop(slot, None)
+            self.carry.pop(slot, None)
+        if self.rs_out is not None:
+            self.rs_out.close(slot)
+            self.out_wait.add(slot)
+            self.out_drain.discard(slot)
+
+    def closed(self, slot):
+        if self.rs_in is not None:
+            self.rs_in.close(slot)
+            self.ending.pop(slot, None)
+            self.carry.pop(slot, None)
+        if self.rs_out is not None:
+            self.rs_out.close(slot)
+            self.out_wait.discard(slot)
+            self.out_drain.discard(slot)
+
+    def finish(self, slot, n_last):
+        """``n_last`` counts client samples; the stream's internal signal S = zeros(lag) ++ resample_poly(x, 22050, client_rate) ends
+        ``lag`` samples later, so the drain starts with the next push, or the one after it where the flushed tail does not fit the hop
+        (``client_finish_plan``); the slot ends with all ``num_frames(len(S))`` frames."""
+        if self.rs_in is None:                                 # a receive session: the library's refusal
+            return self.sc._finish(slot, n_last)
+        slot, n_last = int(slot), int(n_last)
+        if not 0 <= slot < self.B or self.sc.slot_state(slot) != "running" or slot in self.ending or slot in self.carry:
+            raise ValueError(f"finish: slot {slot} is not a running stream")
+        if not 0 <= n_last <= self.hop:
+            raise ValueError(f"finish: n_last {n_last} outside 0..{self.hop}")
+        push = self.n_push - self.open_push[slot]              # the coming push, counted from the stream's first
+        c = self.conf
+        len_s, at, n22 = client_finish_plan(push * self.hop + n_last, self.hop, self.rate, c["fs"])
+        if len_s <= c["winsize"] - c["hopsize"] - c["mel_pad_left"]:
+            raise ValueError(f"finish: a stream of {len_s} internal samples is too short for the right reflect padding")
+        self.rs_in.end(slot, n_last)
+        self.ending[slot] = (n22, at > push)
+
+    def feed(self, x):
+        """A hop of client samples -> d_in, inside the session's stream: one resampler push for all rows, and for a row that ends the
+        flush of its last ``lag`` samples - straight into d_in where they fit the hop, else through a buffer into this hop and the next."""
+        if tuple(x.shape) != (self.B, self.hop) or x.dtype != PCM_DTYPES[self.fmt]:
+            raise ValueError(f"push: expected a {PCM_DTYPES[self.fmt]} tensor ({self.B}, {self.hop})")
+        x = x.to(self.dev).contiguous()
+        rs, hop22, s = self.rs_in, self.hop_in, self.stream.cuda_stream
+        counts = rs.push_raw(x.data_ptr(), self.hop, self.hop, self.d_in.data_ptr(), hop22, 0, s)
+        for slot, (frm, n) in list(self.carry.items()):        # the rest of a tail that spilled: the row is idle, its hop zeros
+            self.d_in[slot, :n].copy_(self.tail[slot, frm:frm + n], non_blocking=True)
+            self.sc._finish(slot, n)
+            self.out_drain.add(slot)
+            del self.carry[slot]
+        for slot, (n22, spills) in list(self.ending.items()):
+            e = counts[slot]                                   # what the row's last client samples completed
+            if not spills:
+                rs.flush_raw(slot, self.d_in.data_ptr() + 4 * (slot * hop22 + e), s)
+                self.sc._finish(slot, n22)
+                self.out_drain.add(slot)
+            else:
+                rs.flush_raw(slot, self.tail.data_ptr() + 4 * slot * self.tail.shape[1], s)
+                self.d_in[slot, e:].copy_(self.tail[slot, :hop22 - e], non_blocking=True)
+                self.carry[slot] = (hop22 - e, n22)
+            del self.ending[slot]
+        self.n_push += 1
+
+    def drain(self, k):
+        """The tick's k frames of d_wav -> client samples: (wav (B, n_max) view, counts (B,) int64 CPU tensor); None on a send session."""
+        rs = self.rs_out
+        if rs is None:
+            return None
+        if k == 0:
+            return torch.empty(self.B, 0, dtype=PCM_DTYPES[self.fmt], device=self.dev), torch.zeros(self.B, dtype=torch.int64)
+        for slot in list(self.out_wait):                       # a row's resampler starts with its stream's frame 0
+            first, count, frame0 = self.sc.slot_frames(slot)
+            if count > 0 and frame0 == 0:
+                rs.open(slot, self.spf * first)
+                self.out_wait.discard(slot)
+        for slot in list(self.out_drain):                      # ... and ends with its last one (the last lag' samples stay inside)
+            if self.sc.slot_state(slot) == "idle":
+                first, count, _ = self.sc.slot_frames(slot)
+                if slot in rs.running:
+                    rs.end(slot, self.spf * (first + max(0, count)))
+                    rs.running.discard(slot)
+                self.out_drain.discard(slot)
+                self.out_wait.discard(slot)                    # (a stream that ended before its frame 0 came out)
+        n = k * self.spf
+        counts = rs.push_raw(self.wav_ptr, n, n, self.cwav.data_ptr(), self.cwav.shape[1], 0, self.stream.cuda_stream)
+        return self.cwav[:, :-(-n * rs.up // rs.down)], torch.tensor(counts, dtype=torch.int64)

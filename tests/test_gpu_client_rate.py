@@ -4,8 +4,9 @@ session's samples then ``preprocess.resample_poly`` - with ``torch.equal``.  Nee
 import pytest
 import torch
 
+from gpu_sessions import DEV
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 FS = 22050
 RATES = (8000, 16000, 24000, 32000, 44100, 48000)
 PAIRS = [(r, FS) for r in RATES] + [(FS, r) for r in RATES]          # (rate_in, rate_out)
@@ -324,7 +325,7 @@ def test_session_without_client_rate_is_unchanged(model):
     x = torch.stack([speech(pushes * hop, 300 + b) * 0.9 for b in range(B)]).to(DEV)
     other = StreamingCodec(model, B, 3000, hop=960, client_rate=48000)
     sc = StreamingCodec(model, B, 3000, hop=hop)
-    assert sc.client_rate is None and sc._rs_in is None and sc._rs_out is None and sc.hop == hop
+    assert sc.client_rate is None and sc._client is None and sc.hop == hop                # (no resampler on either side)
     codes, wavs = [], []
     for t in range(pushes):
         res = sc.push(x[:, t * hop:(t + 1) * hop])
@@ -340,5 +341,5 @@ def test_session_without_client_rate_is_unchanged(model):
     assert torch.equal(codes, off[:, :F])
     assert (wav - model.decode(off, pushes * hop)[:, :256 * F]).abs().max().item() <= 2e-6
     same = StreamingCodec(model, B, 3000, hop=hop, client_rate=FS)    # the session's own rate: the session it is today
-    assert same._rs_in is None and len(same.push(x[:, :hop])) == 2
+    assert same._client is None and len(same.push(x[:, :hop])) == 2
     model.check_status()

@@ -197,15 +197,15 @@ def test_send_session_feeds_receive_session_at_sizes(h_dim, z_dim):
     codes, zeros behind each row's bits, and a receive session fed with them gives the offline decode's samples.  z_dim 144: a frame
     of 18 bytes is more than a late packet carries, so the repair window is refused and the session runs without it."""
     from bvcodec import synth
-    from bvcodec.streaming import StreamingCodec
-    from test_gpu_stream_direction import drive_sender, receive
+    import gpu_sessions as gs
     model = make_model(True, h_dim, z_dim=z_dim)[0]
     B, hop, ticks = 5, 441, 3
     bpf = (z_dim + 7) // 8
     part, full = wire_rates(model, z_dim)
     rates = [part if b % 2 == 0 else full for b in range(B)]
     x = synth.synthetic_speech(B, hop * ticks, seed=z_dim, kind="speech").to(DEV)
-    ks, packets, codes = drive_sender(model, "send", B, hop, ticks, x, rates)
+    s = gs.drive_sender(model, "send", x, hop, rates)
+    ks, packets, codes = s.ks, s.first, s.second
     F = sum(ks)
     assert F == (hop * ticks - 768) // 256 + 1 == 3 and packets.dtype == torch.uint8 and tuple(packets.shape) == (B, F, bpf)
     packets, codes = packets.clone(), codes.clone()
@@ -217,7 +217,8 @@ def test_send_session_feeds_receive_session_at_sizes(h_dim, z_dim):
         got, used = packets[b].cpu().numpy(), (n + 7) // 8
         assert np.array_equal(got[:, :used], packbits(off[0], n)), b
         assert not got[:, used:].any(), b
-    wav, sc = receive(model, B, rates, packets, [k for k in ks if k])
+    r = gs.drive_receiver(model, packets, [k for k in ks if k], rates, on_tick=gs.every_row_runs)
+    wav, sc = r.wav, r.sc
     assert sc.bytes_per_frame == bpf
     if bpf > 16:
         with pytest.raises(ValueError, match=f"bvc_stream_codec_set_repair: frames of {bpf} bytes"):

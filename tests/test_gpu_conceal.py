@@ -12,9 +12,9 @@ from conftest import load_golden
 
 import conceal_oracle as co
 from gpu_common import on_schedule
+from gpu_sessions import DEV, RATES, send_packets, set_schedule
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 def t(a):
@@ -214,26 +214,6 @@ def test_no_loss_agrees_with_plain_decode_to_rounding(B):
 
 
 # ------------------------------------------------------------------------------------------------ 7: sessions
-RATES = (2200, 3000, 6000, 1500)
-
-
-def send_packets(model, B, ticks=50, hop=441, seed=70):
-    from bvcodec import synth
-    from bvcodec.streaming import StreamingCodec
-    x = synth.synthetic_speech(B, hop * ticks, seed=seed + B, kind="speech").to(DEV)
-    sc = StreamingCodec(model, B, 3000, hop=hop, open_all=False, direction="send")
-    for b in range(B):
-        sc.open(b, RATES[b % 4])
-    ks, pk = [], []
-    for i in range(ticks):
-        p, _ = sc.push(x[:, i * hop:(i + 1) * hop])
-        if p.shape[1]:
-            ks.append(p.shape[1])
-            pk.append(p.clone())
-    torch.cuda.synchronize()
-    return ks, torch.cat(pk, 1)
-
-
 def offline_stream(model, packets, present, rates):
     """bvc_decode_conceal of ONE stream's own packets: packets (F, 8), present (F,), rates (F,) the bitrate in force per frame.
     Returns (wav (256 F,), filled codes (F, 64))."""
@@ -259,13 +239,6 @@ def offline_stream(model, packets, present, rates):
     return wav[0, 0], filled[0]
 
 
-def set_schedule(monkeypatch, schedule):
-    """"flow": the ticks' recurrences on the persistent kernel (the default); "graph": launch-per-layer kernels, replayed from the
-    session's graph table once the streams are warm (a concealing tick has a table of its own)."""
-    if schedule != "flow":
-        monkeypatch.setenv("BVC_STREAM_FLOW", "0")
-
-
 @pytest.mark.parametrize("B,schedule", [(3, "flow"), (40, "flow"), (256, "flow"), (3, "graph"), (40, "graph")])
 def test_receive_sessions_conceal_like_the_offline_call(B, schedule, monkeypatch):
     """Receive sessions with conceal="prior" fed from a send session's packets, 5 % of the frames dropped plus a burst per row, the
@@ -275,7 +248,7 @@ def test_receive_sessions_conceal_like_the_offline_call(B, schedule, monkeypatch
     from bvcodec.streaming import StreamingCodec
     model = mk(True, 1024)[0]
     set_schedule(monkeypatch, schedule)
-    ks, packets = send_packets(model, B)
+    ks, packets = send_packets(model, B, 50)
     F = packets.shape[1]
     present = co.loss_pattern(B, F, 0.05, seed=30 + B, burst=6).to(DEV)
     present[0, 0] = False
@@ -346,7 +319,7 @@ def test_set_conceal_switches_from_the_next_tick(schedule, monkeypatch):
     model = mk(True, 1024)[0]
     set_schedule(monkeypatch, schedule)
     B = 3
-    ks, packets = send_packets(model, B, ticks=60)
+    ks, packets = send_packets(model, B, 60)
     F = packets.shape[1]
     present = co.loss_pattern(B, F, 0.1, seed=3, burst=5).to(DEV)
     SWITCH = {26: "prior", 34: "none", 42: "prior"}

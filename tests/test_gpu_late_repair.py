@@ -7,13 +7,12 @@ import pytest
 import torch
 
 import bvrnn_draws
+import gpu_sessions as gs
 from gpu_common import make_model
+from gpu_sessions import DEV, RATES
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-RATES = (2200, 3000, 6000, 1500)
 REACH = 26                                                      # bvcodec.streaming.generator_reach: frames one mel frame reaches ahead
-_PACKETS = {}
 
 
 def mk(var_bit=True):
@@ -22,22 +21,7 @@ def mk(var_bit=True):
 
 def send_packets(model, var_bit, B, ticks, hop=441):
     """(B, F, 8) uint8: a send session of the same model on a short seeded signal, row b at RATES[b % 4]; computed once per case."""
-    key = (var_bit, B, ticks)
-    if key not in _PACKETS:
-        from bvcodec import synth
-        from bvcodec.streaming import StreamingCodec
-        x = synth.synthetic_speech(B, hop * ticks, seed=70 + B, kind="speech").to(DEV)
-        sc = StreamingCodec(model, B, 3000, hop=hop, open_all=False, direction="send")
-        for b in range(B):
-            sc.open(b, RATES[b % 4])
-        pk = []
-        for i in range(ticks):
-            p, _ = sc.push(x[:, i * hop:(i + 1) * hop])
-            if p.shape[1]:
-                pk.append(p.clone())
-        torch.cuda.synchronize()
-        _PACKETS[key] = torch.cat(pk, 1)
-    return _PACKETS[key]
+    return gs.memo(("late_repair", var_bit, B, ticks), lambda: gs.send_packets(model, B, ticks, hop)[1])
 
 
 def chunks(F):
@@ -68,31 +52,10 @@ def run(model, packets, ticks, lost, actions=None, conceal="none", repair=0, ope
     """One receive session.  lost (B, F) bool: frames pushed as not present.  actions {tick index: [(what, ...), ...]}, carried out in
     front of that push: ("late", row, stream_frame, session frame whose bytes are handed in), ("open", row, rate), ("close", row),
     ("rate", row, rate), ("conceal", mode).  Returns (wav (B, 256 F), filled codes (B, F, 64), [late's answers])."""
-    from bvcodec.streaming import StreamingCodec
-    B = packets.shape[0]
-    sc = StreamingCodec(model, B, 3000, open_all=False, direction="recv", conceal=conceal, repair=repair)
-    for b in range(B):
-        if opened is None or b in opened:
-            sc.open(b, RATES[b % 4])
-    pushed = lossy(packets, lost)
-    present = (~lost).to(torch.uint8)
-    wav, codes, taken = [], [], []
-    for i, (f, k) in enumerate(ticks):
-        for a in (actions or {}).get(i, ()):
-            if a[0] == "late":
-                taken.append(sc.late(a[1], a[2], packets[a[1], a[3]]))
-            elif a[0] == "open":
-                sc.open(a[1], a[2])
-            elif a[0] == "close":
-                sc.close(a[1])
-            elif a[0] == "rate":
-                sc.set_bitrate(a[1], a[2])
-            elif a[0] == "conceal":
-                sc.set_conceal(a[1])
-        wav.append(sc.push_packets(pushed[:, f:f + k], present[:, f:f + k]).clone())
-        codes.append(sc.filled_codes(k).clone())
-    torch.cuda.synchronize()
-    return torch.cat(wav, 1), torch.cat(codes, 1), taken
+    actions = {i: [a[:3] + (packets[a[1], a[3]],) if a[0] == "late" else a for a in acts] for i, acts in (actions or {}).items()}
+    r = gs.drive_receiver(model, lossy(packets, lost), [k for _, k in ticks], [RATES[b % 4] for b in range(packets.shape[0])],
+                          (~lost).to(torch.uint8), actions, opened, conceal=conceal, repair=repair)
+    return r.wav, r.codes, r.taken
 
 
 def mask(B, F, frames):
@@ -128,8 +91,7 @@ def test_one_late_frame(d, conceal, var_bit, schedule, monkeypatch):
     """Frame 34 of row 1 is lost in its push and handed in d ticks later ("graph": launch-per-layer ticks replayed from the session's
     graph table from frame 33 on, so the repair happens between two replayed ticks).  With conceal="prior" frame 54 is lost for good in
     all three sessions: what LATE generates for it are ON-TIME's bits."""
-    if schedule == "graph":
-        monkeypatch.setenv("BVC_STREAM_FLOW", "0")
+    gs.set_schedule(monkeypatch, schedule)
     model = mk(var_bit)
     B, FL, GONE = 3, 34, 54
     packets = send_packets(model, var_bit, B, 52)

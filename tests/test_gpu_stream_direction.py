@@ -6,31 +6,21 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_stream_slots import churn_schedule
+import gpu_sessions as gs
+from gpu_sessions import DEV, RATES, chunked, churn_schedule
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-RATES = (2200, 3000, 6000, 1500)                             # 26, 35, 64 and 17 bits per frame (26: a frame that ends inside a byte)
 BAR = 2e-6                                                   # streaming waveform against the offline launch-per-layer model
 
 
 @pytest.fixture(scope="module")
 def model():
-    from gpu_common import make_model
-    return make_model(True, 1024)[0]
+    return gs.product_model()
 
 
 @pytest.fixture(scope="module")
 def ref_model():
-    from gpu_common import make_model
-    return make_model(True, 1024, env={"BVC_RECURRENCE": "layers"})[0]
-
-
-def set_schedule(monkeypatch, schedule):
-    if schedule != "flow":
-        monkeypatch.setenv("BVC_STREAM_FLOW", "0")
-    if schedule == "eager":
-        monkeypatch.setenv("BVC_STREAM_NO_GRAPH", "1")
+    return gs.reference_model()
 
 
 def nbits_of(model, rate):
@@ -47,41 +37,18 @@ def host_pack(codes, nbits):
     return out
 
 
-def drive_sender(model, direction, B, hop, ticks, x, rates):
-    """One session on x (B, ticks * hop), row b opened at `rates[b]` before the first push.  Returns per tick the frame count, and the
-    concatenated outputs: codes (B, F, z), and wav (B, 256 F) (duplex) or packets (B, F, 8) (send)."""
-    from bvcodec.streaming import StreamingCodec
-    sc = StreamingCodec(model, B, 3000, hop=hop, open_all=False, direction=direction)
-    for b in range(B):
-        assert sc.open(b, rates[b]) == 0
-    ks, first, second = [], [], []
-    for t in range(ticks):
-        a, c = sc.push(x[:, t * hop:(t + 1) * hop])
-        k = a.shape[1]
-        ks.append(k)
-        first.append(a.clone())
-        second.append(c.clone())
-        assert all(sc.slot_frames(b)[:2] == (0, k) for b in (0, B - 1))
-    torch.cuda.synchronize()
-    return ks, torch.cat(first, 1), torch.cat(second, 1)
-
-
-_SENT = {}
-
-
 def sent(model, schedule, B, monkeypatch):
     """The duplex and the send session of test 1 on one input, per tick schedule and batch (shared with the receive tests)."""
     from bvcodec import synth
-    set_schedule(monkeypatch, schedule)
-    key = (schedule, B)
-    if key not in _SENT:
+    gs.set_schedule(monkeypatch, schedule)
+
+    def make():
         hop, ticks = 441, 120
         x = synth.synthetic_speech(B, hop * ticks, seed=60 + B, kind="speech").to(DEV)
         rates = [RATES[b % 4] for b in range(B)]
-        ks_d, codes_d, wav_d = drive_sender(model, "duplex", B, hop, ticks, x, rates)
-        ks_s, packets, codes_s = drive_sender(model, "send", B, hop, ticks, x, rates)
-        _SENT[key] = SimpleNamespace(x=x, rates=rates, ks=ks_s, ks_d=ks_d, codes_d=codes_d, wav_d=wav_d, packets=packets, codes=codes_s)
-    return _SENT[key]
+        d, s = gs.drive_sender(model, "duplex", x, hop, rates), gs.drive_sender(model, "send", x, hop, rates)
+        return SimpleNamespace(x=x, rates=rates, ks=s.ks, ks_d=d.ks, codes_d=d.first, wav_d=d.second, packets=s.first, codes=s.second)
+    return gs.memo(("direction", schedule, B), make)
 
 
 @pytest.mark.parametrize("B", [3, 40])
@@ -113,26 +80,9 @@ def test_send_equals_duplex_and_offline(model, B, monkeypatch):
 
 def receive(model, B, rates, packets, chunks, present=None):
     """A receive session fed `packets` (B, F, 8) in ticks of `chunks` frames; returns wav (B, 256 F)."""
-    from bvcodec.streaming import StreamingCodec
-    sc = StreamingCodec(model, B, 3000, open_all=False, direction="recv")
-    for b in range(B):
-        assert sc.open(b, rates[b]) == 0
-        assert sc.slot_state(b) == "waiting"
-    out, f = [], 0
-    for k in chunks:
-        pr = None if present is None else present[:, f:f + k]
-        w = sc.push_packets(packets[:, f:f + k], pr)
-        assert w.shape == (B, 256 * k)
-        out.append(w.clone())
-        assert sc.slot_frames(0) == (0, k, f) and sc.slot_state(B - 1) == "running"
-        f += k
-    assert f == packets.shape[1]
-    torch.cuda.synchronize()
-    return torch.cat(out, 1), sc
-
-
-def chunked(total, k):
-    return [k] * (total // k) + ([total % k] if total % k else [])
+    assert packets.shape[0] == B
+    r = gs.drive_receiver(model, packets, chunks, rates, present, on_tick=gs.every_row_runs)
+    return r.wav, r.sc
 
 
 @pytest.mark.parametrize("B", [3, 40])
@@ -514,13 +464,12 @@ def test_over_the_wire(model, ref_model):
 
 def test_fixed_rate_model_sends_and_receives_all_bits():
     """var_bit = 0: every frame carries all z_dim bits whatever bitrate the slot was opened with."""
-    from gpu_common import make_model
     from bvcodec import synth
-    fixed = make_model(False, 1024)[0]
-    ref = make_model(False, 1024, env={"BVC_RECURRENCE": "layers"})[0]
+    fixed, ref = gs.product_model(False), gs.reference_model(False)
     B, hop, ticks = 3, 441, 60
     x = synth.synthetic_speech(B, hop * ticks, seed=91, kind="speech").to(DEV)
-    ks, packets, codes = drive_sender(fixed, "send", B, hop, ticks, x, [1500, 3000, 6000])
+    s = gs.drive_sender(fixed, "send", x, hop, [1500, 3000, 6000])
+    ks, packets, codes = s.ks, s.first, s.second
     F = codes.shape[1]
     off = ref.encode(x, 3000)[:, :F]
     assert torch.equal(codes, off) and not bool((codes == 0.5).any())

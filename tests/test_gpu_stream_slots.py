@@ -1,24 +1,17 @@
 """Slots of the whole-hop streaming codec: rows of a session are opened, closed, re-used and re-rated while the others keep running,
 and whatever a slot emits is bit for bit the offline call on that stream's own signal alone.  Needs the MI355X."""
-from types import SimpleNamespace
-
 import pytest
 import torch
 
+import gpu_sessions as gs
+from gpu_sessions import DEV, churn_schedule, utt
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module")
 def model():
-    from gpu_common import make_model
-    return make_model(True, 1024)[0]
-
-
-def utt(slot, t_open, t_close, rate, seed, row=0, batch=1):
-    """One utterance of a schedule: it lives in `slot` for the pushes t_open .. t_close - 1; its signal is row `row` of
-    synth.synthetic_speech(batch, n, seed) with n = (t_close - t_open) * hop (filled in by run_session)."""
-    return SimpleNamespace(slot=slot, t_open=t_open, t_close=t_close, rate=rate, seed=seed, row=row, batch=batch)
+    return gs.product_model()
 
 
 def run_session(model, B, hop, ticks, utts, rate_changes=(), check_finite=True):
@@ -80,8 +73,7 @@ def run_session(model, B, hop, ticks, utts, rate_changes=(), check_finite=True):
 def check_against_offline(model, utts):
     """Every utterance against the offline call on its own signal alone: the launch-per-layer reference model (the bar of
     test_whole_hop_codec_equals_offline_and_oracle: codes equal, waveform within 2e-6) and the default model (codes equal)."""
-    from gpu_common import make_model
-    ref_model = make_model(True, 1024, env={"BVC_RECURRENCE": "layers"})[0]
+    ref_model = gs.reference_model()
     for u in utts:
         F = u.frames
         x = u.x[None].to(DEV)
@@ -93,37 +85,13 @@ def check_against_offline(model, utts):
         assert err <= 2e-6, (u.slot, u.t_open, err)
 
 
-# hop 441: the delay of a stream that joins at tick t is 0 at t = 0 and 256, 368 at 16, 369 at 135 and the largest, 370, at 254
-ORACLE_A = dict(rate=1500, seed=41, row=1, batch=2)       # 50 ticks = 22050 samples: the CPU oracle has no probability within 1e-5 of 0.5
-ORACLE_B = dict(rate=6000, seed=42, row=0, batch=2)       # 50 ticks: the oracle's first such probability (active bits) is in frame 69
-
-
-def churn_schedule():
-    return [
-        utt(0, 0, 37, 3000, 101), utt(1, 0, 90, 1500, 102),                  # two slots open in one tick, delay 0
-        utt(2, 5, 55, **ORACLE_B),                                            # delay 355
-        utt(3, 16, 70, 2200, 104),                                            # delay 368, an odd bitrate (26 bits per frame)
-        utt(0, 37, 120, 6000, 105),                                           # closed and re-opened between the same two pushes
-        utt(4, 45, 110, 3000, 106), utt(5, 45, 95, **ORACLE_A),               # two slots open in one tick of a running session
-        utt(2, 63, 135, 3000, 108),
-        utt(4, 117, 180, 1500, 109),
-        utt(3, 128, 190, 6000, 110),                                          # delay 128
-        utt(0, 135, 230, 1500, 111),                                          # slot 0 for the third time; delay 369
-        utt(6, 254, 300, 3000, 112),                                          # the largest delay, 370
-        utt(1, 256, 300, 4100, 113),                                          # delay 0 in a warm session; another odd bitrate
-    ]                                                                         # slot 7 stays idle throughout
-
-
-_RUNS = {}
-
-
 def churn_run(model, schedule):
-    if schedule not in _RUNS:
+    def make():
         utts = churn_schedule()
         run_session(model, 8, 441, 300, utts)
         assert {u.delay for u in utts} >= {0, 355, 368, 369, 370, 128}
-        _RUNS[schedule] = utts
-    return _RUNS[schedule]
+        return utts
+    return gs.memo(("slots churn", schedule), make)
 
 
 @pytest.mark.parametrize("schedule", ["flow", "graph", "eager"])
@@ -131,10 +99,7 @@ def test_churn_equals_offline(model, schedule, monkeypatch):
     """8 slots, 441-sample hops, 300 ticks, 13 utterances of different lengths and bitrates that come and go (delays 0 .. 370, a slot
     used three times, two opened in one tick, a slot closed and re-opened between the same two pushes), slot 7 idle throughout with
     NaN / 1e30 in its input row: every utterance equals the offline call on its own signal, on each of the tick's schedules."""
-    if schedule != "flow":
-        monkeypatch.setenv("BVC_STREAM_FLOW", "0")
-    if schedule == "eager":
-        monkeypatch.setenv("BVC_STREAM_NO_GRAPH", "1")
+    gs.set_schedule(monkeypatch, schedule)
     utts = churn_run(model, schedule)
     check_against_offline(model, utts)
     model.check_status()

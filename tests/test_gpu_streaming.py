@@ -4,14 +4,15 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_sessions as gs
+from gpu_sessions import DEV
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module")
 def model():
-    from gpu_common import make_model
-    return make_model(True, 1024)[0]
+    return gs.product_model()
 
 
 @pytest.mark.parametrize("incremental", [True, False])
@@ -155,10 +156,7 @@ def test_whole_hop_codec_equals_offline_and_oracle(model, B, schedule, monkeypat
     from bvcodec import synth
     from bvcodec.streaming import StreamingCodec
     from oracle import codec as ocodec
-    if schedule != "flow":
-        monkeypatch.setenv("BVC_STREAM_FLOW", "0")
-    if schedule == "eager":
-        monkeypatch.setenv("BVC_STREAM_NO_GRAPH", "1")
+    gs.set_schedule(monkeypatch, schedule)
     _, conf, vr, ge = make_model(True, 1024)
     hop, hops = 441, 120                                            # 2.4 s: ~206 frames, > 170 of them replayed from graphs
     L = hop * hops
@@ -177,7 +175,7 @@ def test_whole_hop_codec_equals_offline_and_oracle(model, B, schedule, monkeypat
     # offline references: the launch-per-layer schedule (the ticks' own recurrence kernels) and the library default (the persistent
     # kernel; phi_x / phi_z on the all-frames GEMMs where a hop runs them frame by frame): one order of summation per output
     # (k_gemm.hip), so the streamed codes are bit for bit the offline ones.  (The hops never emit a frame that needs samples beyond L.)
-    ref_model = make_model(True, 1024, env={"BVC_RECURRENCE": "layers"})[0]
+    ref_model = gs.reference_model()
     codes_off = ref_model.encode(x, 3000)
     assert torch.equal(codes, codes_off[:, :F])
     assert torch.equal(model.encode(x, 3000)[:, :F], codes)

@@ -8,11 +8,12 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_sessions as gs
 import vbr_cap_oracle as vc
 import vbr_oracle as vo
+from gpu_sessions import DEV, chunked
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 BAR = 2e-6                                                   # streaming waveform against the offline launch-per-layer model
 BITRATES = (1500, 3000, 6000)                                # 17, 35 and 64 bits per frame
 CAP_BITRATES = (689, 1378, 2756, 5513)                       # 8, 16, 32 and 64 bits per frame
@@ -22,58 +23,38 @@ INF = float("inf")
 
 @pytest.fixture(scope="module")
 def model():
-    from gpu_common import make_model
-    return make_model(True, 1024)[0]
+    return gs.product_model()
 
 
 @pytest.fixture(scope="module")
 def ref_model():
-    from gpu_common import make_model
-    return make_model(True, 1024, env={"BVC_RECURRENCE": "layers"})[0]
+    return gs.reference_model()
 
 
 def set_schedule(monkeypatch, schedule):
-    if schedule == "eager":
-        monkeypatch.setenv("BVC_STREAM_NO_GRAPH", "1")
-
-
-_SIGNALS = {}
+    gs.set_schedule(monkeypatch, schedule, flow_stays=True)
 
 
 def signals(model, B, bitrates=BITRATES):
     """x (B, TICKS * HOP) and every row's target: +inf (always rung 0), -inf (always the top rung), or the median over frames of the
     second rung's distortion in one offline probe call - in rotation."""
     from bvcodec import synth
-    key = (B, bitrates)
-    if key not in _SIGNALS:
+
+    def make():
         x = synth.synthetic_speech(B, HOP * TICKS, seed=80 + B, kind="speech").to(DEV)
         ladder = [model.active_bits(r) for r in bitrates]
         mel = model.mel_spectrogram(x)
         extra = model.bvrnn.encode_vbr(mel, ladder, -INF, torch.zeros(1, B, 1024, device=DEV), return_all=True)[3]
         med = extra["dist"][:, :, 1].median(dim=1).values.cpu()
-        targets = [(INF, -INF, float(med[b]))[b % 3] for b in range(B)]
-        _SIGNALS[key] = (x, targets)
-    return _SIGNALS[key]
+        return x, [(INF, -INF, float(med[b]))[b % 3] for b in range(B)]
+    return gs.memo(("vbr signals", B, bitrates), make)
 
 
 def drive(model, direction, x, targets, vbr, ticks=TICKS):
     """One vbr session on x, row b opened with targets[b].  Returns ks, per tick outputs concatenated: first (packets or codes), second
     (codes or wav), bits (B, F), sizes (B, F), and the session."""
-    from bvcodec.streaming import StreamingCodec
-    B = x.shape[0]
-    sc = StreamingCodec(model, B, 3000, hop=HOP, open_all=False, direction=direction, vbr=vbr)
-    for b in range(B):
-        assert sc.open(b, target=targets[b]) == 0
-    ks, first, second, bits, sizes = [], [], [], [], []
-    for t in range(ticks):
-        a, c = sc.push(x[:, t * HOP:(t + 1) * HOP])
-        k = a.shape[1]
-        ks.append(k)
-        first.append(a.clone()); second.append(c.clone())
-        bits.append(sc.last_bits.clone()); sizes.append(sc.last_sizes.clone())
-        assert bits[-1].shape == (B, k) and sizes[-1].shape == (B, k)
-    torch.cuda.synchronize()
-    return ks, torch.cat(first, 1), torch.cat(second, 1), torch.cat(bits, 1), torch.cat(sizes, 1), sc
+    r = gs.drive_sender(model, direction, x, HOP, targets=targets, vbr=vbr, ticks=ticks)
+    return r.ks, r.first, r.second, r.bits, r.sizes, r.sc
 
 
 def check_wire(packets, sizes, codes, bits):
@@ -85,16 +66,10 @@ def check_wire(packets, sizes, codes, bits):
     assert not got_p[behind].any()
 
 
-_SENT = {}
-
-
 def sent(model, schedule, B, monkeypatch):
     set_schedule(monkeypatch, schedule)
-    key = (schedule, B)
-    if key not in _SENT:
-        x, targets = signals(model, B)
-        _SENT[key] = (x, targets) + drive(model, "send", x, targets, dict(bitrates=BITRATES, target=0.35))
-    return _SENT[key]
+    x, targets = signals(model, B)
+    return gs.memo(("vbr sent", schedule, B), lambda: (x, targets) + drive(model, "send", x, targets, dict(bitrates=BITRATES, target=0.35)))
 
 
 # ---------------------------------------------------------------------------------------------- 1: every stream is its own offline call
@@ -209,24 +184,10 @@ def test_capped_session(model, schedule, monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------- 4: duplex, and over the wire
-def chunked(total, k):
-    return [k] * (total // k) + ([total % k] if total % k else [])
-
-
 def receive(model, B, packets, chunks, present=None, conceal="none", bitrate=3000):
-    from bvcodec.streaming import StreamingCodec
-    sc = StreamingCodec(model, B, bitrate, open_all=False, direction="recv", vbr=True, conceal=conceal)
-    assert sc.bytes_per_frame == 9
-    for b in range(B):
-        assert sc.open(b, bitrate) == 0
-    wav, codes, bits, f = [], [], [], 0
-    for k in chunks:
-        w = sc.push_packets(packets[:, f:f + k], None if present is None else present[:, f:f + k])
-        wav.append(w.clone()); codes.append(sc.filled_codes(k).clone()); bits.append(sc.last_bits.clone())
-        f += k
-    assert f == packets.shape[1]
-    torch.cuda.synchronize()
-    return torch.cat(wav, 1), torch.cat(codes, 1), torch.cat(bits, 1), sc
+    r = gs.drive_receiver(model, packets, chunks, [bitrate] * B, present, bitrate=bitrate, on_tick=gs.every_row_runs, vbr=True, conceal=conceal)
+    assert r.sc.bytes_per_frame == 9 and r.sc.B == B
+    return r.wav, r.codes, r.bits, r.sc
 
 
 @pytest.mark.parametrize("B", [3, 17])
