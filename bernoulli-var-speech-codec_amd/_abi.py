@@ -185,12 +185,15 @@ class Handle(ctypes.c_void_p):
             pass
 
 
-def ptr(t):
-    """Device (or host) pointer of a contiguous float32 tensor, or None."""
-    if t is None:
-        return None
-    assert t.dtype == torch.float32 and t.is_contiguous(), "float32 contiguous tensors only"
-    return ctypes.c_void_p(t.data_ptr())
+def addr(t, dtype=torch.float32):
+    """Device (or host) address of a contiguous tensor of ``dtype``, an int: for address arithmetic."""
+    assert t.dtype == dtype and t.is_contiguous(), f"{str(dtype)[6:]} contiguous tensors only"
+    return t.data_ptr()
+
+
+def ptr(t, dtype=torch.float32):
+    """Device (or host) pointer of a contiguous tensor of ``dtype`` (float32 unless the argument is a mask, a count or bytes), or None."""
+    return None if t is None else ctypes.c_void_p(addr(t, dtype))
 
 
 def current_stream(device):

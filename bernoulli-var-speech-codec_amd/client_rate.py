@@ -3,6 +3,7 @@ import weakref
 
 import torch
 
+from . import _abi
 from .resampling import PCM_DTYPES, StreamResampler
 from .stream_plans import client_finish_plan
 
@@ -99,7 +100,7 @@ class _ClientRate:
             raise ValueError(f"push: expected a {PCM_DTYPES[self.fmt]} tensor ({self.B}, {self.hop})")
         x = x.to(self.dev).contiguous()
         rs, hop22, s = self.rs_in, self.hop_in, self.stream.cuda_stream
-        counts = rs.push_raw(x.data_ptr(), self.hop, self.hop, self.d_in.data_ptr(), hop22, 0, s)
+        counts = rs.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt]), self.hop, self.hop, _abi.addr(self.d_in), hop22, 0, s)
         for slot, (frm, n) in list(self.carry.items()):        # the rest of a tail that spilled: the row is idle, its hop zeros
             self.d_in[slot, :n].copy_(self.tail[slot, frm:frm + n], non_blocking=True)
             self.sc._finish(slot, n)
@@ -108,11 +109,11 @@ class _ClientRate:
         for slot, (n22, spills) in list(self.ending.items()):
             e = counts[slot]                                   # what the row's last client samples completed
             if not spills:
-                rs.flush_raw(slot, self.d_in.data_ptr() + 4 * (slot * hop22 + e), s)
+                rs.flush_raw(slot, _abi.addr(self.d_in) + 4 * (slot * hop22 + e), s)
                 self.sc._finish(slot, n22)
                 self.out_drain.add(slot)
             else:
-                rs.flush_raw(slot, self.tail.data_ptr() + 4 * slot * self.tail.shape[1], s)
+                rs.flush_raw(slot, _abi.addr(self.tail) + 4 * slot * self.tail.shape[1], s)
                 self.d_in[slot, e:].copy_(self.tail[slot, :hop22 - e], non_blocking=True)
                 self.carry[slot] = (hop22 - e, n22)
             del self.ending[slot]
@@ -139,5 +140,5 @@ class _ClientRate:
                 self.out_drain.discard(slot)
                 self.out_wait.discard(slot)                    # (a stream that ended before its frame 0 came out)
         n = k * self.spf
-        counts = rs.push_raw(self.wav_ptr, n, n, self.cwav.data_ptr(), self.cwav.shape[1], 0, self.stream.cuda_stream)
+        counts = rs.push_raw(self.wav_ptr, n, n, _abi.addr(self.cwav, PCM_DTYPES[self.fmt]), self.cwav.shape[1], 0, self.stream.cuda_stream)
         return self.cwav[:, :-(-n * rs.up // rs.down)], torch.tensor(counts, dtype=torch.int64)

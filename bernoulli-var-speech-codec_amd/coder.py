@@ -1,0 +1,189 @@
+"""The two sub-operators the reference exposes as attributes of its facade: ``BVRNN`` (``model.bvrnn.encode/decode``, bvrnn.py:163-229)
+and ``BigVGAN`` (``model.vocoder(x, length)``, models.py:207-238), each on the engines of the model it is a part of."""
+import torch
+
+from ._abi import ptr
+from .engine import _OnDevice, _prep, _trimmed
+from .vbr_args import _check_cap_q8, _check_ladder
+
+
+def _broadcast_target(target, B, T, device):
+    """A scalar, (B,) or (B,T) distortion target as a contiguous float32 (B,T) tensor on ``device``."""
+    t = torch.as_tensor(target, dtype=torch.float32).detach()
+    if t.dim() == 0:
+        t = t.reshape(1, 1)
+    elif tuple(t.shape) == (B,) and t.dim() == 1:
+        t = t.reshape(B, 1)
+    elif tuple(t.shape) != (B, T):
+        raise ValueError(f"encode_vbr: target must be a scalar, ({B},) or ({B}, {T}), got {tuple(t.shape)}")
+    return t.to(device).expand(B, T).contiguous()
+
+
+class BVRNN(_OnDevice):
+    """``BVRNN.encode`` / ``BVRNN.decode`` (bvrnn.py:163-229) on the HIP recurrent kernels."""
+
+    def __init__(self, conf, tensors, shared=None):
+        super().__init__(conf, tensors, shared)
+        self.h_dim, self.z_dim, self.x_dim = conf["h_dim"], conf["z_dim"], conf["num_mels"]
+        self.varBit = bool(conf["var_bit"])
+
+    @torch.no_grad()
+    def forward(self, y, p_use_gen, greedy, varBitrate, *, r=None, noise=None, return_all=False):
+        """``BVRNN.forward(y, p_use_gen, greedy, varBitrate)`` (bvrnn.py:86-160), forward values only (this build
+        has no autograd): stochastic Bernoulli sampler ``round(u - 0.5 + enc_t)``, prior net, KL term and the
+        teacher-forcing mix.  Returns (all_dec_mean (B,T,x_dim), kld scalar) like the reference.
+
+        Randomness: the reference draws, per frame, ``torch.rand([])`` (compared with p_use_gen) and - unless
+        greedy - ``torch.rand_like(enc_t)``.  By default the same numbers are drawn here, in the same order, from
+        torch's global CPU generator, so ``torch.manual_seed(s)`` followed by this call reproduces the reference
+        run on CPU after the same seed.  ``r`` (T,) / ``noise`` (B,T,z_dim) override them.
+        ``return_all=True`` adds a dict with z (forward value of the sample), prob (enc_t), prior, kld_frames."""
+        eng, out_dev, y = self._enter(y)
+        B, T, _ = y.shape
+        if r is None or (noise is None and not greedy):
+            rs, ns = [], []
+            for _ in range(T):                                    # the reference's draw order (bvrnn.py:111,126)
+                rs.append(torch.rand([]))
+                if not greedy:
+                    ns.append(torch.rand(B, self.z_dim))
+            r = torch.stack(rs) if r is None else r
+            if not greedy and noise is None:
+                noise = torch.stack(ns, 1)
+        use_gen = (torch.as_tensor(r).detach().cpu().float() < p_use_gen).to(torch.uint8).contiguous()
+        assert use_gen.numel() == T
+        bits = _prep(varBitrate, eng.device) if (varBitrate is not None and self.varBit) else None
+        un = None if greedy else _prep(noise, eng.device)
+        dec = torch.empty(B, T, self.x_dim, device=eng.device)
+        kld = torch.empty(T, device=eng.device)
+        extra = {k: torch.empty(B, T, self.z_dim, device=eng.device) for k in ("z", "prob", "prior")} if return_all else {}
+        eng.call("bvc_bvrnn_forward", eng.handle, ptr(y), ptr(bits), ptr(use_gen, torch.uint8), int(p_use_gen < 1), int(p_use_gen > 0),
+                 ptr(un), B, T, ptr(dec), ptr(kld), ptr(extra.get("z")), ptr(extra.get("prob")), ptr(extra.get("prior")), scratch=(B, T))
+        if return_all:
+            extra["kld_frames"] = kld
+        # torch.mean(torch.stack(kld_loss)), bvrnn.py:160
+        out = eng.to_caller(out_dev, dec, torch.mean(kld), *extra.values(), poll=False)
+        return out[:2] + (dict(zip(extra, out[2:])),) if return_all else out
+
+    def _encode(self, y, varBitrate, h, want_all_h=False, want_h_next=False, want_prob=False):
+        """``bvc_bvrnn_encode``: the codes and those of its three optional outputs that are asked for, in the order of the arguments."""
+        eng, out_dev, y = self._enter(y)
+        B, T, _ = y.shape
+        bits = _prep(varBitrate, eng.device) if varBitrate is not None else None
+        h0 = _prep(h.reshape(B, self.h_dim), eng.device)
+        codes = torch.empty(B, T, self.z_dim, device=eng.device)
+        all_h = torch.empty(B, T, self.h_dim, device=eng.device) if want_all_h else None
+        hT = torch.empty(B, self.h_dim, device=eng.device) if want_h_next else None
+        prob = torch.empty(B, T, self.z_dim, device=eng.device) if want_prob else None
+        eng.call("bvc_bvrnn_encode", eng.handle, ptr(y), ptr(bits), ptr(h0), B, T, ptr(codes), ptr(all_h), ptr(hT), ptr(prob),
+                 scratch=(B, T))
+        outs = [codes] + ([all_h] if want_all_h else []) + ([hT.unsqueeze(0)] if want_h_next else []) + ([prob] if want_prob else [])
+        return eng.to_caller(out_dev, *outs)
+
+    @torch.no_grad()
+    def encode(self, y, varBitrate, h, return_prob=False):
+        """y (B,T,x_dim), varBitrate (B,T) bits/frame, h (1,B,h_dim) -> (codes (B,T,z), all_h (B,T,h))."""
+        return self._encode(y, varBitrate, h, want_all_h=True, want_prob=return_prob)
+
+    @torch.no_grad()
+    def encode_stateful(self, y, varBitrate, h):
+        """Like encode() but returns the state AFTER the last frame instead of the per-frame states:
+        (codes (B,T,z), h_next (1,B,h_dim)).  This is what chunked / streaming encoding needs (the
+        reference's encode() only exposes the state before each frame, bvrnn.py:205,209)."""
+        return self._encode(y, varBitrate, h, want_h_next=True)
+
+    @torch.no_grad()
+    def encode_vbr(self, y, ladder, target, h, return_all=False, rate_q8=None, burst_q8=None, tok=None):
+        """``encode`` with the bits of every frame chosen inside the frame (``bvc_bvrnn_encode_vbr``): y (B,T,x_dim), ``ladder`` up to 8
+        ascending bit counts, ``target`` a scalar, (B,) or (B,T) bound on the mean absolute log-mel error of the frame as the receiver
+        will decode it, h (1,B,h_dim).  A frame gets the first rung of the ladder that meets its target, the last one if none does.
+        Returns (codes (B,T,z), bits (B,T), all_h (B,T,h)); ``return_all=True`` adds a dict with prob (B,T,z), dist (B,T,K) - the error
+        of every rung -, dec (B,T,x_dim) - the chosen rung's decoded mel - and h_next (1,B,h_dim).
+
+        ``rate_q8`` and ``burst_q8`` (ints, 1/256 bit; both or neither) put a token bucket per row under the choice
+        (``bvc_bvrnn_encode_vbr_capped``): per frame tok = min(burst_q8, tok + rate_q8), the frame gets the lower of its rung and the
+        highest rung with ladder[k] * 256 <= tok (rung 0 if none), tok = max(0, tok - 256 bits).  ``tok`` (B,) int32: the buckets in
+        front of the first frame (None: full); the dict then carries ``tok_next`` (B,) int32, which the next chunk takes as ``tok``."""
+        lad, K = _check_ladder(ladder, self.z_dim, self.varBit)
+        capped = rate_q8 is not None or burst_q8 is not None
+        if capped:
+            rate_q8, burst_q8 = _check_cap_q8(list(lad), rate_q8, burst_q8)
+        elif tok is not None:
+            raise ValueError("encode_vbr: tok without rate_q8 and burst_q8")
+        if y.dim() != 3:
+            raise ValueError("encode_vbr: y must be (B, T, num_mels)")
+        B, T, _ = y.shape
+        tau = _broadcast_target(target, B, T, "cpu")
+        eng, out_dev, y = self._enter(y)
+        tau = tau.to(eng.device)
+        h0 = _prep(h.reshape(B, self.h_dim), eng.device)
+        codes = torch.empty(B, T, self.z_dim, device=eng.device)
+        bits = torch.empty(B, T, device=eng.device)
+        all_h = torch.empty(B, T, self.h_dim, device=eng.device)
+        extra = {}
+        if return_all:
+            extra = {"prob": torch.empty(B, T, self.z_dim, device=eng.device), "dist": torch.empty(B, T, K, device=eng.device),
+                     "dec": torch.empty(B, T, self.x_dim, device=eng.device), "h_next": torch.empty(B, self.h_dim, device=eng.device)}
+        args = (eng.handle, ptr(y), ptr(tau), lad, K, ptr(h0), B, T, ptr(codes), ptr(bits), ptr(all_h), ptr(extra.get("h_next")),
+                ptr(extra.get("prob")), ptr(extra.get("dist")), ptr(extra.get("dec")))
+        if capped:
+            tok0 = None
+            if tok is not None:
+                tok0 = torch.as_tensor(tok).detach().to(device=eng.device, dtype=torch.int32).contiguous()
+                if tuple(tok0.shape) != (B,):
+                    raise ValueError(f"encode_vbr: tok must be ({B},), got {tuple(tok0.shape)}")
+            tok_next = torch.empty(B, dtype=torch.int32, device=eng.device)
+            eng.call("bvc_bvrnn_encode_vbr_capped", *args, scratch=(B, T, K),
+                     after=(rate_q8, burst_q8, ptr(tok0, torch.int32), ptr(tok_next, torch.int32)))
+        else:
+            eng.call("bvc_bvrnn_encode_vbr", *args, scratch=(B, T, K))
+        if return_all:
+            extra["h_next"] = extra["h_next"].unsqueeze(0)
+            if capped:
+                extra["tok_next"] = tok_next
+        out = eng.to_caller(out_dev, codes, bits, all_h, *extra.values())
+        return out[:3] + (dict(zip(extra, out[3:])),) if return_all else out
+
+    @torch.no_grad()
+    def decode(self, z, h, present=None, bits=None, return_codes=False):
+        """z (B,T,z_dim), h (1,B,h_dim) -> (mel (B,T,x_dim), h (1,B,h_dim)).
+
+        ``present`` (B,T) turns concealment on (``bvc_bvrnn_decode_conceal``): a frame whose entry is 0 did not arrive and is generated
+        from the prior net at the decoder's own state - round(prior(h_t)), masked to ``bits[b, t]`` leading bits on a variable-rate
+        model (``bits`` (B,T) is then required) - whatever ``z`` holds there.  ``return_codes=True`` adds the codes with the gaps
+        filled and the prior's probabilities of every frame: (mel, h, codes_out, prior)."""
+        if present is None:
+            if return_codes or bits is not None:
+                raise ValueError("decode: bits / return_codes belong to concealment (pass present)")
+        elif self.varBit and bits is None:
+            raise ValueError("decode: a variable-rate model needs bits (B,T) to generate lost frames")
+        elif z.dim() != 3 or tuple(present.shape) != tuple(z.shape[:2]) or (bits is not None and tuple(bits.shape) != tuple(z.shape[:2])):
+            raise ValueError("decode: z (B,T,z_dim) with present (B,T) and bits (B,T)")
+        eng, out_dev, z = self._enter(z)
+        B, T, _ = z.shape
+        h0 = _prep(h.reshape(B, self.h_dim), eng.device)
+        mel = torch.empty(B, T, self.x_dim, device=eng.device)
+        hT = torch.empty(B, self.h_dim, device=eng.device)
+        if present is None:
+            eng.call("bvc_bvrnn_decode", eng.handle, ptr(z), ptr(h0), B, T, ptr(mel), ptr(hT), scratch=(B, T))
+            return eng.to_caller(out_dev, mel, hT.unsqueeze(0))
+        pres = present.detach().to(eng.device).ne(0).to(torch.uint8).contiguous()
+        d_bits = _prep(bits, eng.device) if (bits is not None and self.varBit) else None
+        codes = torch.empty(B, T, self.z_dim, device=eng.device) if return_codes else None
+        prior = torch.empty(B, T, self.z_dim, device=eng.device) if return_codes else None
+        eng.call("bvc_bvrnn_decode_conceal", eng.handle, ptr(z), ptr(pres, torch.uint8), ptr(d_bits), ptr(h0), B, T, ptr(mel), ptr(hT),
+                 ptr(codes), ptr(prior), scratch=(B, T))
+        return eng.to_caller(out_dev, mel, hT.unsqueeze(0), *((codes, prior) if return_codes else ()))
+
+
+class BigVGAN(_OnDevice):
+    """``BigVGAN.forward(x, length)`` (models.py:207-238): x (B, num_mels, T) -> (B, 1, n)."""
+
+    @torch.no_grad()
+    def forward(self, x, length, _scale_div=1.0, _time_major=False):
+        eng, out_dev, mel = self._enter(x if _time_major else x.permute(0, 2, 1))        # kernels are time-major
+        B, T, _ = mel.shape
+        n = _trimmed(eng.vocoder_length(T), length)
+        wav = torch.empty(B, n, device=eng.device)
+        if n:
+            eng.call("bvc_bigvgan", eng.handle, ptr(mel), B, T, n, float(_scale_div), ptr(wav), scratch=(B, T))
+        return eng.to_caller(out_dev, wav.unsqueeze(1), poll=False)

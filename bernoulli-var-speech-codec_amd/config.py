@@ -84,6 +84,15 @@ def not_causal_message(conf):
     return NOT_CAUSAL if is_antialiased(conf) else NOT_CAUSAL_SYM
 
 
+def num_frames(conf, L):
+    """Frames the front-end makes of L samples, the count ``bvc_num_frames`` gives; 0 where a reflect padding is not shorter than the
+    signal (the library answers BVC_EINVAL there)."""
+    pr = conf["winsize"] - conf["mel_pad_left"] - conf["hopsize"]
+    if L <= conf["mel_pad_left"] or L <= pr:
+        return 0
+    return (L + conf["mel_pad_left"] + pr - conf["winsize"]) // conf["hopsize"] + 1
+
+
 def generator_length(conf, T, stages=False):
     """Samples the generator makes of T frames: L_0 = T, L_{i+1} = L_i * u_i behind a symmetric upsampler (ConvTranspose1d with
     padding (k - u) / 2, k = 2u), (L_i + 1) * u_i behind a causal one.  ``stages``: the list of the stage lengths instead."""

@@ -6,7 +6,6 @@ The low-pass design restates scipy's defaults (``firwin(2*10*max(up,down)+1, 1/m
 window=('kaiser', 5.0))``, unit DC gain, scaled by ``up``, zero-padded so the output is centred) in numpy
 float64; the filtering itself (upfirdn + slicing) runs in ``bvc_resample_poly`` on the GPU.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -53,7 +52,7 @@ def resample_poly(x, up, down):
     y = torch.empty(B, n_out, device=x.device)
     lib = _abi.load()
     with torch.cuda.device(x.device):
-        _abi.check(lib.bvc_resample_poly(_abi.ptr(x), B, L, ctypes.c_void_p(hd.data_ptr()), len(h), up, down,
+        _abi.check(lib.bvc_resample_poly(_abi.ptr(x), B, L, _abi.ptr(hd, torch.float64), len(h), up, down,
                                          n_pre_remove, _abi.ptr(y), n_out, _abi.current_stream(x.device)))
     return y
 

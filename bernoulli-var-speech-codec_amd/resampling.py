@@ -106,7 +106,8 @@ class StreamResampler:
         if self._out is None:
             self._out = torch.empty(self.B, max(1, self.max_out), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
         with torch.cuda.device(self.dev):
-            counts = self.push_raw(x.data_ptr() if n else self._out.data_ptr(), max(n, 1), n, self._out.data_ptr(), self._out.shape[1], 0,
+            out = _abi.addr(self._out, PCM_DTYPES[self.fmt_out])
+            counts = self.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt_in]) if n else out, max(n, 1), n, out, self._out.shape[1], 0,
                                    torch.cuda.current_stream(self.dev).cuda_stream)
         return self._out[:, :-(-n * self.up // self.down)], torch.tensor(counts, dtype=torch.int64)
 
@@ -115,5 +116,5 @@ class StreamResampler:
         """The rest of the row's outputs (at most ``lag`` samples, a new tensor); the row is idle afterwards."""
         y = torch.empty(max(1, self.lag), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
         with torch.cuda.device(self.dev):
-            n = self.flush_raw(row, y.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream)
+            n = self.flush_raw(row, _abi.addr(y, PCM_DTYPES[self.fmt_out]), torch.cuda.current_stream(self.dev).cuda_stream)
         return y[:n]

@@ -97,27 +97,23 @@ class VocoderStream:
         self.kmax = max_frames_per_push
         self.spf = math.prod(engine.conf["vocoder_config"]["upsample_rates"])
         self.handle = _abi.Handle(engine.lib.bvc_vocoder_stream_destroy, engine)
-        with torch.cuda.device(engine.device):
-            _abi.check(engine.lib.bvc_vocoder_stream_create(engine.handle, batch, max_frames_per_push, ctypes.byref(self.handle)))
+        engine.call("bvc_vocoder_stream_create", engine.handle, batch, max_frames_per_push, ctypes.byref(self.handle), stream=False)
 
     def reset(self):
-        with torch.cuda.device(self.eng.device):
-            _abi.check(self.eng.lib.bvc_vocoder_stream_reset(self.handle, self.eng.stream()))
+        self.eng.call("bvc_vocoder_stream_reset", self.handle)
 
     def push(self, mel, scale_div=1.0):
         """mel (B, k, num_mels) time-major on the engine's device -> wav (B, k*256)."""
         B, k, _ = mel.shape
         assert B == self.B
         out = torch.empty(B, k * self.spf, device=self.eng.device)
-        with torch.cuda.device(self.eng.device):
-            for f in range(0, k, self.kmax):                   # longer chunks go through in kmax-frame pieces
-                n = min(self.kmax, k - f)
-                piece = mel[:, f:f + n].contiguous()
-                dst = out if n == k else torch.empty(B, n * self.spf, device=self.eng.device)
-                _abi.check(self.eng.lib.bvc_vocoder_stream_push(self.handle, _abi.ptr(piece), n, float(scale_div),
-                                                                _abi.ptr(dst), self.eng.stream()))
-                if dst is not out:
-                    out[:, f * self.spf:(f + n) * self.spf] = dst
+        for f in range(0, k, self.kmax):                       # longer chunks go through in kmax-frame pieces
+            n = min(self.kmax, k - f)
+            piece = mel[:, f:f + n].contiguous()
+            dst = out if n == k else torch.empty(B, n * self.spf, device=self.eng.device)
+            self.eng.call("bvc_vocoder_stream_push", self.handle, _abi.ptr(piece), n, float(scale_div), _abi.ptr(dst))
+            if dst is not out:
+                out[:, f * self.spf:(f + n) * self.spf] = dst
         return out
 
 

@@ -18,6 +18,7 @@ from .resampling import (PCM_DELAYED, PCM_DTYPES, PCM_FORMATS, StreamResampler, 
 from .stream_chunked import StreamingDecoder, StreamingEncoder, VocoderStream  # noqa: F401
 from .stream_plans import (CONTEXT_FRAMES, client_finish_plan, client_hop, finish_plan, generator_reach, join_plan,  # noqa: F401
                            repair_plan)
+from .vbr_args import _check_ladder, cap_q8
 
 
 class _DeviceView:
@@ -151,7 +152,6 @@ class StreamingCodec:
         without a cap - or None for a session without it; ValueError for what the library would refuse."""
         if vbr is None or vbr is False:
             return None
-        from .model import _check_ladder, cap_q8
         conf = model.conf
         if not conf["var_bit"]:
             raise ValueError("vbr: a fixed-rate model (var_bit = false) has no bit mask to choose")
