@@ -124,6 +124,7 @@ SIGNATURES = {
     "bvc_test_linear_batched": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "bvc_test_tile_plan": (ctypes.c_int, [_i32, _i64, _i32, _i32, _i32, ctypes.POINTER(_i64)]),
     "bvc_test_snakebeta": (ctypes.c_int, [_vp, _i64, _f, _f, _vp, _vp]),
+    "bvc_test_stft_logmel": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i32, _f, _vp, _vp]),
     "bvc_test_vocoder_tap": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, ctypes.POINTER(_i64), _vp, _sz, _vp]),
     "bvc_test_vocoder_layer": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _i64, _i64, _i64,
                                               _f, ctypes.POINTER(_i64), _vp]),

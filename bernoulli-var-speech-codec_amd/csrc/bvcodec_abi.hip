@@ -581,6 +581,34 @@ int bvc_test_snakebeta(const float *d_x, int64_t n, float alpha, float beta, flo
     return launch_snakebeta_test(d_x, n, a, ib, d_y, (hipStream_t)stream);
 }
 
+int bvc_test_stft_logmel(const bvc_model *m, const float *d_wav, const int64_t *d_lengths, int32_t B, int64_t L, int64_t T,
+                         int32_t pad_left, float scale, float *d_mel, void *stream) {
+    // test helper (synchronises): ONE launch of the front-end with the caller's frame count and left padding.  The shape is checked
+    // first, on the host and without the model, so that a refusal can be had without a device.
+    const char *fn = "bvc_test_stft_logmel";
+    if (pad_left < 0 || pad_left > 768) { set_error("%s: pad_left %d outside [0, 768]", fn, pad_left); return BVC_EINVAL; }
+    if (T < 1) { set_error("%s: T = %lld, at least one frame", fn, (long long)T); return BVC_EINVAL; }
+    if (B < 1 || L < 1 || T > (int64_t)1 << 40) { set_error("%s: B = %d, L = %lld, T = %lld", fn, B, (long long)L, (long long)T); return BVC_EINVAL; }
+    // frame t reads the padded samples 256 t - pad_left + [0, 1024); one reflection maps i < 0 to -i and i >= L to 2 (L - 1) - i
+    const long long last = 256 * (long long)(T - 1) - pad_left + 1023;
+    if (pad_left >= L || last > 2 * ((long long)L - 1)) {
+        set_error("%s: T = %lld frames at pad_left = %d read the reflected sample %lld outside [0, L = %lld)", fn, (long long)T, pad_left,
+                  pad_left >= L ? (long long)pad_left : 2 * ((long long)L - 1) - last, (long long)L);
+        return BVC_EINVAL;
+    }
+    if (d_lengths && T > ragged_frames(L, L, pad_left)) {
+        set_error("%s: with lengths T = %lld exceeds the %lld frames of a full row", fn, (long long)T, ragged_frames(L, L, pad_left));
+        return BVC_EINVAL;
+    }
+    if (!m || !d_wav || !d_mel) { set_error("%s: null argument", fn); return BVC_EINVAL; }
+    if (int st_ = sticky_status(m)) return st_;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = launch_stft_logmel(m->fe, d_wav, B, L, T, pad_left, scale, d_mel, s, reinterpret_cast<const long long *>(d_lengths));
+    hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); rc = BVC_EHIP; }
+    return rc;
+}
+
 int bvc_test_vocoder_tap(const bvc_model *m, const float *d_mel, int32_t B, int64_t T, int32_t which, float *d_out,
                          int64_t *out_numel_per_batch, void *d_ws, size_t ws_bytes, void *stream) {
     Workspace w;

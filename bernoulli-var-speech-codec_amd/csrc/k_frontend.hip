@@ -104,13 +104,16 @@ __global__ __launch_bounds__(256) void stft_logmel_kernel(FrontendTables t, cons
             long long i0 = tt * 256 + 2 * m - pad_left, i1 = i0 + 1;
             i0 = i0 < 0 ? -i0 : (i0 >= Lr ? 2 * (Lr - 1) - i0 : i0);        // reflect, no edge repeat
             i1 = i1 < 0 ? -i1 : (i1 >= Lr ? 2 * (Lr - 1) - i1 : i1);
-            if (RAGGED && dead) {
-                v[n2].re = 0.0f;
-                v[n2].im = 0.0f;
-            } else {
-                v[n2].re = __fmul_rn(__fmul_rn(src[i0], scale), win0[n2]);
-                v[n2].im = __fmul_rn(__fmul_rn(src[i1], scale), win1[n2]);
+            // A dead frame reads nothing: its samples are zeros.  The choice is made on the SAMPLE, so that the products take the same
+            // path in both instantiations - a choice between the products and zero kept the compiler from fusing the window's
+            // multiplication into the first butterfly, which it does in the equal-length kernel: the two then differed in the last bit.
+            float s0 = 0.0f, s1 = 0.0f;
+            if (!(RAGGED && dead)) {
+                s0 = src[i0];
+                s1 = src[i1];
             }
+            v[n2].re = __fmul_rn(__fmul_rn(s0, scale), win0[n2]);
+            v[n2].im = __fmul_rn(__fmul_rn(s1, scale), win1[n2]);
         }
         // ---- pass 1: DFT over n2, twiddle W_512^(lane*k0), scatter to [k0][lane]
         dft8(v);

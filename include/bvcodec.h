@@ -620,6 +620,14 @@ int bvc_test_linear_batched(const float *d_x, const float *d_w, const float *d_b
  * out[6] = tile height, row blocks of that height (GEMM: of the first launch; AMP: tiles per batch item), height of the tail
  * launch's tiles (0: one launch), tiles, rounds, model cost in hundredths of a row. */
 int bvc_test_tile_plan(int32_t kind, int64_t rows, int32_t column_blocks, int32_t ks, int32_t mode, int64_t *out);
+/* ONE launch of the front-end kernel (synchronises) with the caller's frame count T and left padding instead of the model's:
+ * d_wav (B, L) -> d_mel (B, T, num_mels); frame t of a row reads its samples 256 t - pad_left + [0, 1024), reflected once at 0 and
+ * at the row's end.  d_lengths (B) int64 or NULL: the valid samples per row, as in bvc_encode_ragged (the row reflects at its own
+ * end, its frames behind that hold the log floor).  Refused with BVC_EINVAL, in this order and before the model is looked at:
+ * pad_left outside [0, 768]; T < 1; a T whose last frame reads a reflected sample outside [0, L); with d_lengths, a T above the
+ * frames of a full row. */
+int bvc_test_stft_logmel(const bvc_model *m, const float *d_wav, const int64_t *d_lengths, int32_t B, int64_t L, int64_t T,
+                         int32_t pad_left, float scale, float *d_mel, void *stream);
 /* dump of one vocoder intermediate, channels-last: which = 0 conv_pre, 1+2i up_i, 2+2i stage_i.
  * Runs the vocoder up to that point.  d_out (B, len, C); returns len*C via *out_numel_per_batch. */
 int bvc_test_vocoder_tap(const bvc_model *m, const float *d_mel, int32_t B, int64_t T, int32_t which,

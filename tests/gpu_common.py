@@ -11,14 +11,17 @@ _CACHE = {}
 DEV = "cuda:0"
 
 
-def make_model(var_bit=True, h_dim=1024, seed=1234, env=None, mel_stats=None, gains=None, pinned=None, z_dim=None):
+def make_model(var_bit=True, h_dim=1024, seed=1234, env=None, mel_stats=None, gains=None, pinned=None, z_dim=None, frontend=None):
     """Product model on cuda:0 with seeded synthetic checkpoints (+ the matching oracle state dicts).
     env: extra environment variables that are read when the engine is created (BVC_NO_GRAPH, ...).
     gains: synth.bvrnn_state_dict's (g_hidden, g_out, g_gru).  pinned: a name of bvrnn_draws.PINNED - that edit of the coder's
     state dict (one layer's weight zeroed, its bias from a table) is what the model and the returned state dict hold.
-    z_dim: None = the config's own (64)."""
+    z_dim: None = the config's own (64).  frontend: a dict with some of fs, fmin, fmax, mel_pad_left - the front end's keys set to
+    these values."""
     gains = None if gains is None else tuple(float(g) for g in gains)
-    key = (var_bit, h_dim, seed, tuple(sorted((env or {}).items())), mel_stats, gains, pinned, z_dim)
+    frontend = {k: v for k, v in (frontend or {}).items() if v is not None}
+    assert set(frontend) <= {"fs", "fmin", "fmax", "mel_pad_left"}, frontend
+    key = (var_bit, h_dim, seed, tuple(sorted((env or {}).items())), mel_stats, gains, pinned, z_dim, tuple(sorted(frontend.items())))
     if key in _CACHE:
         return _CACHE[key]
     base = config.DEFAULT_CONFIG if var_bit else config.DEFAULT_CONFIG_64BIT
@@ -26,13 +29,17 @@ def make_model(var_bit=True, h_dim=1024, seed=1234, env=None, mel_stats=None, ga
     d = tempfile.mkdtemp(prefix="bvc_test_")
     cfg_path = base
     z_dim = conf["z_dim"] if z_dim is None else z_dim
-    if h_dim != conf["h_dim"] or z_dim != conf["z_dim"]:
+    if h_dim != conf["h_dim"] or z_dim != conf["z_dim"] or any(conf[k] != v for k, v in frontend.items()):
         cfg_path = os.path.join(d, "cfg.toml")
         with open(base) as f:
             txt = f.read()
         assert txt.count("h_dim = 1024") == 1 and txt.count("z_dim = 64") == 1
         txt = txt.replace("h_dim = 1024", f"h_dim = {h_dim}").replace("z_dim = 64", f"z_dim = {z_dim}")
         conf["h_dim"], conf["z_dim"] = h_dim, z_dim
+        for k, v in frontend.items():
+            assert txt.count(f"\n{k} = {conf[k]}\n") == 1, k
+            txt = txt.replace(f"\n{k} = {conf[k]}\n", f"\n{k} = {v}\n")
+            conf[k] = v
         with open(cfg_path, "w") as f:
             f.write(txt)
     p1, p2 = synth.write_checkpoints(conf, d, seed=seed, mel_stats=mel_stats, gains=gains)
