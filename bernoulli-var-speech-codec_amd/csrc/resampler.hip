@@ -44,7 +44,7 @@ double i0_small(double x) {
     return std::exp(x) * (0.5 * (b0 - b2));
 }
 
-// numpy's add.reduce over a contiguous float64 array (pairwise, blocks of 128 with eight partial sums)
+// numpy's pairwise sum, the inner loop of add.reduce over contiguous float64 (blocks of 128 with eight partial sums)
 double pairwise_sum(const double *a, long long n) {
 #pragma clang fp contract(off)
     if (n < 8) {
@@ -65,6 +65,16 @@ double pairwise_sum(const double *a, long long n) {
     long long n2 = n / 2;
     n2 -= n2 % 8;
     return pairwise_sum(a, n2) + pairwise_sum(a + n2, n - n2);
+}
+
+// numpy's sum of a contiguous float64 array: the reduction hands its inner loop 8192 elements at a time (numpy's buffer size), so
+// the pairwise sums of those blocks are added up from left to right; up to 8192 elements it is one pairwise sum
+double numpy_sum(const double *a, long long n) {
+#pragma clang fp contract(off)
+    const long long block = 8192;
+    double res = 0.0;
+    for (long long i = 0; i < n; i += block) res += pairwise_sum(a + i, n - i < block ? n - i : block);
+    return res;
 }
 
 // h (g.ntaps doubles): n_pre_pad zeros, then firwin(2 half_len + 1, 1 / max_rate, window=("kaiser", 5.0)) * up, as preprocess.design
@@ -90,7 +100,7 @@ void design_taps(const Geometry &g, double *h) {
         const double kaiser = i0_small(std::fabs(beta * std::sqrt(1.0 - q * q))) / i0_beta;
         w[i] = cutoff * sinc * kaiser;
     }
-    const double sum = pairwise_sum(w, numtaps);
+    const double sum = numpy_sum(w, numtaps);
     for (int i = 0; i < numtaps; ++i) w[i] = w[i] / sum * (double)g.up;
 }
 

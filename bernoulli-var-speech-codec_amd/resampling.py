@@ -68,7 +68,7 @@ class StreamResampler:
         with torch.cuda.device(self.dev):
             _abi.check_arg(self.lib.bvc_resampler_create(batch, self.rate_in, self.rate_out, self.max_in, PCM_FORMATS[fmt_in],
                                                          PCM_FORMATS[fmt_out] | (PCM_DELAYED if delayed else 0), ctypes.byref(h)))
-            if self.up != self.down:        # the offline call's taps are numpy's: hand them in, whatever the C library's exp and sin round to
+            if self.up != self.down:        # the offline call's taps are preprocess.design's: hand them in (the library designs the same ones)
                 taps = taps.astype("float64")
                 _abi.check_arg(self.lib.bvc_resampler_set_taps(h, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(taps)))
         self._counts = (ctypes.c_int32 * batch)()

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from resample_cases import ChunkedWalk, offline_walk
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FS = 22050
 RATES = (8000, 16000, 24000, 32000, 44100, 48000)
@@ -49,9 +51,9 @@ def test_counts_equal_brute_force(rate_in, rate_out):
 
 @pytest.mark.parametrize("rate_in,rate_out", PAIRS + [(FS, FS)])
 def test_lag_history_and_taps_equal_the_numpy_design(rate_in, rate_out):
-    """bvc_resampler_lag gives preprocess.design's n_pre_remove and ceil(ntaps / up); the library's own taps are that design's to the
-    rounding of exp, sin and sqrt (numpy's exp is not the C library's: a few units in the last place of taps of size <= 1) - which is why
-    StreamResampler hands numpy's taps in."""
+    """bvc_resampler_lag gives preprocess.design's n_pre_remove and ceil(ntaps / up); the library's own taps are that design's within a few
+    units in the last place of taps of size <= 1 (test_resample_cases_cpu.py holds them to equality at the rates it adds: both designs
+    call the C library's exp and sin)."""
     from bvcodec import _abi
     from bvcodec.streaming import resampler_lag
     up, down, taps, lag = geometry(rate_in, rate_out)
@@ -81,70 +83,7 @@ def test_lag_of_the_usual_rates():
 
 
 # ---------------------------------------------------------------------------------------------- the order of the sum
-def offline_walk(x, up, down, h, lag):
-    """resample_poly_kernel's walk (csrc/k_frontend.hip) in numpy float64."""
-    n_out = -(-len(x) * up // down)
-    y = np.zeros(n_out)
-    for m in range(n_out):
-        pos = (m + lag) * down
-        i, k = pos // up, pos % up
-        if i >= len(x):
-            k += (i - (len(x) - 1)) * up
-            i = len(x) - 1
-        acc = 0.0
-        while k < len(h) and i >= 0:
-            acc += h[k] * x[i]
-            k += up
-            i -= 1
-        y[m] = acc
-    return y
-
-
-class ChunkedWalk:
-    """resample_stream_kernel's walk (csrc/k_resample_stream.hip) for one row in numpy float64: the history of ceil(ntaps / up) inputs
-    and the chunk side by side, the outputs E(N) .. E(N + n) of a push, the rest with a clamp at the end in a flush."""
-
-    def __init__(self, rate_in, rate_out):
-        self.rates = (rate_in, rate_out)
-        self.up, self.down, self.h, self.lag = geometry(rate_in, rate_out)
-        self.H = -(-len(self.h) // self.up)
-        self.reset()
-
-    def reset(self):
-        self.hist, self.N = np.zeros(self.H), 0
-
-    def E(self, n):
-        from bvcodec.streaming import resampler_count
-        return resampler_count(*self.rates, n)
-
-    def outputs(self, staged, N1, m0, m1):
-        out = []
-        lo = max(0, self.N - self.H)
-        for m in range(m0, m1):
-            pos = (m + self.lag) * self.down
-            i, k = pos // self.up, pos % self.up
-            if i >= N1:
-                k += (i - (N1 - 1)) * self.up
-                i = N1 - 1
-            acc = 0.0
-            while k < len(self.h) and i >= lo:
-                acc += self.h[k] * staged[i - self.N + self.H]
-                k += self.up
-                i -= 1
-            out.append(acc)
-        return out
-
-    def push(self, chunk):
-        staged = np.concatenate([self.hist, chunk])
-        N1 = self.N + len(chunk)
-        out = self.outputs(staged, N1, self.E(self.N), self.E(N1))
-        self.hist, self.N = staged[len(chunk):], N1
-        return out
-
-    def flush(self):
-        return self.outputs(self.hist, self.N, self.E(self.N), -(-self.N * self.up // self.down))
-
-
+# (offline_walk and ChunkedWalk, the two kernels' walks in numpy float64, are resample_cases.py's)
 @pytest.mark.parametrize("rate_in,rate_out", PAIRS)
 def test_chunked_sum_equals_offline_sum(rate_in, rate_out):
     """Ragged chunks (1, 7, a hop, three hops and 5 samples) with a reset in the middle: every stream's chunked outputs are the offline
