@@ -104,7 +104,7 @@ def generator_length(conf, T, stages=False):
     return out if stages else L
 
 
-GENERATOR_WIDTHS = (16, 32, 64, 128, 256, 512)     # vocoder_config.upsample_initial_channel (check_config in csrc/model.hip)
+GENERATOR_WIDTHS = (16, 32, 64, 128, 256, 512)     # vocoder_config.upsample_initial_channel (check_config in csrc/model_build.hip)
 FINAL_CHANNELS = (8, 16, 32)                       # channels in front of conv_post: the width halved once per upsampling stage
 WIDEST_SWITCHED_STAGE = 64                         # layers_sym / layers_antialias: stages of more channels have the causal kernels only
 

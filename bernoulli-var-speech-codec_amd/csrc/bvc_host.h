@@ -1,5 +1,6 @@
-// Host side of libbvcodec_hip.so, shared by its sources model.hip, recurrence.hip, step_plan.hip, flow_launch.hip, generator.hip,
-// stream_codec.hip and bvcodec_abi.hip (what only the three sources of the recurrence share is in recurrence.h): the model, the workspace layout, the GEMM parameter helpers, the drivers of the offline paths and the state that
+// Host side of libbvcodec_hip.so, shared by its sources model_build.hip, model.hip, recurrence.hip, step_plan.hip, flow_launch.hip,
+// generator.hip, stream_codec.hip and bvcodec_abi.hip (what only the three sources of the recurrence share is in recurrence.h; the
+// arithmetic behind every uploaded weight is weight_pack.h, which model_build.hip alone includes): the model, the workspace layout, the GEMM parameter helpers, the drivers of the offline paths and the state that
 // crosses a file boundary.  Host only.  What more than one source uses lives in namespace bvc, next to the launchers of
 // bvc_internal.h; everything else is local to its file.
 #pragma once
@@ -157,6 +158,10 @@ struct KProbe {
 extern KProbe g_kprobe;
 
 // ---- workspace layout ---------------------------------------------------------------------------
+// n rounded up to a multiple of 16: the rows of a fragment-packed matrix of n utterances (whole 16-row tiles), the bytes of a ring slot
+template <typename T>
+inline T pad16(T rows) { return (rows + 15) / 16 * 16; }
+
 struct Workspace {
     // encode
     float *yn, *pxA, *pxB, *pxC;
@@ -181,7 +186,12 @@ int sticky_status(const bvc_model *m);
 int need_prior(const bvc_model *m, const char *fn);
 extern const char *const NOT_CAUSAL;
 const char *not_causal(const bvc_model *m);     // why a noncausal model is refused: NOT_CAUSAL for a filtered one, else the symmetric text
+int build_flow(bvc_model *m);                   // at model creation: is the model laid out for the persistent kernel?  With the first census
 int flow_census(const bvc_model *m);
+// The environment switches of the model, read by model_switches() alone (model_build.hip, which names them and says when each is read).
+// The first eight as the model keeps them (bvc_model_create); the last two are the residency census's
+struct ModelSwitches { bool use_graph, side_branch, fused_amp, precomp, decode_fold, encode_fold; int mtw, recurrence; bool census_oversubscribe, quiet; };
+ModelSwitches model_switches();
 
 // ---- GEMM parameters ----------------------------------------------------------------------------
 inline GemmSeg mkseg(DynPtr x, const float *w, int wnb, int K, int grp) { return GemmSeg{w, wnb, K, x, grp, 0}; }

@@ -1,5 +1,5 @@
 // C ABI of libbvcodec_hip.so (include/bvcodec.h): the error text, the two probe systems, the offline entry points, the small
-// utilities and the test hooks.  Host-side only: the model is in model.hip, the recurrence in recurrence.hip, step_plan.hip and flow_launch.hip, the generator in
+// utilities and the test hooks.  Host-side only: the model is made in model_build.hip (from what weight_pack.h computes) and used through model.hip, the recurrence is in recurrence.hip, step_plan.hip and flow_launch.hip, the generator in
 // generator.hip, the streaming session in stream_codec.hip and the kernels in k_*.hip.
 #include <cmath>
 #include <cstdarg>

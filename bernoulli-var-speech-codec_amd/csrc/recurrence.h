@@ -6,9 +6,6 @@
 
 namespace bvc {
 
-// rows of a fragment-packed matrix of B utterances: whole 16-row tiles
-inline int pad16(int rows) { return (rows + 15) / 16 * 16; }
-
 // Is this stream being captured?  CAP_FAILED: the query itself failed - the HIP error stays pending for the site to clear
 // (hipGetLastError) where it goes on; with `report` it is written to the error text as BVC_HIP_TRY does, for a site that returns BVC_EHIP.
 enum Capture { CAP_NONE = 0, CAP_ACTIVE = 1, CAP_FAILED = 2 };

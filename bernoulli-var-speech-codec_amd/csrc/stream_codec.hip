@@ -954,10 +954,9 @@ int bvc_stream_codec_set_repair(bvc_stream_codec *st, int32_t window_frames) {
     // tick, so the recurrences find their workspace in the session's own.
     const bvc_config &c = st->m->cfg;
     const int W = window_frames, B = st->B, kmax = st->kmax, Tm = W + kmax - 1;
-    auto up16 = [](long long n) { return (n + 15) / 16 * 16; };
     bvc_stream_codec::RepairWindow rw;                       // built aside: whatever fails, it goes with what it got and the session is as before
     rw.w = rw.n = W;
-    rw.hs = (long long)B * c.h_dim; rw.pks = up16((long long)B * kmax * st->bpf); rw.prs = up16((long long)B * kmax); rw.bs = (long long)B * kmax;
+    rw.hs = (long long)B * c.h_dim; rw.pks = pad16((long long)B * kmax * st->bpf); rw.prs = pad16((long long)B * kmax); rw.bs = (long long)B * kmax;
     PoolLayout pl;
     const size_t o_h = pl.take((size_t)W * rw.hs * 4), o_pk = pl.take((size_t)W * rw.pks), o_pr = pl.take((size_t)W * rw.prs), o_bits = pl.take((size_t)W * rw.bs * 4),
                  o_rh = pl.take((size_t)rw.hs * 4), o_rpk = pl.take((size_t)B * Tm * st->bpf), o_rpr = pl.take((size_t)B * Tm), o_rbits = pl.take((size_t)B * Tm * 4),

@@ -48,7 +48,7 @@ def bank(name):
 
 
 def bank_tables(b):
-    """(kmax, empty filters, largest weight of bin 512), as build_frontend (csrc/model.hip) would find them."""
+    """(kmax, empty filters, largest weight of bin 512), as build_frontend (csrc/model_build.hip) would find them."""
     nz = b != 0
     cols = np.nonzero(nz.any(axis=0))[0]
     return int(cols.max()) + 1, int((~nz.any(axis=1)).sum()), float(b[:, N_FFT // 2].max())
