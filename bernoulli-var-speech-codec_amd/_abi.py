@@ -60,6 +60,10 @@ SIGNATURES = {
     "bvc_vocoder_stream_destroy": (None, [_vp]),
     "bvc_vocoder_stream_reset": (ctypes.c_int, [_vp, _vp]),
     "bvc_vocoder_stream_push": (ctypes.c_int, [_vp, _vp, _i32, _f, _vp, _vp]),
+    "bvc_vocoder_lookahead": (_i64, [_vp]),
+    "bvc_vocoder_stream_create_lookahead": (ctypes.c_int, [_vp, _i32, _i32, ctypes.POINTER(_vp)]),
+    "bvc_vocoder_stream_samples": (_i64, [_vp, _i32]),
+    "bvc_vocoder_stream_flush": (ctypes.c_int, [_vp, _f, _vp, _vp]),
     "bvc_stream_codec_create": (ctypes.c_int, [_vp, _i32, _i32, _f, _f, _f, ctypes.POINTER(_vp)]),
     "bvc_stream_codec_destroy": (None, [_vp]),
     "bvc_stream_codec_buffers": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i32)]),
@@ -128,6 +132,8 @@ SIGNATURES = {
     "bvc_test_vocoder_tap": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, ctypes.POINTER(_i64), _vp, _sz, _vp]),
     "bvc_test_vocoder_layer": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _i64, _i64, _i64,
                                               _f, ctypes.POINTER(_i64), _vp]),
+    "bvc_test_amp_pair_window": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _i64, _i64, _i64,
+                                                ctypes.POINTER(_i64), _vp]),
 }
 
 _lib = None

@@ -104,6 +104,38 @@ def generator_length(conf, T, stages=False):
     return out if stages else L
 
 
+def stream_lags(conf):
+    """The frontier arithmetic of the incremental generator behind a look-ahead window (csrc/generator.hip keeps the same table):
+    after n frames, rows [0, rate * n - lag) of a tensor are final.  By the paddings: conv_pre lags 3 frames where it is symmetric;
+    upsampler i multiplies the lag by its rate and, symmetric, adds rate / 2 (it is the view [u/2, u/2 + L u) of the causal rows); an
+    iteration of a symmetric AMP block adds its reach (ks - 1)(d + 1) / 2, so a stage adds the longest block's sum; conv_post adds 3.
+    Keys: "mel", "conv_pre", "up<i>", "stage<i>" (the oracle's tap names), "wav", and "P" / "Q": per stage, per block, the lag of the
+    block's first and second iteration's result.  A filtered generator has no such table: ValueError with its text."""
+    if is_antialiased(conf):
+        raise ValueError("stream_lags: " + NOT_CAUSAL)
+    v = conf["vocoder_config"]
+    stages, pre, post = symmetric_flags(conf)
+    lags = {"mel": 0, "conv_pre": 3 if pre else 0, "P": [], "Q": []}
+    lag = lags["conv_pre"]
+    for i, u in enumerate(v["upsample_rates"]):
+        lag = lag * u + (u // 2 if stages[i] else 0)
+        lags[f"up{i}"] = lag
+        reaches = [[(ks - 1) * (d + 1) // 2 if stages[i] else 0 for d in ds]
+                   for ks, ds in zip(v["resblock_kernel_sizes"], v["resblock_dilation_sizes"])]
+        lags["P"].append([lag + r[0] for r in reaches])
+        lags["Q"].append([lag + r[0] + r[1] for r in reaches])
+        lag += max(sum(r) for r in reaches)
+        lags[f"stage{i}"] = lag
+    lags["wav"] = lag + (3 if post else 0)
+    return lags
+
+
+def generator_lookahead(conf):
+    """Samples the generator looks ahead: sample t is final once frame (t + this) / 256 has arrived.  0 for a causal generator, -1
+    for one that cannot stream (anti-aliased), as ``bvc_vocoder_lookahead`` answers."""
+    return -1 if is_antialiased(conf) else stream_lags(conf)["wav"]
+
+
 GENERATOR_WIDTHS = (16, 32, 64, 128, 256, 512)     # vocoder_config.upsample_initial_channel (check_config in csrc/model_build.hip)
 FINAL_CHANNELS = (8, 16, 32)                       # channels in front of conv_post: the width halved once per upsampling stage
 WIDEST_SWITCHED_STAGE = 64                         # layers_sym / layers_antialias: stages of more channels have the causal kernels only

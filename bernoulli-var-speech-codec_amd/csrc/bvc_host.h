@@ -127,6 +127,14 @@ struct bvc_vocoder_stream {
     bvc::StreamTensor mel, y0;
     std::vector<bvc::StreamTensor> X, XS;                  // per stage
     std::vector<bvc::StreamTensor> P, Q;                   // per (stage, AMP block): each block's intermediates keep their own history
+    // look-ahead window (bvc_vocoder_stream_create_lookahead; generator.hip): after n frames, rows [0, rate * n - lag) of a tensor are
+    // final.  The tensors of a stage share the row numbering of its X - buffer row 0 is row rate * n - lag_x - H of the stage - and end at
+    // their own frontiers: P and Q of a block lag_p / lag_q rows before X's, XS `spread` rows.
+    bool lookahead = false, flushed = false;
+    int64_t delay = 0;                                     // the waveform's lag, in samples
+    int lag_y0 = 0, lag_post = 0;                          // conv_pre's and conv_post's own (3 where symmetric)
+    std::vector<long long> lag_x, spread, tail;            // per stage; tail: rows of the stage beyond rate * T at the end of the signal
+    std::vector<long long> lag_p, lag_q;                   // per (stage, AMP block), relative to X
     ~bvc_vocoder_stream() {
         if (pool) (void)hipFree(pool);
         if (d_tab) (void)hipFree(d_tab);
@@ -269,6 +277,6 @@ int copy_rows(const float *src, long long src_bs, float *dst, long long dst_bs, 
 
 const int64_t STREAM_WARM_FRAMES = 32;   // rate * 32 - 64 >= 60 = the longest receptive field of an AMP pair, for every stage rate >= 8
 const int STREAM_H = 64;     // history rows per stage: >= (ks-1)*dil + (ks-1) of every AMP pair (max 60) and a multiple of every rate
-int vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_per_push, bool slide, bvc_vocoder_stream **out);
+int vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_per_push, bool slide, bvc_vocoder_stream **out, bool lookahead = false);
 
 }  // namespace bvc

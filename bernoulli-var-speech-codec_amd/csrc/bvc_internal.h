@@ -421,6 +421,9 @@ struct ConvWindow {
     // AMP pairs of a session whose rows start at different times: row b's t_origin is t_origin + age_rate * row_age[b] (device memory)
     const int *row_age = nullptr;
     int age_rate = 0;
+    // a symmetric AMP pair in a look-ahead window: Lin ends the rows it may read, row_end <= Lin the rows it writes
+    bool lookahead = false;
+    long long row_end = 0;
 };
 // in (B, Lin, cin) channels-last; out (B, Lout, cout).  Output row r reads input rows
 // r - (ks-1)*dil ... r  (rows outside [0,Lin) are zero).  res/acc have the layout of out.
@@ -447,7 +450,7 @@ int launch_conv_mfma(const ConvLayer &c, const float *in, long long Lin, float *
 int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, long long L, float *out, int B, int epi,
                     const float *acc, float divisor, hipStream_t s, const ConvWindow *win = nullptr, unsigned kernels = AMPK_ALL,
                     bool sym = false,         // symmetric pair (ks odd): the generic kernel's SYM form, out[t] reads x[t - h .. t + h], h = (ks-1)(d+1)/2;
-                    long long bs = 0);        // win must be null.  bs: floats between the batch items of x / out / acc where that is not L * C
+                    long long bs = 0);        // win must be null or a look-ahead window.  bs: floats between the batch items of x / out / acc where that is not L * C
                                               // (sym only: the stage works on a view of the upsampler's rows; rows outside [0, L) read as zeros)
 // SnakeBeta -> causal conv C->1 (k taps) -> tanh -> / div -> first n_out samples
 // n_rows (B) or nullptr: item b keeps its first n_rows[b] samples, the rest of its n_out are 0

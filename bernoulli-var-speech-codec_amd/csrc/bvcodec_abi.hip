@@ -703,4 +703,32 @@ int bvc_test_vocoder_layer(const bvc_model *m, int32_t kind, int32_t stage, int3
     return rc;
 }
 
+int bvc_test_amp_pair_window(const bvc_model *m, int32_t stage, int32_t block, int32_t iteration, const float *d_x, int32_t B,
+                             int64_t L_in, float *d_out, int32_t epi, const float *d_acc, int64_t row_begin, int64_t row_end,
+                             int64_t t_origin, int64_t *out_info, void *stream) {
+    // test helper (synchronises): ONE launch of a symmetric pair in a look-ahead window, as stream_advance (generator.hip) makes it
+    if (!m || !d_x || !d_out || B <= 0 || L_in <= 0) { set_error("bvc_test_amp_pair_window: bad arguments"); return BVC_EINVAL; }
+    const bvc_config &c = m->cfg;
+    if (stage < 0 || stage >= c.n_up || block < 0 || block >= c.n_resk || iteration < 0 || iteration >= 3) {
+        set_error("bvc_test_amp_pair_window: no AMP pair (%d, %d, %d)", stage, block, iteration); return BVC_EINVAL; }
+    if (epi < CE_RES || epi > CE_RES_ACC_DIV || (epi >= CE_RES_ACC && !d_acc)) { set_error("bvc_test_amp_pair_window: epilogue %d", epi); return BVC_EINVAL; }
+    if (m->antialiased) { set_error("bvc_test_amp_pair_window: %s", not_causal(m)); return BVC_EINVAL; }
+    if (!m->stage_sym[stage]) { set_error("bvc_test_amp_pair_window: stage %d is not symmetric", stage); return BVC_EINVAL; }
+    if (row_begin < 0 || row_end < row_begin || row_end > L_in) { set_error("bvc_test_amp_pair_window: rows [%lld, %lld) of %lld", (long long)row_begin, (long long)row_end, (long long)L_in); return BVC_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    g_last_amp_launch = {0, 0, 0};
+    const AmpPair &ap = m->amp[stage][block][iteration];
+    const long long bs = (long long)L_in * m->stage_ch[stage];
+    ConvWindow w{bs, bs, row_begin, t_origin};
+    w.lookahead = true; w.row_end = row_end;
+    int rc = launch_amp_pair(ap.c1, ap.c2, d_x, L_in, d_out, B, epi, d_acc, (float)c.n_resk, s, &w, m->amp_kernels, true);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) { set_error("bvc_test_amp_pair_window: %s", hipGetErrorString(e)); rc = BVC_EHIP; }
+    if (out_info) {
+        out_info[0] = L_in; out_info[1] = m->stage_ch[stage];
+        out_info[2] = g_last_amp_launch.tiles; out_info[3] = g_last_amp_launch.workgroups; out_info[4] = g_last_amp_launch.tile_rows;
+    }
+    return rc;
+}
+
 }  // extern "C"

@@ -1,4 +1,5 @@
-// The generator (BigVGAN): the offline pass over a whole utterance and the incremental, history-buffer pass of the streaming paths.
+// The generator (BigVGAN): the offline pass over a whole utterance, the incremental, history-buffer pass of the streaming paths, and the
+// same behind a look-ahead window, which admits symmetric layers.
 #include <algorithm>
 #include <memory>
 
@@ -109,6 +110,154 @@ int stream_push(bvc_vocoder_stream *st, const float *d_mel, int k, float div, fl
     return BVC_OK;
 }
 
+// ---- the look-ahead window: symmetric layers behind a bounded delay --------------------------------
+// After n frames, rows [0, rate * n - lag) of a tensor are final (its frontier; below zero: none yet).  By the reference's paddings:
+// mel 0; y0 3 where conv_pre is symmetric; X_i = u_i * lag(previous tensor), + u_i / 2 behind a symmetric upsampler (the view
+// [u/2, u/2 + L u) of the causal rows); an iteration of a symmetric AMP block adds its reach (ks-1)(d+1)/2, so P and Q of a block lag
+// by the partial sums and XS by the longest block's sum (`spread`: all three blocks add to the same rows); the waveform 3 more where
+// conv_post is symmetric.  config.stream_lags (Python) is the same table.
+inline long long amp_reach(const AmpPair &ap) { return (long long)(ap.c1.ks - 1) * (ap.c1.dil + 1) / 2; }
+void stream_lags(const bvc_model *m, bvc_vocoder_stream *st) {
+    const bvc_config &c = m->cfg;
+    st->lag_y0 = m->pre_sym ? (m->conv_pre.ks - 1) / 2 : 0;
+    st->lag_post = m->post_sym ? (m->post_ks - 1) / 2 : 0;
+    long long lag = st->lag_y0, tail = 0;
+    for (int i = 0; i < c.n_up; ++i) {
+        const int u = c.up_rates[i];
+        const bool sym = m->stage_sym[i];
+        lag = lag * u + (sym ? u / 2 : 0);
+        tail = sym ? tail * u : (tail + 1) * u;
+        st->lag_x.push_back(lag);
+        st->tail.push_back(tail);
+        long long spread = 0;
+        for (int j = 0; j < c.n_resk; ++j) {
+            const long long r0 = sym ? amp_reach(m->amp[i][j][0]) : 0, r1 = sym ? amp_reach(m->amp[i][j][1]) : 0;
+            const long long r2 = sym ? amp_reach(m->amp[i][j][2]) : 0;
+            st->lag_p.push_back(r0);
+            st->lag_q.push_back(r0 + r1);
+            spread = std::max(spread, r0 + r1 + r2);
+        }
+        st->spread.push_back(spread);
+        lag += spread;
+    }
+    st->delay = lag + st->lag_post;
+}
+
+__global__ __launch_bounds__(256) void stream_rows_zero_kernel(float *__restrict__ dst, long long dst_bs, long long n) {
+    float *d = dst + (long long)blockIdx.y * dst_bs;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) d[i] = 0.0f;
+}
+
+inline long long not_below_zero(long long v) { return v > 0 ? v : 0; }
+
+// samples a push of k frames (k >= 1) or the flush (k == -1) writes per row
+int64_t stream_samples(const bvc_vocoder_stream *st, int k) {
+    const long long spf = st->X.back().rate, n0 = st->frames;
+    if (!st->lookahead) return k > 0 ? spf * k : 0;
+    const long long done = not_below_zero(spf * n0 - st->delay);
+    if (k > 0) return not_below_zero(spf * (n0 + k) - st->delay) - done;
+    return n0 == 0 ? 0 : spf * n0 + st->tail.back() - done;
+}
+
+// One push (k new frames) or the flush (k = 0) of a look-ahead state.  Every tensor advances from its frontier at the old frame count to its
+// frontier at the new one - at the flush to its true length, with the offline rules of the signal's end: rows behind it read as zeros.
+// The launches are the causal windowed ones with their rows relabelled: conv_pre by 3 (its causal row t + 3 is row t), an upsampler by
+// u / 2 (in buffer rows the same launch as the causal one: the histories are multiples of u), conv_post by 3.  What relabelling cannot
+// give is the start of a symmetric upsampler's signal: its first group of u rows begins u / 2 rows before row 0, and those are zeroed
+// behind the launch (the pairs read rows before the signal as zeros).  Its end needs nothing: the pairs' descriptor ends at the true length.
+int stream_advance(bvc_vocoder_stream *st, const float *d_mel, int k, bool flush, float div, float *d_wav, hipStream_t s) {
+    const bvc_model *m = st->m;
+    const bvc_config &c = m->cfg;
+    const int B = st->B, p = st->parity;
+    const long long n0 = st->frames, n1 = n0 + k;
+    int rc;
+    if (flush && n0 == 0) { st->flushed = true; return BVC_OK; }
+    auto bs = [](const StreamTensor &t) { return t.rows * t.C; };
+    auto at = [&](const StreamTensor &t) { return t.buf[p]; };
+    if (k > 0) {
+        stream_rows_in_kernel<<<dim3((unsigned)((k * st->mel.C + 255) / 256), B), 256, 0, s>>>(
+            d_mel, (long long)k * st->mel.C, at(st->mel) + (long long)st->mel.H * st->mel.C, bs(st->mel), (long long)k * st->mel.C);
+        BVC_HIP_TRY(hipGetLastError());
+    }
+    // the tensor the next layer reads: its frontiers before and after this call, the row its buffer starts at, its true length at n0 frames
+    struct Prev { const StreamTensor *t; long long f0, f1, origin, len; };
+    Prev pv;
+    {
+        // launch row r is causal row n0 - Hm + r = row n0 - Hm + r - lag_y0 of y0
+        const long long sh = st->lag_y0, g0 = n0 - st->mel.H;
+        const long long lo = not_below_zero(n0 - sh) + sh, hi = flush ? n0 + sh : not_below_zero(n1 - sh) + sh;
+        ConvWindow w{bs(st->mel), bs(st->y0), lo - g0, 0};
+        float *out = at(st->y0) + (long long)(st->y0.H - st->mel.H) * st->y0.C;
+        if (hi > lo && (rc = launch_conv_mfma(m->conv_pre, at(st->mel), n1 - g0, out, hi - g0, B, CE_STORE, nullptr, nullptr, 1.0f, s, &w))) return rc;
+        pv = {&st->y0, n0 - sh, n1 - sh, n0 - sh - st->y0.H, n0};
+    }
+    for (int i = 0; i < c.n_up; ++i) {
+        const int u = c.up_rates[i];
+        const bool sym = m->stage_sym[i];
+        const StreamTensor &X = st->X[i], &XS = st->XS[i];
+        const long long H = X.H, hq = H / u, h = sym ? u / 2 : 0;
+        const long long fx0 = u * pv.f0 - h, fx1 = u * pv.f1 - h, origin = fx0 - H;
+        const long long Li = sym ? u * pv.len : u * (pv.len + 1);
+        {
+            // groups of u rows: group q is rows [u q - h, u q - h + u) of X and reads rows q - 1 and q of the previous tensor
+            const long long qlo = not_below_zero(pv.f0), qhi = flush ? pv.len + 1 : not_below_zero(pv.f1);
+            const long long lin = flush ? pv.len : not_below_zero(pv.f1);
+            const long long hh = std::min(hq, pv.f0 - pv.origin), g0 = pv.f0 - hh;       // launch row r is group g0 + r
+            ConvWindow w{bs(*pv.t), bs(X), qlo - g0, 0};
+            const float *in = at(*pv.t) + (g0 - pv.origin) * pv.t->C;
+            float *out = at(X) + (hq - hh) * u * X.C;
+            if (qhi > qlo && (rc = launch_conv_mfma(m->ups[i], in, lin - g0, out, qhi - g0, B, CE_STORE, nullptr, nullptr, 1.0f, s, &w))) return rc;
+            if (sym && qlo == 0 && qhi > 0) {                  // group 0 was written: its first u / 2 rows lie before the signal
+                stream_rows_zero_kernel<<<dim3((unsigned)((h * X.C + 255) / 256), B), 256, 0, s>>>(at(X) + (-h - origin) * X.C, bs(X), h * X.C);
+                BVC_HIP_TRY(hipGetLastError());
+            }
+        }
+        // rows of the stage -> buffer rows: minus origin.  rel: how far a tensor's frontier lies before X's
+        auto lo_of = [&](long long rel) { return not_below_zero(fx0 - rel) - origin; };
+        auto hi_of = [&](long long rel) { return (flush ? Li : not_below_zero(fx1 - rel)) - origin; };
+        for (int j = 0; j < c.n_resk; ++j) {
+            const StreamTensor &P = st->P[i * c.n_resk + j], &Q = st->Q[i * c.n_resk + j];
+            float *const bufs[3] = {at(P), at(Q), at(XS)};
+            const long long rels[3] = {st->lag_p[i * c.n_resk + j], st->lag_q[i * c.n_resk + j], st->spread[i]};
+            const float *cur = at(X);
+            long long cur_rel = 0;
+            for (int d = 0; d < 3; ++d) {
+                const AmpPair &ap = m->amp[i][j][d];
+                const AmpTarget t = amp_target(c, j, d);
+                float *const dst = bufs[t.buf];
+                const long long rb = lo_of(rels[t.buf]), re = hi_of(rels[t.buf]);
+                if (re > rb) {
+                    ConvWindow w{bs(X), bs(X), rb, origin};
+                    w.lookahead = sym; w.row_end = re;
+                    if ((rc = launch_amp_pair(ap.c1, ap.c2, cur, sym ? hi_of(cur_rel) : re, dst, B, t.epi, at(XS), (float)c.n_resk, s, &w,
+                                              m->amp_kernels, sym))) return rc;
+                }
+                cur = dst;
+                cur_rel = rels[t.buf];
+            }
+        }
+        pv = {&XS, fx0 - st->spread[i], fx1 - st->spread[i], origin, Li};
+    }
+    {
+        // launch row r is row origin + r of the last stage; sample t reads its rows t + lag_post - 6 .. t + lag_post
+        const long long sh = st->lag_post;
+        const long long lo = not_below_zero(pv.f0 - sh), hi = flush ? pv.len : not_below_zero(pv.f1 - sh);
+        const long long lin = (flush ? pv.len : not_below_zero(pv.f1)) - pv.origin;
+        ConvWindow w{bs(*pv.t), 0, lo + sh - pv.origin, 0};
+        if (hi > lo) {
+            if (!d_wav) { set_error("bvc_vocoder_stream: null output for %lld samples", hi - lo); return BVC_EINVAL; }
+            if ((rc = launch_conv_post(at(*pv.t), lin, m->post_c, m->post_ks, m->post_w, m->post_b, m->post_a, m->post_ib, div, d_wav,
+                                       hi - lo, B, s, &w))) return rc;
+        }
+    }
+    if (flush) { st->flushed = true; return BVC_OK; }
+    stream_rotate_kernel<<<dim3((unsigned)((st->max_hc4 + 255) / 256), B, st->n_ten), 256, 0, s>>>(st->d_tab, k, p);
+    BVC_HIP_TRY(hipGetLastError());
+    st->parity ^= 1;
+    st->frames += k;
+    return BVC_OK;
+}
+
 }  // namespace
 
 namespace bvc {
@@ -181,9 +330,17 @@ int copy_rows(const float *src, long long src_bs, float *dst, long long dst_bs, 
     return BVC_OK;
 }
 
-int vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_per_push, bool slide, bvc_vocoder_stream **out) {
-    if (!m || !out || B <= 0 || max_frames_per_push <= 0) { set_error("bvc_vocoder_stream_create: bad arguments"); return BVC_EINVAL; }
-    if (m->noncausal) { set_error("bvc_vocoder_stream_create: %s", not_causal(m)); return BVC_EINVAL; }
+// lookahead: the state of bvc_vocoder_stream_create_lookahead (twin buffers only).  A stage's history grows from STREAM_H by the spread of
+// the lags inside it, so that the last iteration of a block, which writes `spread` rows before X's frontier, still finds its reach
+// behind it; every buffer has room for the rows of the flush, from the tensor's frontier to its true length.
+int vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_per_push, bool slide, bvc_vocoder_stream **out, bool lookahead) {
+    const char *const fn = lookahead ? "bvc_vocoder_stream_create_lookahead" : "bvc_vocoder_stream_create";
+    if (!m || !out || B <= 0 || max_frames_per_push <= 0 || (lookahead && slide)) { set_error("%s: bad arguments", fn); return BVC_EINVAL; }
+    if (lookahead ? m->antialiased : m->noncausal) {
+        if (m->antialiased) set_error("%s: %s", fn, not_causal(m));
+        else set_error("%s: %s (bvc_vocoder_stream_create_lookahead streams it behind bvc_vocoder_lookahead samples of delay)", fn, not_causal(m));
+        return BVC_EINVAL;
+    }
     const bvc_config &c = m->cfg;
     // the history must cover every receptive field and stay aligned with the transposed-conv views
     long long rate = 1;
@@ -203,20 +360,43 @@ int vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_per_
     std::unique_ptr<bvc_vocoder_stream> st(new bvc_vocoder_stream());
     st->m = m; st->B = B; st->kmax = max_frames_per_push;
     st->slide = slide;
+    st->lookahead = lookahead;
+    std::vector<int> hist(c.n_up, STREAM_H);               // history rows per stage
+    std::vector<long long> room_flush(c.n_up, 0);          // rows of the flush beyond the history
+    if (lookahead) {
+        stream_lags(m, st.get());
+        for (int i = 0; i < c.n_up; ++i) {
+            const int u = c.up_rates[i];
+            hist[i] = STREAM_H + (int)st->spread[i];
+            while (hist[i] % u || hist[i] % 4) ++hist[i];
+            room_flush[i] = st->lag_x[i] + st->tail[i] + u;
+            // every launch's reach-back lies inside the history: checked, not clamped
+            long long back = 0;
+            for (int j = 0; j < c.n_resk; ++j)
+                for (int d = 0; d < 3; ++d)
+                    back = std::max(back, m->stage_sym[i] ? amp_reach(m->amp[i][j][d]) : (long long)(m->amp[i][j][d].c1.ks - 1) * (m->amp[i][j][d].c1.dil + 1));
+            const long long prev_left = i == 0 ? 1 : hist[i - 1] - st->spread[i - 1];
+            if (hist[i] - st->spread[i] < back || prev_left < 1 || (i + 1 == c.n_up && hist[i] - st->spread[i] < m->post_ks - 1)) {
+                set_error("%s: the history of stage %d (%d rows) does not cover its look-ahead (%lld) and reach (%lld)", fn, i, hist[i], st->spread[i], back);
+                return BVC_EINVAL;
+            }
+        }
+    }
     // frames of room behind the history: 32 (16 hops of one or two frames between two moves of the histories; 2.2 GB of buffers at 256 streams),
     // more only where longer hops need it
     st->cap_frames = slide ? std::max(2 * max_frames_per_push + 8, 32) : max_frames_per_push;
     const long long room = st->cap_frames;
-    auto mk = [&](int C, int H, int r) { StreamTensor t; t.buf[0] = t.buf[1] = nullptr; t.C = C; t.H = H; t.rate = r; t.rows = H + (long long)r * room; return t; };
+    auto mk = [&](int C, int H, int r, long long flush_rows = 0) {
+        StreamTensor t; t.buf[0] = t.buf[1] = nullptr; t.C = C; t.H = H; t.rate = r; t.rows = H + std::max((long long)r * room, flush_rows); return t;
+    };
     st->mel = mk(c.num_mels, (m->conv_pre.ks - 1) * m->conv_pre.dil, 1);
-    st->y0 = mk(c.upsample_initial_channel, STREAM_H / c.up_rates[0], 1);
-    if (st->y0.H < st->mel.H) st->y0.H = st->mel.H, st->y0.rows = st->y0.H + room;
+    st->y0 = mk(c.upsample_initial_channel, std::max(hist[0] / c.up_rates[0], st->mel.H), 1, st->lag_y0);
     rate = 1;
     for (int i = 0; i < c.n_up; ++i) {
         rate *= c.up_rates[i];
-        for (auto *v : {&st->X, &st->XS}) v->push_back(mk(m->stage_ch[i], STREAM_H, (int)rate));
+        for (auto *v : {&st->X, &st->XS}) v->push_back(mk(m->stage_ch[i], hist[i], (int)rate, room_flush[i]));
         for (int j = 0; j < c.n_resk; ++j)
-            for (auto *v : {&st->P, &st->Q}) v->push_back(mk(m->stage_ch[i], STREAM_H, (int)rate));
+            for (auto *v : {&st->P, &st->Q}) v->push_back(mk(m->stage_ch[i], hist[i], (int)rate, room_flush[i]));
     }
     std::vector<StreamTensor *> all = {&st->mel, &st->y0};
     for (auto *v : {&st->X, &st->XS, &st->P, &st->Q})
@@ -260,20 +440,46 @@ int bvc_vocoder_stream_create(const bvc_model *m, int32_t B, int32_t max_frames_
     return vocoder_stream_create(m, B, max_frames_per_push, false, out);
 }
 
+int64_t bvc_vocoder_lookahead(const bvc_model *m) {
+    if (!m || m->antialiased) return -1;
+    bvc_vocoder_stream st;
+    stream_lags(m, &st);
+    return st.delay;
+}
+
+int bvc_vocoder_stream_create_lookahead(const bvc_model *m, int32_t B, int32_t max_frames_per_push, bvc_vocoder_stream **out) {
+    return vocoder_stream_create(m, B, max_frames_per_push, false, out, true);
+}
+
+int64_t bvc_vocoder_stream_samples(const bvc_vocoder_stream *st, int32_t k) {
+    if (!st || st->flushed || (k != -1 && (k <= 0 || k > st->kmax))) return 0;
+    return stream_samples(st, k);
+}
+
+int bvc_vocoder_stream_flush(bvc_vocoder_stream *st, float out_scale_div, float *d_wav, void *stream) {
+    if (!st) { set_error("null stream state"); return BVC_EINVAL; }
+    if (int st_ = sticky_status(st->m)) return st_;
+    if (!st->lookahead) { set_error("bvc_vocoder_stream_flush: the state was not made by bvc_vocoder_stream_create_lookahead"); return BVC_EINVAL; }
+    if (st->flushed) { set_error("bvc_vocoder_stream_flush: the stream is flushed; only bvc_vocoder_stream_reset is legal"); return BVC_EINVAL; }
+    return stream_advance(st, nullptr, 0, true, out_scale_div, d_wav, (hipStream_t)stream);
+}
+
 void bvc_vocoder_stream_destroy(bvc_vocoder_stream *st) { delete st; }
 
 int bvc_vocoder_stream_reset(bvc_vocoder_stream *st, void *stream) {
     if (!st) { set_error("null stream state"); return BVC_EINVAL; }
     BVC_HIP_TRY(hipMemsetAsync(st->pool, 0, st->pool_floats * sizeof(float), (hipStream_t)stream));
-    st->parity = 0; st->frames = 0; st->cursor = 0;
+    st->parity = 0; st->frames = 0; st->cursor = 0; st->flushed = false;
     return BVC_OK;
 }
 
 int bvc_vocoder_stream_push(bvc_vocoder_stream *st, const float *d_mel, int32_t k, float out_scale_div, float *d_wav,
                             void *stream) {
-    if (!st || !d_mel || !d_wav) { set_error("null argument"); return BVC_EINVAL; }
+    if (!st || !d_mel || (!d_wav && !st->lookahead)) { set_error("null argument"); return BVC_EINVAL; }
     if (int st_ = sticky_status(st->m)) return st_;
     if (k <= 0 || k > st->kmax) { set_error("bvc_vocoder_stream_push: k=%d outside 1..%d", (int)k, st->kmax); return BVC_EINVAL; }
+    if (st->flushed) { set_error("bvc_vocoder_stream_push: the stream is flushed; only bvc_vocoder_stream_reset is legal"); return BVC_EINVAL; }
+    if (st->lookahead) return stream_advance(st, d_mel, k, false, out_scale_div, d_wav, (hipStream_t)stream);
     return stream_push(st, d_mel, k, out_scale_div, d_wav, (hipStream_t)stream);
 }
 

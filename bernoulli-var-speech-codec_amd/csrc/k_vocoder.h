@@ -134,6 +134,9 @@ struct AmpArgs {
     long long t_origin;           // global time of buffer row 0 (streaming); 0 offline
     const int *row_age;           // streaming sessions whose rows start at different times: frames since row b's own start (capped where
     int age_rate;                 // no row of a window lies before it any more); row b's t_origin is t_origin + age_rate * row_age[b]
+    int row_end;                  // symmetric pair (amp_pair_kernel<..., SYM = true>, whose rows fit 31 bits): one past the last output row - L
+                                  // offline; in a look-ahead window L ends the readable input and row_end <= L the rows written.  0 for every
+                                  // other kernel: none reads it (it fills the struct's padding: their arguments lie where they lay)
     const float *fu1, *fd1, *fu2, *fd2;   // anti-aliased pair (amp_pair_kernel<..., AA = true>): the 12-tap up / down filters of S1 and S2
 };
 __device__ __forceinline__ long long amp_t_origin(const AmpArgs &a, int b) {

@@ -2,6 +2,7 @@
 // count, with its anti-aliased, symmetric and wide forms), the persistent kernels of the C = 8 and C = 16 stages, and launch_amp_pair,
 // which picks among them.  The conv kernel they share their conventions with is in k_vocoder.hip, the device helpers in k_vocoder.h.
 #include <cstdlib>
+#include <cstring>
 #include <initializer_list>
 
 #include "k_vocoder.h"
@@ -39,7 +40,10 @@ __device__ unsigned long long g_phase[16];
 // (ks-1) d / 2 rows before conv1's first row instead of (ks-1) d, conv1's rows start (ks-1) / 2 before the tile instead of ks - 1, and the
 // S2 rows behind the signal's end are zeros like the ones before its start (the reference pads AFTER the activation on both sides; the
 // S1 rows there read as zeros through the descriptor, whatever lies behind the signal in memory).  LDS, TR, TT, the MFMA loops, the
-// order of summation and the epilogues are the causal kernel's.  Offline only, and not with AA.
+// order of summation and the epilogues are the causal kernel's.  Not with AA.  In a streaming window (row_begin, t_origin as in the
+// causal form) the pair looks ahead, so the rows it writes end before the rows it may read: a.L ends the readable input - rows from
+// there on read as zeros and the S2 tile is zero behind it - and a.row_end <= a.L bounds the stores and the tile count.  Mid-stream
+// row_end = L - h, so no stored row consumes those zeros; at the end of the signal row_end = L, the offline meaning of a.L.
 template <int C, int MT, int OCC, bool ALIAS, int CS = 1, bool AA = false, bool SYM = false>
 __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
     static_assert(!(SYM && AA), "a filtered stage is a causal stage");
@@ -345,7 +349,8 @@ __global__ __launch_bounds__(256, OCC) void amp_pair_kernel(AmpArgs a) {
     // the conv2 result transposed from the MFMA layout through LDS (the S1(x) tile is dead by now).
     const long long ob = (long long)b * a.bs + t0 * C;
     constexpr int NLD3 = (TR * C4 + 255) / 256;
-    const long long rows_left = a.L - t0;
+    long long rows_left = a.L - t0;
+    if constexpr (SYM) rows_left = a.row_end - t0;
     const int nvalid4 = (int)(rows_left < TT ? rows_left : TT) * C4;
     f32x4 resq[NLD3], accq[NLD3];
     const bool with_acc = a.epi >= CE_RES_ACC;             // (uniform)
@@ -780,7 +785,7 @@ static int amp_slots(const char *name) {
 // that the XCD-contiguous renumbering covers every tile exactly once.
 template <class Prepare>
 static int launch_amp_tiles(AmpKernel kern, AmpArgs a, int B, int TT, size_t lds, hipStream_t s, Prepare prepare) {
-    a.tiles_per_batch = (int)((a.L - a.row_begin + TT - 1) / TT);
+    a.tiles_per_batch = (int)(((a.row_end ? a.row_end : a.L) - a.row_begin + TT - 1) / TT);
     if (a.tiles_per_batch <= 0) return BVC_OK;
     a.tpb_magic = tpb_magic_of((unsigned)a.tiles_per_batch);
     if ((unsigned long long)a.tiles_per_batch * a.tiles_per_batch * (unsigned long long)B >= 0x100000000ull) { set_error("vocoder: tile count beyond the reciprocal's range"); return BVC_EINVAL; }
@@ -936,6 +941,22 @@ static AmpLauncher amp_symmetric(int C) {
     }
 }
 
+// symmetric pair in a look-ahead window (the incremental generator, generator.hip): a hop brings 8 - 512 new rows per stage, of which the
+// offline shapes above (128 - 256 rows per workgroup) would mostly compute rows nobody reads - the causal short windows' situation
+// (amp_short_window below), and the same cuts: C = 64 one 32-row tile with the waves along the columns for the one or two frames of
+// stage 0, else 64-row tiles; C = 32 and 16 up to three 64-row tiles; C = 8 up to three 128-row tiles.  BVC_SYM_WINDOW_TILES=offline
+// (read per call: tools/lookahead_stream_cost.py runs both in one process) keeps the offline shapes; profiles/lookahead_stream_cost.md
+static AmpLauncher amp_symmetric_window(int C, int ks, long long new_rows) {
+    const char *force = getenv("BVC_SYM_WINDOW_TILES");
+    if (force && !strcmp(force, "offline")) return nullptr;
+    if (C == 64 && new_rows <= 32 - (ks - 1)) return launch_amp_t<64, 2, 2, true, 4, false, true>;
+    if (C == 64 && new_rows <= 2 * (64 - (ks - 1))) return launch_amp_t<64, 1, 2, true, 1, false, true>;
+    if (C == 32 && new_rows <= 3 * (64 - (ks - 1))) return launch_amp_t<32, 1, 3, true, 1, false, true>;
+    if (C == 16 && new_rows <= 3 * (64 - (ks - 1))) return launch_amp_t<16, 1, 4, false, 1, false, true>;
+    if (C == 8 && new_rows <= 3 * (128 - (ks - 1))) return launch_amp_t<8, 2, 4, true, 1, false, true>;
+    return nullptr;
+}
+
 // wide stages (generators of 256 / 512 initial channels): the generic pair with the waves along the columns (a conv's weights
 // are 0.7 - 2.9 MB: a fragment is read once per workgroup) and the S2 tile in the S1 tile's LDS.  C = 256: 64 rows, 114 x 258
 // floats = 117.6 KB at ks = 11, d = 5, one workgroup per CU: 32.9 ms for the stage at 64 x 430 frames; 96 rows (150.7 KB), the
@@ -1035,6 +1056,7 @@ int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, lo
     a.row_age = win ? win->row_age : nullptr;
     a.age_rate = win ? win->age_rate : 0;
     a.fu1 = c1.aa_up; a.fd1 = c1.aa_down; a.fu2 = c2.aa_up; a.fd2 = c2.aa_down;
+    a.row_end = 0;
     // wide stages (C = 128 / 256) exist as causal, unfiltered pairs only; their rows go through 32-bit byte offsets (rows_load4)
     const bool wide = C >= 128;
     if (wide) {
@@ -1049,9 +1071,18 @@ int launch_amp_pair(const ConvLayer &c1, const ConvLayer &c2, const float *x, lo
         return launch_by(amp_antialiased(C), a, C, B, s);
     }
     if (sym) {
-        if (win) { set_error("amp_pair: a symmetric pair looks ahead and has no streaming window"); return BVC_EINVAL; }
+        if (win && !win->lookahead) { set_error("amp_pair: a symmetric pair looks ahead and has no streaming window (but a look-ahead window)"); return BVC_EINVAL; }
         if (c1.ks % 2 == 0) { set_error("amp_pair: a symmetric pair needs an odd kernel size (got %d)", c1.ks); return BVC_EINVAL; }
         if (L + 512 > 0x7FFFFFFFll / C / 4) { set_error("amp_pair: %lld rows are beyond the symmetric kernel's row index", L); return BVC_EINVAL; }
+        a.row_end = (int)L;
+        if (win) {
+            if (win->row_age || a.row_begin < 0 || win->row_end < a.row_begin || win->row_end > L) {
+                set_error("amp_pair: look-ahead window rows [%lld, %lld) of %lld readable rows", a.row_begin, win->row_end, L); return BVC_EINVAL;
+            }
+            if (win->row_end == a.row_begin) return BVC_OK;
+            a.row_end = (int)win->row_end;
+            if (const AmpLauncher launch = amp_symmetric_window(C, c1.ks, a.row_end - a.row_begin)) return launch(a, B, s);
+        }
         return launch_by(amp_symmetric(C), a, C, B, s);
     }
     if (bs) { set_error("amp_pair: a batch stride of its own belongs to a symmetric stage's view"); return BVC_EINVAL; }

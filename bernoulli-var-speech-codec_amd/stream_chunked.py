@@ -17,7 +17,10 @@ to rounding, <= 1e-6 - long offline decodes batch two dot-product halves over al
   mel frames (conv_pre 6 frames + per stage 12*(k-1) = 120 samples of AMP halo + 1 sample of
   transposed conv), so each hop re-runs the generator over [context | new frames] and keeps the new
   samples (≈4x the work per 20 ms hop).  The tail beyond the last full frame (``flush``) always uses
-  the context scheme.
+  the context scheme.  A generator with symmetric layers is not causal, but its look-ahead is bounded
+  (``config.generator_lookahead``): ``lookahead=True`` runs the library's state behind that delay
+  (``bvc_vocoder_stream_create_lookahead``) - a push returns the samples that became final, ``flush`` /
+  ``finish`` the rest, bit for bit the offline call.
 
 ``tests/test_gpu_streaming.py`` checks that any chunking reproduces the offline encode()/decode().
 """
@@ -27,7 +30,7 @@ import math
 import torch
 
 from . import _abi
-from .config import is_causal, not_causal_message
+from .config import generator_lookahead, is_antialiased, is_causal, not_causal_message
 from .model import SCALING
 from .stream_plans import CONTEXT_FRAMES
 
@@ -87,25 +90,62 @@ class StreamingEncoder:
 
 
 class VocoderStream:
-    """Handle of the library's incremental generator state for `batch` parallel streams."""
+    """Handle of the library's incremental generator state for `batch` parallel streams.
 
-    def __init__(self, engine, batch, max_frames_per_push):
-        if not is_causal(engine.conf):
-            raise ValueError("VocoderStream: " + not_causal_message(engine.conf))
+    ``lookahead=True``: the state behind a look-ahead window (``bvc_vocoder_stream_create_lookahead``), which also runs generators
+    with symmetric layers.  ``.lookahead`` is the delay in samples (0 for a causal generator); ``push`` then returns the samples that
+    became final with its frames - ``(B, n)``, ``n`` possibly 0 - and ``flush`` the rest up to the generator's length.  The pushes and
+    the flush concatenated are the offline call's bits."""
+
+    def __init__(self, engine, batch, max_frames_per_push, lookahead=False):
+        if is_antialiased(engine.conf) if lookahead else not is_causal(engine.conf):
+            raise ValueError("VocoderStream: " + not_causal_message(engine.conf)
+                             + ("" if lookahead or is_antialiased(engine.conf) else
+                                f"; lookahead=True streams it behind {generator_lookahead(engine.conf)} samples of delay"))
         self.eng = engine
         self.B = batch
         self.kmax = max_frames_per_push
         self.spf = math.prod(engine.conf["vocoder_config"]["upsample_rates"])
+        self.windowed = bool(lookahead)
+        self.lookahead = generator_lookahead(engine.conf) if lookahead else 0
         self.handle = _abi.Handle(engine.lib.bvc_vocoder_stream_destroy, engine)
-        engine.call("bvc_vocoder_stream_create", engine.handle, batch, max_frames_per_push, ctypes.byref(self.handle), stream=False)
+        engine.call("bvc_vocoder_stream_create_lookahead" if lookahead else "bvc_vocoder_stream_create", engine.handle, batch,
+                    max_frames_per_push, ctypes.byref(self.handle), stream=False)
 
     def reset(self):
         self.eng.call("bvc_vocoder_stream_reset", self.handle)
 
+    def samples(self, k):
+        """Samples per row the next push of k frames (1 <= k <= max_frames_per_push) writes, or with k = -1 the flush."""
+        return int(self.eng.lib.bvc_vocoder_stream_samples(self.handle, k))
+
+    def _windowed(self, mel, scale_div):
+        """One library call of a look-ahead state: a push of mel's frames, or with mel None the flush.  A misuse (a push after the
+        flush) is the library's BVC_EINVAL: ValueError."""
+        out = torch.empty(self.B, self.samples(-1 if mel is None else mel.shape[1]), device=self.eng.device)
+        with torch.cuda.device(self.eng.device):
+            if mel is None:
+                _abi.check_arg(self.eng.lib.bvc_vocoder_stream_flush(self.handle, float(scale_div), _abi.ptr(out), self.eng.stream()))
+            else:
+                _abi.check_arg(self.eng.lib.bvc_vocoder_stream_push(self.handle, _abi.ptr(mel), mel.shape[1], float(scale_div), _abi.ptr(out),
+                                                                    self.eng.stream()))
+        return out
+
+    def flush(self, scale_div=1.0):
+        """End of the signal (look-ahead states): the samples no push has returned, up to the generator's length; afterwards only
+        ``reset`` is legal."""
+        if not self.windowed:
+            raise ValueError("VocoderStream.flush: a state made with lookahead=True has a flush")
+        return self._windowed(None, scale_div)
+
     def push(self, mel, scale_div=1.0):
-        """mel (B, k, num_mels) time-major on the engine's device -> wav (B, k*256)."""
+        """mel (B, k, num_mels) time-major on the engine's device -> wav (B, k*256); behind a look-ahead window the samples that
+        became final, (B, n)."""
         B, k, _ = mel.shape
         assert B == self.B
+        if self.windowed:                                      # longer chunks go through in kmax-frame pieces
+            pieces = [self._windowed(mel[:, f:f + self.kmax].contiguous(), scale_div) for f in range(0, k, self.kmax)]
+            return torch.cat(pieces, 1) if pieces else torch.empty(B, 0, device=self.eng.device)
         out = torch.empty(B, k * self.spf, device=self.eng.device)
         for f in range(0, k, self.kmax):                       # longer chunks go through in kmax-frame pieces
             n = min(self.kmax, k - f)
@@ -118,9 +158,17 @@ class VocoderStream:
 
 
 class StreamingDecoder:
-    def __init__(self, model, batch, device=None, incremental=True, max_frames_per_push=8):
-        if not is_causal(model.conf):                          # (the context scheme counts on the same causality)
-            raise ValueError("StreamingDecoder: " + not_causal_message(model.conf))
+    """``lookahead=True``: the generator runs behind its look-ahead window (``VocoderStream(lookahead=True)``), which admits
+    symmetric layers: ``push`` returns the samples that became final - ``.lookahead`` samples behind the frames pushed - and
+    ``finish(length)`` the rest, so that ``cat(pushes + [finish(length)])`` is ``model.decode(codes, length)``."""
+
+    def __init__(self, model, batch, device=None, incremental=True, max_frames_per_push=8, lookahead=False):
+        if lookahead and not incremental:                      # the context scheme counts on causality
+            raise ValueError("StreamingDecoder: lookahead=True runs the incremental generator; incremental=False counts on a causal one")
+        if is_antialiased(model.conf) if lookahead else not is_causal(model.conf):
+            raise ValueError("StreamingDecoder: " + not_causal_message(model.conf)
+                             + ("" if lookahead or is_antialiased(model.conf) else
+                                f"; lookahead=True streams it behind {generator_lookahead(model.conf)} samples of delay"))
         self.m = model
         self.B = batch
         eng = model.engine(None if device is None else torch.empty(0, device=device))
@@ -130,7 +178,10 @@ class StreamingDecoder:
         self.ctx = torch.empty(batch, 0, c["num_mels"], device=self.dev)     # last CONTEXT_FRAMES mel frames
         self.spf = math.prod(c["vocoder_config"]["upsample_rates"])         # samples per frame (256)
         self.tail = None
-        self.voc = VocoderStream(eng, batch, max_frames_per_push) if incremental else None
+        self.voc = VocoderStream(eng, batch, max_frames_per_push, lookahead=lookahead) if incremental else None
+        self.windowed = bool(lookahead)
+        self.lookahead = self.voc.lookahead if lookahead else 0
+        self.emitted = 0                                       # samples the pushes have returned (look-ahead window)
 
     @torch.no_grad()
     def push(self, codes):
@@ -142,6 +193,10 @@ class StreamingDecoder:
         allmel = torch.cat([self.ctx, mel], 1)
         nctx = self.ctx.shape[1]
         self.ctx = allmel[:, -CONTEXT_FRAMES:].contiguous()
+        if self.windowed:
+            out = self.voc.push(mel, SCALING)
+            self.emitted += out.shape[1]
+            return out
         if self.voc is not None:
             self.tail = None
             return self.voc.push(mel, SCALING)
@@ -151,8 +206,20 @@ class StreamingDecoder:
         return out
 
     @torch.no_grad()
+    def finish(self, length=None):
+        """End of the utterance (look-ahead window): the samples no push has returned, up to the generator's length, or up to
+        ``length`` samples of the whole utterance as ``decode(codes, length)`` cuts it (what the pushes returned stays returned).
+        Afterwards the decoder is done."""
+        if not self.windowed:
+            raise ValueError("StreamingDecoder.finish: a decoder made with lookahead=True has a finish (see flush)")
+        rest = self.voc.flush(SCALING)
+        return rest if length is None else rest[:, :max(0, int(length) - self.emitted)]
+
+    @torch.no_grad()
     def flush(self, n_extra):
         """Up to 294 samples beyond the last full frame (what decode(codes, length) returns past 256*T)."""
+        if self.windowed:
+            raise ValueError("StreamingDecoder.flush: a decoder made with lookahead=True ends with finish()")
         if n_extra <= 0 or self.ctx.shape[1] == 0:
             return torch.empty(self.B, 0, device=self.dev)
         if self.tail is None:                                  # incremental mode: the tail comes from the context

@@ -116,7 +116,9 @@ typedef struct bvc_config {
  * keeps its layout.  A symmetric upsampler makes L * rate rows instead of (L + 1) * rate: bvc_vocoder_length(m, T) follows.  A stage that
  * is symmetric and anti-aliased, post_sym with antialias_post, an even resblock kernel size on a symmetric stage and a symmetric stage
  * with BVC_UNFUSED_AMP set are BVC_EINVAL from bvc_model_create.  The same entry points as above work for such a model and the same
- * ones return BVC_EINVAL (bvc_last_error() says "symmetric" unless the model is filtered too). */
+ * ones return BVC_EINVAL (bvc_last_error() says "symmetric" unless the model is filtered too).  A symmetric layer reads as many rows
+ * ahead as behind, a bounded number: bvc_vocoder_stream_create_lookahead runs such a generator incrementally behind that delay (a
+ * filtered one stays refused there too). */
 typedef struct bvc_tensor {
     const char  *name;
     const float *h_data;
@@ -270,6 +272,23 @@ void bvc_vocoder_stream_destroy(bvc_vocoder_stream *st);
 int bvc_vocoder_stream_reset(bvc_vocoder_stream *st, void *stream);
 int bvc_vocoder_stream_push(bvc_vocoder_stream *st, const float *d_mel, int32_t k, float out_scale_div,
                             float *d_wav, void *stream);
+
+/* The same behind a look-ahead window, for generators with symmetric layers (and for causal ones).  A symmetric generator is not
+ * causal, but its look-ahead is bounded: sample t is final once frame (t + D) / hop has arrived, D = bvc_vocoder_lookahead(m) - 0
+ * for a causal model, 3258 samples (148 ms) when every layer of the shipped geometry is symmetric, < 0 for a model that cannot
+ * stream (anti-aliased activations).  On a state made by bvc_vocoder_stream_create_lookahead, bvc_vocoder_stream_push writes the
+ * samples that BECAME final with its k frames - [max(0, hop n_old - D), max(0, hop n_new - D)), dense (B, that many), possibly none
+ * (d_wav may then be NULL) - and bvc_vocoder_stream_flush writes the rest up to bvc_vocoder_length(m, n) with the offline rules of
+ * the signal's end; after it only bvc_vocoder_stream_reset is legal (push and flush: BVC_EINVAL).  A flush without frames writes
+ * nothing.  bvc_vocoder_stream_samples says how many samples per row the next push of k frames (1 <= k <= max_frames_per_push) or,
+ * k == -1, the flush writes: host arithmetic, no synchronisation.  The pushes and the flush, concatenated, equal bvc_bigvgan over the
+ * whole mel bit for bit, however the frames are cut into pushes.  For a causal model every push is the plain state's and the flush
+ * is the (L + 1) u tail behind hop * n (294 samples).  An anti-aliased model is BVC_EINVAL. */
+int64_t bvc_vocoder_lookahead(const bvc_model *m);
+int bvc_vocoder_stream_create_lookahead(const bvc_model *m, int32_t B, int32_t max_frames_per_push,
+                                        bvc_vocoder_stream **out);
+int64_t bvc_vocoder_stream_samples(const bvc_vocoder_stream *st, int32_t k);
+int bvc_vocoder_stream_flush(bvc_vocoder_stream *st, float out_scale_div, float *d_wav, void *stream);
 
 /* Whole-hop streaming codec (BASELINE.json configs[4]; not in the reference, which has no streaming mode): B parallel
  * streams, `hop_samples` new samples per stream and tick (e.g. 441 = 20 ms).  A tick runs the front-end for the frames the
@@ -650,6 +669,15 @@ int bvc_test_vocoder_layer(const bvc_model *m, int32_t kind, int32_t stage, int3
                            const float *d_x, int32_t B, int64_t L, float *d_out, int32_t epi, const float *d_acc,
                            int32_t window, int64_t row_begin, int64_t t_origin, int64_t length, float div,
                            int64_t *out_info, void *stream);
+
+/* ONE symmetric AMP pair (stage, block, iteration) in a look-ahead window, as the incremental generator launches it: d_x (B, L_in, C)
+ * is a window whose row 0 is global time t_origin and whose L_in rows are all the pair may read (rows from L_in on read as zeros,
+ * and S2 is zero behind it as before global time 0); only rows [row_begin, row_end) of d_out (B, L_in, C) are written, 0 <= row_begin
+ * <= row_end <= L_in.  Mid-stream row_end = L_in - (ks-1)(d+1)/2; row_end = L_in is the end of the signal.  epi, d_acc and out_info
+ * as in bvc_test_vocoder_layer.  BVC_EINVAL unless the stage is symmetric. */
+int bvc_test_amp_pair_window(const bvc_model *m, int32_t stage, int32_t block, int32_t iteration, const float *d_x, int32_t B,
+                             int64_t L_in, float *d_out, int32_t epi, const float *d_acc, int64_t row_begin, int64_t row_end,
+                             int64_t t_origin, int64_t *out_info, void *stream);
 
 /* y[i] = SnakeBeta(x[i]) = x + sin(x*exp(alpha))^2 / (exp(beta) + 1e-9)  (activations.py:107-120), through the
  * device routines of the generator kernels (their sin^2 is a hand-written range reduction, not ocml's sinf). */
