@@ -98,6 +98,13 @@ SIGNATURES = {
     "bvc_pack_codes_vbr": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "bvc_unpack_codes_vbr": (ctypes.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "bvc_test_vbr_select": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "bvc_entropy_stride": (_i64, [_i32, _i64]),
+    "bvc_entropy_workspace_bytes": (_sz, [_vp, _i32, _i64]),
+    "bvc_entropy_encode": (ctypes.c_int, [_vp, _vp, _vp, _f, _i32, _i64, _i32, _i64, _vp, _i64, _vp, _vp]),
+    "bvc_entropy_decode": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _f, _i32, _i64, _i32, _i64, _vp, _vp]),
+    "bvc_bvrnn_entropy_pack": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "bvc_bvrnn_entropy_unpack": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "bvc_decode_entropy": (ctypes.c_int, [_vp, _vp, _i64, _vp, _f, _i32, _i64, _i64, _i64, _f, _vp, _vp, _vp, _sz, _vp]),
     "bvc_forward": (ctypes.c_int, [_vp, _vp, _i32, _i64, _f, _f, _i64, _f, _vp, _vp, _vp, _sz, _vp]),
     "bvc_encode_ragged": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _f, _vp, _f, _vp, _vp, _sz, _vp]),
     "bvc_decode_ragged": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _f, _vp, _vp, _sz, _vp]),

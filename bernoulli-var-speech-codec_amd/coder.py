@@ -1,5 +1,6 @@
 """The two sub-operators the reference exposes as attributes of its facade: ``BVRNN`` (``model.bvrnn.encode/decode``, bvrnn.py:163-229)
 and ``BigVGAN`` (``model.vocoder(x, length)``, models.py:207-238), each on the engines of the model it is a part of."""
+import numpy as np
 import torch
 
 from ._abi import ptr
@@ -17,6 +18,34 @@ def _broadcast_target(target, B, T, device):
     elif tuple(t.shape) != (B, T):
         raise ValueError(f"encode_vbr: target must be a scalar, ({B},) or ({B}, {T}), got {tuple(t.shape)}")
     return t.to(device).expand(B, T).contiguous()
+
+
+def _entropy_segments(frames, segment, who):
+    """(S, nseg) of a call of ``frames`` frames cut into segments of ``segment`` (None: the whole call)."""
+    if isinstance(frames, bool) or int(frames) != frames or frames < 1:
+        raise ValueError(f"{who}: frames must be a positive integer, got {frames!r}")
+    segment = frames if segment is None else segment
+    if isinstance(segment, bool) or not isinstance(segment, (int, np.integer)) or segment < 1:
+        raise ValueError(f"{who}: segment must be an integer of at least 1 (frames per independently coded segment), got {segment!r}")
+    S = min(int(segment), int(frames))
+    return S, -(-int(frames) // S)
+
+
+def _check_stream(data, sizes, nseg, who):
+    """The shapes of an entropy-coded stream: data uint8 (B, nseg, stride), sizes an integer tensor (B, nseg)."""
+    if not torch.is_tensor(data) or data.dtype != torch.uint8 or data.dim() != 3:
+        raise ValueError(f"{who}: data must be a uint8 tensor (batch, segments, stride)")
+    if not torch.is_tensor(sizes) or sizes.is_floating_point() or tuple(sizes.shape) != tuple(data.shape[:2]):
+        raise ValueError(f"{who}: sizes must be an integer tensor {tuple(data.shape[:2])} like data's first two dimensions")
+    if data.shape[0] < 1 or data.shape[1] != nseg:
+        raise ValueError(f"{who}: {data.shape[1]} segments given, the frames and the segment length make {nseg}")
+
+
+def _check_frame_bits(bits, B, T, var_bit, who):
+    if var_bit and bits is None:
+        raise ValueError(f"{who}: a variable-rate model needs the bits of every frame (a bitrate, or bits (batch, frames))")
+    if bits is not None and (not torch.is_tensor(bits) or tuple(bits.shape) != (B, T)):
+        raise ValueError(f"{who}: bits must be a tensor ({B}, {T})")
 
 
 class BVRNN(_OnDevice):
@@ -173,6 +202,52 @@ class BVRNN(_OnDevice):
         eng.call("bvc_bvrnn_decode_conceal", eng.handle, ptr(z), ptr(pres, torch.uint8), ptr(d_bits), ptr(h0), B, T, ptr(mel), ptr(hT),
                  ptr(codes), ptr(prior), scratch=(B, T))
         return eng.to_caller(out_dev, mel, hT.unsqueeze(0), *((codes, prior) if return_codes else ()))
+
+    # ---- entropy-coded wire format (include/bvcodec.h): the codes range-coded under the prior net at the decoder's own states
+    @torch.no_grad()
+    def entropy_pack(self, z, bits, h, segment=None, return_prior=False):
+        """z (B,T,z_dim), bits (B,T) or None on a fixed-rate model, h (1,B,h_dim) -> (data uint8 (B, nseg, stride), sizes int32
+        (B, nseg), h_next (1,B,h_dim)) (``bvc_bvrnn_entropy_pack``): segment s of row b is data[b, s, :sizes[b, s]], the frames
+        [s S, (s + 1) S) coded on their own coder, S = ``segment`` (None: all T frames), stride = the safe stride that no segment
+        exceeds.  ``return_prior=True`` adds the probabilities the bits were coded under, (B,T,z_dim)."""
+        if z.dim() != 3 or z.shape[2] != self.z_dim or z.shape[0] < 1:
+            raise ValueError(f"entropy_pack: z must be (B, T, {self.z_dim})")
+        B, T, _ = z.shape
+        S, nseg = _entropy_segments(T, segment, "entropy_pack")
+        _check_frame_bits(bits, B, T, self.varBit, "entropy_pack")
+        eng, out_dev, z = self._enter(z)
+        d_bits = _prep(bits, eng.device) if (bits is not None and self.varBit) else None
+        h0 = _prep(h.reshape(B, self.h_dim), eng.device)
+        stride = int(eng.lib.bvc_entropy_stride(self.z_dim, S))
+        data = torch.empty(B, nseg, stride, dtype=torch.uint8, device=eng.device)
+        sizes = torch.empty(B, nseg, dtype=torch.int32, device=eng.device)
+        hT = torch.empty(B, self.h_dim, device=eng.device)
+        prior = torch.empty(B, T, self.z_dim, device=eng.device) if return_prior else None
+        eng.call("bvc_bvrnn_entropy_pack", eng.handle, ptr(z), ptr(d_bits), ptr(h0), B, T, S, ptr(data, torch.uint8), stride,
+                 ptr(sizes, torch.int32), ptr(hT), ptr(prior), scratch=(B, T, "entropy"))
+        return eng.to_caller(out_dev, data, sizes, hT.unsqueeze(0), *((prior,) if return_prior else ()))
+
+    @torch.no_grad()
+    def entropy_unpack(self, data, sizes, frames, bits, h, segment=None, return_prior=False):
+        """The inverse, and the decoder in one recurrence (``bvc_bvrnn_entropy_unpack``): data (B, nseg, any stride >= max size), sizes
+        (B, nseg), ``frames`` = T, bits (B,T) or None on a fixed-rate model, h (1,B,h_dim) -> (codes (B,T,z_dim), mel (B,T,x_dim),
+        h_next (1,B,h_dim)); with ``return_prior=True`` also the prior's probabilities.  Same ``segment`` as the sender's."""
+        S, nseg = _entropy_segments(frames, segment, "entropy_unpack")
+        _check_stream(data, sizes, nseg, "entropy_unpack")
+        B, T = data.shape[0], int(frames)
+        _check_frame_bits(bits, B, T, self.varBit, "entropy_unpack")
+        eng, out_dev = self.engine(data), data.device
+        data = data.to(eng.device).contiguous()
+        sizes = sizes.detach().to(device=eng.device, dtype=torch.int32).contiguous()
+        d_bits = _prep(bits, eng.device) if (bits is not None and self.varBit) else None
+        h0 = _prep(h.reshape(B, self.h_dim), eng.device)
+        codes = torch.empty(B, T, self.z_dim, device=eng.device)
+        mel = torch.empty(B, T, self.x_dim, device=eng.device)
+        hT = torch.empty(B, self.h_dim, device=eng.device)
+        prior = torch.empty(B, T, self.z_dim, device=eng.device) if return_prior else None
+        eng.call("bvc_bvrnn_entropy_unpack", eng.handle, ptr(data, torch.uint8) if data.numel() else None, data.shape[2],
+                 ptr(sizes, torch.int32), ptr(d_bits), ptr(h0), B, T, S, ptr(codes), ptr(mel), ptr(hT), ptr(prior), scratch=(B, T, "entropy"))
+        return eng.to_caller(out_dev, codes, mel, hT.unsqueeze(0), *((prior,) if return_prior else ()))
 
 
 class BigVGAN(_OnDevice):

@@ -266,6 +266,21 @@ void carve_vbr(const bvc_model *m, int B, int K, char *base, VbrWorkspace *v);
 int run_encode_vbr(const bvc_model *m, const Workspace &w, const VbrWorkspace &v, void *ws_base, const float *d_mel, const float *d_tau,
                    const int *h_ladder, int K, const float *d_h0, int B, int64_t T, float *d_codes, float *d_bits, float *d_all_h,
                    float *d_hT, float *d_prob, float *d_dist, float *d_dec, hipStream_t s, const VbrCap *cap = nullptr);
+// ---- entropy-coded wire format (bvc_bvrnn_entropy_pack / _unpack): its workspace is what the decode node of a frame holds - the coder's
+// state per row and the call's stream, whose size depends on B alone - FOLLOWED by the ordinary workspace of (B, T) and, behind that, the
+// prior's probabilities of all frames (B,T,z_dim): every address a captured step holds is a function of (base, B)
+struct EntropyWorkspace {
+    unsigned *state;            // [B][4]
+    EntropyCall *call;
+    size_t total;               // bytes in front of the ordinary workspace
+    size_t prob_bytes;          // bytes behind it
+};
+void carve_entropy(const bvc_model *m, int B, int64_t T, char *base, EntropyWorkspace *e);
+// The receive program: bvc_bvrnn_decode_conceal's step with every frame's codes decoded from the stream inside the frame.  d_sel (B,T):
+// the bit count of every frame, not below 0 (launch_entropy_bits).  Always the launch-per-layer schedule.
+int run_entropy_unpack(const bvc_model *m, const Workspace &w, const EntropyWorkspace &e, void *ws_base, const EntropyCall &call,
+                       const float *d_sel, const float *d_h0, int B, int64_t T, float *d_codes, float *d_mel, float *d_hT, float *d_prior,
+                       hipStream_t s);
 int run_forward(const bvc_model *m, const Workspace &w, const float *d_mel, const float *d_bits, const uint8_t *h_use_gen, bool update_h,
                 bool update_h2, const float *d_noise, int B, int64_t T, float *d_dec, float *d_kld, float *d_z, float *d_prob,
                 float *d_prior, hipStream_t s);

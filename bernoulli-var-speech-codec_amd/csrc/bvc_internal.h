@@ -393,6 +393,39 @@ int launch_pack_rows_vbr(const float *codes, const float *bits, int B, int k, in
 int launch_unpack_rows_vbr(const unsigned char *in, const unsigned char *present, const int *row_off, int B, int k, int z, int kstride,
                            float *codes, float *bits_out, hipStream_t s);
 
+// ------------------------------------------------------------------ entropy-coded wire format (k_entropy.hip)
+// A binary range coder with carry propagation under the prior net's probabilities: 32-bit range, 33-bit low, 16-bit probabilities
+// q = clamp(rint(p * 65536), 1, 65535) = P(bit = 1), one independent stream per (row, segment of S frames).  Position n of frame t
+// is coded when bits[b, t] > n (the mask rule of EPI_CODE), the coded bit is code > 0.5, a position without a bit decodes to 0.5.
+// data (B, nseg, stride) bytes, sizes (B, nseg) int32, nseg = ceil(T / S); the first emitted byte (always 0) is not stored, trailing
+// zeros are stripped, and the decoder reads 0 at or beyond `size` - so no read leaves a segment and no write its stride.
+inline long long entropy_stride(int z_dim, long long segment) { return 2 * segment * z_dim + segment / 16 + 8; }
+// The caller's stream of one receive call, resident in the call's workspace (like VbrCall: the step is captured once and replayed)
+struct EntropyCall {
+    const unsigned char *data;       // (B, nseg, stride)
+    const int *sizes;                // (B, nseg); an entry outside [0, stride] reads as 0 bytes
+    long long stride;
+    int segment, nseg;
+};
+// The decode node of a frame (OP_ENTROPY_DECODE): p_t from DS_PROB, the row's bit count from DS_BITS, z_t to DS_CODES (natural
+// (B,T,Z) floats); per row the coder's state - code, range, bytes consumed, unused - re-initialised where t % segment == 0
+struct EntropyStep {
+    const CallDesc *desc;
+    const EntropyCall *call;
+    unsigned *state;                 // [B][4]
+    int B, Z;
+};
+int launch_entropy_set_call(EntropyCall *d, const EntropyCall &v, hipStream_t s);
+int launch_entropy_decode_step(const EntropyStep &a, int tstep, hipStream_t s);
+// the coder on given tensors: codes / prob (B,T,Z), bits (B,T) or null = bits_per_frame everywhere.  Encode clears data first; a segment
+// that does not fit `stride` gets size -1
+int launch_entropy_encode(const float *codes, const float *prob, const float *bits, float bits_per_frame, int B, long long T, int Z,
+                          long long segment, unsigned char *data, long long stride, int *sizes, hipStream_t s);
+int launch_entropy_decode(const unsigned char *data, long long stride, const int *sizes, const float *prob, const float *bits,
+                          float bits_per_frame, int B, long long T, int Z, long long segment, float *codes, hipStream_t s);
+// sel (B,T) = the bit count of every frame as the code epilogue's selector takes it: bits (or dflt where null), not below 0
+int launch_entropy_bits(const float *bits, float dflt, long long n, float *sel, hipStream_t s);
+
 // ------------------------------------------------------------------ vocoder (k_vocoder.hip; the AMP pairs: k_vocoder_amp.hip)
 struct ConvLayer {               // one causal conv as implicit GEMM on fp32 MFMA
     int cin;                     // input channels (multiple of 4)

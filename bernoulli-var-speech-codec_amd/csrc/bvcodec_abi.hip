@@ -89,6 +89,46 @@ int enter_vbr(const bvc_model *m, int B, int64_t T, const int32_t *h_ladder, int
     return BVC_OK;
 }
 
+// the checks of an entropy-coded call that need no tensor, in the order in which they are reported; on success the workspaces are carved:
+// the decode node's state, the ordinary workspace behind it, the prior's probabilities behind that (*prob)
+int enter_entropy(const bvc_model *m, int B, int64_t T, int64_t segment, int64_t stride, void *d_ws, size_t ws_bytes, Workspace *w,
+                  EntropyWorkspace *e, float **prob, const char *fn) {
+    if (!m) { set_error("null model"); return BVC_EINVAL; }
+    if (int rc = sticky_status(m)) return rc;
+    if (int rc = need_prior(m, fn)) return rc;
+    if (B <= 0 || T <= 0) { set_error("B and T must be positive (B=%d, T=%lld)", B, (long long)T); return BVC_EINVAL; }
+    if (segment < 1) { set_error("%s: segment = %lld: a segment holds at least one frame", fn, (long long)segment); return BVC_EINVAL; }
+    if (stride < 0 || stride > 0x7FFFFFFFll) { set_error("%s: stride = %lld outside [0, 2^31)", fn, (long long)stride); return BVC_EINVAL; }
+    if (m->cfg.z_dim > 3 * m->cfg.h_dim) { set_error("%s: z_dim > 3 h_dim is not supported", fn); return BVC_EINVAL; }
+    carve_entropy(m, B, T, static_cast<char *>(d_ws), e);
+    carve(m, B, T, static_cast<char *>(d_ws) + e->total, w);
+    const size_t need = e->total + w->total + e->prob_bytes;
+    if (!d_ws || ws_bytes < need) {
+        set_error("%s: workspace too small: %zu bytes given, %zu needed (bvc_entropy_workspace_bytes)", fn, ws_bytes, need);
+        return BVC_ENOMEM;
+    }
+    *prob = reinterpret_cast<float *>(static_cast<char *>(d_ws) + e->total + w->total);
+    return BVC_OK;
+}
+
+// sizes that the host can read (pinned memory) are checked before anything is launched; the kernels take any other bad entry as 0 bytes
+int check_host_sizes(const int32_t *sizes, long long n, int64_t stride, const char *fn) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, sizes) != hipSuccess) { (void)hipGetLastError(); return BVC_OK; }
+    if (at.type != hipMemoryTypeHost) return BVC_OK;
+    for (long long i = 0; i < n; ++i)
+        if (sizes[i] < 0 || sizes[i] > stride) {
+            set_error("%s: sizes[%lld] = %d outside [0, stride = %lld]", fn, i, (int)sizes[i], (long long)stride);
+            return BVC_EINVAL;
+        }
+    return BVC_OK;
+}
+
+EntropyCall entropy_call(const uint8_t *d_data, int64_t stride, const int32_t *d_sizes, int64_t T, int64_t segment) {
+    const int64_t S = segment < T ? segment : T;
+    return EntropyCall{d_data, d_sizes, stride, (int)S, (int)((T + S - 1) / S)};
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -161,6 +201,92 @@ int bvc_decode_conceal(const bvc_model *m, const float *d_codes, const uint8_t *
     hipStream_t s = (hipStream_t)stream;
     if ((rc = launch_conceal_select(d_present, T, nullptr, m->cfg.var_bit ? bits_per_frame : (float)m->cfg.z_dim, nullptr, B, T, w.bits, s))) return rc;
     if ((rc = run_decode_conceal(m, w, d_ws, d_codes, w.bits, nullptr, B, T, w.mel, nullptr, d_codes_out, nullptr, s))) return rc;
+    return run_vocoder(m, w, w.mel, B, T, length, out_scale_div, d_wav, -1, nullptr, nullptr, nullptr, s);
+}
+
+// ---- entropy-coded wire format: the coder on given tensors, the sender's pass, the receive program and the whole decoder
+int64_t bvc_entropy_stride(int32_t z_dim, int64_t segment) {
+    if (z_dim <= 0 || segment < 1) return BVC_EINVAL;
+    return entropy_stride(z_dim, segment);
+}
+
+size_t bvc_entropy_workspace_bytes(const bvc_model *m, int32_t B, int64_t T) {
+    if (!m || B <= 0 || T <= 0) return 0;
+    Workspace w;
+    EntropyWorkspace e;
+    carve(m, B, T, nullptr, &w);
+    carve_entropy(m, B, T, nullptr, &e);
+    return e.total + w.total + e.prob_bytes;
+}
+
+int bvc_entropy_encode(const float *d_codes, const float *d_prob, const float *d_bits, float bits_per_frame, int32_t B, int64_t T,
+                       int32_t z_dim, int64_t segment, uint8_t *d_data, int64_t stride, int32_t *d_sizes, void *stream) {
+    if (!d_codes || !d_prob || !d_sizes || (!d_data && stride > 0)) { set_error("bvc_entropy_encode: null argument"); return BVC_EINVAL; }
+    return launch_entropy_encode(d_codes, d_prob, d_bits, bits_per_frame, B, T, z_dim, segment, d_data, stride, d_sizes, (hipStream_t)stream);
+}
+
+int bvc_entropy_decode(const uint8_t *d_data, int64_t stride, const int32_t *d_sizes, const float *d_prob, const float *d_bits,
+                       float bits_per_frame, int32_t B, int64_t T, int32_t z_dim, int64_t segment, float *d_codes, void *stream) {
+    if (!d_codes || !d_prob || !d_sizes || (!d_data && stride > 0)) { set_error("bvc_entropy_decode: null argument"); return BVC_EINVAL; }
+    if (B > 0 && T > 0 && segment >= 1)
+        if (int rc = check_host_sizes(d_sizes, (long long)B * ((T + (segment < T ? segment : T) - 1) / (segment < T ? segment : T)), stride, "bvc_entropy_decode")) return rc;
+    return launch_entropy_decode(d_data, stride, d_sizes, d_prob, d_bits, bits_per_frame, B, T, z_dim, segment, d_codes, (hipStream_t)stream);
+}
+
+int bvc_bvrnn_entropy_pack(const bvc_model *m, const float *d_codes, const float *d_bits, const float *d_h0, int32_t B, int64_t T,
+                           int64_t segment, uint8_t *d_data, int64_t stride, int32_t *d_sizes, float *d_hT, float *d_prior, void *d_ws,
+                           size_t ws_bytes, void *stream) {
+    const char *fn = "bvc_bvrnn_entropy_pack";
+    Workspace w;
+    EntropyWorkspace e;
+    float *prob = nullptr;
+    int rc = enter_entropy(m, B, T, segment, stride, d_ws, ws_bytes, &w, &e, &prob, fn);
+    if (rc) return rc;
+    if (!d_codes || !d_sizes || (!d_data && stride > 0)) { set_error("%s: null argument", fn); return BVC_EINVAL; }
+    if (m->cfg.var_bit && !d_bits) { set_error("bits per frame required when var_bit=1"); return BVC_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if (d_prior) prob = d_prior;
+    // the concealing pass with every frame present, on whatever schedule the model takes (its probabilities are the same bits on each);
+    // its captured steps are keyed by the ordinary workspace's own base
+    if ((rc = launch_fill(w.bits, -1.0f, (long long)B * T, s))) return rc;
+    if ((rc = run_decode_conceal(m, w, static_cast<char *>(d_ws) + e.total, d_codes, w.bits, d_h0, B, T, w.mel, d_hT, nullptr, prob, s))) return rc;
+    return launch_entropy_encode(d_codes, prob, m->cfg.var_bit ? d_bits : nullptr, (float)m->cfg.z_dim, B, T, m->cfg.z_dim, segment, d_data,
+                                 stride, d_sizes, s);
+}
+
+int bvc_bvrnn_entropy_unpack(const bvc_model *m, const uint8_t *d_data, int64_t stride, const int32_t *d_sizes, const float *d_bits,
+                             const float *d_h0, int32_t B, int64_t T, int64_t segment, float *d_codes, float *d_mel, float *d_hT,
+                             float *d_prior, void *d_ws, size_t ws_bytes, void *stream) {
+    const char *fn = "bvc_bvrnn_entropy_unpack";
+    Workspace w;
+    EntropyWorkspace e;
+    float *prob = nullptr;
+    int rc = enter_entropy(m, B, T, segment, stride, d_ws, ws_bytes, &w, &e, &prob, fn);
+    if (rc) return rc;
+    if (!d_sizes || !d_mel || (!d_data && stride > 0)) { set_error("%s: null argument", fn); return BVC_EINVAL; }
+    if (m->cfg.var_bit && !d_bits) { set_error("bits per frame required when var_bit=1"); return BVC_EINVAL; }
+    const EntropyCall call = entropy_call(d_data, stride, d_sizes, T, segment);
+    if ((rc = check_host_sizes(d_sizes, (long long)B * call.nseg, stride, fn))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = launch_entropy_bits(m->cfg.var_bit ? d_bits : nullptr, (float)m->cfg.z_dim, (long long)B * T, w.bits, s))) return rc;
+    return run_entropy_unpack(m, w, e, d_ws, call, w.bits, d_h0, B, T, d_codes, d_mel, d_hT, d_prior, s);
+}
+
+int bvc_decode_entropy(const bvc_model *m, const uint8_t *d_data, int64_t stride, const int32_t *d_sizes, float bits_per_frame, int32_t B,
+                       int64_t T, int64_t segment, int64_t length, float out_scale_div, float *d_wav, float *d_codes, void *d_ws,
+                       size_t ws_bytes, void *stream) {
+    const char *fn = "bvc_decode_entropy";
+    Workspace w;
+    EntropyWorkspace e;
+    float *prob = nullptr;
+    int rc = enter_entropy(m, B, T, segment, stride, d_ws, ws_bytes, &w, &e, &prob, fn);
+    if (rc) return rc;
+    if (!d_sizes || !d_wav || (!d_data && stride > 0) || length <= 0) { set_error("%s: %s", fn, BAD_LENGTH); return BVC_EINVAL; }
+    const EntropyCall call = entropy_call(d_data, stride, d_sizes, T, segment);
+    if ((rc = check_host_sizes(d_sizes, (long long)B * call.nseg, stride, fn))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = launch_entropy_bits(nullptr, m->cfg.var_bit ? bits_per_frame : (float)m->cfg.z_dim, (long long)B * T, w.bits, s))) return rc;
+    if ((rc = run_entropy_unpack(m, w, e, d_ws, call, w.bits, nullptr, B, T, d_codes, w.mel, nullptr, nullptr, s))) return rc;
     return run_vocoder(m, w, w.mel, B, T, length, out_scale_div, d_wav, -1, nullptr, nullptr, nullptr, s);
 }
 

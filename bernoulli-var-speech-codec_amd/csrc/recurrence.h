@@ -22,15 +22,18 @@ inline Capture capture_state(hipStream_t s, bool report = false) {
 // ---- step_plan.hip ------------------------------------------------------------------------------
 // One operation of a step: a kernel on the main or the side branch, or an event record / wait that
 // forks and joins the two branches (they become graph dependencies under stream capture).
-enum { OP_KERNEL = 0, OP_RECORD = 1, OP_WAIT = 2, OP_VBR_CANDIDATES = 3, OP_VBR_SELECT = 4 };   // _VBR_*: the two kernels of k_vbr.hip (v)
+enum { OP_KERNEL = 0, OP_RECORD = 1, OP_WAIT = 2, OP_VBR_CANDIDATES = 3, OP_VBR_SELECT = 4, OP_ENTROPY_DECODE = 5 };   // _VBR_*: the two kernels of k_vbr.hip (v)
+                                                                  // _ENTROPY_DECODE: the range decoder of a frame, k_entropy.hip (e)
 enum { BR_MAIN = 0, BR_SIDE = 1 };
-struct StepNode { int op; int branch; int event; GemmParams p; int epi; VbrStep v; };
-enum { STEP_ENCODE = 0, STEP_DECODE = 1, STEP_DECODE_PRE = 2, STEP_CONCEAL = 3, STEP_ENCODE_VBR = 4 };   // _PRE: phi_z halves of dec.0 / GRU arrive pre-computed
+struct StepNode { int op; int branch; int event; GemmParams p; int epi; VbrStep v; EntropyStep e; };
+enum { STEP_ENCODE = 0, STEP_DECODE = 1, STEP_DECODE_PRE = 2, STEP_CONCEAL = 3, STEP_ENCODE_VBR = 4, STEP_ENTROPY = 5 };   // _PRE: phi_z halves of dec.0 / GRU arrive pre-computed
                                                                   // _CONCEAL: the concealing decoder - the encode step with the prior net in the encoder's place
                                                                   // _VBR: the encode step with K candidate rungs per frame (build_vbr_step)
+                                                                  // _ENTROPY: the receive program of the entropy-coded wire - the _CONCEAL step with the
+                                                                  //   frame's range decoder behind the code epilogue (`es`)
 enum { STEP_KIND_MASK = 0xF, STEP_FOLD = 0x10, STEP_RUNGS_SHIFT = 8 };   // | STEP_FOLD: the folded hop (step_fold); | K << STEP_RUNGS_SHIFT: the rungs of a
                                                                   // _VBR step (part of the graph-cache key: the candidate launches have K * B rows)
-std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, int kind_and_fold);
+std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, int kind_and_fold, const EntropyStep *es = nullptr);
 std::vector<StepNode> build_vbr_step(const bvc_model *m, const Workspace &w, const VbrWorkspace &vw, int B, int nrungs);
 std::vector<StepNode> build_forward_step(const bvc_model *m, const Workspace &w, int B, int sel, bool greedy, bool update_h, bool update_h2);
 int count_kernels(const std::vector<StepNode> &plan);

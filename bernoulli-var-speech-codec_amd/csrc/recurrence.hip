@@ -261,6 +261,36 @@ int run_decode_conceal(const bvc_model *m, const Workspace &w, void *ws_base, co
     });
 }
 
+// ---- the entropy-coded wire's receive program (bvc_bvrnn_entropy_unpack) -------------------------------
+void carve_entropy(const bvc_model *m, int B, int64_t T, char *base, EntropyWorkspace *e) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    e->state = reinterpret_cast<unsigned *>(base);
+    e->call = reinterpret_cast<EntropyCall *>(base + up((size_t)B * 4 * sizeof(unsigned)));
+    e->total = up((size_t)B * 4 * sizeof(unsigned)) + up(sizeof(EntropyCall));
+    e->prob_bytes = up((size_t)B * (size_t)T * m->cfg.z_dim * sizeof(float));
+}
+
+// The concealing step with one node more (build_step, STEP_ENTROPY): prior.{0,2,4} and the code epilogue are the concealing call's own
+// launches, so p_t is the number the sender coded under; the node decodes z_t from the stream and phi_z goes on from it.  The decoder
+// needs p_t of every frame, so where the caller wants no d_prior it goes to the tail of the workspace.
+int run_entropy_unpack(const bvc_model *m, const Workspace &w, const EntropyWorkspace &e, void *ws_base, const EntropyCall &call,
+                       const float *d_sel, const float *d_h0, int B, int64_t T, float *d_codes, float *d_mel, float *d_hT, float *d_prior,
+                       hipStream_t s) {
+    return end_call(s, [&]() -> int {
+        int rc;
+        if ((rc = launch_entropy_set_call(e.call, call, s))) return rc;
+        CallDesc d;
+        memset(&d, 0, sizeof(d));
+        d.p[DS_CODES] = d_codes ? d_codes : w.part_gru;
+        d.p[DS_BITS] = const_cast<float *>(d_sel);
+        d.p[DS_PROB] = d_prior ? d_prior : reinterpret_cast<float *>(static_cast<char *>(ws_base) + e.total + w.total);
+        const int kind = STEP_ENTROPY | step_fold(m, false);
+        float *mel_out = route_decoder_output(d, w, kind, DS_KEEP_ENC, d_mel);
+        const EntropyStep es{w.desc, e.call, e.state, B, m->cfg.z_dim};
+        return run_layers(m, w, ws_base, d, build_step(m, w, B, kind, &es), kind, d_h0, B, T, d_hT, mel_out, s);
+    });
+}
+
 int run_forward(const bvc_model *m, const Workspace &w, const float *d_mel, const float *d_bits,
                 const uint8_t *h_use_gen, bool update_h, bool update_h2, const float *d_noise, int B, int64_t T,
                 float *d_dec, float *d_kld, float *d_z, float *d_prob, float *d_prior, hipStream_t s) {

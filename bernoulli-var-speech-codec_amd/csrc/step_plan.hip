@@ -119,15 +119,18 @@ namespace bvc {
 //   encode (bvrnn.py:187-206): enc -> sigmoid/round/mask -> phi_z -> dec -> phi_x(norm) -> GRU
 //   decode (bvrnn.py:222-227): [phi_z batched over all frames beforehand] dec -> phi_x(norm) -> GRU
 //   conceal (bvc_bvrnn_decode_conceal): prior -> sigmoid/round/mask, SELECTED against the received codes -> phi_z -> ... as encode
+//   entropy (bvc_bvrnn_entropy_unpack): conceal's step, layer for layer, with the frame's range decoder behind the code epilogue: it
+//     reads p_t (DS_PROB) and overwrites the frame's DS_CODES with the decoded bits, which phi_z then reads
 //   closed-loop rates (bvc_bvrnn_encode_vbr): enc -> sigmoid/round -> K masked candidates -> phi_z -> dec on K * B rows -> select -> ... as encode
 //     (build_vbr_step below; never folded: dec.6 must exist to be measured)
 // Side branch: the halves of the split dot products that do not depend on the current frame's chain -
 // dec.0[:, H:] h, W_hh h + b_hh, W_ih[:, H:] phi_z + b_ih - run concurrently with the chain (which is
 // latency-bound), so the GRU kernel on the critical path only streams W_ih[:, :H].
-std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, int kind_and_fold) {
+std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, int kind_and_fold, const EntropyStep *es) {
     const int kind = kind_and_fold & STEP_KIND_MASK;
     const bool fold = (kind_and_fold & STEP_FOLD) != 0;       // dec.6 -> norm -> phi_x.0 as one layer (bvc_model::px0_dec3)
-    const bool enc_like = kind == STEP_ENCODE || kind == STEP_CONCEAL;    // phi_z is computed inside the step
+    const bool conceal_like = kind == STEP_CONCEAL || kind == STEP_ENTROPY;
+    const bool enc_like = kind == STEP_ENCODE || conceal_like;            // phi_z is computed inside the step
     StepBuilder b(m, w, B, g_kprobe.enabled);
     const int H = b.H, Z = b.Z, X = b.X;
     std::vector<StepNode> &plan = b.plan;
@@ -145,7 +148,7 @@ std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, 
     };
 
     DynPtr pz_final = enc_like ? S(b.pz3, H) : dp_frame(DS_PZ, H, 0, 1);
-    if (kind == STEP_CONCEAL) {
+    if (conceal_like) {
         // p_t = prior(h_t) (bvrnn.py:68-73): no pre-computed half, the first layer's bias is its own; the code epilogue SELECTS between the
         // received codes (DS_NOISE carries them) and the generated bits, by the selector in DS_BITS; p_t goes to DS_PROB
         b.elu(m->prior[0], h_cur, B, b.e1);
@@ -156,6 +159,11 @@ std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, 
         p.y2 = dp_frame(DS_NOISE, Z);
         p.y3 = dp_frame(DS_PROB, Z);
         b.K(p, EPI_CODE);
+        if (kind == STEP_ENTROPY && es) {
+            GemmParams z; memset(&z, 0, sizeof(z));
+            VbrStep v; memset(&v, 0, sizeof(v));
+            plan.push_back(StepNode{OP_ENTROPY_DECODE, BR_MAIN, -1, z, 0, v, *es});
+        }
     }
     if (kind == STEP_ENCODE) {
         b.enc02(h_cur);
@@ -349,6 +357,8 @@ int launch_steps(const bvc_model *m, const std::vector<StepNode> &plan, const Wo
                 if ((rc = launch_vbr_candidates(n.v, k, st))) return rc;
             } else if (n.op == OP_VBR_SELECT) {
                 if ((rc = launch_vbr_select(n.v, k, st))) return rc;
+            } else if (n.op == OP_ENTROPY_DECODE) {
+                if ((rc = launch_entropy_decode_step(n.e, k, st))) return rc;
             } else if (side) {
                 if (n.op == OP_RECORD) BVC_HIP_TRY(hipEventRecord(m->cap_events[n.event], st));
                 else                   BVC_HIP_TRY(hipStreamWaitEvent(st, m->cap_events[n.event], 0));

@@ -17,7 +17,7 @@ from torch import nn
 
 from . import _abi, ragged, weights
 from ._abi import ptr
-from .coder import BVRNN, BigVGAN, _broadcast_target
+from .coder import BVRNN, BigVGAN, _broadcast_target, _check_stream, _entropy_segments
 from .config import DEFAULT_CONFIG, is_causal, load_config, not_causal_message, num_frames
 from .engine import _Engine  # noqa: F401  (importable from here as before)
 from .engine import _codes_dims, _OnDevice, _prep, _trimmed, _wave_dims, _wave_frames
@@ -303,6 +303,89 @@ class BVRNNCodecModel(_OnDevice):
         codes = torch.empty(B, T, Z, device=eng.device)
         eng.call("bvc_unpack_codes", ptr(packed, torch.uint8) if packed.numel() else None, B, T, Z, self.active_bits(bitrate), ptr(codes))
         return eng.to_caller(out_dev, codes, poll=False)
+
+    # ---- entropy-coded wire format: the codes range-coded under the model's prior net (lossless; storage and reliable transport)
+    def _frame_bits(self, who, B, T, bitrate, bits):
+        """The bits of every frame of an entropy-coded call, (B, T) on the CPU, or None on a fixed-rate model: ``bits`` as encode_vbr
+        returns them, or the constant of ``bitrate``."""
+        if bitrate is not None and np.ndim(bitrate.detach().cpu().numpy() if hasattr(bitrate, "detach") else bitrate) != 0:
+            raise ValueError(f"{who}: one bitrate for the whole batch (mixed-length and mixed-rate batches are not supported)")
+        if bits is not None and bitrate is not None:
+            raise ValueError(f"{who}: bitrate or bits, not both")
+        if not self.conf["var_bit"]:
+            return None
+        if bits is None and bitrate is None:
+            raise ValueError(f"{who}: a variable-rate model needs the bitrate (or bits (batch, frames)) the codes were made with")
+        if bits is not None:
+            if not torch.is_tensor(bits) or tuple(bits.shape) != (B, T):
+                raise ValueError(f"{who}: bits must be a tensor ({B}, {T})")
+            return bits
+        return torch.full((B, T), float(self.active_bits(bitrate)))
+
+    def _state(self, h0, B):
+        return torch.zeros(1, B, self.conf["h_dim"]) if h0 is None else h0
+
+    @torch.no_grad()
+    def pack_entropy(self, codes, bitrate=None, bits=None, segment=None, h0=None, return_state=False):
+        """codes (B,T,z_dim) from encode(x, bitrate) - or from encode_vbr, with its ``bits`` - -> (data uint8 (B, nseg, n), sizes int32
+        (B, nseg)): every bit coded under the probability the prior net gives it at the decoder's own state, so a bit costs about
+        -log2 p instead of one stored bit (``bvc_bvrnn_entropy_pack``).  Segment s of row b is data[b, s, :sizes[b, s]]; a segment
+        holds ``segment`` frames (None: the whole call) and is decodable on its own coder, though not without the decoder state its
+        first frame starts from.  n = the largest size in use.  ``h0`` (1,B,h_dim): the decoder's state in front of the first frame
+        (None: zero); ``return_state=True`` adds the state behind the last.  Lossless, for storage and reliable transport: a receiver
+        that misses a segment cannot decode the rest of the row.  The gain depends on the checkpoint's prior and has not been measured
+        on trained weights; an untrained prior can make the stream longer than ``pack``'s."""
+        if codes.dim() != 3 or codes.shape[2] != self.conf["z_dim"] or codes.shape[0] < 1 or codes.shape[1] < 1:
+            raise ValueError(f"pack_entropy: codes must be (batch, frames, {self.conf['z_dim']})")
+        B, T, _ = codes.shape
+        fb = self._frame_bits("pack_entropy", B, T, bitrate, bits)
+        data, sizes, hT = self.bvrnn.entropy_pack(codes, fb, self._state(h0, B), segment=segment)
+        if bool((sizes < 0).any()):
+            raise RuntimeError("pack_entropy: a segment did not fit the safe stride")      # (cannot happen: the stride is a bound)
+        data = data[:, :, :int(sizes.max())].contiguous()
+        return (data, sizes, hT) if return_state else (data, sizes)
+
+    @torch.no_grad()
+    def unpack_entropy(self, data, sizes, frames, bitrate=None, bits=None, segment=None, h0=None, return_mel=False):
+        """Inverse of pack_entropy(): (data, sizes) of ``frames`` frames -> float32 codes (B, frames, z_dim) with 0.5 at the positions
+        without a bit; same ``bitrate`` / ``bits``, ``segment`` and ``h0`` as the sender's (``bvc_bvrnn_entropy_unpack``).  The
+        decoder runs its recurrence to do so: ``return_mel=True`` adds the decoded mel (B, frames, num_mels) and the state behind the
+        last frame (1,B,h_dim)."""
+        if not torch.is_tensor(data) or data.dim() != 3:
+            raise ValueError("unpack_entropy: data must be a uint8 tensor (batch, segments, stride)")
+        _entropy_segments(frames, segment, "unpack_entropy")
+        fb = self._frame_bits("unpack_entropy", data.shape[0], int(frames), bitrate, bits)
+        codes, mel, hT = self.bvrnn.entropy_unpack(data, sizes, frames, fb, self._state(h0, data.shape[0]), segment=segment)
+        return (codes, mel, hT) if return_mel else codes
+
+    @torch.no_grad()
+    def encode_entropy(self, x, bitrate, segment=None):
+        """``encode(x, bitrate)`` followed by ``pack_entropy``: waveforms (batch, samples) -> (data, sizes)."""
+        return self.pack_entropy(self.encode(x, bitrate), bitrate=bitrate, segment=segment)
+
+    @torch.no_grad()
+    def decode_entropy(self, data, sizes, frames, length, bitrate=None, segment=None, return_codes=False):
+        """(data, sizes) of pack_entropy / encode_entropy back to waveforms, as ``decode(unpack_entropy(...), length)`` gives them but
+        with ONE recurrence (``bvc_decode_entropy``): the receive program decodes the codes and the mel in the same frame loop.
+        ``return_codes=True`` returns (wav, codes)."""
+        S, nseg = _entropy_segments(frames, segment, "decode_entropy")
+        _check_stream(data, sizes, nseg, "decode_entropy")
+        B, T, Z = data.shape[0], int(frames), self.conf["z_dim"]
+        if np.ndim(length.detach().cpu().numpy() if hasattr(length, "detach") else length) != 0:
+            raise ValueError("decode_entropy: one length for the whole batch (mixed-length batches are not supported)")
+        self._frame_bits("decode_entropy", B, T, bitrate, None)
+        eng, out_dev = self.engine(data), data.device
+        data = data.to(eng.device).contiguous()
+        sizes = sizes.detach().to(device=eng.device, dtype=torch.int32).contiguous()
+        n = _trimmed(eng.vocoder_length(T), length)
+        if not n:
+            raise ValueError("decode_entropy: a non-empty output is needed (length > 0)")
+        wav = torch.empty(B, n, device=eng.device)
+        codes = torch.empty(B, T, Z, device=eng.device) if return_codes else None
+        bpf = float(self.active_bits(bitrate)) if self.conf["var_bit"] else float(Z)
+        eng.call("bvc_decode_entropy", eng.handle, ptr(data, torch.uint8) if data.numel() else None, data.shape[2], ptr(sizes, torch.int32),
+                 bpf, B, T, S, n, float(SCALING), ptr(wav), ptr(codes), scratch=(B, T, "entropy"))
+        return eng.to_caller(out_dev, wav, *((codes,) if return_codes else ()))
 
     @torch.no_grad()
     def pack_vbr(self, codes, bits):

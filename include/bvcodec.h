@@ -471,6 +471,59 @@ int bvc_decode_conceal(const bvc_model *m, const float *d_codes, const uint8_t *
                        int64_t length, float out_scale_div, float *d_wav, float *d_codes_out, void *d_ws, size_t ws_bytes,
                        void *stream);
 
+/* Entropy-coded wire format (new: the reference has no bit stream).  pack / pack_vbr and the session packets spend one stored bit per
+ * active code bit; here a bit costs about -log2 of the probability the model's prior net (bvrnn.py:68-73) gives it at the decoder's own
+ * state.  Lossless, for storage and reliable transport: a backward-adaptive coder loses synchronism for the rest of a row when a
+ * segment is lost, so lossy transport keeps the fixed wire and concealment.  The rate gain on trained checkpoints has NOT been
+ * measured (the shipped checkpoints are stubs); a prior that does not predict the bits makes the stream LONGER than the fixed wire.
+ * A stream is decodable by the same build on the same architecture only (format tag 0x01, kept in documentation, not in the stream).
+ *
+ * The coder: a binary range coder with carry propagation, 32-bit range, 33-bit low, 16-bit probabilities
+ * q = clamp(rint(p * 65536), 1, 65535) = P(bit = 1), p the float32 probability (round-half-even).  Encoder state low = 0 (64-bit),
+ * range = 0xFFFFFFFF, cache = 0, cache_size = 1.  One bit b under q: bound = (range >> 16) * (65536 - q); b == 0: range = bound, else
+ * low += bound, range -= bound; while range < 2^24: shift_low(), range <<= 8.  shift_low: if (uint32)low < 0xFF000000 or low >> 32:
+ * emit cache + carry, then cache_size - 1 bytes 0xFF + carry (carry = low >> 32), cache = (low >> 24) & 0xFF, cache_size = 0; always
+ * cache_size += 1, low = (low & 0x00FFFFFF) << 8.  End of a segment: five times shift_low; the first emitted byte (always 0) is not
+ * stored, trailing zero bytes are stripped, a segment without a coded bit has 0 bytes.  Decoder: range = 0xFFFFFFFF, code = the first
+ * four stored bytes big-endian, a read at or beyond the segment's size yields 0; one bit: code < bound: 0, range = bound, else 1,
+ * code -= bound, range -= bound; while range < 2^24: code = (code << 8) | next byte, range <<= 8.
+ * What is coded: for frame t of a row the positions n = 0 .. z_dim - 1 in order that carry a bit, bits[b, t] > n (every position on a
+ * fixed-rate model); the coded bit is code > 0.5; a position without a bit is not coded and decodes to 0.5.  Segment s of a row holds
+ * the frames [s S, min((s + 1) S, T)), S = min(segment, T), and starts a fresh coder.  d_data (B, nseg, stride) uint8, d_sizes
+ * (B, nseg) int32, nseg = ceil(T / S); bytes from size to stride are zero.  bvc_entropy_stride(z_dim, segment) =
+ * 2 S z_dim + S / 16 + 8 is a stride no segment exceeds; with a smaller one a segment that does not fit gets size -1 and nothing is
+ * written beyond the stride.  The decoder takes a size outside [0, stride] as 0 bytes (BVC_EINVAL before anything is launched where
+ * d_sizes is pinned host memory).
+ *
+ * bvc_entropy_encode / bvc_entropy_decode: the coder on a GIVEN probability tensor d_prob (B,T,z_dim), no model involved; d_bits (B,T)
+ * or NULL for bits_per_frame everywhere.  z_dim a multiple of 4.
+ * bvc_bvrnn_entropy_pack: bvc_bvrnn_decode_conceal with every frame present - on whatever schedule the model takes - and the encoder
+ * behind it, under that call's prior probabilities.  d_bits (B,T) required when var_bit = 1.  Optional: d_h0, d_hT, d_prior (B,T,z_dim).
+ * bvc_bvrnn_entropy_unpack: the receive program.  The decoder must know prior(h_t) before it knows z_t, and h_{t+1} depends on z_t, so
+ * the range decoder runs INSIDE the frame: the concealing call's step - prior.{0,2,4} and the code epilogue by the same kernel,
+ * parameters and order of summation, so p_t is the sender's number - then one node that decodes z_t from the stream, then phi_z, dec,
+ * the hop and the GRU unchanged.  By induction it visits the sender's states and returns its mel and h_T bit for bit.  Always the
+ * launch-per-layer schedule (cached hipGraph replay, or eager).  d_codes (B,T,z_dim), d_hT, d_prior optional; d_mel (B,T,num_mels).
+ * bvc_decode_entropy: zero state, the receive program, the generator, / out_scale_div - as bvc_decode_conceal is composed.
+ * Workspace of the three model calls: bvc_entropy_workspace_bytes(m, B, T) - NOT bvc_workspace_bytes.  BVC_EMISSING without prior.*;
+ * BVC_EINVAL: segment < 1, stride < 0, z_dim > 3 h_dim, a null argument.  Not supported: streaming sessions, mixed-length batches,
+ * bit counts carried in the stream. */
+int64_t bvc_entropy_stride(int32_t z_dim, int64_t segment);
+size_t bvc_entropy_workspace_bytes(const bvc_model *m, int32_t B, int64_t T);
+int bvc_entropy_encode(const float *d_codes, const float *d_prob, const float *d_bits, float bits_per_frame, int32_t B, int64_t T,
+                       int32_t z_dim, int64_t segment, uint8_t *d_data, int64_t stride, int32_t *d_sizes, void *stream);
+int bvc_entropy_decode(const uint8_t *d_data, int64_t stride, const int32_t *d_sizes, const float *d_prob, const float *d_bits,
+                       float bits_per_frame, int32_t B, int64_t T, int32_t z_dim, int64_t segment, float *d_codes, void *stream);
+int bvc_bvrnn_entropy_pack(const bvc_model *m, const float *d_codes, const float *d_bits, const float *d_h0, int32_t B, int64_t T,
+                           int64_t segment, uint8_t *d_data, int64_t stride, int32_t *d_sizes, float *d_hT, float *d_prior, void *d_ws,
+                           size_t ws_bytes, void *stream);
+int bvc_bvrnn_entropy_unpack(const bvc_model *m, const uint8_t *d_data, int64_t stride, const int32_t *d_sizes, const float *d_bits,
+                             const float *d_h0, int32_t B, int64_t T, int64_t segment, float *d_codes, float *d_mel, float *d_hT,
+                             float *d_prior, void *d_ws, size_t ws_bytes, void *stream);
+int bvc_decode_entropy(const bvc_model *m, const uint8_t *d_data, int64_t stride, const int32_t *d_sizes, float bits_per_frame, int32_t B,
+                       int64_t T, int64_t segment, int64_t length, float out_scale_div, float *d_wav, float *d_codes, void *d_ws,
+                       size_t ws_bytes, void *stream);
+
 /* Mixed-length batches: utterances of their own lengths (and bitrates) in ONE call, each coded exactly as it would be alone.
  * d_lengths / d_frames are DEVICE int64 arrays (B).  The library cannot look at them without synchronising, so validating them is
  * the CALLER's job; the kernels only clamp (lengths into [0, L], frames into [0, T]), and a row too short for the reflect padding
