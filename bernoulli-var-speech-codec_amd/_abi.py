@@ -133,6 +133,9 @@ SIGNATURES = {
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i32)]),
     "bvc_test_linear": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "bvc_test_linear_batched": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "bvc_test_skinny_pick": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_i32)]),
+    "bvc_test_skinny_counts": (ctypes.c_int, [ctypes.POINTER(_i64)]),
+    "bvc_test_linear_tiles": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "bvc_test_tile_plan": (ctypes.c_int, [_i32, _i64, _i32, _i32, _i32, ctypes.POINTER(_i64)]),
     "bvc_test_snakebeta": (ctypes.c_int, [_vp, _i64, _f, _f, _vp, _vp]),
     "bvc_test_stft_logmel": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i32, _f, _vp, _vp]),

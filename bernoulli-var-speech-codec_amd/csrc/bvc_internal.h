@@ -131,6 +131,15 @@ struct GemmParams {
 
 int launch_gemm_skinny(const GemmParams &p, int epi, hipStream_t s, int mtw = 1);
 int skinny_kernels_init();
+// The instantiations of the recurrent-layer kernel (the table in k_gemm.hip) and the rule by which launch_gemm_skinny chooses one:
+// a pure function of the row count, the epilogue, the weight layout, the row tiles per workgroup the caller asks for and the
+// BVC_LATENCY switch (host only, no HIP calls).  mtw of the answer: the row tiles per workgroup of the kernel that runs.
+enum SkinnyId { SK_GRU, SK_GRU_IL, SK_GRU_IL2, SK_GRU_PART, SK_LIN, SK_LIN_LATENCY, SK_LIN2, SK_LIN4, SK_COUNT };
+struct SkinnyPick { SkinnyId id; int mtw; };
+SkinnyPick skinny_pick(int M, int epi, int gate_il, int mtw, bool latency);
+// host-side launches of this process per kernel (tests): [id] one-frame launches, [SK_COUNT + id] multi-frame ones.  A launch
+// captured into a graph counts once, at capture
+void skinny_launch_counts(long long *out);
 int launch_step_advance(CallDesc *d, int by, hipStream_t s);
 int launch_set_desc(CallDesc *d, const CallDesc &v, hipStream_t s);
 

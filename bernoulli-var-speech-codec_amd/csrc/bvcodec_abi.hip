@@ -684,6 +684,43 @@ int bvc_test_linear_batched(const float *d_x, const float *d_w, const float *d_b
     return launch_gemm_batched(d_x, K, d_w, K, d_bias, M, N, K, act, d_y, N, (hipStream_t)stream);
 }
 
+int bvc_test_skinny_pick(int32_t M, int32_t epi, int32_t gate_il, int32_t mtw, int32_t latency, int32_t *out) {
+    if (!out || M < 1 || epi < EPI_LINEAR || epi > EPI_SIGMOID) { set_error("bvc_test_skinny_pick: bad arguments"); return BVC_EINVAL; }
+    if (gate_il && epi != EPI_GRU) { set_error("bvc_test_skinny_pick: gate-interleaved weights are for the GRU launch only"); return BVC_EINVAL; }
+    const SkinnyPick k = skinny_pick(M, epi, gate_il, mtw, latency != 0);
+    out[0] = k.id; out[1] = k.mtw;
+    return BVC_OK;
+}
+
+int bvc_test_skinny_counts(int64_t *out) {
+    if (!out) { set_error("bvc_test_skinny_counts: bad arguments"); return BVC_EINVAL; }
+    long long n[2 * SK_COUNT];
+    skinny_launch_counts(n);
+    for (int i = 0; i < 2 * SK_COUNT; ++i) out[i] = n[i];
+    return BVC_OK;
+}
+
+int bvc_test_linear_tiles(const float *d_x, const float *d_w, const float *d_bias, int32_t M, int32_t N, int32_t K, int32_t act,
+                          int32_t mtw, int32_t frames, float *d_y, void *stream) {
+    // test helper (allocates + synchronises): bvc_test_linear with the caller's row tiles per workgroup, over `frames` frames
+    const char *fn = "bvc_test_linear_tiles";
+    if (K % 16 || N % 16 || K < 16 || N < 16) { set_error("%s: N and K must be multiples of 16", fn); return BVC_EINVAL; }
+    if (frames < 1) { set_error("%s: frames = %d, at least one", fn, frames); return BVC_EINVAL; }
+    if (!d_x || !d_w || !d_y || M < 1 || (long long)M * K > INT32_MAX || (long long)M * N > INT32_MAX) { set_error("%s: bad arguments", fn); return BVC_EINVAL; }
+    float *wp = nullptr;
+    BVC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&wp), (size_t)N * K * sizeof(float)));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = launch_repack_rows(d_w, wp, K, N, K, 0, s);
+    Linear l; l.w = d_w; l.wp = wp; l.b = d_bias; l.in = K; l.out = N;
+    GemmParams p = lin_params(l, dp_static_frames(d_x, K, (long long)M * K), M, dp_static_frames(d_y, N, (long long)M * N));
+    p.frames = frames;                 // 1: the one-frame kernel (which never reads the frame stride), else the frame in grid.y
+    if (!rc) rc = launch_gemm_skinny(p, act ? EPI_ELU : EPI_LINEAR, s, mtw);
+    hipError_t e = hipStreamSynchronize(s);
+    (void)hipFree(wp);
+    if (!rc && e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); rc = BVC_EHIP; }
+    return rc;
+}
+
 int bvc_test_tile_plan(int32_t kind, int64_t rows, int32_t column_blocks, int32_t ks, int32_t mode, int64_t *out) {
     if (!out || kind < 0 || kind > 1) { set_error("bvc_test_tile_plan: bad arguments"); return BVC_EINVAL; }
     const bool last = mode == -1, legacy = mode == 1;

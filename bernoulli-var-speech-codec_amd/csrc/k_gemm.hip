@@ -24,6 +24,7 @@
 //
 // Reference semantics: nn.Linear / nn.ELU / nn.Sigmoid / torch.round / nn.GRU as used at
 // bvrnn.py:44-83,163-229.
+#include <atomic>
 #include <cstdlib>
 
 #include "k_gemm.h"
@@ -335,6 +336,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmParams p, int 
 
 // The instantiations launch_gemm_skinny can choose, listed once: this table is the only place the host names a skinny kernel.
 // `frames` is the multi-frame (MF) twin; the GRU-shaped kernels have none (launch_gemm_skinny refuses frames > 1 for them).
+// The order is SkinnyId's (bvc_internal.h).
 typedef void (*SkinnyFn)(GemmParams, int);
 struct SkinnyKernel {
     int ng, ngrp, nw, mtw;
@@ -344,7 +346,6 @@ struct SkinnyKernel {
 #define BVC_SKINNY(NG, NGRP, NW, U, MTW, GIL, FRAMES) \
     {NG, NGRP, NW, MTW, gemm_skinny_kernel<NG, NGRP, NW, U, MTW, GIL, false>, FRAMES}
 #define BVC_SKINNY_LIN(U, MTW) BVC_SKINNY(1, 1, 8, U, MTW, false, (gemm_skinny_kernel<1, 1, 8, U, MTW, false, true>))
-enum SkinnyId { SK_GRU, SK_GRU_IL, SK_GRU_IL2, SK_GRU_PART, SK_LIN, SK_LIN_LATENCY, SK_LIN2, SK_LIN4, SK_COUNT };
 static const SkinnyKernel SKINNY_KERNELS[SK_COUNT] = {
     BVC_SKINNY(3, 2, 8, 1, 1, false, nullptr),           // SK_GRU       natural weights
     BVC_SKINNY(3, 2, 8, 1, 1, true, nullptr),            // SK_GRU_IL    gate-interleaved weights
@@ -376,6 +377,42 @@ int skinny_kernels_init() {
 // mtw = row tiles (of 16) per workgroup: 1 maximises the number of workgroups (lowest latency of a single
 // dependent chain), 2 / 4 share every weight fragment among more rows (less L2->CU traffic: higher
 // throughput when several independent chains run concurrently).
+// How many k-blocks a wave keeps in flight is a trade between one chain and several: chunks of 4 give the shortest
+// single launch (4.0 us, 4,180 audio-s/s on one stream) but their load bursts crowd out the other streams' kernels.
+// With FOUR chains in flight: chunks of 4 -> 6,750 audio-s/s, of 2 -> 6,830 (one stream 4,080), of 1 -> 6,850 (3,850);
+// with three chains the spread was 6,100 / 6,100 / 6,270.  Default: chunks of 2 (1 at K = 2048, 12 waves);
+// BVC_LATENCY=1 (`latency`) selects the single-chain optimum.
+// EIGHT waves everywhere: a wave is one chunk of the summation order (head of this file), so the wave count is part of the result.
+// (Round 1 ran the GRU launch and the K = 2048 layers on 12 / 16 waves for 2 % more throughput with three chains in flight.)
+SkinnyPick skinny_pick(int M, int epi, int gate_il, int mtw, bool latency) {
+    const int m_tiles = M / 16 + (M % 16 != 0);              // (no M + 15: the test entry passes any M on)
+    if (mtw > m_tiles) mtw = m_tiles >= 4 ? 4 : (m_tiles >= 2 ? 2 : 1);
+    if (mtw != 2 && mtw != 4) mtw = 1;
+    SkinnyId id;
+    if (epi == EPI_GRU) {
+        // chunks of ONE k-block in flight: a workgroup that bursts 8 KiB of loads per wave only queues them (tools/gru_splitk_bench.hip)
+        if (!gate_il)      id = SK_GRU;
+        else if (mtw >= 2) id = SK_GRU_IL2;               // (mtw 4: two row tiles per workgroup here - four sets of partial tiles exceed the LDS)
+        else               id = SK_GRU_IL;
+    } else if (epi == EPI_GRU_PART) {
+        id = SK_GRU_PART;
+    } else {
+        // mtw 1: chunks of 4 k-blocks (52 VGPRs) measured 2 % faster than chunks of 8 (88 VGPRs), alone and
+        // with three chains in flight
+        if (mtw == 4)      id = SK_LIN4;
+        else if (mtw == 2) id = SK_LIN2;
+        else               id = latency ? SK_LIN_LATENCY : SK_LIN;
+    }
+    return {id, SKINNY_KERNELS[id].mtw};
+}
+
+// what launch_gemm_skinny launched in this process (tests): see skinny_launch_counts in bvc_internal.h
+static std::atomic<long long> g_skinny_launches[2 * SK_COUNT];
+
+void skinny_launch_counts(long long *out) {
+    for (int i = 0; i < 2 * SK_COUNT; ++i) out[i] = g_skinny_launches[i].load(std::memory_order_relaxed);
+}
+
 int launch_gemm_skinny(const GemmParams &p, int epi, hipStream_t s, int mtw) {
     if (p.M <= 0) return BVC_OK;
     if (p.N % 16) { set_error("gemm_skinny: N=%d not a multiple of 16", p.N); return BVC_EINVAL; }
@@ -397,36 +434,13 @@ int launch_gemm_skinny(const GemmParams &p, int epi, hipStream_t s, int mtw) {
         if (epi == EPI_GRU || epi == EPI_GRU_PART) { set_error("gemm_skinny: a multi-frame launch has no GRU epilogue (frames=%d)", p.frames); return BVC_EINVAL; }
     }
     if (nb != p.nb_total) { set_error("gemm_skinny: nb_total %d does not match the segments (%d)", p.nb_total, nb); return BVC_EINVAL; }
-    const int m_tiles = (p.M + 15) / 16;
-    if (mtw > m_tiles) mtw = m_tiles >= 4 ? 4 : (m_tiles >= 2 ? 2 : 1);
-    if (mtw != 2 && mtw != 4) mtw = 1;
-    // How many k-blocks a wave keeps in flight is a trade between one chain and several: chunks of 4 give the shortest
-    // single launch (4.0 us, 4,180 audio-s/s on one stream) but their load bursts crowd out the other streams' kernels.
-    // With FOUR chains in flight: chunks of 4 -> 6,750 audio-s/s, of 2 -> 6,830 (one stream 4,080), of 1 -> 6,850 (3,850);
-    // with three chains the spread was 6,100 / 6,100 / 6,270.  Default: chunks of 2 (1 at K = 2048, 12 waves);
-    // BVC_LATENCY=1 selects the single-chain optimum.
     static const bool latency_mode = getenv("BVC_LATENCY") != nullptr && getenv("BVC_LATENCY")[0] == '1';
     ProbeScope probe((epi == EPI_GRU || epi == EPI_GRU_PART) ? PK_GRU : PK_LINEAR, s);
     if (p.gate_il && epi != EPI_GRU) { set_error("gemm_skinny: gate-interleaved weights are for the GRU launch only"); return BVC_EINVAL; }
-    // EIGHT waves everywhere: a wave is one chunk of the summation order (head of this file), so the wave count is part of the result.
-    // (Round 1 ran the GRU launch and the K = 2048 layers on 12 / 16 waves for 2 % more throughput with three chains in flight.)
-    SkinnyId id;
-    if (epi == EPI_GRU) {
-        // chunks of ONE k-block in flight: a workgroup that bursts 8 KiB of loads per wave only queues them (tools/gru_splitk_bench.hip)
-        if (!p.gate_il)    id = SK_GRU;
-        else if (mtw >= 2) id = SK_GRU_IL2;               // (mtw 4: two row tiles per workgroup here - four sets of partial tiles exceed the LDS)
-        else               id = SK_GRU_IL;
-    } else if (epi == EPI_GRU_PART) {
-        id = SK_GRU_PART;
-    } else {
-        // mtw 1: chunks of 4 k-blocks (52 VGPRs) measured 2 % faster than chunks of 8 (88 VGPRs), alone and
-        // with three chains in flight
-        if (mtw == 4)      id = SK_LIN4;
-        else if (mtw == 2) id = SK_LIN2;
-        else               id = latency_mode ? SK_LIN_LATENCY : SK_LIN;
-    }
+    const SkinnyId id = skinny_pick(p.M, epi, p.gate_il, mtw, latency_mode).id;
     launch_skinny(SKINNY_KERNELS[id], p, epi, s);
     BVC_HIP_TRY(hipGetLastError());
+    g_skinny_launches[(p.frames > 1 ? SK_COUNT : 0) + id].fetch_add(1, std::memory_order_relaxed);
     return BVC_OK;
 }
 

@@ -686,6 +686,19 @@ int bvc_test_linear(const float *d_x, const float *d_w, const float *d_bias, int
 /* same contract through the batched (all-frames) GEMM kernel */
 int bvc_test_linear_batched(const float *d_x, const float *d_w, const float *d_bias, int32_t M,
                             int32_t N, int32_t K, int32_t act, float *d_y, void *stream);
+/* Which instantiation of the recurrent-step kernel a launch of M rows takes (host arithmetic only: needs no GPU).  epi: 0 linear, 1 ELU,
+ * 2 code, 3 mel, 4 GRU, 5 GRU with side-branch parts, 6 sigmoid; gate_il: gate-interleaved weights (GRU only); mtw: the row tiles of 16
+ * per workgroup asked for (BVC_MTW); latency: BVC_LATENCY=1.  out[2] = the kernel (0 SK_GRU, 1 SK_GRU_IL, 2 SK_GRU_IL2, 3 SK_GRU_PART,
+ * 4 SK_LIN, 5 SK_LIN_LATENCY, 6 SK_LIN2, 7 SK_LIN4) and the row tiles per workgroup it runs. */
+int bvc_test_skinny_pick(int32_t M, int32_t epi, int32_t gate_il, int32_t mtw, int32_t latency, int32_t *out);
+/* Host-side launches of the recurrent-step kernel in this process so far: out[16], [k] the one-frame launches of kernel k (numbered as
+ * above), [8 + k] its multi-frame launches (several frames in one grid).  A launch captured into a graph counts once, at capture. */
+int bvc_test_skinny_counts(int64_t *out);
+/* bvc_test_linear with the caller's row tiles per workgroup (mtw; clamped by the row count as in the path) over `frames` independent
+ * frames: d_x (frames, M, K) -> d_y (frames, M, N); frames > 1 is ONE multi-frame launch.  BVC_EINVAL, with nothing launched, if N or K
+ * is no multiple of 16 or frames < 1. */
+int bvc_test_linear_tiles(const float *d_x, const float *d_w, const float *d_bias, int32_t M, int32_t N, int32_t K, int32_t act,
+                          int32_t mtw, int32_t frames, float *d_y, void *stream);
 /* How a launch is cut into tiles (host arithmetic only: needs no GPU).  kind 0: the batched GEMM over rows x (column_blocks *
  * 128) outputs; 1: the offline AMP pair of the C = 64 stage over rows output rows x column_blocks batch items with ks taps.  mode 0: the planned cut, 1: the cut of before the plan (BVC_TILE_CUT=legacy), >= 16: that tile height forced (height 0
  * comes back if it is not compiled), -1: what the last launch of that kind in this process used (other arguments ignored).
