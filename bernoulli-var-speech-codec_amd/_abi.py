@@ -121,6 +121,10 @@ SIGNATURES = {
     "bvc_resampler_count": (_i64, [_i32, _i32, _i64]),
     "bvc_resampler_lag": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "bvc_resampler_taps": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(ctypes.c_double), _i32]),
+    "bvc_resampler_create_multi": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(_i32), _i32, _i32, ctypes.POINTER(_i32), _i32, _i32, ctypes.POINTER(_vp)]),
+    "bvc_resampler_set_taps_rate": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(ctypes.c_double), _i32]),
+    "bvc_resampler_open_rate": (ctypes.c_int, [_vp, _i32, _i32, _i32]),
+    "bvc_resampler_push_multi": (ctypes.c_int, [_vp, _vp, _i64, ctypes.POINTER(_i32), _vp, _i64, _i64, ctypes.POINTER(_i32), _vp]),
     "bvc_pack_codes": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _vp, _vp]),
     "bvc_unpack_codes": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _vp, _vp]),
     "bvc_probe_begin": (ctypes.c_int, [_i32, _i32, _i32]),

@@ -4,7 +4,7 @@ import weakref
 import torch
 
 from . import _abi
-from .resampling import PCM_DTYPES, StreamResampler
+from .resampling import PCM_DTYPES, MultiRateResampler, StreamResampler
 from .stream_plans import client_finish_plan
 
 
@@ -52,10 +52,26 @@ class _ClientRate:
             for b in range(self.B):
                 self.opened(b)
 
+    def slot_rate(self, slot):
+        """The client rate, the client hop and the send side's lag of a slot: the session's (``_MixedClientRate``: the slot's own)."""
+        return self.rate
+
+    def slot_hop(self, slot):
+        return self.hop
+
+    def slot_lag(self, slot):
+        return self.lag
+
+    def _open_in(self, slot):
+        self.rs_in.open(slot, 0)
+
+    def _open_out(self, slot, offset):
+        self.rs_out.open(slot, offset)
+
     def opened(self, slot):
         if self.rs_in is not None:
             self.rs_in.close(slot)
-            self.rs_in.open(slot, 0)
+            self._open_in(slot)
             self.open_push[slot] = self.n_push
             self.ending.pop(slot, None)
             self.carry.pop(slot, None)
@@ -83,11 +99,12 @@ class _ClientRate:
         slot, n_last = int(slot), int(n_last)
         if not 0 <= slot < self.B or self.sc.slot_state(slot) != "running" or slot in self.ending or slot in self.carry:
             raise ValueError(f"finish: slot {slot} is not a running stream")
-        if not 0 <= n_last <= self.hop:
-            raise ValueError(f"finish: n_last {n_last} outside 0..{self.hop}")
+        hop = self.slot_hop(slot)
+        if not 0 <= n_last <= hop:
+            raise ValueError(f"finish: n_last {n_last} outside 0..{hop}")
         push = self.n_push - self.open_push[slot]              # the coming push, counted from the stream's first
         c = self.conf
-        len_s, at, n22 = client_finish_plan(push * self.hop + n_last, self.hop, self.rate, c["fs"])
+        len_s, at, n22 = client_finish_plan(push * hop + n_last, hop, self.slot_rate(slot), c["fs"])
         if len_s <= c["winsize"] - c["hopsize"] - c["mel_pad_left"]:
             raise ValueError(f"finish: a stream of {len_s} internal samples is too short for the right reflect padding")
         self.rs_in.end(slot, n_last)
@@ -99,8 +116,13 @@ class _ClientRate:
         if tuple(x.shape) != (self.B, self.hop) or x.dtype != PCM_DTYPES[self.fmt]:
             raise ValueError(f"push: expected a {PCM_DTYPES[self.fmt]} tensor ({self.B}, {self.hop})")
         x = x.to(self.dev).contiguous()
+        self._end_streams(self.rs_in.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt]), self.hop, self.hop, _abi.addr(self.d_in), self.hop_in, 0,
+                                              self.stream.cuda_stream))
+        self.n_push += 1
+
+    def _end_streams(self, counts):
+        """Behind the input side's push (``counts``: what it gave every row): the tails of the rows that end."""
         rs, hop22, s = self.rs_in, self.hop_in, self.stream.cuda_stream
-        counts = rs.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt]), self.hop, self.hop, _abi.addr(self.d_in), hop22, 0, s)
         for slot, (frm, n) in list(self.carry.items()):        # the rest of a tail that spilled: the row is idle, its hop zeros
             self.d_in[slot, :n].copy_(self.tail[slot, frm:frm + n], non_blocking=True)
             self.sc._finish(slot, n)
@@ -117,7 +139,6 @@ class _ClientRate:
                 self.d_in[slot, e:].copy_(self.tail[slot, :hop22 - e], non_blocking=True)
                 self.carry[slot] = (hop22 - e, n22)
             del self.ending[slot]
-        self.n_push += 1
 
     def drain(self, k):
         """The tick's k frames of d_wav -> client samples: (wav (B, n_max) view, counts (B,) int64 CPU tensor); None on a send session."""
@@ -126,10 +147,18 @@ class _ClientRate:
             return None
         if k == 0:
             return torch.empty(self.B, 0, dtype=PCM_DTYPES[self.fmt], device=self.dev), torch.zeros(self.B, dtype=torch.int64)
+        self._start_and_end_out()
+        n = k * self.spf
+        counts = rs.push_raw(self.wav_ptr, n, n, _abi.addr(self.cwav, PCM_DTYPES[self.fmt]), self.cwav.shape[1], 0, self.stream.cuda_stream)
+        return self.cwav[:, :-(-n * rs.up // rs.down)], torch.tensor(counts, dtype=torch.int64)
+
+    def _start_and_end_out(self):
+        """In front of the output side's push: the rows whose stream starts or ends inside the tick's frames."""
+        rs = self.rs_out
         for slot in list(self.out_wait):                       # a row's resampler starts with its stream's frame 0
             first, count, frame0 = self.sc.slot_frames(slot)
             if count > 0 and frame0 == 0:
-                rs.open(slot, self.spf * first)
+                self._open_out(slot, self.spf * first)
                 self.out_wait.discard(slot)
         for slot in list(self.out_drain):                      # ... and ends with its last one (the last lag' samples stay inside)
             if self.sc.slot_state(slot) == "idle":
@@ -139,6 +168,82 @@ class _ClientRate:
                     rs.running.discard(slot)
                 self.out_drain.discard(slot)
                 self.out_wait.discard(slot)                    # (a stream that ended before its frame 0 came out)
-        n = k * self.spf
-        counts = rs.push_raw(self.wav_ptr, n, n, _abi.addr(self.cwav, PCM_DTYPES[self.fmt]), self.cwav.shape[1], 0, self.stream.cuda_stream)
-        return self.cwav[:, :-(-n * rs.up // rs.down)], torch.tensor(counts, dtype=torch.int64)
+
+
+class _MixedClientRate(_ClientRate):
+    """What ``StreamingCodec(client_rate=(8000, 16000, 48000))`` adds to a session: ``_ClientRate`` with a client rate PER SLOT, one of
+    the 1 .. 8 listed, given to ``open(slot, ..., client_rate=fs)`` and fixed until the slot is opened again (``open_all``: the first
+    listed).  One ``MultiRateResampler`` on either side resamples all rows in the one launch per direction the single-rate session
+    has.  ``hop`` counts INTERNAL samples - there is no single client rate to count in - and every listed rate must give a whole client
+    hop (``hop * rate % 22050 == 0``); slot b's client hop is ``slot_hop(b) = hop * slot_rate(b) / 22050`` and its send-side lag
+    ``slot_lag(b)``.  ``push(x)`` takes (batch, the largest client hop) and reads the first ``slot_hop(b)`` samples of row b;
+    ``finish(slot, n_last)`` counts the slot's own client samples (``client_finish_plan`` at its rate); on the receive side ``n_max``
+    is the fastest listed rate's.  The format is the session's.  The contract: a slot at rate r gives - packets, codes, samples and
+    counts, bit for bit - what the same stream gives in a session ``client_rate=r`` of the same format, whatever the other slots
+    speak, so ``_ClientRate``'s offline contracts hold per slot.  (A listed 22050 goes through the resampler like any other rate -
+    the unit impulse, 11 samples of lag - as ``client_rate=22050, sample_format="s16"`` does.)
+
+    Per slot the adapter keeps the index of the rate, and what ``_ClientRate`` keeps: the tail buffer (as wide as the largest lag) and
+    the carry."""
+
+    def __init__(self, session, conf, rates, fmt, hop, open_all):
+        sc = self.sc = weakref.proxy(session)
+        self.conf, self.rates, self.fmt, self.hop_in = conf, tuple(rates), fmt, hop
+        self.B, self.dev, self.spf, self.stream, self.d_in, self.wav_ptr = sc.B, sc.dev, sc.spf, sc.stream, sc._in, sc._wav_ptr
+        self.n_push, self.open_push, self.ending, self.carry = 0, [0] * self.B, {}, {}
+        self.out_wait, self.out_drain = set(), set()
+        self.rate_of = [0] * self.B                            # slot -> the index of its rate
+        self.rs_in = self.rs_out = None
+        fs = conf["fs"]
+        if sc.direction != "recv":
+            self.hops = [hop * r // fs for r in rates]         # the client hop at every rate
+            self.hop = max(self.hops)                          # the row that push takes
+            self.rs_in = MultiRateResampler(self.B, rates, fs, "in", self.hops, fmt, "f32", delayed=True, device=self.dev)
+            self.lags = self.rs_in.lag
+            self.tail = torch.zeros(self.B, max(1, max(self.lags)), device=self.dev)
+        if sc.direction != "send":
+            self.rs_out = MultiRateResampler(self.B, rates, fs, "out", sc.kmax * self.spf, "f32", fmt, device=self.dev)
+            self.cwav = torch.zeros(self.B, max(1, max(self.rs_out.max_out)), dtype=PCM_DTYPES[fmt], device=self.dev)
+        if open_all:
+            for b in range(self.B):
+                self.opened(b, self.rates[0])
+
+    def slot_rate(self, slot):
+        return self.rates[self.rate_of[slot]]
+
+    def slot_hop(self, slot):
+        return self.hops[self.rate_of[slot]]
+
+    def slot_lag(self, slot):
+        return self.lags[self.rate_of[slot]]
+
+    def _open_in(self, slot):
+        self.rs_in.open(slot, self.slot_rate(slot), 0)
+
+    def _open_out(self, slot, offset):
+        self.rs_out.open(slot, self.slot_rate(slot), offset)
+
+    def opened(self, slot, rate):
+        self.rate_of[slot] = self.rates.index(rate)
+        super().opened(slot)
+
+    def feed(self, x):
+        """A hop of every client's samples -> d_in: row b's first ``slot_hop(b)`` samples are read, every row gets a whole internal hop."""
+        if tuple(x.shape) != (self.B, self.hop) or x.dtype != PCM_DTYPES[self.fmt]:
+            raise ValueError(f"push: expected a {PCM_DTYPES[self.fmt]} tensor ({self.B}, {self.hop})")
+        x = x.to(self.dev).contiguous()
+        self._end_streams(self.rs_in.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt]), self.hop, self.hops, _abi.addr(self.d_in), self.hop_in, 0,
+                                              self.stream.cuda_stream))
+        self.n_push += 1
+
+    def drain(self, k):
+        """The tick's k frames of d_wav -> every client's samples; n_max is the fastest listed rate's."""
+        rs = self.rs_out
+        if rs is None:
+            return None
+        if k == 0:
+            return torch.empty(self.B, 0, dtype=PCM_DTYPES[self.fmt], device=self.dev), torch.zeros(self.B, dtype=torch.int64)
+        self._start_and_end_out()
+        n = [k * self.spf] * len(self.rates)
+        counts = rs.push_raw(self.wav_ptr, n[0], n, _abi.addr(self.cwav, PCM_DTYPES[self.fmt]), self.cwav.shape[1], 0, self.stream.cuda_stream)
+        return self.cwav[:, :rs.out_len(n)], torch.tensor(counts, dtype=torch.int64)

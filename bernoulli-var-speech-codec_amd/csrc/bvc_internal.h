@@ -324,15 +324,24 @@ __host__ __device__ inline long long rs_count(long long n, int up, int down, int
     const long long c = rs_ceil_mul(n, up, down);
     return delayed ? c : (c > n_pre_remove ? c - n_pre_remove : 0);
 }
-struct RsRow { long long n; int run, start, valid, pad_; };     // device state of a row: inputs so far; running; where it starts in the
-                                                                // next chunk; how many of that chunk's samples are its (-1: all)
+struct RsRow { long long n; int run, start, valid, rate; };      // device state of a row: inputs so far; running; where it starts in the
+                                                                // next chunk; how many of that chunk's samples are its (-1: all); the
+                                                                // index of its filter in a multi-rate resampler's table (else 0)
 const int RS_LIST = 64;                                         // row changes per launch: they travel as a kernel argument
-struct RsUpdate { int row, run, start, valid, reset, pad_[3]; };
+struct RsUpdate { int row, run, start, valid, reset, rate, pad_[2]; };    // rate: taken over where reset is set (the row is opened)
 struct RsUpdateList { int n; int pad_[3]; RsUpdate e[RS_LIST]; };
 struct RsFilter { const double *h; int ntaps, up, down, n_pre_remove, H; };      // H = ceil(ntaps / up) inputs of history per row
 struct RsCall { const void *x; long long xs; void *y; long long ys, yoff; int n_in, n_fill, fmt_in, fmt_out, delayed, flush_row; };
+// a multi-rate resampler: one filter per rate, the row's index in RsRow.rate; the rows' histories lie H_max = max H apart.  A call has
+// a chunk length and an output block per rate, n_fill[r] = ceil(n_in[r] up_r / down_r); every row's block is written up to n_fill_max
+// (a flush: the row's rest, n_fill_max samples)
+const int RS_MAX_RATES = 8;
+struct RsFilterTable { RsFilter f[RS_MAX_RATES]; int n; };
+struct RsCallMulti { const void *x; long long xs; void *y; long long ys, yoff; int n_in[RS_MAX_RATES], n_fill[RS_MAX_RATES];
+                     int n_fill_max, H_max, fmt_in, fmt_out, delayed, flush_row; };
 int launch_rs_update(const RsUpdateList &l, RsRow *ctl, float *hist, int H, hipStream_t s);
 int launch_rs_push(const RsFilter &f, const RsCall &c, RsRow *ctl, float *hist, int B, hipStream_t s);
+int launch_rs_push_multi(const RsFilterTable &t, const RsCallMulti &c, int lds_floats, RsRow *ctl, float *hist, int B, hipStream_t s);
 
 int launch_pack_codes(const float *codes, long long frames, int z, int nbits, unsigned char *out, hipStream_t s);
 int launch_unpack_codes(const unsigned char *in, long long frames, int z, int nbits, float *codes, hipStream_t s);

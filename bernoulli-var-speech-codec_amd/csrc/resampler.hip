@@ -1,5 +1,6 @@
 // bvc_resampler_* (include/bvcodec.h): the host side of the streaming resampler - the filter design, the rows' book and the two
-// launches of a push.  Host only; the kernels are in k_resample_stream.hip.
+// launches of a push - for the single-rate object and for the multi-rate one (a filter per rate, a rate per row), which share the
+// book, close / end / flush and the update launch.  Host only; the kernels are in k_resample_stream.hip.
 #include <cmath>
 
 #include "bvc_internal.h"
@@ -116,11 +117,18 @@ struct bvc_resampler {
     double *d_h = nullptr;
     float *d_hist = nullptr;
     RsRow *d_ctl = nullptr;
-    // the book: what the device holds for a row once the pending changes have been sent
-    struct Row { int state = ROW_IDLE; long long n = 0; int start = 0, valid = -1; bool dirty = false, reset = false; };
+    int hist_stride = 0;                                     // floats between two rows' histories: g.H, or the largest H of the table
+    // a multi-rate object (bvc_resampler_create_multi): n_rates > 0 filters, one per rate, and max_in per rate; g, d_h, max_in unused
+    int n_rates = 0;
+    Geometry gs[RS_MAX_RATES] = {};
+    int max_ins[RS_MAX_RATES] = {};
+    double *d_hs[RS_MAX_RATES] = {};
+    // the book: what the device holds for a row once the pending changes have been sent (rate: the row's filter, from open to idle)
+    struct Row { int state = ROW_IDLE; long long n = 0; int start = 0, valid = -1; bool dirty = false, reset = false; int rate = 0; };
     std::vector<Row> rows;
     int n_dirty = 0;
     ~bvc_resampler() {
+        for (double *p : d_hs) if (p) (void)hipFree(p);
         if (d_h) (void)hipFree(d_h);
         if (d_hist) (void)hipFree(d_hist);
         if (d_ctl) (void)hipFree(d_ctl);
@@ -135,6 +143,18 @@ int row_arg(const bvc_resampler *r, int row, const char *fn) {
     return BVC_OK;
 }
 
+// the filter and the longest chunk of a row: the object's own, or on a multi-rate object those of the row's rate
+const Geometry &geometry_of(const bvc_resampler *r, const bvc_resampler::Row &w) { return r->n_rates ? r->gs[w.rate] : r->g; }
+int max_in_of(const bvc_resampler *r, const bvc_resampler::Row &w) { return r->n_rates ? r->max_ins[w.rate] : r->max_in; }
+
+// open, push and set_taps come in a single-rate and a multi-rate form: BVC_EINVAL for the form that is not the object's
+int kind_arg(const bvc_resampler *r, bool multi, const char *fn, const char *other) {
+    if (!r) { set_error("%s: null resampler", fn); return BVC_EINVAL; }
+    if ((r->n_rates > 0) == multi) return BVC_OK;
+    set_error("%s: a %s resampler takes %s", fn, multi ? "single-rate" : "multi-rate", other);
+    return BVC_EINVAL;
+}
+
 void mark(bvc_resampler *r, bvc_resampler::Row &w) {
     if (!w.dirty) { w.dirty = true; ++r->n_dirty; }
 }
@@ -146,19 +166,46 @@ int send_changes(bvc_resampler *r, hipStream_t s) {
     for (int b = 0; b < r->B && r->n_dirty > 0; ++b) {
         bvc_resampler::Row &w = r->rows[b];
         if (!w.dirty) continue;
-        l.e[l.n++] = RsUpdate{b, w.state == ROW_RUNNING ? 1 : 0, w.start, w.valid, w.reset ? 1 : 0, {0, 0, 0}};
+        l.e[l.n++] = RsUpdate{b, w.state == ROW_RUNNING ? 1 : 0, w.start, w.valid, w.reset ? 1 : 0, w.rate, {0, 0}};
         w.dirty = w.reset = false;
         --r->n_dirty;
         if (l.n == RS_LIST) {
-            if (int rc = launch_rs_update(l, r->d_ctl, r->d_hist, r->g.H, s)) return rc;
+            if (int rc = launch_rs_update(l, r->d_ctl, r->d_hist, r->hist_stride, s)) return rc;
             l.n = 0;
         }
     }
     r->n_dirty = 0;
-    return launch_rs_update(l, r->d_ctl, r->d_hist, r->g.H, s);
+    return launch_rs_update(l, r->d_ctl, r->d_hist, r->hist_stride, s);
 }
 
 RsFilter filter_of(const bvc_resampler *r) { return RsFilter{r->d_h, r->g.ntaps, r->g.up, r->g.down, r->g.n_pre_remove, r->g.H}; }
+
+// the book after a push of n_in samples to a row with filter g: the outputs the push gave it, by the kernel's arithmetic
+int take_chunk(bvc_resampler::Row &w, const Geometry &g, int n_in, bool delayed) {
+    if (w.state != ROW_RUNNING) return 0;
+    const int end = w.valid >= 0 ? w.valid : n_in;
+    const long long n1 = w.n + (end - w.start);
+    const int count = (int)(rs_count(n1, g.up, g.down, g.n_pre_remove, delayed) - rs_count(w.n, g.up, g.down, g.n_pre_remove, delayed));
+    w.n = n1; w.start = 0;
+    if (w.valid >= 0) { w.state = ROW_ENDED; w.valid = -1; }
+    return count;
+}
+
+RsFilterTable table_of(const bvc_resampler *r) {
+    RsFilterTable t{};
+    t.n = r->n_rates;
+    for (int q = 0; q < r->n_rates; ++q) {
+        const Geometry &g = r->gs[q];
+        t.f[q] = RsFilter{r->d_hs[q], g.ntaps, g.up, g.down, g.n_pre_remove, g.H};
+    }
+    return t;
+}
+
+bool pcm_formats_ok(int fmt_in, int fmt_out) {
+    const int fo = fmt_out & FMT_MASK;
+    return (fmt_in == BVC_PCM_F32 || fmt_in == BVC_PCM_S16) && (fo == BVC_PCM_F32 || fo == BVC_PCM_S16) &&
+           !(fmt_out & ~(FMT_MASK | BVC_PCM_DELAYED));
+}
 
 }  // namespace
 
@@ -188,8 +235,7 @@ int bvc_resampler_taps(int32_t rate_in, int32_t rate_out, double *h_taps, int32_
 int bvc_resampler_create(int32_t B, int32_t rate_in, int32_t rate_out, int32_t max_in, int32_t fmt_in, int32_t fmt_out, bvc_resampler **out) {
     Geometry g;
     const int fo = fmt_out & FMT_MASK;
-    if (!out || B <= 0 || max_in <= 0 || !geometry(rate_in, rate_out, &g) || (fmt_in != BVC_PCM_F32 && fmt_in != BVC_PCM_S16) ||
-        (fo != BVC_PCM_F32 && fo != BVC_PCM_S16) || (fmt_out & ~(FMT_MASK | BVC_PCM_DELAYED))) {
+    if (!out || B <= 0 || max_in <= 0 || !geometry(rate_in, rate_out, &g) || !pcm_formats_ok(fmt_in, fmt_out)) {
         set_error("bvc_resampler_create: B, max_in and both rates must be positive, the formats BVC_PCM_F32 or BVC_PCM_S16");
         return BVC_EINVAL;
     }
@@ -207,6 +253,7 @@ int bvc_resampler_create(int32_t B, int32_t rate_in, int32_t rate_out, int32_t m
     if (!r) { set_error("bvc_resampler_create: out of host memory"); return BVC_ENOMEM; }
     r->B = B; r->max_in = max_in; r->fmt_in = fmt_in; r->fmt_out = fo; r->delayed = (fmt_out & BVC_PCM_DELAYED) != 0;
     r->g = g;
+    r->hist_stride = g.H;
     r->rows.resize(B);
     std::vector<double> h(g.ntaps);
     design_taps(g, h.data());
@@ -237,7 +284,8 @@ int bvc_resampler_create(int32_t B, int32_t rate_in, int32_t rate_out, int32_t m
 void bvc_resampler_destroy(bvc_resampler *r) { delete r; }
 
 int bvc_resampler_set_taps(bvc_resampler *r, const double *h_taps, int32_t ntaps) {
-    if (!r || !h_taps || ntaps != r->g.ntaps) {
+    if (int rc = kind_arg(r, false, "bvc_resampler_set_taps", "bvc_resampler_set_taps_rate")) return rc;
+    if (!h_taps || ntaps != r->g.ntaps) {
         set_error("bvc_resampler_set_taps: null argument, or not the %d taps of the design", r ? r->g.ntaps : 0);
         return BVC_EINVAL;
     }
@@ -246,6 +294,7 @@ int bvc_resampler_set_taps(bvc_resampler *r, const double *h_taps, int32_t ntaps
 }
 
 int bvc_resampler_open(bvc_resampler *r, int32_t row, int32_t offset_in_next_push) {
+    if (int rc = kind_arg(r, false, "bvc_resampler_open", "bvc_resampler_open_rate")) return rc;
     if (int rc = row_arg(r, row, "bvc_resampler_open")) return rc;
     bvc_resampler::Row &w = r->rows[row];
     if (w.state == ROW_RUNNING) { set_error("bvc_resampler_open: row %d is running", (int)row); return BVC_EINVAL; }
@@ -271,8 +320,8 @@ int bvc_resampler_end(bvc_resampler *r, int32_t row, int32_t n_valid_in_next_pus
     if (int rc = row_arg(r, row, "bvc_resampler_end")) return rc;
     bvc_resampler::Row &w = r->rows[row];
     if (w.state != ROW_RUNNING) { set_error("bvc_resampler_end: row %d is not running", (int)row); return BVC_EINVAL; }
-    if (n_valid_in_next_push < w.start || n_valid_in_next_push > r->max_in) {
-        set_error("bvc_resampler_end: %d samples outside %d..%d", (int)n_valid_in_next_push, w.start, r->max_in);
+    if (n_valid_in_next_push < w.start || n_valid_in_next_push > max_in_of(r, w)) {
+        set_error("bvc_resampler_end: %d samples outside %d..%d", (int)n_valid_in_next_push, w.start, max_in_of(r, w));
         return BVC_EINVAL;
     }
     w.valid = n_valid_in_next_push;
@@ -282,7 +331,8 @@ int bvc_resampler_end(bvc_resampler *r, int32_t row, int32_t n_valid_in_next_pus
 
 int bvc_resampler_push(bvc_resampler *r, const void *d_x, int64_t x_row_stride, int32_t n_in, void *d_y, int64_t y_row_stride,
                        int64_t y_offset, int32_t *h_counts, void *stream) {
-    if (!r || !d_x || !d_y) { set_error("bvc_resampler_push: null argument"); return BVC_EINVAL; }
+    if (int rc = kind_arg(r, false, "bvc_resampler_push", "bvc_resampler_push_multi")) return rc;
+    if (!d_x || !d_y) { set_error("bvc_resampler_push: null argument"); return BVC_EINVAL; }
     if (n_in < 0 || n_in > r->max_in) { set_error("bvc_resampler_push: n_in %d outside 0..%d (max_in)", (int)n_in, r->max_in); return BVC_EINVAL; }
     const int n_fill = (int)rs_ceil_mul(n_in, r->g.up, r->g.down);
     if (x_row_stride < n_in || y_row_stride < n_fill || y_offset < 0) {
@@ -301,16 +351,7 @@ int bvc_resampler_push(bvc_resampler *r, const void *d_x, int64_t x_row_stride, 
     const RsCall c{d_x, x_row_stride, d_y, y_row_stride, y_offset, n_in, n_fill, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, -1};
     if (int rc = launch_rs_push(filter_of(r), c, r->d_ctl, r->d_hist, r->B, s)) return rc;
     for (int b = 0; b < r->B; ++b) {
-        bvc_resampler::Row &w = r->rows[b];
-        int count = 0;
-        if (w.state == ROW_RUNNING) {
-            const int end = w.valid >= 0 ? w.valid : n_in;
-            const long long n1 = w.n + (end - w.start);
-            count = (int)(rs_count(n1, r->g.up, r->g.down, r->g.n_pre_remove, r->delayed) -
-                          rs_count(w.n, r->g.up, r->g.down, r->g.n_pre_remove, r->delayed));
-            w.n = n1; w.start = 0;
-            if (w.valid >= 0) { w.state = ROW_ENDED; w.valid = -1; }
-        }
+        const int count = take_chunk(r->rows[b], r->g, n_in, r->delayed);
         if (h_counts) h_counts[b] = count;
     }
     return BVC_OK;
@@ -320,16 +361,151 @@ int bvc_resampler_flush(bvc_resampler *r, int32_t row, void *d_y_row, int32_t *c
     if (int rc = row_arg(r, row, "bvc_resampler_flush")) return rc;
     bvc_resampler::Row &w = r->rows[row];
     if (w.state == ROW_IDLE) { set_error("bvc_resampler_flush: row %d is idle", (int)row); return BVC_EINVAL; }
-    const long long done = rs_count(w.n, r->g.up, r->g.down, r->g.n_pre_remove, r->delayed);
-    const long long all = rs_ceil_mul(w.n, r->g.up, r->g.down) + (r->delayed ? r->g.n_pre_remove : 0);
+    const Geometry &g = geometry_of(r, w);
+    const long long done = rs_count(w.n, g.up, g.down, g.n_pre_remove, r->delayed);
+    const long long all = rs_ceil_mul(w.n, g.up, g.down) + (r->delayed ? g.n_pre_remove : 0);
     const int n = (int)(all - done);                         // <= n_pre_remove
     if (n > 0 && !d_y_row) { set_error("bvc_resampler_flush: null d_y_row for %d samples", n); return BVC_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
     if (r->n_dirty > 0) { if (int rc = send_changes(r, s)) return rc; }       // (a row opened since the last push is reset first)
     w.state = ROW_IDLE; w.start = 0; w.valid = -1;           // the kernel leaves the device's copy of the row idle
-    const RsCall c{nullptr, 0, d_y_row, 0, 0, 0, n, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, row};
-    if (int rc = launch_rs_push(filter_of(r), c, r->d_ctl, r->d_hist, r->B, s)) return rc;
+    if (r->n_rates) {                                        // the row's own filter; its rate stays until it is opened again
+        const RsCallMulti c{nullptr, 0, d_y_row, 0, 0, {}, {}, n, r->hist_stride, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, row};
+        if (int rc = launch_rs_push_multi(table_of(r), c, g.H, r->d_ctl, r->d_hist, r->B, s)) return rc;
+    } else {
+        const RsCall c{nullptr, 0, d_y_row, 0, 0, 0, n, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, row};
+        if (int rc = launch_rs_push(filter_of(r), c, r->d_ctl, r->d_hist, r->B, s)) return rc;
+    }
     if (count) *count = n;
+    return BVC_OK;
+}
+
+// ---- the multi-rate object: one filter per rate, a rate per row
+int bvc_resampler_create_multi(int32_t B, int32_t n_rates, const int32_t *rates, int32_t fixed_rate, int32_t direction, const int32_t *max_in,
+                               int32_t fmt_in, int32_t fmt_out, bvc_resampler **out) {
+    const char *fn = "bvc_resampler_create_multi";
+    if (!out || !rates || !max_in || B <= 0 || n_rates < 1 || n_rates > RS_MAX_RATES || (direction != 0 && direction != 1) ||
+        !pcm_formats_ok(fmt_in, fmt_out)) {
+        set_error("%s: B must be positive, n_rates 1..%d, direction 0 or 1, the formats BVC_PCM_F32 or BVC_PCM_S16", fn, RS_MAX_RATES);
+        return BVC_EINVAL;
+    }
+    Geometry gs[RS_MAX_RATES];
+    int H_max = 0;
+    for (int q = 0; q < n_rates; ++q) {
+        for (int p = 0; p < q; ++p)
+            if (rates[p] == rates[q]) { set_error("%s: rate %d is listed twice", fn, (int)rates[q]); return BVC_EINVAL; }
+        if (max_in[q] <= 0 || !geometry(direction ? fixed_rate : rates[q], direction ? rates[q] : fixed_rate, &gs[q])) {
+            set_error("%s: rate %d: the rates and max_in must be positive", fn, (int)rates[q]);
+            return BVC_EINVAL;
+        }
+        if ((size_t)(gs[q].H + (long long)max_in[q]) * sizeof(float) > 64 * 1024) {
+            set_error("%s: rate %d: history %d + max_in %d samples do not fit the 64 KiB of LDS a push stages them in", fn, (int)rates[q],
+                      gs[q].H, (int)max_in[q]);
+            return BVC_EINVAL;
+        }
+        if (gs[q].H > H_max) H_max = gs[q].H;
+    }
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+        (void)hipGetLastError();
+        set_error("%s: no HIP device", fn);
+        return BVC_ENODEVICE;
+    }
+    bvc_resampler *r = new (std::nothrow) bvc_resampler;
+    if (!r) { set_error("%s: out of host memory", fn); return BVC_ENOMEM; }
+    r->B = B; r->fmt_in = fmt_in; r->fmt_out = fmt_out & FMT_MASK; r->delayed = (fmt_out & BVC_PCM_DELAYED) != 0;
+    r->n_rates = n_rates; r->hist_stride = H_max;
+    r->rows.resize(B);
+    const size_t hist_bytes = (size_t)B * H_max * sizeof(float), ctl_bytes = (size_t)B * sizeof(RsRow);
+    std::vector<RsRow> ctl(B, RsRow{0, 0, 0, -1, 0});
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&r->d_hist), hist_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_ctl), ctl_bytes);
+    for (int q = 0; q < n_rates && e == hipSuccess; ++q) {
+        r->gs[q] = gs[q]; r->max_ins[q] = max_in[q];
+        std::vector<double> h(gs[q].ntaps);
+        design_taps(gs[q], h.data());
+        e = hipMalloc(reinterpret_cast<void **>(&r->d_hs[q]), h.size() * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpy(r->d_hs[q], h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMemset(r->d_hist, 0, hist_bytes);
+    if (e == hipSuccess) e = hipMemcpy(r->d_ctl, ctl.data(), ctl_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        delete r;
+        set_error("%s: %s", fn, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? BVC_ENOMEM : BVC_EHIP;
+    }
+    *out = r;
+    return BVC_OK;
+}
+
+int bvc_resampler_set_taps_rate(bvc_resampler *r, int32_t rate_index, const double *h_taps, int32_t ntaps) {
+    if (int rc = kind_arg(r, true, "bvc_resampler_set_taps_rate", "bvc_resampler_set_taps")) return rc;
+    if (rate_index < 0 || rate_index >= r->n_rates || !h_taps || ntaps != r->gs[rate_index].ntaps) {
+        set_error("bvc_resampler_set_taps_rate: rate_index %d outside 0..%d, null taps, or not the taps of that rate's design", (int)rate_index,
+                  r->n_rates - 1);
+        return BVC_EINVAL;
+    }
+    BVC_HIP_TRY(hipMemcpy(r->d_hs[rate_index], h_taps, (size_t)ntaps * sizeof(double), hipMemcpyHostToDevice));
+    return BVC_OK;
+}
+
+int bvc_resampler_open_rate(bvc_resampler *r, int32_t row, int32_t rate_index, int32_t offset_in_next_push) {
+    if (int rc = kind_arg(r, true, "bvc_resampler_open_rate", "bvc_resampler_open")) return rc;
+    if (int rc = row_arg(r, row, "bvc_resampler_open_rate")) return rc;
+    bvc_resampler::Row &w = r->rows[row];
+    if (w.state == ROW_RUNNING) { set_error("bvc_resampler_open_rate: row %d is running", (int)row); return BVC_EINVAL; }
+    if (rate_index < 0 || rate_index >= r->n_rates) {
+        set_error("bvc_resampler_open_rate: rate_index %d outside 0..%d", (int)rate_index, r->n_rates - 1);
+        return BVC_EINVAL;
+    }
+    if (offset_in_next_push < 0 || offset_in_next_push > r->max_ins[rate_index]) {
+        set_error("bvc_resampler_open_rate: offset %d outside 0..%d", (int)offset_in_next_push, r->max_ins[rate_index]);
+        return BVC_EINVAL;
+    }
+    w.state = ROW_RUNNING; w.n = 0; w.start = offset_in_next_push; w.valid = -1; w.reset = true; w.rate = rate_index;
+    mark(r, w);
+    return BVC_OK;
+}
+
+int bvc_resampler_push_multi(bvc_resampler *r, const void *d_x, int64_t x_row_stride, const int32_t *n_in, void *d_y, int64_t y_row_stride,
+                             int64_t y_offset, int32_t *h_counts, void *stream) {
+    if (int rc = kind_arg(r, true, "bvc_resampler_push_multi", "bvc_resampler_push")) return rc;
+    if (!d_x || !d_y || !n_in) { set_error("bvc_resampler_push_multi: null argument"); return BVC_EINVAL; }
+    RsCallMulti c{d_x, x_row_stride, d_y, y_row_stride, y_offset, {}, {}, 0, r->hist_stride, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, -1};
+    int n_in_max = 0, lds_floats = 0;
+    for (int q = 0; q < r->n_rates; ++q) {
+        if (n_in[q] < 0 || n_in[q] > r->max_ins[q]) {
+            set_error("bvc_resampler_push_multi: n_in[%d] = %d outside 0..%d (max_in)", q, (int)n_in[q], r->max_ins[q]);
+            return BVC_EINVAL;
+        }
+        c.n_in[q] = n_in[q];
+        c.n_fill[q] = (int)rs_ceil_mul(n_in[q], r->gs[q].up, r->gs[q].down);
+        if (n_in[q] > n_in_max) n_in_max = n_in[q];
+        if (c.n_fill[q] > c.n_fill_max) c.n_fill_max = c.n_fill[q];
+        if (r->gs[q].H + n_in[q] > lds_floats) lds_floats = r->gs[q].H + n_in[q];
+    }
+    if (x_row_stride < n_in_max || y_row_stride < c.n_fill_max || y_offset < 0) {
+        set_error("bvc_resampler_push_multi: a row of d_x holds the longest chunk, %d samples, a row of d_y the longest block, %d, behind y_offset >= 0",
+                  n_in_max, c.n_fill_max);
+        return BVC_EINVAL;
+    }
+    for (int b = 0; b < r->B; ++b) {
+        const bvc_resampler::Row &w = r->rows[b];
+        if (w.state == ROW_RUNNING && (w.start > n_in[w.rate] || w.valid > n_in[w.rate])) {
+            set_error("bvc_resampler_push_multi: row %d starts at %d / ends at %d of a chunk of %d", b, w.start, w.valid, (int)n_in[w.rate]);
+            return BVC_EINVAL;
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (r->n_dirty > 0) { if (int rc = send_changes(r, s)) return rc; }
+    if (int rc = launch_rs_push_multi(table_of(r), c, lds_floats, r->d_ctl, r->d_hist, r->B, s)) return rc;
+    for (int b = 0; b < r->B; ++b) {
+        bvc_resampler::Row &w = r->rows[b];
+        const int count = take_chunk(w, r->gs[w.rate], n_in[w.rate], r->delayed);
+        if (h_counts) h_counts[b] = count;
+    }
     return BVC_OK;
 }
 

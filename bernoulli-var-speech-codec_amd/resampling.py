@@ -118,3 +118,102 @@ class StreamResampler:
         with torch.cuda.device(self.dev):
             n = self.flush_raw(row, _abi.addr(y, PCM_DTYPES[self.fmt_out]), torch.cuda.current_stream(self.dev).cuda_stream)
         return y[:n]
+
+
+class MultiRateResampler(StreamResampler):
+    """``StreamResampler`` with a rate per row (``bvc_resampler_create_multi``): ``batch`` rows, each converted between one of ``rates``
+    (1 .. 8 distinct ones) and ``fixed_rate`` - ``direction="in"``: from its rate to ``fixed_rate``, ``"out"``: from ``fixed_rate`` to
+    its rate - all rows in the one launch of a push.  What a row at rate r has got after any chunking is a bit-exact prefix of
+    ``preprocess.resample_poly`` of its own signal between r and ``fixed_rate``: what ``StreamResampler`` at that rate gives.
+
+    ``open(row, rate, offset=0)`` starts an idle row at ``rate`` (one of ``rates``, in Hz); the rate is the row's until it is idle again.
+    ``close``, ``end`` and ``flush`` are inherited.  ``max_in``: the longest chunk per rate on the input side (a number: the
+    same for all).  ``push(x, n)``: ``n`` has one chunk length per rate, in the order of ``rates`` (rows of one rate share the chunk
+    length of a push, different rates do not; 0 is allowed); x is (batch, >= max(n)) and row b's first ``n[its rate]`` samples are read.
+    Returns ``(y (batch, n_max) view, counts)``, n_max the call's largest ``ceil(n up / down)``; row b's samples are ``y[b, :counts[b]]``,
+    zeros behind them up to n_max for every row."""
+
+    def __init__(self, batch, rates, fixed_rate, direction="in", max_in=None, fmt_in="f32", fmt_out="f32", delayed=False, device=None):
+        from . import preprocess
+        if fmt_in not in PCM_FORMATS or fmt_out not in PCM_FORMATS:
+            raise ValueError(f"sample formats are {sorted(PCM_FORMATS)}")
+        if direction not in ("in", "out"):
+            raise ValueError('MultiRateResampler: direction is "in" or "out"')
+        rates = [int(r) for r in rates]
+        if not 1 <= len(rates) <= 8 or len(set(rates)) != len(rates) or min(rates) <= 0 or int(fixed_rate) <= 0:
+            raise ValueError("MultiRateResampler: 1 to 8 distinct positive rates and a positive fixed_rate")
+        n = len(rates)
+        self.max_in = [int(max_in)] * n if isinstance(max_in, int) else [int(m) for m in max_in]
+        if len(self.max_in) != n:
+            raise ValueError("MultiRateResampler: max_in is a number or one number per rate")
+        self.lib = _abi.load()
+        self.dev = torch.device("cuda" if device is None else device)
+        if self.dev.index is None:
+            self.dev = torch.device("cuda", torch.cuda.current_device())
+        self.B, self.rates, self.fixed_rate, self.direction = batch, tuple(rates), int(fixed_rate), direction
+        self.fmt_in, self.fmt_out, self.delayed = fmt_in, fmt_out, bool(delayed)
+        pairs = [(r, self.fixed_rate) if direction == "in" else (self.fixed_rate, r) for r in rates]      # (rate_in, rate_out)
+        designs = [preprocess.design(rate_out, rate_in) for rate_in, rate_out in pairs]
+        self.up, self.down, self.lag = ([d[i] for d in designs] for i in (0, 1, 3))
+        self.max_out = [-(-m * u // d) for m, u, d in zip(self.max_in, self.up, self.down)]
+        self.running = set()
+        self.row_rate = [None] * batch                          # the index of a row's rate, from open until it is idle again
+        h = self.handle = _abi.Handle(self.lib.bvc_resampler_destroy)
+        i32s = ctypes.c_int32 * n
+        with torch.cuda.device(self.dev):
+            _abi.check_arg(self.lib.bvc_resampler_create_multi(batch, n, i32s(*rates), self.fixed_rate, 0 if direction == "in" else 1,
+                                                               i32s(*self.max_in), PCM_FORMATS[fmt_in],
+                                                               PCM_FORMATS[fmt_out] | (PCM_DELAYED if delayed else 0), ctypes.byref(h)))
+            for i, (up, down, taps, _) in enumerate(designs):   # the offline call's taps, as StreamResampler hands them in
+                if up != down:
+                    taps = taps.astype("float64")
+                    _abi.check_arg(self.lib.bvc_resampler_set_taps_rate(h, i, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(taps)))
+        self._counts = (ctypes.c_int32 * batch)()
+        self._n = i32s()
+        self._out = None
+
+    def index(self, rate):
+        if rate not in self.rates:
+            raise ValueError(f"MultiRateResampler: rate {rate} is not one of {self.rates}")
+        return self.rates.index(rate)
+
+    def open(self, row, rate, offset=0):
+        i = self.index(rate)
+        _abi.check_arg(self.lib.bvc_resampler_open_rate(self.handle, int(row), i, int(offset)))
+        self.running.add(int(row))
+        self.row_rate[int(row)] = i
+
+    def out_len(self, n):
+        """The call's largest block: max over the rates of ceil(n[i] up / down)."""
+        return max(-(-int(m) * u // d) for m, u, d in zip(n, self.up, self.down))
+
+    def push_raw(self, x_ptr, x_row_stride, n_in, y_ptr, y_row_stride, y_offset, stream):
+        """The C call on raw device addresses (strides and offset in elements, n_in per rate); returns the rows' counts as a list."""
+        self._n[:] = [int(m) for m in n_in]
+        _abi.check_arg(self.lib.bvc_resampler_push_multi(self.handle, ctypes.c_void_p(x_ptr), int(x_row_stride), self._n, ctypes.c_void_p(y_ptr),
+                                                         int(y_row_stride), int(y_offset), self._counts, ctypes.c_void_p(stream)))
+        return list(self._counts)
+
+    @torch.no_grad()
+    def push(self, x, n):
+        n = [int(m) for m in n]
+        if (x.dim() != 2 or x.shape[0] != self.B or x.dtype != PCM_DTYPES[self.fmt_in] or len(n) != len(self.rates)
+                or x.shape[1] < max(n) or any(not 0 <= m <= lim for m, lim in zip(n, self.max_in))):
+            raise ValueError(f"MultiRateResampler.push: expected a {PCM_DTYPES[self.fmt_in]} tensor ({self.B}, >= max(n)) and one chunk "
+                             f"length per rate, at most {self.max_in}")
+        x = x.to(self.dev).contiguous()
+        if self._out is None:
+            self._out = torch.empty(self.B, max(1, max(self.max_out)), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
+        with torch.cuda.device(self.dev):
+            out = _abi.addr(self._out, PCM_DTYPES[self.fmt_out])
+            counts = self.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt_in]) if x.shape[1] else out, max(x.shape[1], 1), n, out,
+                                   self._out.shape[1], 0, torch.cuda.current_stream(self.dev).cuda_stream)
+        return self._out[:, :self.out_len(n)], torch.tensor(counts, dtype=torch.int64)
+
+    @torch.no_grad()
+    def flush(self, row):
+        """The rest of the row's outputs (at most its rate's lag, a new tensor); the row is idle afterwards."""
+        y = torch.empty(max(1, max(self.lag)), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
+        with torch.cuda.device(self.dev):
+            n = self.flush_raw(row, _abi.addr(y, PCM_DTYPES[self.fmt_out]), torch.cuda.current_stream(self.dev).cuda_stream)
+        return y[:n]

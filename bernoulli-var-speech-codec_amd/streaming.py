@@ -10,10 +10,10 @@ import math
 import torch
 
 from . import _abi
-from .client_rate import _ClientRate
+from .client_rate import _ClientRate, _MixedClientRate
 from .config import is_causal, not_causal_message
 from .model import SCALING
-from .resampling import (PCM_DELAYED, PCM_DTYPES, PCM_FORMATS, StreamResampler, pcm_f32_to_s16, pcm_s16_to_f32,  # noqa: F401
+from .resampling import (PCM_DELAYED, PCM_DTYPES, PCM_FORMATS, MultiRateResampler, StreamResampler, pcm_f32_to_s16, pcm_s16_to_f32,  # noqa: F401
                          resampler_count, resampler_lag)
 from .stream_chunked import StreamingDecoder, StreamingEncoder, VocoderStream  # noqa: F401
 from .stream_plans import (CONTEXT_FRAMES, client_finish_plan, client_hop, finish_plan, generator_reach, join_plan,  # noqa: F401
@@ -75,7 +75,10 @@ class StreamingCodec:
 
     ``client_rate=fs``, ``sample_format="f32"`` or ``"s16"``: the session speaks the client's rate and format on both sides, through
     the adapter in ``self._client``; ``client_rate._ClientRate`` holds that contract (what ``hop``, ``finish`` and ``lag`` then mean,
-    and the three-value returns).
+    and the three-value returns).  ``client_rate=(8000, 16000, 48000)`` - a tuple or list of 1 to 8 distinct rates - makes a mixed-rate
+    session: every slot speaks one of them, given to ``open(slot, ..., client_rate=fs)`` (``open_all``: the first listed), ``hop``
+    counts internal samples, ``push`` takes (batch, the largest client hop) and ``slot_rate`` / ``slot_hop`` / ``slot_lag`` tell a
+    slot's values; ``client_rate._MixedClientRate`` holds that contract: a slot gives what it gives in a session of its rate alone.
 
     ``vbr=dict(bitrates=(1500, 3000, 6000), target=0.35, rate_cap=None, burst=None)`` (send and duplex sessions; ``bitrate`` is then
     ignored): the session chooses every frame's rate itself, as ``model.encode_vbr(x, target, bitrates, rate_cap=, burst=)`` does -
@@ -107,7 +110,10 @@ class StreamingCodec:
         self._map_buffers()
         self.frames = 0
         self._client = None
-        if self.client_rate is not None:
+        if isinstance(self.client_rate, tuple):
+            self._client = _MixedClientRate(self, model.conf, self.client_rate, sample_format, self._hop_in, open_all)
+            self.hop = 0 if direction == "recv" else self._client.hop
+        elif self.client_rate is not None:
             self._client = _ClientRate(self, model.conf, self.client_rate, sample_format, hop, self._hop_in, open_all)
         if not open_all:
             for b in range(batch):
@@ -122,18 +128,22 @@ class StreamingCodec:
     @classmethod
     def _check_args(cls, model, hop, direction, conceal, repair, client_rate, sample_format, vbr):
         """Every refusal of the constructor's arguments, before anything is created: ``(vbr as _check_vbr gives it, the client's rate
-        where the session converts else None, the internal hop)``."""
+        where the session converts (a tuple of rates for a mixed-rate session) else None, the internal hop)``."""
         vbr = cls._check_vbr(model, direction, repair, vbr)
         if sample_format not in PCM_FORMATS:
             raise ValueError(f"sample_format must be one of {sorted(PCM_FORMATS)}")
         if client_rate is None and sample_format != "f32":
             raise ValueError("sample_format: a session without client_rate speaks float32")
         fs = model.conf["fs"]
-        if client_rate is not None and (client_rate != int(client_rate) or client_rate <= 0):
-            raise ValueError(f"client_rate must be a positive number of Hz, not {client_rate}")
-        converting = client_rate is not None and (int(client_rate) != fs or sample_format != "f32")
-        if converting and direction != "recv":
-            hop = client_hop(hop, int(client_rate), fs)
+        mixed = isinstance(client_rate, (tuple, list))
+        if mixed:
+            converting, client_rate = True, cls._check_rates(client_rate, hop, fs, direction)
+        else:
+            if client_rate is not None and (client_rate != int(client_rate) or client_rate <= 0):
+                raise ValueError(f"client_rate must be a positive number of Hz, not {client_rate}")
+            converting = client_rate is not None and (int(client_rate) != fs or sample_format != "f32")
+            if converting and direction != "recv":
+                hop = client_hop(hop, int(client_rate), fs)
         if direction not in cls.DIRECTIONS:
             raise ValueError(f"direction must be one of {sorted(cls.DIRECTIONS)}")
         if conceal not in cls.CONCEAL:
@@ -144,7 +154,27 @@ class StreamingCodec:
             raise ValueError("repair: only a receive session has late packets to repair from")
         if direction != "send" and not is_causal(model.conf):
             raise ValueError("StreamingCodec: " + not_causal_message(model.conf))
-        return vbr, (int(client_rate) if converting else None), (0 if direction == "recv" else hop)
+        return vbr, (client_rate if mixed else int(client_rate) if converting else None), (0 if direction == "recv" else hop)
+
+    @staticmethod
+    def _check_rates(rates, hop, fs, direction):
+        """The rates of a mixed-rate session as a tuple of ints: 1 to 8, positive whole numbers, distinct, and (send and duplex) each with
+        a whole client hop for ``hop`` internal samples."""
+        if not 1 <= len(rates) <= 8:
+            raise ValueError(f"client_rate: a mixed-rate session lists 1 to 8 rates, not {len(rates)}")
+        if direction != "recv" and int(hop) <= 0:
+            raise ValueError(f"hop {hop} must be positive")
+        out = []
+        for r in rates:
+            if r != int(r) or r <= 0:
+                raise ValueError(f"client_rate lists positive numbers of Hz, not {r}")
+            if int(r) in out:
+                raise ValueError(f"client_rate lists {int(r)} Hz twice")
+            if direction != "recv" and hop * int(r) % fs:
+                raise ValueError(f"client_rate {int(r)}: a hop of {hop} internal samples is {hop * int(r) / fs:g} samples at {int(r)} Hz: "
+                                 "not a whole number")
+            out.append(int(r))
+        return tuple(out)
 
     @classmethod
     def _check_vbr(cls, model, direction, repair, vbr):
@@ -217,7 +247,28 @@ class StreamingCodec:
     @property
     def lag(self):
         """Rate-converting send and duplex sessions: the internal samples a stream is late by (``client_rate._ClientRate``)."""
+        if isinstance(self._client, _MixedClientRate):
+            raise ValueError("lag: a mixed-rate session has a lag per slot (slot_lag(slot))")
         return self._client.lag
+
+    def slot_rate(self, slot):
+        """Rate-converting sessions: the client rate of a slot - on a mixed-rate session the one it was last opened with."""
+        return self._slot_value("slot_rate", slot)
+
+    def slot_hop(self, slot):
+        """Rate-converting send and duplex sessions: the client samples of a slot that a push takes."""
+        return self._slot_value("slot_hop", slot)
+
+    def slot_lag(self, slot):
+        """Rate-converting send and duplex sessions: the internal samples the slot's stream is late by."""
+        return self._slot_value("slot_lag", slot)
+
+    def _slot_value(self, what, slot):
+        if self._client is None or (what != "slot_rate" and self.direction == "recv"):
+            raise ValueError(f"{what}: not a rate-converting {'send or duplex ' if what != 'slot_rate' else ''}session")
+        if not 0 <= int(slot) < self.B:
+            raise ValueError(f"{what}: slot {slot} outside 0..{self.B - 1}")
+        return getattr(self._client, what)(int(slot))
 
     @property
     def last_bits(self):
@@ -238,10 +289,16 @@ class StreamingCodec:
         """vbr send / duplex sessions: the distortion target of an open slot from the next push on."""
         _abi.check_arg(self.eng.lib.bvc_stream_codec_set_target(self.handle, int(slot), float(target)))
 
-    def open(self, slot, bitrate=None, target=None):
+    def open(self, slot, bitrate=None, target=None, client_rate=None):
         """Start a new stream in idle row `slot` from the next push on; returns its delay in (internal) samples.  A rate-converting
         send side delays the stream by ``lag`` more: its filter looks that far ahead (``self.lag`` internal samples).  A vbr send or
-        duplex session takes ``target`` (None: the session's) instead of ``bitrate``."""
+        duplex session takes ``target`` (None: the session's) instead of ``bitrate``.  A mixed-rate session takes the slot's
+        ``client_rate``, one of the session's; no other session does."""
+        mixed = isinstance(self._client, _MixedClientRate)
+        if mixed and client_rate not in self.client_rate:
+            raise ValueError(f"open: client_rate must be one of the session's rates {self.client_rate}, not {client_rate}")
+        if not mixed and client_rate is not None:
+            raise ValueError("open: client_rate belongs to a mixed-rate session (StreamingCodec(client_rate=(...)))")
         choosing = self.vbr is not None and self.direction != "recv"
         if choosing and bitrate is not None:
             raise ValueError("open: a vbr session chooses its own rates (open(slot, target=...))")
@@ -252,7 +309,9 @@ class StreamingCodec:
                                                           ctypes.byref(d)))
         if choosing and target is not None:
             self.set_target(slot, target)
-        if self._client is not None:
+        if mixed:
+            self._client.opened(int(slot), int(client_rate))
+        elif self._client is not None:
             self._client.opened(int(slot))
         return d.value
 
@@ -278,7 +337,8 @@ class StreamingCodec:
         """The stream in `slot` ends with the first `n_last` samples of the next push's row (None: the whole hop; 0: it ended with
         the last push).  The slot drains from that push on and is idle once its last frame is out.  On a rate-converting session `n_last`
         counts client samples, and the drain starts ``lag`` internal samples later (``client_rate._ClientRate.finish``)."""
-        n_last = self.hop if n_last is None else n_last
+        if n_last is None:
+            n_last = self.slot_hop(slot) if isinstance(self._client, _MixedClientRate) and self.direction != "recv" else self.hop
         if self._client is not None:
             return self._client.finish(slot, n_last)
         self._finish(slot, n_last)

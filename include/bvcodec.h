@@ -12,7 +12,7 @@
  *  - every pointer named d_* is DEVICE memory owned by the caller, contiguous float32;
  *    every pointer named h_* is HOST memory;
  *  - the compute entry points (bvc_stft_logmel, bvc_bvrnn_*, bvc_bigvgan, bvc_encode, bvc_decode, bvc_decode_conceal,
- *    bvc_encode_ragged, bvc_decode_ragged, bvc_vocoder_stream_push, bvc_pack/unpack_codes, bvc_resample_poly, bvc_peak_normalize, bvc_resampler_push / flush) are
+ *    bvc_encode_ragged, bvc_decode_ragged, bvc_vocoder_stream_push, bvc_pack/unpack_codes, bvc_resample_poly, bvc_peak_normalize, bvc_resampler_push / push_multi / flush) are
  *    asynchronous on `stream` and use only the caller-provided workspace.  They do not allocate or
  *    synchronise, with these exceptions: the first calls per process create a handful of HIP events (the
  *    persistent launches' ticket, the end-of-call mark of the "auto" schedule, one per bvc_flow_fence slot in
@@ -52,7 +52,8 @@ extern "C" {
                              *    + bvc_stream_codec_open / close / set_bits / slot_frames;
                              *    + bvc_stream_codec_create_dir / packets / tick_recv / finish / slot_state;
                              *    + bvc_bvrnn_decode_conceal, bvc_decode_conceal, bvc_stream_codec_set_conceal;
-                             *    + bvc_resampler_* */
+                             *    + bvc_resampler_*;
+                             *    + bvc_resampler_create_multi / set_taps_rate / open_rate / push_multi */
 
 enum {
     BVC_OK = 0,
@@ -652,6 +653,34 @@ int  bvc_resampler_flush(bvc_resampler *r, int32_t row, void *d_y_row, int32_t *
 int64_t bvc_resampler_count(int32_t rate_in, int32_t rate_out, int64_t n_inputs);
 int  bvc_resampler_lag(int32_t rate_in, int32_t rate_out, int32_t *n_pre_remove, int32_t *history);
 int  bvc_resampler_taps(int32_t rate_in, int32_t rate_out, double *h_taps, int32_t capacity);   /* returns ntaps; writes if capacity >= ntaps */
+
+/* The multi-rate streaming resampler: the same object with a RATE PER ROW, for a session whose clients speak different rates.  Every row
+ * is converted between ITS rate and one fixed rate, all rows in the one launch of a push; a row at rate r gets, bit for bit, what a
+ * single-rate object between r and fixed_rate gives it (both kernels form an output in the same function), so the prefix contract above
+ * holds per row.
+ *  - create_multi: n_rates = 1 .. 8 distinct positive rates; direction 0 converts rates[i] -> fixed_rate (a session's input side), 1
+ *    fixed_rate -> rates[i] (its output side).  max_in[i]: the longest chunk of a row at rates[i], on the input side; history_i +
+ *    max_in[i] float32 must fit 64 KiB for every i.  Formats and BVC_PCM_DELAYED as above, for the whole object.  Entry i has its own
+ *    filter, designed as above; set_taps_rate hands in a caller's taps for entry rate_index (the design's ntaps of THAT pair of rates).
+ *    All arguments are checked before a device is touched (BVC_EINVAL).
+ *  - open_rate: open with the row's rate, an index into rates[].  The rate is the row's from there until the row is idle again (close,
+ *    or flush) and opened anew - at any rate: its history is reset over the widest entry's length.  close, end, flush and destroy are
+ *    the calls above and work on either kind of object; end's bound is the row's own max_in, flush uses the row's own filter.
+ *  - push_multi: n_in[i] (n_rates entries, 0 allowed) is the chunk length of the rows at rates[i]: rows of one rate share it, different
+ *    rates need not.  Row b reads n_in[its rate] samples from d_x + b * x_row_stride (x_row_stride >= the largest n_in[i]) and writes
+ *    its outputs from d_y + b * y_row_stride + y_offset on; the positions behind them are written as zeros up to the call's largest
+ *    ceil(n_in[i] * up_i / down_i), for EVERY row (y_row_stride >= that), so an idle row's block is zeros and its input is never read.
+ *    One launch over all rows, its LDS the largest history_i + n_in[i] of the call; no allocation, no synchronisation.  h_counts: each
+ *    row's count by its own rate's E.
+ * BVC_EINVAL with the object untouched, and a message that names the other call: open, push or set_taps on a multi-rate object;
+ * open_rate, push_multi or set_taps_rate on a single-rate one.  Also: n_rates outside 1 .. 8, a rate <= 0 or listed twice, a
+ * rate_index out of range, n_in[i] > max_in[i], a running row that starts or ends behind n_in of its rate. */
+int  bvc_resampler_create_multi(int32_t B, int32_t n_rates, const int32_t *rates, int32_t fixed_rate, int32_t direction,
+                                const int32_t *max_in, int32_t fmt_in, int32_t fmt_out, bvc_resampler **out);
+int  bvc_resampler_set_taps_rate(bvc_resampler *r, int32_t rate_index, const double *h_taps, int32_t ntaps);
+int  bvc_resampler_open_rate(bvc_resampler *r, int32_t row, int32_t rate_index, int32_t offset_in_next_push);
+int  bvc_resampler_push_multi(bvc_resampler *r, const void *d_x, int64_t x_row_stride, const int32_t *n_in, void *d_y,
+                              int64_t y_row_stride, int64_t y_offset, int32_t *h_counts, void *stream);
 
 /* Wire format for the codes (new: the reference keeps them as float32 {0,1,0.5}, bvrnn.py:191-196, and
  * defines no bit stream).  A frame is ceil(nbits/8) bytes, bit i at byte i/8 position i%8 (LSB first);
