@@ -32,8 +32,17 @@ class _ClientRate:
     the d_in view, the address of d_wav, the stream, ``spf`` and ``kmax``."""
 
     def __init__(self, session, conf, rate, fmt, hop, hop_in, open_all):
+        self.rate = rate
+        self._attach(session, conf, fmt, hop, hop, hop_in)
+        if open_all:
+            for b in range(self.B):
+                self.opened(b)
+
+    def _attach(self, session, conf, fmt, hop, n_in, hop_in):
+        """The adapter's book and its resamplers (``_resampler``).  ``hop``: the row a push takes; ``n_in``: what the input side's push
+        is told of it - the hop, or ``_MixedClientRate``'s hop per rate; ``lag`` follows ``n_in`` (a number, or one per rate)."""
         sc = self.sc = weakref.proxy(session)                  # (the session owns the adapter: no cycle)
-        self.conf, self.rate, self.fmt, self.hop, self.hop_in = conf, rate, fmt, hop, hop_in
+        self.conf, self.fmt, self.hop, self.n_in, self.hop_in = conf, fmt, hop, n_in, hop_in
         self.B, self.dev, self.spf, self.stream, self.d_in, self.wav_ptr = sc.B, sc.dev, sc.spf, sc.stream, sc._in, sc._wav_ptr
         self.n_push = 0                                        # pushes so far
         self.open_push = [0] * self.B                          # the push that took a slot's first client samples
@@ -42,15 +51,21 @@ class _ClientRate:
         self.out_wait, self.out_drain = set(), set()           # slots whose samples have yet to start / are about to end on the wav side
         self.rs_in = self.rs_out = None
         if sc.direction != "recv":                             # in front of d_in (delayed: a fixed hop in, a fixed hop out)
-            self.rs_in = StreamResampler(self.B, rate, conf["fs"], hop, fmt, "f32", delayed=True, device=self.dev)
+            self.rs_in = self._resampler("in", n_in, fmt, "f32", delayed=True)
             self.lag = self.rs_in.lag
-            self.tail = torch.zeros(self.B, max(1, self.lag), device=self.dev)
+            self.tail = torch.zeros(self.B, max(1, self.rs_in.widths()[1]), device=self.dev)
         if sc.direction != "send":                             # behind d_wav
-            self.rs_out = StreamResampler(self.B, conf["fs"], rate, sc.kmax * self.spf, "f32", fmt, device=self.dev)
-            self.cwav = torch.zeros(self.B, max(1, self.rs_out.max_out), dtype=PCM_DTYPES[fmt], device=self.dev)
-        if open_all:
-            for b in range(self.B):
-                self.opened(b)
+            self.rs_out = self._resampler("out", sc.kmax * self.spf, "f32", fmt)
+            self.cwav = torch.zeros(self.B, max(1, self.rs_out.widths()[0]), dtype=PCM_DTYPES[fmt], device=self.dev)
+
+    def _resampler(self, direction, max_in, fmt_in, fmt_out, delayed=False):
+        fs = self.conf["fs"]
+        rate_in, rate_out = (self.rate, fs) if direction == "in" else (fs, self.rate)
+        return StreamResampler(self.B, rate_in, rate_out, max_in, fmt_in, fmt_out, delayed=delayed, device=self.dev)
+
+    def _out_chunk(self, n):
+        """n internal samples for every row of the output side: what its push is told, and the width of what comes back."""
+        return n, -(-n * self.rs_out.up // self.rs_out.down)
 
     def slot_rate(self, slot):
         """The client rate, the client hop and the send side's lag of a slot: the session's (``_MixedClientRate``: the slot's own)."""
@@ -112,11 +127,12 @@ class _ClientRate:
 
     def feed(self, x):
         """A hop of client samples -> d_in, inside the session's stream: one resampler push for all rows, and for a row that ends the
-        flush of its last ``lag`` samples - straight into d_in where they fit the hop, else through a buffer into this hop and the next."""
+        flush of its last ``lag`` samples - straight into d_in where they fit the hop, else through a buffer into this hop and the next.
+        (``_MixedClientRate``: row b's first ``slot_hop(b)`` samples are read, every row gets a whole internal hop.)"""
         if tuple(x.shape) != (self.B, self.hop) or x.dtype != PCM_DTYPES[self.fmt]:
             raise ValueError(f"push: expected a {PCM_DTYPES[self.fmt]} tensor ({self.B}, {self.hop})")
         x = x.to(self.dev).contiguous()
-        self._end_streams(self.rs_in.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt]), self.hop, self.hop, _abi.addr(self.d_in), self.hop_in, 0,
+        self._end_streams(self.rs_in.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt]), self.hop, self.n_in, _abi.addr(self.d_in), self.hop_in, 0,
                                               self.stream.cuda_stream))
         self.n_push += 1
 
@@ -141,7 +157,8 @@ class _ClientRate:
             del self.ending[slot]
 
     def drain(self, k):
-        """The tick's k frames of d_wav -> client samples: (wav (B, n_max) view, counts (B,) int64 CPU tensor); None on a send session."""
+        """The tick's k frames of d_wav -> client samples: (wav (B, n_max) view, counts (B,) int64 CPU tensor); None on a send session.
+        (``_MixedClientRate``: n_max is the fastest listed rate's.)"""
         rs = self.rs_out
         if rs is None:
             return None
@@ -149,8 +166,9 @@ class _ClientRate:
             return torch.empty(self.B, 0, dtype=PCM_DTYPES[self.fmt], device=self.dev), torch.zeros(self.B, dtype=torch.int64)
         self._start_and_end_out()
         n = k * self.spf
-        counts = rs.push_raw(self.wav_ptr, n, n, _abi.addr(self.cwav, PCM_DTYPES[self.fmt]), self.cwav.shape[1], 0, self.stream.cuda_stream)
-        return self.cwav[:, :-(-n * rs.up // rs.down)], torch.tensor(counts, dtype=torch.int64)
+        n_in, n_out = self._out_chunk(n)
+        counts = rs.push_raw(self.wav_ptr, n, n_in, _abi.addr(self.cwav, PCM_DTYPES[self.fmt]), self.cwav.shape[1], 0, self.stream.cuda_stream)
+        return self.cwav[:, :n_out], torch.tensor(counts, dtype=torch.int64)
 
     def _start_and_end_out(self):
         """In front of the output side's push: the rows whose stream starts or ends inside the tick's frames."""
@@ -187,26 +205,20 @@ class _MixedClientRate(_ClientRate):
     the carry."""
 
     def __init__(self, session, conf, rates, fmt, hop, open_all):
-        sc = self.sc = weakref.proxy(session)
-        self.conf, self.rates, self.fmt, self.hop_in = conf, tuple(rates), fmt, hop
-        self.B, self.dev, self.spf, self.stream, self.d_in, self.wav_ptr = sc.B, sc.dev, sc.spf, sc.stream, sc._in, sc._wav_ptr
-        self.n_push, self.open_push, self.ending, self.carry = 0, [0] * self.B, {}, {}
-        self.out_wait, self.out_drain = set(), set()
-        self.rate_of = [0] * self.B                            # slot -> the index of its rate
-        self.rs_in = self.rs_out = None
-        fs = conf["fs"]
-        if sc.direction != "recv":
-            self.hops = [hop * r // fs for r in rates]         # the client hop at every rate
-            self.hop = max(self.hops)                          # the row that push takes
-            self.rs_in = MultiRateResampler(self.B, rates, fs, "in", self.hops, fmt, "f32", delayed=True, device=self.dev)
-            self.lags = self.rs_in.lag
-            self.tail = torch.zeros(self.B, max(1, max(self.lags)), device=self.dev)
-        if sc.direction != "send":
-            self.rs_out = MultiRateResampler(self.B, rates, fs, "out", sc.kmax * self.spf, "f32", fmt, device=self.dev)
-            self.cwav = torch.zeros(self.B, max(1, max(self.rs_out.max_out)), dtype=PCM_DTYPES[fmt], device=self.dev)
+        self.rates = tuple(rates)
+        self.rate_of = [0] * session.B                         # slot -> the index of its rate
+        self.hops = [hop * r // conf["fs"] for r in rates]     # the client hop at every rate; the row that push takes is the longest
+        self._attach(session, conf, fmt, max(self.hops), self.hops, hop)
         if open_all:
             for b in range(self.B):
                 self.opened(b, self.rates[0])
+
+    def _resampler(self, direction, max_in, fmt_in, fmt_out, delayed=False):
+        return MultiRateResampler(self.B, self.rates, self.conf["fs"], direction, max_in, fmt_in, fmt_out, delayed=delayed, device=self.dev)
+
+    def _out_chunk(self, n):
+        n = [n] * len(self.rates)
+        return n, self.rs_out.out_len(n)
 
     def slot_rate(self, slot):
         return self.rates[self.rate_of[slot]]
@@ -215,7 +227,7 @@ class _MixedClientRate(_ClientRate):
         return self.hops[self.rate_of[slot]]
 
     def slot_lag(self, slot):
-        return self.lags[self.rate_of[slot]]
+        return self.lag[self.rate_of[slot]]
 
     def _open_in(self, slot):
         self.rs_in.open(slot, self.slot_rate(slot), 0)
@@ -226,24 +238,3 @@ class _MixedClientRate(_ClientRate):
     def opened(self, slot, rate):
         self.rate_of[slot] = self.rates.index(rate)
         super().opened(slot)
-
-    def feed(self, x):
-        """A hop of every client's samples -> d_in: row b's first ``slot_hop(b)`` samples are read, every row gets a whole internal hop."""
-        if tuple(x.shape) != (self.B, self.hop) or x.dtype != PCM_DTYPES[self.fmt]:
-            raise ValueError(f"push: expected a {PCM_DTYPES[self.fmt]} tensor ({self.B}, {self.hop})")
-        x = x.to(self.dev).contiguous()
-        self._end_streams(self.rs_in.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt]), self.hop, self.hops, _abi.addr(self.d_in), self.hop_in, 0,
-                                              self.stream.cuda_stream))
-        self.n_push += 1
-
-    def drain(self, k):
-        """The tick's k frames of d_wav -> every client's samples; n_max is the fastest listed rate's."""
-        rs = self.rs_out
-        if rs is None:
-            return None
-        if k == 0:
-            return torch.empty(self.B, 0, dtype=PCM_DTYPES[self.fmt], device=self.dev), torch.zeros(self.B, dtype=torch.int64)
-        self._start_and_end_out()
-        n = [k * self.spf] * len(self.rates)
-        counts = rs.push_raw(self.wav_ptr, n[0], n, _abi.addr(self.cwav, PCM_DTYPES[self.fmt]), self.cwav.shape[1], 0, self.stream.cuda_stream)
-        return self.cwav[:, :rs.out_len(n)], torch.tensor(counts, dtype=torch.int64)

@@ -340,7 +340,7 @@ struct RsFilterTable { RsFilter f[RS_MAX_RATES]; int n; };
 struct RsCallMulti { const void *x; long long xs; void *y; long long ys, yoff; int n_in[RS_MAX_RATES], n_fill[RS_MAX_RATES];
                      int n_fill_max, H_max, fmt_in, fmt_out, delayed, flush_row; };
 int launch_rs_update(const RsUpdateList &l, RsRow *ctl, float *hist, int H, hipStream_t s);
-int launch_rs_push(const RsFilter &f, const RsCall &c, RsRow *ctl, float *hist, int B, hipStream_t s);
+int launch_rs_push(const RsFilter &f, const RsCall &c, int lds_floats, RsRow *ctl, float *hist, int B, hipStream_t s);
 int launch_rs_push_multi(const RsFilterTable &t, const RsCallMulti &c, int lds_floats, RsRow *ctl, float *hist, int B, hipStream_t s);
 
 int launch_pack_codes(const float *codes, long long frames, int z, int nbits, unsigned char *out, hipStream_t s);

@@ -1,6 +1,7 @@
 // bvc_resampler_* (include/bvcodec.h): the host side of the streaming resampler - the filter design, the rows' book and the two
-// launches of a push - for the single-rate object and for the multi-rate one (a filter per rate, a rate per row), which share the
-// book, close / end / flush and the update launch.  Host only; the kernels are in k_resample_stream.hip.
+// launches of a push.  One object serves both forms of the ABI: a table of filters, one per rate, and a rate per row; the single-rate
+// form is the table of one, and differs in the calls it takes and the kernel it launches.  Host only; the kernels are in
+// k_resample_stream.hip.
 #include <cmath>
 
 #include "bvc_internal.h"
@@ -111,25 +112,23 @@ const int FMT_MASK = 15;
 }  // namespace
 
 struct bvc_resampler {
-    int B = 0, max_in = 0, fmt_in = 0, fmt_out = 0;
+    int B = 0, fmt_in = 0, fmt_out = 0;
     bool delayed = false;
-    Geometry g{};
-    double *d_h = nullptr;
-    float *d_hist = nullptr;
-    RsRow *d_ctl = nullptr;
-    int hist_stride = 0;                                     // floats between two rows' histories: g.H, or the largest H of the table
-    // a multi-rate object (bvc_resampler_create_multi): n_rates > 0 filters, one per rate, and max_in per rate; g, d_h, max_in unused
+    bool multi = false;                                      // made by bvc_resampler_create_multi: it takes the calls of that form, and the table kernel
+    // one filter per rate and the longest chunk at each; a single-rate object is the table of one: rate 0, hist_stride == gs[0].H
     int n_rates = 0;
     Geometry gs[RS_MAX_RATES] = {};
     int max_ins[RS_MAX_RATES] = {};
     double *d_hs[RS_MAX_RATES] = {};
+    float *d_hist = nullptr;
+    RsRow *d_ctl = nullptr;
+    int hist_stride = 0;                                     // floats between two rows' histories: the largest H of the table
     // the book: what the device holds for a row once the pending changes have been sent (rate: the row's filter, from open to idle)
     struct Row { int state = ROW_IDLE; long long n = 0; int start = 0, valid = -1; bool dirty = false, reset = false; int rate = 0; };
     std::vector<Row> rows;
     int n_dirty = 0;
     ~bvc_resampler() {
         for (double *p : d_hs) if (p) (void)hipFree(p);
-        if (d_h) (void)hipFree(d_h);
         if (d_hist) (void)hipFree(d_hist);
         if (d_ctl) (void)hipFree(d_ctl);
     }
@@ -143,20 +142,80 @@ int row_arg(const bvc_resampler *r, int row, const char *fn) {
     return BVC_OK;
 }
 
-// the filter and the longest chunk of a row: the object's own, or on a multi-rate object those of the row's rate
-const Geometry &geometry_of(const bvc_resampler *r, const bvc_resampler::Row &w) { return r->n_rates ? r->gs[w.rate] : r->g; }
-int max_in_of(const bvc_resampler *r, const bvc_resampler::Row &w) { return r->n_rates ? r->max_ins[w.rate] : r->max_in; }
-
 // open, push and set_taps come in a single-rate and a multi-rate form: BVC_EINVAL for the form that is not the object's
 int kind_arg(const bvc_resampler *r, bool multi, const char *fn, const char *other) {
     if (!r) { set_error("%s: null resampler", fn); return BVC_EINVAL; }
-    if ((r->n_rates > 0) == multi) return BVC_OK;
+    if (r->multi == multi) return BVC_OK;
     set_error("%s: a %s resampler takes %s", fn, multi ? "single-rate" : "multi-rate", other);
     return BVC_EINVAL;
 }
 
+bool pcm_formats_ok(int fmt_in, int fmt_out) {
+    const int fo = fmt_out & FMT_MASK;
+    return (fmt_in == BVC_PCM_F32 || fmt_in == BVC_PCM_S16) && (fo == BVC_PCM_F32 || fo == BVC_PCM_S16) &&
+           !(fmt_out & ~(FMT_MASK | BVC_PCM_DELAYED));
+}
+
+bool fits_lds(const Geometry &g, int max_in) { return (size_t)(g.H + (long long)max_in) * sizeof(float) <= 64 * 1024; }
+
+// The object of either create, for n validated filters and the longest chunk at each: the book, the device's buffers, the designed taps,
+// zero histories, idle rows.  BVC_ENODEVICE and the host's BVC_ENOMEM are reported here.  A failing device call is BVC_EHIP with its
+// error in e (allocated: the buffers were all there) and the object freed: each create maps that to its own code and text.
+struct Created { int rc; hipError_t e; bool allocated; };
+
+Created create(const char *fn, int B, int n, const Geometry *gs, const int32_t *max_in, int fmt_in, int fmt_out, bool multi, bvc_resampler **out) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+        (void)hipGetLastError();
+        set_error("%s: no HIP device", fn);
+        return {BVC_ENODEVICE, hipSuccess, false};
+    }
+    bvc_resampler *r = new (std::nothrow) bvc_resampler;
+    if (!r) { set_error("%s: out of host memory", fn); return {BVC_ENOMEM, hipSuccess, false}; }
+    r->B = B; r->fmt_in = fmt_in; r->fmt_out = fmt_out & FMT_MASK; r->delayed = (fmt_out & BVC_PCM_DELAYED) != 0;
+    r->multi = multi; r->n_rates = n;
+    for (int q = 0; q < n; ++q) {
+        r->gs[q] = gs[q]; r->max_ins[q] = max_in[q];
+        if (gs[q].H > r->hist_stride) r->hist_stride = gs[q].H;
+    }
+    r->rows.resize(B);
+    const size_t hist_bytes = (size_t)B * r->hist_stride * sizeof(float), ctl_bytes = (size_t)B * sizeof(RsRow);
+    const std::vector<RsRow> ctl(B, RsRow{0, 0, 0, -1, 0});
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&r->d_hist), hist_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_ctl), ctl_bytes);
+    for (int q = 0; q < n && e == hipSuccess; ++q) e = hipMalloc(reinterpret_cast<void **>(&r->d_hs[q]), (size_t)gs[q].ntaps * sizeof(double));
+    const bool allocated = e == hipSuccess;
+    for (int q = 0; q < n && e == hipSuccess; ++q) {
+        std::vector<double> h(gs[q].ntaps);
+        design_taps(gs[q], h.data());
+        e = hipMemcpy(r->d_hs[q], h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMemset(r->d_hist, 0, hist_bytes);
+    if (e == hipSuccess) e = hipMemcpy(r->d_ctl, ctl.data(), ctl_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        delete r;
+        return {BVC_EHIP, e, allocated};
+    }
+    *out = r;
+    return {BVC_OK, hipSuccess, true};
+}
+
 void mark(bvc_resampler *r, bvc_resampler::Row &w) {
     if (!w.dirty) { w.dirty = true; ++r->n_dirty; }
+}
+
+// open and open_rate behind their kind_arg: an idle row starts at `offset` of the next chunk with the filter of `rate`
+int open_row(bvc_resampler *r, const char *fn, int row, int rate, int offset) {
+    if (int rc = row_arg(r, row, fn)) return rc;
+    bvc_resampler::Row &w = r->rows[row];
+    if (w.state == ROW_RUNNING) { set_error("%s: row %d is running", fn, row); return BVC_EINVAL; }
+    if (rate < 0 || rate >= r->n_rates) { set_error("%s: rate_index %d outside 0..%d", fn, rate, r->n_rates - 1); return BVC_EINVAL; }
+    if (offset < 0 || offset > r->max_ins[rate]) { set_error("%s: offset %d outside 0..%d", fn, offset, r->max_ins[rate]); return BVC_EINVAL; }
+    w.state = ROW_RUNNING; w.n = 0; w.start = offset; w.valid = -1; w.reset = true; w.rate = rate;
+    mark(r, w);
+    return BVC_OK;
 }
 
 // the changed rows -> device, RS_LIST rows per launch, ahead of the push or flush on its stream
@@ -178,33 +237,63 @@ int send_changes(bvc_resampler *r, hipStream_t s) {
     return launch_rs_update(l, r->d_ctl, r->d_hist, r->hist_stride, s);
 }
 
-RsFilter filter_of(const bvc_resampler *r) { return RsFilter{r->d_h, r->g.ntaps, r->g.up, r->g.down, r->g.n_pre_remove, r->g.H}; }
-
-// the book after a push of n_in samples to a row with filter g: the outputs the push gave it, by the kernel's arithmetic
-int take_chunk(bvc_resampler::Row &w, const Geometry &g, int n_in, bool delayed) {
-    if (w.state != ROW_RUNNING) return 0;
-    const int end = w.valid >= 0 ? w.valid : n_in;
-    const long long n1 = w.n + (end - w.start);
-    const int count = (int)(rs_count(n1, g.up, g.down, g.n_pre_remove, delayed) - rs_count(w.n, g.up, g.down, g.n_pre_remove, delayed));
-    w.n = n1; w.start = 0;
-    if (w.valid >= 0) { w.state = ROW_ENDED; w.valid = -1; }
-    return count;
+// A push of n_in[q] samples to the rows of rate q, as the kernels take it: the block of every rate and the call's longest
+RsCallMulti push_call(const bvc_resampler *r, const void *d_x, long long xs, const int32_t *n_in, void *d_y, long long ys, long long yoff) {
+    RsCallMulti c{d_x, xs, d_y, ys, yoff, {}, {}, 0, r->hist_stride, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, -1};
+    for (int q = 0; q < r->n_rates; ++q) {
+        c.n_in[q] = n_in[q];
+        c.n_fill[q] = (int)rs_ceil_mul(n_in[q], r->gs[q].up, r->gs[q].down);
+        if (c.n_fill[q] > c.n_fill_max) c.n_fill_max = c.n_fill[q];
+    }
+    return c;
 }
 
-RsFilterTable table_of(const bvc_resampler *r) {
+RsFilter filter_of(const bvc_resampler *r, int q) {
+    const Geometry &g = r->gs[q];
+    return RsFilter{r->d_hs[q], g.ntaps, g.up, g.down, g.n_pre_remove, g.H};
+}
+
+// The launch of a push or flush, staging the largest H_q + n_in[q] floats of the call (a flush: the H of the row's rate): the
+// single-rate kernel with the one filter and its form of the call for a single-rate object, the table kernel for the other
+int launch(const bvc_resampler *r, const RsCallMulti &c, hipStream_t s) {
+    int lds_floats = c.flush_row >= 0 ? r->gs[r->rows[c.flush_row].rate].H : 0;
+    for (int q = 0; q < r->n_rates && c.flush_row < 0; ++q)
+        if (r->gs[q].H + c.n_in[q] > lds_floats) lds_floats = r->gs[q].H + c.n_in[q];
+    if (!r->multi) {
+        const RsCall c1{c.x, c.xs, c.y, c.ys, c.yoff, c.n_in[0], c.n_fill_max, c.fmt_in, c.fmt_out, c.delayed, c.flush_row};
+        return launch_rs_push(filter_of(r, 0), c1, lds_floats, r->d_ctl, r->d_hist, r->B, s);
+    }
     RsFilterTable t{};
     t.n = r->n_rates;
-    for (int q = 0; q < r->n_rates; ++q) {
-        const Geometry &g = r->gs[q];
-        t.f[q] = RsFilter{r->d_hs[q], g.ntaps, g.up, g.down, g.n_pre_remove, g.H};
-    }
-    return t;
+    for (int q = 0; q < r->n_rates; ++q) t.f[q] = filter_of(r, q);
+    return launch_rs_push_multi(t, c, lds_floats, r->d_ctl, r->d_hist, r->B, s);
 }
 
-bool pcm_formats_ok(int fmt_in, int fmt_out) {
-    const int fo = fmt_out & FMT_MASK;
-    return (fmt_in == BVC_PCM_F32 || fmt_in == BVC_PCM_S16) && (fo == BVC_PCM_F32 || fo == BVC_PCM_S16) &&
-           !(fmt_out & ~(FMT_MASK | BVC_PCM_DELAYED));
+// push and push_multi behind their argument checks: the rows' starts and ends against their chunks, the pending changes, the launch,
+// and the book - the outputs the push gave every row, by the kernel's arithmetic
+int push_rows(bvc_resampler *r, const char *fn, const RsCallMulti &c, int32_t *h_counts, hipStream_t s) {
+    for (int b = 0; b < r->B; ++b) {
+        const bvc_resampler::Row &w = r->rows[b];
+        if (w.state == ROW_RUNNING && (w.start > c.n_in[w.rate] || w.valid > c.n_in[w.rate])) {
+            set_error("%s: row %d starts at %d / ends at %d of a chunk of %d", fn, b, w.start, w.valid, c.n_in[w.rate]);
+            return BVC_EINVAL;
+        }
+    }
+    if (r->n_dirty > 0) { if (int rc = send_changes(r, s)) return rc; }
+    if (int rc = launch(r, c, s)) return rc;
+    for (int b = 0; b < r->B; ++b) {
+        bvc_resampler::Row &w = r->rows[b];
+        int count = 0;
+        if (w.state == ROW_RUNNING) {
+            const Geometry &g = r->gs[w.rate];
+            const long long n1 = w.n + ((w.valid >= 0 ? w.valid : c.n_in[w.rate]) - w.start);
+            count = (int)(rs_count(n1, g.up, g.down, g.n_pre_remove, r->delayed) - rs_count(w.n, g.up, g.down, g.n_pre_remove, r->delayed));
+            w.n = n1; w.start = 0;
+            if (w.valid >= 0) { w.state = ROW_ENDED; w.valid = -1; }
+        }
+        if (h_counts) h_counts[b] = count;
+    }
+    return BVC_OK;
 }
 
 }  // namespace
@@ -233,78 +322,38 @@ int bvc_resampler_taps(int32_t rate_in, int32_t rate_out, double *h_taps, int32_
 }
 
 int bvc_resampler_create(int32_t B, int32_t rate_in, int32_t rate_out, int32_t max_in, int32_t fmt_in, int32_t fmt_out, bvc_resampler **out) {
+    const char *fn = "bvc_resampler_create";
     Geometry g;
-    const int fo = fmt_out & FMT_MASK;
     if (!out || B <= 0 || max_in <= 0 || !geometry(rate_in, rate_out, &g) || !pcm_formats_ok(fmt_in, fmt_out)) {
-        set_error("bvc_resampler_create: B, max_in and both rates must be positive, the formats BVC_PCM_F32 or BVC_PCM_S16");
+        set_error("%s: B, max_in and both rates must be positive, the formats BVC_PCM_F32 or BVC_PCM_S16", fn);
         return BVC_EINVAL;
     }
-    if ((size_t)(g.H + (long long)max_in) * sizeof(float) > 64 * 1024) {
-        set_error("bvc_resampler_create: history %d + max_in %d samples do not fit the 64 KiB of LDS a push stages them in", g.H, (int)max_in);
+    if (!fits_lds(g, max_in)) {
+        set_error("%s: history %d + max_in %d samples do not fit the 64 KiB of LDS a push stages them in", fn, g.H, (int)max_in);
         return BVC_EINVAL;
     }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        (void)hipGetLastError();
-        set_error("bvc_resampler_create: no HIP device");
-        return BVC_ENODEVICE;
-    }
-    bvc_resampler *r = new (std::nothrow) bvc_resampler;
-    if (!r) { set_error("bvc_resampler_create: out of host memory"); return BVC_ENOMEM; }
-    r->B = B; r->max_in = max_in; r->fmt_in = fmt_in; r->fmt_out = fo; r->delayed = (fmt_out & BVC_PCM_DELAYED) != 0;
-    r->g = g;
-    r->hist_stride = g.H;
-    r->rows.resize(B);
-    std::vector<double> h(g.ntaps);
-    design_taps(g, h.data());
-    const size_t hist_bytes = (size_t)B * g.H * sizeof(float), ctl_bytes = (size_t)B * sizeof(RsRow);
-    std::vector<RsRow> ctl(B, RsRow{0, 0, 0, -1, 0});
-    bool ok = hipMalloc(reinterpret_cast<void **>(&r->d_h), (size_t)g.ntaps * sizeof(double)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void **>(&r->d_hist), hist_bytes) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void **>(&r->d_ctl), ctl_bytes) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        delete r;
-        set_error("bvc_resampler_create: device allocation failed");
-        return BVC_ENOMEM;
-    }
-    hipError_t e = hipMemcpy(r->d_h, h.data(), (size_t)g.ntaps * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(r->d_hist, 0, hist_bytes);
-    if (e == hipSuccess) e = hipMemcpy(r->d_ctl, ctl.data(), ctl_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        delete r;
-        set_error("bvc_resampler_create: %s", hipGetErrorString(e));
-        return BVC_EHIP;
-    }
-    *out = r;
-    return BVC_OK;
+    const Created c = create(fn, B, 1, &g, &max_in, fmt_in, fmt_out, false, out);
+    if (c.rc != BVC_EHIP) return c.rc;
+    if (!c.allocated) { set_error("%s: device allocation failed", fn); return BVC_ENOMEM; }      // (whatever the device gave as the reason)
+    set_error("%s: %s", fn, hipGetErrorString(c.e));
+    return BVC_EHIP;
 }
 
 void bvc_resampler_destroy(bvc_resampler *r) { delete r; }
 
 int bvc_resampler_set_taps(bvc_resampler *r, const double *h_taps, int32_t ntaps) {
     if (int rc = kind_arg(r, false, "bvc_resampler_set_taps", "bvc_resampler_set_taps_rate")) return rc;
-    if (!h_taps || ntaps != r->g.ntaps) {
-        set_error("bvc_resampler_set_taps: null argument, or not the %d taps of the design", r ? r->g.ntaps : 0);
+    if (!h_taps || ntaps != r->gs[0].ntaps) {
+        set_error("bvc_resampler_set_taps: null argument, or not the %d taps of the design", r->gs[0].ntaps);
         return BVC_EINVAL;
     }
-    BVC_HIP_TRY(hipMemcpy(r->d_h, h_taps, (size_t)ntaps * sizeof(double), hipMemcpyHostToDevice));
+    BVC_HIP_TRY(hipMemcpy(r->d_hs[0], h_taps, (size_t)ntaps * sizeof(double), hipMemcpyHostToDevice));
     return BVC_OK;
 }
 
 int bvc_resampler_open(bvc_resampler *r, int32_t row, int32_t offset_in_next_push) {
     if (int rc = kind_arg(r, false, "bvc_resampler_open", "bvc_resampler_open_rate")) return rc;
-    if (int rc = row_arg(r, row, "bvc_resampler_open")) return rc;
-    bvc_resampler::Row &w = r->rows[row];
-    if (w.state == ROW_RUNNING) { set_error("bvc_resampler_open: row %d is running", (int)row); return BVC_EINVAL; }
-    if (offset_in_next_push < 0 || offset_in_next_push > r->max_in) {
-        set_error("bvc_resampler_open: offset %d outside 0..%d", (int)offset_in_next_push, r->max_in);
-        return BVC_EINVAL;
-    }
-    w.state = ROW_RUNNING; w.n = 0; w.start = offset_in_next_push; w.valid = -1; w.reset = true;
-    mark(r, w);
-    return BVC_OK;
+    return open_row(r, "bvc_resampler_open", row, 0, offset_in_next_push);
 }
 
 int bvc_resampler_close(bvc_resampler *r, int32_t row) {
@@ -320,8 +369,8 @@ int bvc_resampler_end(bvc_resampler *r, int32_t row, int32_t n_valid_in_next_pus
     if (int rc = row_arg(r, row, "bvc_resampler_end")) return rc;
     bvc_resampler::Row &w = r->rows[row];
     if (w.state != ROW_RUNNING) { set_error("bvc_resampler_end: row %d is not running", (int)row); return BVC_EINVAL; }
-    if (n_valid_in_next_push < w.start || n_valid_in_next_push > max_in_of(r, w)) {
-        set_error("bvc_resampler_end: %d samples outside %d..%d", (int)n_valid_in_next_push, w.start, max_in_of(r, w));
+    if (n_valid_in_next_push < w.start || n_valid_in_next_push > r->max_ins[w.rate]) {
+        set_error("bvc_resampler_end: %d samples outside %d..%d", (int)n_valid_in_next_push, w.start, r->max_ins[w.rate]);
         return BVC_EINVAL;
     }
     w.valid = n_valid_in_next_push;
@@ -333,54 +382,34 @@ int bvc_resampler_push(bvc_resampler *r, const void *d_x, int64_t x_row_stride, 
                        int64_t y_offset, int32_t *h_counts, void *stream) {
     if (int rc = kind_arg(r, false, "bvc_resampler_push", "bvc_resampler_push_multi")) return rc;
     if (!d_x || !d_y) { set_error("bvc_resampler_push: null argument"); return BVC_EINVAL; }
-    if (n_in < 0 || n_in > r->max_in) { set_error("bvc_resampler_push: n_in %d outside 0..%d (max_in)", (int)n_in, r->max_in); return BVC_EINVAL; }
-    const int n_fill = (int)rs_ceil_mul(n_in, r->g.up, r->g.down);
-    if (x_row_stride < n_in || y_row_stride < n_fill || y_offset < 0) {
-        set_error("bvc_resampler_push: a row of d_x holds n_in = %d samples, a row of d_y ceil(n_in up / down) = %d behind y_offset >= 0", (int)n_in, n_fill);
+    if (n_in < 0 || n_in > r->max_ins[0]) { set_error("bvc_resampler_push: n_in %d outside 0..%d (max_in)", (int)n_in, r->max_ins[0]); return BVC_EINVAL; }
+    const RsCallMulti c = push_call(r, d_x, x_row_stride, &n_in, d_y, y_row_stride, y_offset);
+    if (x_row_stride < n_in || y_row_stride < c.n_fill_max || y_offset < 0) {
+        set_error("bvc_resampler_push: a row of d_x holds n_in = %d samples, a row of d_y ceil(n_in up / down) = %d behind y_offset >= 0", (int)n_in, c.n_fill_max);
         return BVC_EINVAL;
     }
-    for (int b = 0; b < r->B; ++b) {
-        const bvc_resampler::Row &w = r->rows[b];
-        if (w.state == ROW_RUNNING && (w.start > n_in || w.valid > n_in)) {
-            set_error("bvc_resampler_push: row %d starts at %d / ends at %d of a chunk of %d", b, w.start, w.valid, (int)n_in);
-            return BVC_EINVAL;
-        }
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (r->n_dirty > 0) { if (int rc = send_changes(r, s)) return rc; }
-    const RsCall c{d_x, x_row_stride, d_y, y_row_stride, y_offset, n_in, n_fill, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, -1};
-    if (int rc = launch_rs_push(filter_of(r), c, r->d_ctl, r->d_hist, r->B, s)) return rc;
-    for (int b = 0; b < r->B; ++b) {
-        const int count = take_chunk(r->rows[b], r->g, n_in, r->delayed);
-        if (h_counts) h_counts[b] = count;
-    }
-    return BVC_OK;
+    return push_rows(r, "bvc_resampler_push", c, h_counts, (hipStream_t)stream);
 }
 
 int bvc_resampler_flush(bvc_resampler *r, int32_t row, void *d_y_row, int32_t *count, void *stream) {
     if (int rc = row_arg(r, row, "bvc_resampler_flush")) return rc;
     bvc_resampler::Row &w = r->rows[row];
     if (w.state == ROW_IDLE) { set_error("bvc_resampler_flush: row %d is idle", (int)row); return BVC_EINVAL; }
-    const Geometry &g = geometry_of(r, w);
+    const Geometry &g = r->gs[w.rate];
     const long long done = rs_count(w.n, g.up, g.down, g.n_pre_remove, r->delayed);
     const long long all = rs_ceil_mul(w.n, g.up, g.down) + (r->delayed ? g.n_pre_remove : 0);
     const int n = (int)(all - done);                         // <= n_pre_remove
     if (n > 0 && !d_y_row) { set_error("bvc_resampler_flush: null d_y_row for %d samples", n); return BVC_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
     if (r->n_dirty > 0) { if (int rc = send_changes(r, s)) return rc; }       // (a row opened since the last push is reset first)
-    w.state = ROW_IDLE; w.start = 0; w.valid = -1;           // the kernel leaves the device's copy of the row idle
-    if (r->n_rates) {                                        // the row's own filter; its rate stays until it is opened again
-        const RsCallMulti c{nullptr, 0, d_y_row, 0, 0, {}, {}, n, r->hist_stride, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, row};
-        if (int rc = launch_rs_push_multi(table_of(r), c, g.H, r->d_ctl, r->d_hist, r->B, s)) return rc;
-    } else {
-        const RsCall c{nullptr, 0, d_y_row, 0, 0, 0, n, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, row};
-        if (int rc = launch_rs_push(filter_of(r), c, r->d_ctl, r->d_hist, r->B, s)) return rc;
-    }
+    w.state = ROW_IDLE; w.start = 0; w.valid = -1;           // the kernel leaves the device's copy of the row idle; its rate stays
+    const RsCallMulti c{nullptr, 0, d_y_row, 0, 0, {}, {}, n, r->hist_stride, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, row};
+    if (int rc = launch(r, c, s)) return rc;
     if (count) *count = n;
     return BVC_OK;
 }
 
-// ---- the multi-rate object: one filter per rate, a rate per row
+// ---- the multi-rate form: one filter per rate, a rate per row
 int bvc_resampler_create_multi(int32_t B, int32_t n_rates, const int32_t *rates, int32_t fixed_rate, int32_t direction, const int32_t *max_in,
                                int32_t fmt_in, int32_t fmt_out, bvc_resampler **out) {
     const char *fn = "bvc_resampler_create_multi";
@@ -390,7 +419,6 @@ int bvc_resampler_create_multi(int32_t B, int32_t n_rates, const int32_t *rates,
         return BVC_EINVAL;
     }
     Geometry gs[RS_MAX_RATES];
-    int H_max = 0;
     for (int q = 0; q < n_rates; ++q) {
         for (int p = 0; p < q; ++p)
             if (rates[p] == rates[q]) { set_error("%s: rate %d is listed twice", fn, (int)rates[q]); return BVC_EINVAL; }
@@ -398,46 +426,16 @@ int bvc_resampler_create_multi(int32_t B, int32_t n_rates, const int32_t *rates,
             set_error("%s: rate %d: the rates and max_in must be positive", fn, (int)rates[q]);
             return BVC_EINVAL;
         }
-        if ((size_t)(gs[q].H + (long long)max_in[q]) * sizeof(float) > 64 * 1024) {
+        if (!fits_lds(gs[q], max_in[q])) {
             set_error("%s: rate %d: history %d + max_in %d samples do not fit the 64 KiB of LDS a push stages them in", fn, (int)rates[q],
                       gs[q].H, (int)max_in[q]);
             return BVC_EINVAL;
         }
-        if (gs[q].H > H_max) H_max = gs[q].H;
     }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        (void)hipGetLastError();
-        set_error("%s: no HIP device", fn);
-        return BVC_ENODEVICE;
-    }
-    bvc_resampler *r = new (std::nothrow) bvc_resampler;
-    if (!r) { set_error("%s: out of host memory", fn); return BVC_ENOMEM; }
-    r->B = B; r->fmt_in = fmt_in; r->fmt_out = fmt_out & FMT_MASK; r->delayed = (fmt_out & BVC_PCM_DELAYED) != 0;
-    r->n_rates = n_rates; r->hist_stride = H_max;
-    r->rows.resize(B);
-    const size_t hist_bytes = (size_t)B * H_max * sizeof(float), ctl_bytes = (size_t)B * sizeof(RsRow);
-    std::vector<RsRow> ctl(B, RsRow{0, 0, 0, -1, 0});
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&r->d_hist), hist_bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_ctl), ctl_bytes);
-    for (int q = 0; q < n_rates && e == hipSuccess; ++q) {
-        r->gs[q] = gs[q]; r->max_ins[q] = max_in[q];
-        std::vector<double> h(gs[q].ntaps);
-        design_taps(gs[q], h.data());
-        e = hipMalloc(reinterpret_cast<void **>(&r->d_hs[q]), h.size() * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpy(r->d_hs[q], h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemset(r->d_hist, 0, hist_bytes);
-    if (e == hipSuccess) e = hipMemcpy(r->d_ctl, ctl.data(), ctl_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        delete r;
-        set_error("%s: %s", fn, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? BVC_ENOMEM : BVC_EHIP;
-    }
-    *out = r;
-    return BVC_OK;
+    const Created c = create(fn, B, n_rates, gs, max_in, fmt_in, fmt_out, true, out);
+    if (c.rc != BVC_EHIP) return c.rc;
+    set_error("%s: %s", fn, hipGetErrorString(c.e));
+    return c.e == hipErrorOutOfMemory ? BVC_ENOMEM : BVC_EHIP;                                    // (only where the device says so)
 }
 
 int bvc_resampler_set_taps_rate(bvc_resampler *r, int32_t rate_index, const double *h_taps, int32_t ntaps) {
@@ -453,60 +451,28 @@ int bvc_resampler_set_taps_rate(bvc_resampler *r, int32_t rate_index, const doub
 
 int bvc_resampler_open_rate(bvc_resampler *r, int32_t row, int32_t rate_index, int32_t offset_in_next_push) {
     if (int rc = kind_arg(r, true, "bvc_resampler_open_rate", "bvc_resampler_open")) return rc;
-    if (int rc = row_arg(r, row, "bvc_resampler_open_rate")) return rc;
-    bvc_resampler::Row &w = r->rows[row];
-    if (w.state == ROW_RUNNING) { set_error("bvc_resampler_open_rate: row %d is running", (int)row); return BVC_EINVAL; }
-    if (rate_index < 0 || rate_index >= r->n_rates) {
-        set_error("bvc_resampler_open_rate: rate_index %d outside 0..%d", (int)rate_index, r->n_rates - 1);
-        return BVC_EINVAL;
-    }
-    if (offset_in_next_push < 0 || offset_in_next_push > r->max_ins[rate_index]) {
-        set_error("bvc_resampler_open_rate: offset %d outside 0..%d", (int)offset_in_next_push, r->max_ins[rate_index]);
-        return BVC_EINVAL;
-    }
-    w.state = ROW_RUNNING; w.n = 0; w.start = offset_in_next_push; w.valid = -1; w.reset = true; w.rate = rate_index;
-    mark(r, w);
-    return BVC_OK;
+    return open_row(r, "bvc_resampler_open_rate", row, rate_index, offset_in_next_push);
 }
 
 int bvc_resampler_push_multi(bvc_resampler *r, const void *d_x, int64_t x_row_stride, const int32_t *n_in, void *d_y, int64_t y_row_stride,
                              int64_t y_offset, int32_t *h_counts, void *stream) {
     if (int rc = kind_arg(r, true, "bvc_resampler_push_multi", "bvc_resampler_push")) return rc;
     if (!d_x || !d_y || !n_in) { set_error("bvc_resampler_push_multi: null argument"); return BVC_EINVAL; }
-    RsCallMulti c{d_x, x_row_stride, d_y, y_row_stride, y_offset, {}, {}, 0, r->hist_stride, r->fmt_in, r->fmt_out, r->delayed ? 1 : 0, -1};
-    int n_in_max = 0, lds_floats = 0;
+    int n_in_max = 0;
     for (int q = 0; q < r->n_rates; ++q) {
         if (n_in[q] < 0 || n_in[q] > r->max_ins[q]) {
             set_error("bvc_resampler_push_multi: n_in[%d] = %d outside 0..%d (max_in)", q, (int)n_in[q], r->max_ins[q]);
             return BVC_EINVAL;
         }
-        c.n_in[q] = n_in[q];
-        c.n_fill[q] = (int)rs_ceil_mul(n_in[q], r->gs[q].up, r->gs[q].down);
         if (n_in[q] > n_in_max) n_in_max = n_in[q];
-        if (c.n_fill[q] > c.n_fill_max) c.n_fill_max = c.n_fill[q];
-        if (r->gs[q].H + n_in[q] > lds_floats) lds_floats = r->gs[q].H + n_in[q];
     }
+    const RsCallMulti c = push_call(r, d_x, x_row_stride, n_in, d_y, y_row_stride, y_offset);
     if (x_row_stride < n_in_max || y_row_stride < c.n_fill_max || y_offset < 0) {
         set_error("bvc_resampler_push_multi: a row of d_x holds the longest chunk, %d samples, a row of d_y the longest block, %d, behind y_offset >= 0",
                   n_in_max, c.n_fill_max);
         return BVC_EINVAL;
     }
-    for (int b = 0; b < r->B; ++b) {
-        const bvc_resampler::Row &w = r->rows[b];
-        if (w.state == ROW_RUNNING && (w.start > n_in[w.rate] || w.valid > n_in[w.rate])) {
-            set_error("bvc_resampler_push_multi: row %d starts at %d / ends at %d of a chunk of %d", b, w.start, w.valid, (int)n_in[w.rate]);
-            return BVC_EINVAL;
-        }
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (r->n_dirty > 0) { if (int rc = send_changes(r, s)) return rc; }
-    if (int rc = launch_rs_push_multi(table_of(r), c, lds_floats, r->d_ctl, r->d_hist, r->B, s)) return rc;
-    for (int b = 0; b < r->B; ++b) {
-        bvc_resampler::Row &w = r->rows[b];
-        const int count = take_chunk(w, r->gs[w.rate], n_in[w.rate], r->delayed);
-        if (h_counts) h_counts[b] = count;
-    }
-    return BVC_OK;
+    return push_rows(r, "bvc_resampler_push_multi", c, h_counts, (hipStream_t)stream);
 }
 
 }  // extern "C"

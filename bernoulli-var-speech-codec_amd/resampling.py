@@ -55,24 +55,38 @@ class StreamResampler:
             raise ValueError(f"sample formats are {sorted(PCM_FORMATS)}")
         if int(rate_in) <= 0 or int(rate_out) <= 0:
             raise ValueError("StreamResampler: rates must be positive")
+        self.rate_in, self.rate_out, self.max_in = int(rate_in), int(rate_out), int(max_in)
+        design = preprocess.design(rate_out, rate_in)
+        self.up, self.down, _, self.lag = design
+        self.max_out = -(-self.max_in * self.up // self.down)
+        self._create(batch, fmt_in, fmt_out, delayed, device, [design], "bvc_resampler_create", (batch, self.rate_in, self.rate_out, self.max_in))
+
+    def _create(self, batch, fmt_in, fmt_out, delayed, device, designs, create, args):
+        """What a constructor does once its arguments and geometry stand: the device, the library's object (the call named ``create``:
+        ``args``, the two formats, the handle), the taps of ``designs`` - the offline call's, ``preprocess.design``'s - handed in one by
+        one (``_set_taps``; the library designs the same ones), the counts."""
         self.lib = _abi.load()
         self.dev = torch.device("cuda" if device is None else device)
         if self.dev.index is None:
             self.dev = torch.device("cuda", torch.cuda.current_device())
-        self.B, self.rate_in, self.rate_out, self.max_in = batch, int(rate_in), int(rate_out), int(max_in)
-        self.fmt_in, self.fmt_out, self.delayed = fmt_in, fmt_out, bool(delayed)
-        self.up, self.down, taps, self.lag = preprocess.design(rate_out, rate_in)
-        self.max_out = -(-self.max_in * self.up // self.down)
+        self.B, self.fmt_in, self.fmt_out, self.delayed = batch, fmt_in, fmt_out, bool(delayed)
         self.running = set()
-        h = self.handle = _abi.Handle(self.lib.bvc_resampler_destroy)
+        self.handle = _abi.Handle(self.lib.bvc_resampler_destroy)
         with torch.cuda.device(self.dev):
-            _abi.check_arg(self.lib.bvc_resampler_create(batch, self.rate_in, self.rate_out, self.max_in, PCM_FORMATS[fmt_in],
-                                                         PCM_FORMATS[fmt_out] | (PCM_DELAYED if delayed else 0), ctypes.byref(h)))
-            if self.up != self.down:        # the offline call's taps are preprocess.design's: hand them in (the library designs the same ones)
-                taps = taps.astype("float64")
-                _abi.check_arg(self.lib.bvc_resampler_set_taps(h, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(taps)))
+            _abi.check_arg(getattr(self.lib, create)(*args, PCM_FORMATS[fmt_in], PCM_FORMATS[fmt_out] | (PCM_DELAYED if delayed else 0), ctypes.byref(self.handle)))
+            for i, (up, down, taps, _) in enumerate(designs):
+                if up != down:
+                    taps = taps.astype("float64")
+                    _abi.check_arg(self._set_taps(i, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(taps)))
         self._counts = (ctypes.c_int32 * batch)()
         self._out = None
+
+    def _set_taps(self, i, taps, ntaps):
+        return self.lib.bvc_resampler_set_taps(self.handle, taps, ntaps)
+
+    def widths(self):
+        """(columns of the out buffer, length of a flush's tensor): ``max_out`` and ``lag`` (``MultiRateResampler``: the largest)."""
+        return self.max_out, self.lag
 
     def open(self, row, offset=0):
         _abi.check_arg(self.lib.bvc_resampler_open(self.handle, int(row), int(offset)))
@@ -101,20 +115,23 @@ class StreamResampler:
     def push(self, x):
         if x.dim() != 2 or x.shape[0] != self.B or x.shape[1] > self.max_in or x.dtype != PCM_DTYPES[self.fmt_in]:
             raise ValueError(f"StreamResampler.push: expected a {PCM_DTYPES[self.fmt_in]} tensor ({self.B}, n <= {self.max_in})")
+        return self._push(x, x.shape[1], -(-x.shape[1] * self.up // self.down))
+
+    def _push(self, x, n_in, n_out):
+        """A checked push: ``n_in`` as ``push_raw`` takes it, ``n_out`` the width of the view that is returned."""
         x = x.to(self.dev).contiguous()
-        n = x.shape[1]
         if self._out is None:
-            self._out = torch.empty(self.B, max(1, self.max_out), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
+            self._out = torch.empty(self.B, max(1, self.widths()[0]), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
         with torch.cuda.device(self.dev):
             out = _abi.addr(self._out, PCM_DTYPES[self.fmt_out])
-            counts = self.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt_in]) if n else out, max(n, 1), n, out, self._out.shape[1], 0,
-                                   torch.cuda.current_stream(self.dev).cuda_stream)
-        return self._out[:, :-(-n * self.up // self.down)], torch.tensor(counts, dtype=torch.int64)
+            counts = self.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt_in]) if x.shape[1] else out, max(x.shape[1], 1), n_in, out,
+                                   self._out.shape[1], 0, torch.cuda.current_stream(self.dev).cuda_stream)
+        return self._out[:, :n_out], torch.tensor(counts, dtype=torch.int64)
 
     @torch.no_grad()
     def flush(self, row):
-        """The rest of the row's outputs (at most ``lag`` samples, a new tensor); the row is idle afterwards."""
-        y = torch.empty(max(1, self.lag), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
+        """The rest of the row's outputs (at most ``lag`` samples - its rate's - in a new tensor); the row is idle afterwards."""
+        y = torch.empty(max(1, self.widths()[1]), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
         with torch.cuda.device(self.dev):
             n = self.flush_raw(row, _abi.addr(y, PCM_DTYPES[self.fmt_out]), torch.cuda.current_stream(self.dev).cuda_stream)
         return y[:n]
@@ -146,31 +163,22 @@ class MultiRateResampler(StreamResampler):
         self.max_in = [int(max_in)] * n if isinstance(max_in, int) else [int(m) for m in max_in]
         if len(self.max_in) != n:
             raise ValueError("MultiRateResampler: max_in is a number or one number per rate")
-        self.lib = _abi.load()
-        self.dev = torch.device("cuda" if device is None else device)
-        if self.dev.index is None:
-            self.dev = torch.device("cuda", torch.cuda.current_device())
-        self.B, self.rates, self.fixed_rate, self.direction = batch, tuple(rates), int(fixed_rate), direction
-        self.fmt_in, self.fmt_out, self.delayed = fmt_in, fmt_out, bool(delayed)
+        self.rates, self.fixed_rate, self.direction = tuple(rates), int(fixed_rate), direction
         pairs = [(r, self.fixed_rate) if direction == "in" else (self.fixed_rate, r) for r in rates]      # (rate_in, rate_out)
         designs = [preprocess.design(rate_out, rate_in) for rate_in, rate_out in pairs]
         self.up, self.down, self.lag = ([d[i] for d in designs] for i in (0, 1, 3))
         self.max_out = [-(-m * u // d) for m, u, d in zip(self.max_in, self.up, self.down)]
-        self.running = set()
         self.row_rate = [None] * batch                          # the index of a row's rate, from open until it is idle again
-        h = self.handle = _abi.Handle(self.lib.bvc_resampler_destroy)
         i32s = ctypes.c_int32 * n
-        with torch.cuda.device(self.dev):
-            _abi.check_arg(self.lib.bvc_resampler_create_multi(batch, n, i32s(*rates), self.fixed_rate, 0 if direction == "in" else 1,
-                                                               i32s(*self.max_in), PCM_FORMATS[fmt_in],
-                                                               PCM_FORMATS[fmt_out] | (PCM_DELAYED if delayed else 0), ctypes.byref(h)))
-            for i, (up, down, taps, _) in enumerate(designs):   # the offline call's taps, as StreamResampler hands them in
-                if up != down:
-                    taps = taps.astype("float64")
-                    _abi.check_arg(self.lib.bvc_resampler_set_taps_rate(h, i, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(taps)))
-        self._counts = (ctypes.c_int32 * batch)()
         self._n = i32s()
-        self._out = None
+        self._create(batch, fmt_in, fmt_out, delayed, device, designs, "bvc_resampler_create_multi",
+                     (batch, n, i32s(*rates), self.fixed_rate, 0 if direction == "in" else 1, i32s(*self.max_in)))
+
+    def _set_taps(self, i, taps, ntaps):
+        return self.lib.bvc_resampler_set_taps_rate(self.handle, i, taps, ntaps)
+
+    def widths(self):
+        return max(self.max_out), max(self.lag)
 
     def index(self, rate):
         if rate not in self.rates:
@@ -201,19 +209,4 @@ class MultiRateResampler(StreamResampler):
                 or x.shape[1] < max(n) or any(not 0 <= m <= lim for m, lim in zip(n, self.max_in))):
             raise ValueError(f"MultiRateResampler.push: expected a {PCM_DTYPES[self.fmt_in]} tensor ({self.B}, >= max(n)) and one chunk "
                              f"length per rate, at most {self.max_in}")
-        x = x.to(self.dev).contiguous()
-        if self._out is None:
-            self._out = torch.empty(self.B, max(1, max(self.max_out)), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
-        with torch.cuda.device(self.dev):
-            out = _abi.addr(self._out, PCM_DTYPES[self.fmt_out])
-            counts = self.push_raw(_abi.addr(x, PCM_DTYPES[self.fmt_in]) if x.shape[1] else out, max(x.shape[1], 1), n, out,
-                                   self._out.shape[1], 0, torch.cuda.current_stream(self.dev).cuda_stream)
-        return self._out[:, :self.out_len(n)], torch.tensor(counts, dtype=torch.int64)
-
-    @torch.no_grad()
-    def flush(self, row):
-        """The rest of the row's outputs (at most its rate's lag, a new tensor); the row is idle afterwards."""
-        y = torch.empty(max(1, max(self.lag)), dtype=PCM_DTYPES[self.fmt_out], device=self.dev)
-        with torch.cuda.device(self.dev):
-            n = self.flush_raw(row, _abi.addr(y, PCM_DTYPES[self.fmt_out]), torch.cuda.current_stream(self.dev).cuda_stream)
-        return y[:n]
+        return self._push(x, n, self.out_len(n))

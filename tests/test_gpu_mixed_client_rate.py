@@ -187,6 +187,70 @@ def test_s16_strides_offset_and_the_wrong_kind_of_call():
     multi.end(1, 160)
 
 
+ONE_RATE_CASES = [(r, d, delayed, "f32") for r in (8000, 48000, 22050) for d in ("in", "out") for delayed in (False, True)]
+ONE_RATE_CASES.append((48000, "in", True, "s16"))
+
+
+@pytest.mark.parametrize("rate,direction,delayed,fmt", ONE_RATE_CASES)
+def test_one_listed_rate_equals_the_single_rate_resampler(rate, direction, delayed, fmt):
+    """The table of one rate and the single-rate object share everything but the kernel's entry point: a MultiRateResampler that lists
+    only `rate` and a StreamResampler at it go through one ragged script - max_in one 20 ms hop of the input side; row 0 opens 3 samples
+    into push 0, row 1 at its start; chunks of a hop, 0, 1, 7, a hop (row 1 ends with 5 samples of it and is flushed), a hop less one
+    (row 1 opens again 2 samples in), 33 and a hop; then both rows are flushed.  Row 2 is never opened and its input is NaN, Inf and 1e38
+    (s16: a constant).  Every push's whole block - the samples, the zeros behind a row's count, the idle row's zeros - its counts, and
+    every flush are equal."""
+    from bvcodec.streaming import MultiRateResampler, StreamResampler
+    rate_in, rate_out = (rate, FS) if direction == "in" else (FS, rate)
+    hop = rate_in // 50
+    dtype = torch.int16 if fmt == "s16" else torch.float32
+    multi = MultiRateResampler(3, (rate,), FS, direction, hop, fmt, fmt, delayed=delayed)
+    single = StreamResampler(3, rate_in, rate_out, hop, fmt, fmt, delayed=delayed)
+    assert multi.max_in == [single.max_in] and multi.lag == [single.lag] and multi.max_out == [single.max_out]
+    g = torch.Generator().manual_seed(rate // 50 + delayed)
+
+    def both(call, *args):
+        return call(multi, *args), call(single, *args)
+
+    def flush(row):
+        a, b = both(lambda rs: rs.flush(row).clone())
+        assert a.dtype == b.dtype == dtype and a.shape == b.shape and torch.equal(a, b) and a.numel() <= single.lag, (row, a.shape, b.shape)
+        return a.numel()
+
+    start = {0: 3, 1: 0}                                              # row -> where its stream starts in the coming chunk
+    multi.open(0, rate, 3), single.open(0, 3), multi.open(1, rate), single.open(1)
+    flushed = []
+    for p, n in enumerate((hop, 0, 1, 7, hop, hop - 1, 33, hop)):
+        end = {}
+        if p == 4:
+            both(lambda rs: rs.end(1, 5))
+            end[1] = 5
+        if p == 5:
+            multi.open(1, rate, 2), single.open(1, 2)
+            start[1] = 2
+        x = garbage(3, n, dtype)
+        for row in (0, 1):
+            lo, hi = min(start.get(row, 0), n), end.get(row, n)
+            x[row, lo:hi] = (torch.randint(-20000, 20000, (hi - lo,), generator=g, dtype=dtype) if fmt == "s16"
+                             else torch.randn(hi - lo, generator=g))
+        start = {}
+        x = x.to(DEV)
+        (ym, cm), (ys, cs) = multi.push(x, [n]), single.push(x)
+        assert ym.shape == ys.shape == (3, -(-n * single.up // single.down)) and ym.dtype == ys.dtype == dtype, (p, ym.shape, ys.shape)
+        assert torch.equal(cm, cs) and torch.equal(ym, ys), (p, cm, cs)
+        assert int(cm[2]) == 0 and not bool(ym[2].any())
+        for row in (0, 1):
+            assert not bool(ym[row, int(cm[row]):].any()), (p, row)
+        if fmt == "f32":
+            assert bool(torch.isfinite(ym).all())
+        if p == 4:
+            flushed.append(flush(1))
+    flushed += [flush(0), flush(1)]
+    assert any(flushed) and int(cm[0]) > 0
+    for rs in (multi, single):
+        with pytest.raises(ValueError):
+            rs.flush(2)
+
+
 # ---------------------------------------------------------------------------------------------- sessions
 def speech(n, seed):
     from bvcodec import synth
