@@ -55,6 +55,12 @@ SIGNATURES = {
     "bvc_decode_conceal": (ctypes.c_int, [_vp, _vp, _vp, _f, _i32, _i64, _i64, _f, _vp, _vp, _vp, _sz, _vp]),
     "bvc_bvrnn_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _sz, _vp]),
+    "bvc_bvrnn_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i64, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _sz, _vp]),
+    "bvc_bvrnn_backward_workspace_bytes": (_sz, [_vp, _i32, _i64]),
+    "bvc_bvrnn_backward_prepare": (ctypes.c_int, [_vp, _vp]),
+    "bvc_bvrnn_grad_layout": (ctypes.c_int, [ctypes.POINTER(BvcConfig), ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i32,
+                                             ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
     "bvc_bigvgan": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i64, _f, _vp, _vp, _sz, _vp]),
     "bvc_vocoder_stream_create": (ctypes.c_int, [_vp, _i32, _i32, ctypes.POINTER(_vp)]),
     "bvc_vocoder_stream_destroy": (None, [_vp]),
@@ -137,7 +143,8 @@ SIGNATURES = {
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i32)]),
     "bvc_test_linear": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "bvc_test_linear_batched": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
-    "bvc_test_skinny_pick": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_i32)]),
+    "bvc_test_weight_grad": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, ctypes.POINTER(_i64), _vp]),
+    "bvc_test_skinny_pick":(ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_i32)]),
     "bvc_test_skinny_counts": (ctypes.c_int, [ctypes.POINTER(_i64)]),
     "bvc_test_linear_tiles": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "bvc_test_tile_plan": (ctypes.c_int, [_i32, _i64, _i32, _i32, _i32, ctypes.POINTER(_i64)]),

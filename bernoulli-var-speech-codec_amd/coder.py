@@ -3,7 +3,7 @@ and ``BigVGAN`` (``model.vocoder(x, length)``, models.py:207-238), each on the e
 import numpy as np
 import torch
 
-from ._abi import ptr
+from ._abi import BvcConfig, check as _abi_check, load as _abi_load, ptr
 from .engine import _OnDevice, _prep, _trimmed
 from .vbr_args import _check_cap_q8, _check_ladder
 
@@ -48,6 +48,21 @@ def _check_frame_bits(bits, B, T, var_bit, who):
         raise ValueError(f"{who}: bits must be a tensor ({B}, {T})")
 
 
+def _draw_randomness(B, T, z_dim, greedy, r, noise):
+    """The random numbers of ``BVRNN.forward`` that the caller did not give, in the reference's draw order (bvrnn.py:111,126) from
+    torch's global CPU generator: per frame ``torch.rand([])`` and - unless greedy - ``torch.rand(B, z_dim)``."""
+    if r is None or (noise is None and not greedy):
+        rs, ns = [], []
+        for _ in range(T):
+            rs.append(torch.rand([]))
+            if not greedy:
+                ns.append(torch.rand(B, z_dim))
+        r = torch.stack(rs) if r is None else r
+        if not greedy and noise is None:
+            noise = torch.stack(ns, 1)
+    return r, noise
+
+
 class BVRNN(_OnDevice):
     """``BVRNN.encode`` / ``BVRNN.decode`` (bvrnn.py:163-229) on the HIP recurrent kernels."""
 
@@ -58,8 +73,8 @@ class BVRNN(_OnDevice):
 
     @torch.no_grad()
     def forward(self, y, p_use_gen, greedy, varBitrate, *, r=None, noise=None, return_all=False):
-        """``BVRNN.forward(y, p_use_gen, greedy, varBitrate)`` (bvrnn.py:86-160), forward values only (this build
-        has no autograd): stochastic Bernoulli sampler ``round(u - 0.5 + enc_t)``, prior net, KL term and the
+        """``BVRNN.forward(y, p_use_gen, greedy, varBitrate)`` (bvrnn.py:86-160), forward values only (their gradients:
+        ``backward``, or ``forward_train`` for torch.autograd): stochastic Bernoulli sampler ``round(u - 0.5 + enc_t)``, prior net, KL term and the
         teacher-forcing mix.  Returns (all_dec_mean (B,T,x_dim), kld scalar) like the reference.
 
         Randomness: the reference draws, per frame, ``torch.rand([])`` (compared with p_use_gen) and - unless
@@ -69,15 +84,7 @@ class BVRNN(_OnDevice):
         ``return_all=True`` adds a dict with z (forward value of the sample), prob (enc_t), prior, kld_frames."""
         eng, out_dev, y = self._enter(y)
         B, T, _ = y.shape
-        if r is None or (noise is None and not greedy):
-            rs, ns = [], []
-            for _ in range(T):                                    # the reference's draw order (bvrnn.py:111,126)
-                rs.append(torch.rand([]))
-                if not greedy:
-                    ns.append(torch.rand(B, self.z_dim))
-            r = torch.stack(rs) if r is None else r
-            if not greedy and noise is None:
-                noise = torch.stack(ns, 1)
+        r, noise = _draw_randomness(B, T, self.z_dim, greedy, r, noise)
         use_gen = (torch.as_tensor(r).detach().cpu().float() < p_use_gen).to(torch.uint8).contiguous()
         assert use_gen.numel() == T
         bits = _prep(varBitrate, eng.device) if (varBitrate is not None and self.varBit) else None
@@ -92,6 +99,86 @@ class BVRNN(_OnDevice):
         # torch.mean(torch.stack(kld_loss)), bvrnn.py:160
         out = eng.to_caller(out_dev, dec, torch.mean(kld), *extra.values(), poll=False)
         return out[:2] + (dict(zip(extra, out[2:])),) if return_all else out
+
+    def grad_parameters(self):
+        """The trainable tensors of ``BVRNN.forward`` as this model holds them: a dict of float32 CPU copies keyed by the reference's
+        state-dict names (36 tensors; not mean_mel / std_mel, which are buffers, nor log_sigma, which does not enter forward)."""
+        names = [n for n in self._tensors if n.split(".")[0] in ("phi_x", "phi_z", "enc", "prior", "dec", "rnn")]
+        return {n: self._tensors[n].detach().clone() for n in names}
+
+    def grad_layout(self):
+        """``bvc_bvrnn_grad_layout``: ([(name, offset, numel)], total floats) of the flat gradient buffer of ``backward`` (needs no GPU)."""
+        import ctypes
+        lib = _abi_load()
+        cfg = BvcConfig()
+        cfg.num_mels, cfg.h_dim, cfg.z_dim, cfg.var_bit = self.x_dim, self.h_dim, self.z_dim, int(self.varBit)
+        n, total = ctypes.c_int32(0), ctypes.c_int64(0)
+        _abi_check(lib.bvc_bvrnn_grad_layout(ctypes.byref(cfg), None, None, None, 0, ctypes.byref(n), ctypes.byref(total)))
+        names, offs, nums = (ctypes.c_char_p * n.value)(), (ctypes.c_int64 * n.value)(), (ctypes.c_int64 * n.value)()
+        _abi_check(lib.bvc_bvrnn_grad_layout(ctypes.byref(cfg), names, offs, nums, n.value, None, None))
+        return [(names[i].decode(), int(offs[i]), int(nums[i])) for i in range(n.value)], int(total.value)
+
+    def _check_backward_args(self, y, greedy, varBitrate, grad_dec, grad_kld, r, noise):
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[2] != self.x_dim or y.shape[0] < 1 or y.shape[1] < 1:
+            raise ValueError(f"backward: y must be (B, T, {self.x_dim})")
+        B, T, _ = y.shape
+        if not torch.is_tensor(grad_dec) or tuple(grad_dec.shape) != (B, T, self.x_dim):
+            raise ValueError(f"backward: grad_dec must be ({B}, {T}, {self.x_dim}) like all_dec_mean, got "
+                             f"{tuple(grad_dec.shape) if torch.is_tensor(grad_dec) else type(grad_dec).__name__}")
+        if torch.is_tensor(grad_kld):
+            if grad_kld.numel() != 1 or grad_kld.dim() > 0:
+                raise ValueError(f"backward: grad_kld must be a scalar, got a tensor {tuple(grad_kld.shape)}")
+        elif isinstance(grad_kld, bool) or not isinstance(grad_kld, (int, float, np.floating, np.integer)):
+            raise ValueError(f"backward: grad_kld must be a scalar, got {type(grad_kld).__name__}")
+        if r is not None and tuple(torch.as_tensor(r).shape) != (T,):
+            raise ValueError(f"backward: r must be ({T},), got {tuple(torch.as_tensor(r).shape)}")
+        if noise is not None and not greedy and tuple(torch.as_tensor(noise).shape) != (B, T, self.z_dim):
+            raise ValueError(f"backward: noise must be ({B}, {T}, {self.z_dim}), got {tuple(torch.as_tensor(noise).shape)}")
+        if self.varBit and (varBitrate is None or not torch.is_tensor(varBitrate) or tuple(varBitrate.shape) != (B, T)):
+            raise ValueError(f"backward: a variable-rate model needs varBitrate ({B}, {T})")
+        return B, T
+
+    @torch.no_grad()
+    def backward(self, y, p_use_gen, greedy, varBitrate, grad_dec, grad_kld, *, r=None, noise=None, grad_input=False,
+                 return_forward=False):
+        """The vector-Jacobian product of ``forward`` (``bvc_bvrnn_backward``): given ``grad_dec`` (B,T,x_dim), the gradient of a
+        loss with respect to all_dec_mean, and the scalar ``grad_kld``, its gradient with respect to the returned kld, a dict of the
+        loss's gradients keyed by the reference's state-dict names, each of its state-dict shape (``grad_parameters`` has the same
+        keys); ``grad_input=True`` adds "y", the gradient with respect to the input mel.  The call runs its own forward, with the
+        randomness of ``forward``: the same draws in the same order from the global CPU generator unless ``r`` / ``noise`` are
+        given.  ``return_forward=True``: (grads, dict(dec, kld, kld_frames, z, prob, prior)), that forward's values - the bits
+        ``forward`` returns for the same inputs.  The model's weights are not touched: an optimiser step means a new model."""
+        B, T = self._check_backward_args(y, greedy, varBitrate, grad_dec, grad_kld, r, noise)
+        eng, out_dev, y = self._enter(y)
+        r, noise = _draw_randomness(B, T, self.z_dim, greedy, r, noise)
+        use_gen = (torch.as_tensor(r).detach().cpu().float() < p_use_gen).to(torch.uint8).contiguous()
+        bits = _prep(varBitrate, eng.device) if (varBitrate is not None and self.varBit) else None
+        un = None if greedy else _prep(noise, eng.device)
+        gdec = _prep(grad_dec, eng.device)
+        layout, total = self.grad_layout()
+        flat = torch.empty(total, device=eng.device)
+        gy = torch.empty(B, T, self.x_dim, device=eng.device) if grad_input else None
+        fwd = {}
+        if return_forward:
+            fwd = {"dec": torch.empty(B, T, self.x_dim, device=eng.device), "kld_frames": torch.empty(T, device=eng.device)}
+            fwd.update({k: torch.empty(B, T, self.z_dim, device=eng.device) for k in ("z", "prob", "prior")})
+        eng.call("bvc_bvrnn_backward", eng.handle, ptr(y), ptr(bits), ptr(use_gen, torch.uint8), int(p_use_gen < 1), int(p_use_gen > 0),
+                 ptr(un), B, T, ptr(gdec), float(grad_kld), ptr(flat), ptr(gy), ptr(fwd.get("dec")), ptr(fwd.get("kld_frames")),
+                 ptr(fwd.get("z")), ptr(fwd.get("prob")), ptr(fwd.get("prior")), scratch=(B, T, "backward"))
+        grads = {name: flat[off:off + numel].view(self._tensors[name].shape).to(out_dev) for name, off, numel in layout}
+        if grad_input:
+            grads["y"] = gy.to(out_dev)
+        if not return_forward:
+            return grads
+        fwd["kld"] = torch.mean(fwd["kld_frames"])
+        return grads, {k: v.to(out_dev) for k, v in fwd.items()}
+
+    def forward_train(self, y, p_use_gen, greedy, varBitrate, params, *, r=None, noise=None):
+        """``forward`` attached to torch.autograd (``bvcodec.autograd``): (all_dec_mean, kld) whose ``.backward()`` fills ``.grad`` of
+        ``y``, if it requires grad, and of the leaf tensors in ``params`` - a dict like ``grad_parameters()``.  The values are
+        computed with the MODEL's weights: ``params`` must hold the model's values, nothing checks it."""
+        from .autograd import forward_train
+        return forward_train(self, y, p_use_gen, greedy, varBitrate, params, r=r, noise=noise)
 
     def _encode(self, y, varBitrate, h, want_all_h=False, want_h_next=False, want_prob=False):
         """``bvc_bvrnn_encode``: the codes and those of its three optional outputs that are asked for, in the order of the arguments."""

@@ -95,6 +95,14 @@ struct bvc_model {
     bvc::Linear px0_dec3{};
     int decode_fold = 1;
     int encode_fold = 1;
+    // The backward pass (backward.hip): the transposed weights, natural (.w) and fragment-packed (.wp) with in / out swapped, so that
+    // dX = dY W is a forward layer of the kernels as they stand.  Made on the first bvc_bvrnn_backward (or bvc_bvrnn_backward_prepare),
+    // under bwd_mu; a model that never calls them allocates nothing.  Order: phi_x.0/2/4, phi_z.0/2/4, enc.0/2/4, prior.0/2/4, dec.0/2/4/6,
+    // rnn.weight_ih, rnn.weight_hh.
+    mutable std::mutex bwd_mu;
+    mutable bool bwd_ready = false;
+    mutable bvc::Linear bwd_t[18];
+    mutable std::vector<void *> bwd_allocs;
 
     ~bvc_model() {
         for (auto &g : graphs) { (void)hipGraphExecDestroy(g.exec1); (void)hipGraphExecDestroy(g.execN); if (g.idle) (void)hipEventDestroy(g.idle); }
@@ -105,6 +113,7 @@ struct bvc_model {
         for (auto e : cap_events) (void)hipEventDestroy(e);
         if (h_status) (void)hipHostFree(const_cast<unsigned *>(h_status));
         for (void *p : allocs) (void)hipFree(p);
+        for (void *p : bwd_allocs) (void)hipFree(p);
     }
 };
 
@@ -281,9 +290,30 @@ void carve_entropy(const bvc_model *m, int B, int64_t T, char *base, EntropyWork
 int run_entropy_unpack(const bvc_model *m, const Workspace &w, const EntropyWorkspace &e, void *ws_base, const EntropyCall &call,
                        const float *d_sel, const float *d_h0, int B, int64_t T, float *d_codes, float *d_mel, float *d_hT, float *d_prior,
                        hipStream_t s);
+struct ForwardTapeSpec;         // (below, with the backward pass)
 int run_forward(const bvc_model *m, const Workspace &w, const float *d_mel, const float *d_bits, const uint8_t *h_use_gen, bool update_h,
                 bool update_h2, const float *d_noise, int B, int64_t T, float *d_dec, float *d_kld, float *d_z, float *d_prob,
-                float *d_prior, hipStream_t s);
+                float *d_prior, hipStream_t s, const ForwardTapeSpec *tape = nullptr);
+int forward_tape_phi_x(const bvc_model *m, const Workspace &w, int B, int64_t T, float *p1, float *p2, float *p3, hipStream_t s);
+// Where run_forward keeps every frame for the backward pass: the FORWARD_TAPE_SLOTS scratch vectors of frame t at steps + (t * SLOTS + k) *
+// slot (fragment-packed, in the order of Workspace::step: e1 e2 pz1 pz2 pz3 d1 d2 d3 dn g1 g2 g3 q1 q2), and the two GRU chains as T + 1
+// fragment-packed [mt16][H] matrices each, zeroed by the caller: [t] the state frame t starts from.  With a tape, d_z / d_prob / d_prior
+// are the caller's (the workspace buffers they fall back to hold phi_x's hidden layers, which the backward pass reads).
+enum { FORWARD_TAPE_SLOTS = 14 };
+struct ForwardTapeSpec { float *steps; size_t slot; float *state[2]; };
+// ---- the backward pass of run_forward (backward.hip): its workspace is the ordinary one of (B, T) FOLLOWED by the tape and the gradients
+size_t backward_extra_bytes(const bvc_model *m, int B, int64_t T);
+int backward_prepare(const bvc_model *m, hipStream_t s);
+struct BackwardCall {
+    const float *d_mel, *d_bits; const uint8_t *h_use_gen; bool update_h, update_h2; const float *d_noise; int B; int64_t T;
+    const float *d_gdec; float g_kld;
+    float *d_grads, *d_gmel, *d_dec, *d_kld, *d_z, *d_prob, *d_prior;
+};
+int run_backward(const bvc_model *m, const Workspace &w, char *extra, const BackwardCall &c, hipStream_t s);
+// the layout of d_grads: entry i is tensor `name` (state-dict key) of `numel` floats at float offset `offset`; returns the entry count
+struct GradEntry { const char *name; long long offset, numel; };
+int grad_layout(const bvc_config &c, GradEntry *out, long long *total);
+enum { GRAD_ENTRIES = 36 };
 int run_vocoder(const bvc_model *m, const Workspace &w, const float *d_mel, int B, int64_t T, int64_t length, float div, float *d_wav,
                 int stop_after, const float **tap, int64_t *tap_len, int *tap_ch, hipStream_t s, const long long *lim = nullptr,
                 int64_t *tap_bs = nullptr);     // tap_bs: floats between the tap's batch items (a symmetric stage works on a view)

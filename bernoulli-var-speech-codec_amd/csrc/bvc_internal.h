@@ -201,6 +201,32 @@ int launch_copy_rows(const float *src, long long lds, float *dst, long long ldd,
 // natural [rows][n] (row stride ld) <-> fragment-packed [rows/16][n/16][64][4]; dir 0: pack, 1: unpack
 int launch_repack_rows(const float *src, float *dst, long long ld_natural, int rows, int n, int dir, hipStream_t s);
 
+// ------------------------------------------------------------------ backward pass (k_backward.hip)
+// How the M summed rows of a weight gradient are cut: `chunks` chunks of `chunk_rows` rows, their sums in ws_floats floats of
+// workspace (0: one chunk, written in place).  A function of (M, N, K) alone: it fixes the order of summation.
+struct WeightGradCut { int chunks, chunk_rows; size_t ws_floats; };
+WeightGradCut weight_grad_cut(int M, int N, int K);
+// dW (N, K) = dY (M, N)^T X (M, K), overwritten; natural dense matrices, N and K multiples of 16
+int launch_weight_grad(const float *dY, const float *X, int M, int N, int K, float *dW, float *ws, hipStream_t s, long long ldo = 0);
+// The row-wise kernels of the reverse recurrence (natural matrices; frame-major rows are t * B + b, utterance-major rows b * T + t):
+// T taped fragment-packed [mt16][n] matrices `fstride` floats apart -> frame-major rows
+int launch_unpack_frames(const float *src, long long fstride, long long T, int B, int n, float *dst, hipStream_t s);
+// dir 0: utterance-major -> frame-major, 1: back; scale (may be null): divided by scale[column] on the way
+int launch_reorder_rows(const float *src, int B, long long T, int n, float *dst, int dir, const float *scale, hipStream_t s);
+int launch_transpose(const float *src, int R, int C, float *dst, hipStream_t s);
+// out = dy * ELU'(from the output y); out may be dy
+int launch_elu_bwd(const float *dy, const float *y, float *out, long long total, hipStream_t s);
+// out (B, X) = gdec[:, t] + gdn / std (gdn may be null)
+int launch_mel_bwd(const float *gdec, long long T, long long t, const float *gdn, const float *stdv, int B, int X, float *out, hipStream_t s);
+// frame t of the straight-through sample and the KLD, back to the encoder's and the prior's logits xe, xq (B, Z); scale = g_kld / (T B)
+int launch_code_bwd(const float *gz, const float *xe, const float *xq, const float *bits, long long T, long long t, int B, int Z,
+                    float scale, float *d_enc_logit, float *d_prior_logit, hipStream_t s);
+// the GRU cell from its gate sums gi, gh (B, 3H), the state h it started from and the gradient of the state it produced
+int launch_gru_bwd(const float *dhn, const float *gi, const float *gh, const float *h, int B, int H, float *dgi, float *dgh, float *dh_direct,
+                   hipStream_t s);
+// out (N) = column sums of dY (M, N), rows in a fixed order
+int launch_col_sum(const float *dY, int M, int N, float *out, hipStream_t s);
+
 // ------------------------------------------------------------------ persistent recurrence (k_flow.hip, k_flow_support.hip)
 // All frames of BVRNN.encode / BVRNN.decode in one launch; layers are chained by "poisoned buffer" dataflow
 // (see k_flow_handoff.h).  Activations live in the flow region of the workspace: FlowBuf id, frame parity ->

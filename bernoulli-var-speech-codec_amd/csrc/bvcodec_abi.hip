@@ -305,6 +305,60 @@ int bvc_bvrnn_forward(const bvc_model *m, const float *d_mel, const float *d_bit
                        d_prob, d_prior, (hipStream_t)stream);
 }
 
+size_t bvc_bvrnn_backward_workspace_bytes(const bvc_model *m, int32_t B, int64_t T) {
+    if (!m || B <= 0 || T <= 0) return 0;
+    Workspace w;
+    carve(m, B, T, nullptr, &w);
+    return w.total + backward_extra_bytes(m, B, T);
+}
+
+int bvc_bvrnn_grad_layout(const bvc_config *cfg, const char **names, int64_t *offsets, int64_t *numels, int32_t capacity, int32_t *count,
+                          int64_t *total) {
+    if (!cfg || cfg->h_dim < 16 || cfg->z_dim < 16 || cfg->num_mels < 16) { set_error("bvc_bvrnn_grad_layout: no configuration, or not a coder's"); return BVC_EINVAL; }
+    GradEntry ge[GRAD_ENTRIES];
+    long long tot = 0;
+    const int n = grad_layout(*cfg, ge, &tot);
+    if (count) *count = n;
+    if (total) *total = tot;
+    if ((names || offsets || numels) && capacity < n) { set_error("bvc_bvrnn_grad_layout: room for %d entries, %d needed", (int)capacity, n); return BVC_EINVAL; }
+    for (int i = 0; i < n; ++i) {
+        if (names) names[i] = ge[i].name;
+        if (offsets) offsets[i] = ge[i].offset;
+        if (numels) numels[i] = ge[i].numel;
+    }
+    return BVC_OK;
+}
+
+int bvc_bvrnn_backward_prepare(const bvc_model *m, void *stream) {
+    if (!m) { set_error("null model"); return BVC_EINVAL; }
+    if (int rc = need_prior(m, "bvc_bvrnn_forward")) return rc;
+    return backward_prepare(m, (hipStream_t)stream);
+}
+
+int bvc_bvrnn_backward(const bvc_model *m, const float *d_mel, const float *d_bits, const uint8_t *h_use_gen, int32_t update_h,
+                       int32_t update_h2, const float *d_noise, int32_t B, int64_t T, const float *d_gdec, float g_kld, float *d_grads,
+                       float *d_gmel, float *d_dec, float *d_kld, float *d_z, float *d_prob, float *d_prior, void *d_ws, size_t ws_bytes,
+                       void *stream) {
+    // the refusals of bvc_bvrnn_forward, with its messages and before anything is launched, then this call's own
+    Workspace w;
+    if (int rc = enter(m, B, nullptr, &T, d_ws, ws_bytes, &w, d_mel && h_use_gen && d_gdec && d_grads)) return rc;
+    const size_t need = w.total + backward_extra_bytes(m, B, T);
+    if (ws_bytes < need) { set_error("workspace too small: %zu bytes given, %zu needed", ws_bytes, need); return BVC_ENOMEM; }
+    if (int rc = need_prior(m, "bvc_bvrnn_forward")) return rc;
+    if (m->cfg.var_bit && !d_bits) { set_error("bits per frame required when var_bit=1"); return BVC_EINVAL; }
+    if (m->cfg.z_dim > m->cfg.h_dim) { set_error("bvc_bvrnn_forward: z_dim > h_dim is not supported"); return BVC_EINVAL; }
+    if (!update_h && !update_h2) { set_error("bvc_bvrnn_forward: at least one state must be updated"); return BVC_EINVAL; }
+    for (int64_t t = 0; t < T; ++t)
+        if ((h_use_gen[t] && !update_h2) || (!h_use_gen[t] && !update_h)) {
+            set_error("bvc_bvrnn_forward: frame %lld is conditioned on a state that is never updated", (long long)t);
+            return BVC_EINVAL;
+        }
+    if ((long long)B * T * 3 * m->cfg.h_dim * 2 > INT32_MAX) { set_error("bvc_bvrnn_backward: B T = %lld rows is more than one call takes", (long long)B * T); return BVC_EINVAL; }
+    const BackwardCall c = {d_mel, d_bits, h_use_gen, update_h != 0, update_h2 != 0, d_noise, B, T, d_gdec, g_kld,
+                            d_grads, d_gmel, d_dec, d_kld, d_z, d_prob, d_prior};
+    return run_backward(m, w, static_cast<char *>(d_ws) + w.total, c, (hipStream_t)stream);
+}
+
 int bvc_bigvgan(const bvc_model *m, const float *d_mel, int32_t B, int64_t T, int64_t length, float out_scale_div,
                 float *d_wav, void *d_ws, size_t ws_bytes, void *stream) {
     Workspace w;
@@ -682,6 +736,23 @@ int bvc_test_linear(const float *d_x, const float *d_w, const float *d_bias, int
 int bvc_test_linear_batched(const float *d_x, const float *d_w, const float *d_bias, int32_t M, int32_t N, int32_t K,
                             int32_t act, float *d_y, void *stream) {
     return launch_gemm_batched(d_x, K, d_w, K, d_bias, M, N, K, act, d_y, N, (hipStream_t)stream);
+}
+
+int bvc_test_weight_grad(const float *d_dy, const float *d_x, int32_t M, int32_t N, int32_t K, float *d_dw, int64_t *out_cut, void *stream) {
+    // test helper (allocates + synchronises); the shape is checked first, on the host, so that a refusal can be had without a device
+    const char *fn = "bvc_test_weight_grad";
+    if (M < 1 || N < 16 || K < 16 || N % 16 || K % 16) { set_error("%s: M = %d, N = %d, K = %d: N and K must be multiples of 16, M at least 1", fn, M, N, K); return BVC_EINVAL; }
+    if (!d_dy || !d_x || !d_dw || ((uintptr_t)d_dy | (uintptr_t)d_x | (uintptr_t)d_dw) % 16) { set_error("%s: the matrices must be there and 16-byte aligned", fn); return BVC_EINVAL; }
+    const WeightGradCut c = weight_grad_cut(M, N, K);
+    if (out_cut) { out_cut[0] = c.chunks; out_cut[1] = c.chunk_rows; }
+    float *ws = nullptr;
+    if (c.ws_floats) BVC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ws), c.ws_floats * sizeof(float)));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = launch_weight_grad(d_dy, d_x, M, N, K, d_dw, ws, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (ws) (void)hipFree(ws);
+    if (!rc && e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); rc = BVC_EHIP; }
+    return rc;
 }
 
 int bvc_test_skinny_pick(int32_t M, int32_t epi, int32_t gate_il, int32_t mtw, int32_t latency, int32_t *out) {

@@ -35,7 +35,10 @@ enum { STEP_KIND_MASK = 0xF, STEP_FOLD = 0x10, STEP_RUNGS_SHIFT = 8 };   // | ST
                                                                   // _VBR step (part of the graph-cache key: the candidate launches have K * B rows)
 std::vector<StepNode> build_step(const bvc_model *m, const Workspace &w, int B, int kind_and_fold, const EntropyStep *es = nullptr);
 std::vector<StepNode> build_vbr_step(const bvc_model *m, const Workspace &w, const VbrWorkspace &vw, int B, int nrungs);
-std::vector<StepNode> build_forward_step(const bvc_model *m, const Workspace &w, int B, int sel, bool greedy, bool update_h, bool update_h2);
+// the states of one taped frame of BVRNN.forward, fragment-packed [mt16][H]: [0] the teacher-forced chain h, [1] the generated-feature chain h2
+struct ForwardTape { float *h_in[2], *h_out[2]; };
+std::vector<StepNode> build_forward_step(const bvc_model *m, const Workspace &w, int B, int sel, bool greedy, bool update_h, bool update_h2,
+                                         const ForwardTape *tape = nullptr);
 int count_kernels(const std::vector<StepNode> &plan);
 int step_fold(const bvc_model *m, bool encode);
 // probes: the plan's kernels carry in-kernel probes (the buffer is sized and cleared for steps_nodes kernels per step)

@@ -293,7 +293,7 @@ int run_entropy_unpack(const bvc_model *m, const Workspace &w, const EntropyWork
 
 int run_forward(const bvc_model *m, const Workspace &w, const float *d_mel, const float *d_bits,
                 const uint8_t *h_use_gen, bool update_h, bool update_h2, const float *d_noise, int B, int64_t T,
-                float *d_dec, float *d_kld, float *d_z, float *d_prob, float *d_prior, hipStream_t s) {
+                float *d_dec, float *d_kld, float *d_z, float *d_prob, float *d_prior, hipStream_t s, const ForwardTapeSpec *tape) {
     const int H = m->cfg.h_dim, X = m->cfg.num_mels, Z = m->cfg.z_dim;
     const long long BT = (long long)B * T;
     int rc;
@@ -322,9 +322,32 @@ int run_forward(const bvc_model *m, const Workspace &w, const float *d_mel, cons
     const std::vector<StepNode> plan0 = build_forward_step(m, w, B, 0, greedy, update_h, update_h2);
     const std::vector<StepNode> plan1 = build_forward_step(m, w, B, 1, greedy, update_h, update_h2);
     rc = begin_call(m, w, d, count_kernels(plan0), false, s);      // no probes: they index by a fixed kernel count per step
-    for (int64_t t = 0; !rc && t < T; ++t) rc = launch_steps(m, h_use_gen[t] ? plan1 : plan0, w, 1, s, nullptr);
+    if (!tape)
+        for (int64_t t = 0; !rc && t < T; ++t) rc = launch_steps(m, h_use_gen[t] ? plan1 : plan0, w, 1, s, nullptr);
+    // the backward pass's forward: the same launches, every frame into scratch vectors and state matrices of its own
+    for (int64_t t = 0; tape && !rc && t < T; ++t) {
+        Workspace wt = w;
+        for (int k = 0; k < FORWARD_TAPE_SLOTS; ++k) wt.step[k] = tape->steps + ((size_t)t * FORWARD_TAPE_SLOTS + k) * tape->slot;
+        const ForwardTape ft = {{tape->state[0] + t * MH, tape->state[1] + t * MH}, {tape->state[0] + (t + 1) * MH, tape->state[1] + (t + 1) * MH}};
+        rc = launch_steps(m, build_forward_step(m, wt, B, h_use_gen[t], greedy, update_h, update_h2, &ft), wt, 1, s, nullptr);
+    }
     if (rc) return rc;
     return launch_kld_frames(prob, prior, m->cfg.var_bit ? d_bits : nullptr, B, T, Z, d_kld, s);
+}
+
+// phi_x.0 / .2 / .4 of all frames, as run_forward's prologue left them (mlp3_frames, MLP3_PACKED), as natural matrices with frame-major
+// rows t * B + b: p1, p2, p3 (T B, H)
+int forward_tape_phi_x(const bvc_model *m, const Workspace &w, int B, int64_t T, float *p1, float *p2, float *p3, hipStream_t s) {
+    const int H = m->cfg.h_dim;
+    const long long FS = (long long)pad16(B) * H;
+    int rc;
+    if ((rc = launch_unpack_frames(w.pxA, FS, T, B, H, p3, s))) return rc;
+    if (T <= SMALL_T_FRAMES) {
+        if ((rc = launch_unpack_frames(w.pxC, FS, T, B, H, p1, s))) return rc;
+        return launch_unpack_frames(w.pxB, FS, T, B, H, p2, s);
+    }
+    if ((rc = launch_reorder_rows(w.pxC, B, T, H, p1, 0, nullptr, s))) return rc;
+    return launch_reorder_rows(w.pxB, B, T, H, p2, 0, nullptr, s);
 }
 
 }  // namespace bvc

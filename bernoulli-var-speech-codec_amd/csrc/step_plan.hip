@@ -86,21 +86,23 @@ struct StepBuilder {
         elu(m->phi_x[2], S(g2, H), B, g3);
     }
     // The GRU cell on the state in `hbuf`: everything but the segments.  all_h: all_h[:, t+1] (bvrnn.py:205), or null
-    GemmParams gru_cell(float *hbuf, DynPtr all_h) const {
+    GemmParams gru_cell(DynPtr h_in, DynPtr h_out, DynPtr all_h) const {
         GemmParams p;
         memset(&p, 0, sizeof(p));
         p.M = B; p.N = H; p.gate_rows = H;
-        p.y = h_next(hbuf);
+        p.y = h_out;
         p.y2 = all_h;
-        p.aux = h_cur(hbuf);
+        p.aux = h_in;
         return p;
     }
+    GemmParams gru_cell(float *hbuf, DynPtr all_h) const { return gru_cell(h_cur(hbuf), h_next(hbuf), all_h); }
     // ... as one launch over cat([phi_x, phi_z]) (bvrnn.py:206) and h: three gate-interleaved K-segments, summed in the order given
     GemmSeg gru_x(DynPtr px) const { return mkseg(px, m->w_ih_il, 2 * H / 16, H, 0); }
     GemmSeg gru_z(DynPtr pz) const { return mkseg(pz, m->w_ih_il + (size_t)(H / 16) * 3 * 256, 2 * H / 16, H, 0); }
     GemmSeg gru_h(DynPtr h) const { return mkseg(h, m->w_hh_il, H / 16, H, 1); }
-    void gru(GemmSeg s0, GemmSeg s1, GemmSeg s2, float *hbuf, DynPtr all_h) {
-        GemmParams p = gru_cell(hbuf, all_h);
+    void gru(GemmSeg s0, GemmSeg s1, GemmSeg s2, float *hbuf, DynPtr all_h) { gru(s0, s1, s2, h_cur(hbuf), h_next(hbuf), all_h); }
+    void gru(GemmSeg s0, GemmSeg s1, GemmSeg s2, DynPtr h_in, DynPtr h_out, DynPtr all_h) {
+        GemmParams p = gru_cell(h_in, h_out, all_h);
         p.nseg = 3;
         p.gate_il = 1;
         p.seg[0] = s0; p.seg[1] = s1; p.seg[2] = s2;
@@ -295,13 +297,17 @@ std::vector<StepNode> build_vbr_step(const bvc_model *m, const Workspace &w, con
 // features).  h2 lives in part_i (the side-branch buffer, unused here), both states ping-pong by frame parity.
 // Never carries probes (two plans alternate: the probes index by a fixed kernel count per step).  Its concatenated inputs are summed
 // in the order of torch.cat: dec.0 over [phi_z, h], the GRU over [phi_x, phi_z], h.
+// tape (the backward pass, backward.hip): the frame's states come from and go to the tape's own matrices instead of the two ping-pong
+// buffers, and `w` is a copy of the workspace whose scratch vectors are the frame's own; the kernels and their order are the same.
 std::vector<StepNode> build_forward_step(const bvc_model *m, const Workspace &w, int B, int sel, bool greedy,
-                                         bool update_h, bool update_h2) {
+                                         bool update_h, bool update_h2, const ForwardTape *tape) {
     StepBuilder b(m, w, B, false);
     const int H = b.H, Z = b.Z, X = b.X;
     float *hb[2] = {w.hbuf, w.part_i};
     auto S = StepBuilder::S;
-    const DynPtr hs = b.h_cur(hb[sel]);
+    const DynPtr h_in[2] = {tape ? S(tape->h_in[0], H) : b.h_cur(hb[0]), tape ? S(tape->h_in[1], H) : b.h_cur(hb[1])};
+    const DynPtr h_out[2] = {tape ? S(tape->h_out[0], H) : b.h_next(hb[0]), tape ? S(tape->h_out[1], H) : b.h_next(hb[1])};
+    const DynPtr hs = h_in[sel];
     const DynPtr px = dp_frame(DS_PX, H, 0, 1);
     // enc_t and the sample (bvrnn.py:115-129)
     b.K(lin2_params(m->enc[0], px, H, hs, H, B, S(b.e1, H)), EPI_ELU);
@@ -324,7 +330,7 @@ std::vector<StepNode> build_forward_step(const bvc_model *m, const Workspace &w,
     b.dec0(b.dec0_z(S(b.pz3, H)), b.dec0_h(hs), B, b.d1);
     b.dec24(b.d1, B, b.d2, b.d3);
     b.dec6(b.d3, B, dp_frame(DS_MEL, X), b.dn);
-    auto gru = [&](DynPtr xin, int which) { b.gru(b.gru_x(xin), b.gru_z(S(b.pz3, H)), b.gru_h(b.h_cur(hb[which])), hb[which], dp_null()); };
+    auto gru = [&](DynPtr xin, int which) { b.gru(b.gru_x(xin), b.gru_z(S(b.pz3, H)), b.gru_h(h_in[which]), h_in[which], h_out[which], dp_null()); };
     if (update_h) gru(px, 0);                                        // h  <- GRU([phi_x_t, phi_z_t], h)      bvrnn.py:142-143
     if (update_h2) {                                                 // h2 <- GRU([phi_x_t_gen, phi_z_t], h2) bvrnn.py:139,144-145
         b.elu(m->phi_x[0], S(b.dn, X), B, b.g1);

@@ -61,11 +61,13 @@ class _Engine:
         """Scratch for one call, owned by the CURRENT stream (the C ABI allows one in-flight call per
         (model, workspace); independent batches issued on different streams therefore overlap): the stream's buffer, grown if
         need be.  ``K``: the rungs of a closed-loop call, which takes ``bvc_vbr_workspace_bytes``, or "entropy" for a call of the
-        entropy-coded wire format, which takes ``bvc_entropy_workspace_bytes``."""
+        entropy-coded wire format, which takes ``bvc_entropy_workspace_bytes``, or "backward" for ``bvc_bvrnn_backward``."""
         if K is None:
             need = self.lib.bvc_workspace_bytes(self.handle, B, T)
         elif K == "entropy":
             need = self.lib.bvc_entropy_workspace_bytes(self.handle, B, T)
+        elif K == "backward":
+            need = self.lib.bvc_bvrnn_backward_workspace_bytes(self.handle, B, T)
         else:
             need = self.lib.bvc_vbr_workspace_bytes(self.handle, B, T, K)
         key = torch.cuda.current_stream(self.device).cuda_stream

@@ -237,7 +237,7 @@ int bvc_bvrnn_decode_conceal(const bvc_model *m, const float *d_codes, const uin
                              const float *d_h0, int32_t B, int64_t T, float *d_mel, float *d_hT, float *d_codes_out,
                              float *d_prior, void *d_ws, size_t ws_bytes, void *stream);
 
-/* BVRNN.forward (bvrnn.py:86-160), forward VALUES only (no autograd): the training-time pass with the
+/* BVRNN.forward (bvrnn.py:86-160), forward VALUES only (their gradients: bvc_bvrnn_backward below): the training-time pass with the
  * stochastic Bernoulli sampler round(u - 0.5 + p), the prior net and the KL term.
  *   d_mel (B,T,num_mels), d_bits (B,T) (NULL unless var_bit);
  *   h_use_gen: HOST array of T bytes, use_gen[t] = (random_num_t < p_use_gen), bvrnn.py:111-120: frame t is
@@ -252,6 +252,34 @@ int bvc_bvrnn_forward(const bvc_model *m, const float *d_mel, const float *d_bit
                       const float *d_noise, int32_t B, int64_t T, float *d_dec, float *d_kld,
                       float *d_z, float *d_prob, float *d_prior, void *d_ws, size_t ws_bytes,
                       void *stream);
+
+/* The backward pass of bvc_bvrnn_forward: the vector-Jacobian product of BVRNN.forward at d_gdec (B,T,num_mels), the gradient of a loss
+ * with respect to all_dec_mean, and g_kld, its gradient with respect to the scalar kld the reference returns (the mean of d_kld).  The
+ * sample is differentiated as the reference does (bvrnn.py:124,126: straight through, d z / d enc_t = the bit mask), the KLD's clips
+ * as torch.clip does.  Inputs as bvc_bvrnn_forward; the call runs its own forward - the launches of bvc_bvrnn_forward, every frame
+ * kept - so d_dec, d_kld, d_z, d_prob, d_prior (all optional here) are that call's bits.
+ *   d_grads: bvc_bvrnn_grad_layout's `total` floats, OVERWRITTEN (never accumulated into): the gradient of every trainable BVRNN
+ *     tensor in its state-dict layout (weight (out, in), bias (out), rnn.weight_ih_l0 (3H, 2H), ...).  mean_mel / std_mel are not
+ *     trainable and log_sigma does not enter the pass: they have no entry.
+ *   d_gmel (B,T,num_mels), optional: the gradient with respect to d_mel.
+ * f32 throughout, no atomics: the order of every sum is a function of the shapes alone, two calls give the same
+ * bits.  Workspace: bvc_bvrnn_backward_workspace_bytes(m, B, T) - the tape and every layer's gradient of all frames, about 70 (B T
+ * h_dim) floats.  The first call on a model uploads the transposed weights (or bvc_bvrnn_backward_prepare does, which synchronises the
+ * stream; needed before a call is captured into a graph); a model that never calls either allocates nothing.  Refusals as
+ * bvc_bvrnn_forward, with its messages: BVC_EMISSING without the prior.* tensors; BVC_EINVAL for z_dim > h_dim, var_bit without
+ * d_bits, no state updated, a frame conditioned on a state that is never updated; BVC_ENOMEM for a short workspace.  The model's
+ * packed weights are not updated in place: an optimiser step means a new model. */
+int bvc_bvrnn_backward(const bvc_model *m, const float *d_mel, const float *d_bits, const uint8_t *h_use_gen, int32_t update_h,
+                       int32_t update_h2, const float *d_noise, int32_t B, int64_t T, const float *d_gdec, float g_kld,
+                       float *d_grads, float *d_gmel, float *d_dec, float *d_kld, float *d_z, float *d_prob, float *d_prior,
+                       void *d_ws, size_t ws_bytes, void *stream);
+size_t bvc_bvrnn_backward_workspace_bytes(const bvc_model *m, int32_t B, int64_t T);
+int bvc_bvrnn_backward_prepare(const bvc_model *m, void *stream);
+/* Where every gradient is in d_grads, for a model of this configuration (host arithmetic only: needs no GPU): entry i is the tensor names[i] (its state-dict key; the strings live as long as the library) of
+ * numels[i] floats at float offset offsets[i].  *count = the entries (36), *total = the floats of d_grads.  names / offsets / numels
+ * may be NULL (to ask for count and total); otherwise each has room for `capacity` entries, BVC_EINVAL if that is too few. */
+int bvc_bvrnn_grad_layout(const bvc_config *cfg, const char **names, int64_t *offsets, int64_t *numels, int32_t capacity, int32_t *count,
+                          int64_t *total);
 
 /* BigVGAN.forward(x, length) (models.py:207-238) followed by `/ out_scale_div`
  * (bvrnn_codec_model.py:71: .squeeze(1) / SCALING).  d_mel is TIME-major (B,T,num_mels), i.e. what
@@ -715,6 +743,13 @@ int bvc_test_linear(const float *d_x, const float *d_w, const float *d_bias, int
 /* same contract through the batched (all-frames) GEMM kernel */
 int bvc_test_linear_batched(const float *d_x, const float *d_w, const float *d_bias, int32_t M,
                             int32_t N, int32_t K, int32_t act, float *d_y, void *stream);
+/* The weight-gradient kernel of the backward pass alone (allocates, synchronises): d_dw (N, K) = d_dy (M, N)^T d_x (M, K), the sum over
+ * the M rows of the outer products, overwritten.  All three natural, dense, 16-byte aligned, in device memory; f32 in, f32 accumulated
+ * (v_mfma_f32_16x16x4_f32), no atomics: the order of summation is a function of (M, N, K) alone, two calls give
+ * the same bits.  out_cut[2] (may be NULL) = the chunks the rows were cut into, and the rows of a chunk.  BVC_EINVAL, before anything
+ * touches a device, unless M >= 1 and N and K are multiples of 16, and for a missing or misaligned matrix. */
+int bvc_test_weight_grad(const float *d_dy, const float *d_x, int32_t M, int32_t N, int32_t K, float *d_dw, int64_t *out_cut,
+                         void *stream);
 /* Which instantiation of the recurrent-step kernel a launch of M rows takes (host arithmetic only: needs no GPU).  epi: 0 linear, 1 ELU,
  * 2 code, 3 mel, 4 GRU, 5 GRU with side-branch parts, 6 sigmoid; gate_il: gate-interleaved weights (GRU only); mtw: the row tiles of 16
  * per workgroup asked for (BVC_MTW); latency: BVC_LATENCY=1.  out[2] = the kernel (0 SK_GRU, 1 SK_GRU_IL, 2 SK_GRU_IL2, 3 SK_GRU_PART,
