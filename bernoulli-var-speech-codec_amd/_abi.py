@@ -32,6 +32,10 @@ class BvcTensor(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("h_data", ctypes.c_void_p), ("numel", ctypes.c_int64)]
 
 
+class BvcAdamWConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_grad_norm")]
+
+
 # name -> (restype, argtypes); every symbol include/bvcodec.h declares
 _vp, _i32, _i64, _f, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -61,6 +65,14 @@ SIGNATURES = {
     "bvc_bvrnn_backward_prepare": (ctypes.c_int, [_vp, _vp]),
     "bvc_bvrnn_grad_layout": (ctypes.c_int, [ctypes.POINTER(BvcConfig), ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i32,
                                              ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
+    "bvc_bvrnn_params_get": (ctypes.c_int, [_vp, _vp, _vp]),
+    "bvc_bvrnn_params_set": (ctypes.c_int, [_vp, _vp, _vp]),
+    "bvc_optimizer_create": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "bvc_optimizer_destroy": (None, [_vp]),
+    "bvc_optimizer_step": (ctypes.c_int, [_vp, ctypes.POINTER(BvcAdamWConfig), _vp, _vp, _vp]),
+    "bvc_optimizer_state_get": (ctypes.c_int, [_vp, ctypes.POINTER(_i64), _vp, _vp, _vp]),
+    "bvc_optimizer_state_set": (ctypes.c_int, [_vp, ctypes.POINTER(_i64), _vp, _vp, _vp]),
+    "bvc_test_folded_hop": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "bvc_bigvgan": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i64, _f, _vp, _vp, _sz, _vp]),
     "bvc_vocoder_stream_create": (ctypes.c_int, [_vp, _i32, _i32, ctypes.POINTER(_vp)]),
     "bvc_vocoder_stream_destroy": (None, [_vp]),

@@ -1,6 +1,7 @@
 """``BVRNN.forward`` as a node of a torch.autograd graph: the values come from ``BVRNN.forward`` (``bvc_bvrnn_forward``), the gradients
 from ``BVRNN.backward`` (``bvc_bvrnn_backward``), which runs its own forward with the same random numbers.  Thin by design: no state
-of its own, no optimiser, and the model's packed weights are not updated - after a step, build a new model from the new values."""
+of its own and no optimiser: ``bvrnn.optimizer()`` (``bvcodec.optim``) takes the ``.grad`` tensors, updates the live model in place and,
+given ``params=``, writes the new values back into the leaf tensors, so that they keep holding the model's values."""
 import torch
 
 from .coder import _draw_randomness
@@ -32,7 +33,8 @@ def forward_train(bvrnn, y, p_use_gen, greedy, varBitrate, params, *, r=None, no
     keyed like ``bvrnn.grad_parameters()``.  The values are the MODEL's: ``params`` must hold the model's values, nothing checks it.
     Randomness as in ``forward``; it is drawn once, here, and shared by the forward and the backward call."""
     names = tuple(params)
-    unknown = [n for n in names if n not in bvrnn.grad_parameters()]
+    known = {n for n, _, _ in bvrnn.grad_layout()[0]}
+    unknown = [n for n in names if n not in known]
     if unknown:
         raise ValueError(f"forward_train: {unknown} are no trainable tensors of BVRNN.forward")
     if not torch.is_tensor(y) or y.dim() != 3:

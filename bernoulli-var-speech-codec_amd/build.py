@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libbvcodec_hip.so")
-SOURCES = ["bvcodec_abi.hip", "model_build.hip", "model.hip", "recurrence.hip", "step_plan.hip", "backward.hip", "flow_launch.hip", "generator.hip", "stream_codec.hip", "resampler.hip", "k_gemm.hip", "k_gemm_batched.hip", "k_rows.hip", "k_backward.hip", "k_vbr.hip", "k_entropy.hip", "k_flow.hip", "k_flow_support.hip", "k_frontend.hip", "k_resample_stream.hip", "k_vocoder.hip", "k_vocoder_amp.hip"]
+SOURCES = ["bvcodec_abi.hip", "model_build.hip", "model.hip", "recurrence.hip", "step_plan.hip", "backward.hip", "optimizer.hip", "flow_launch.hip", "generator.hip", "stream_codec.hip", "resampler.hip", "k_gemm.hip", "k_gemm_batched.hip", "k_rows.hip", "k_backward.hip", "k_optimizer.hip", "k_vbr.hip", "k_entropy.hip", "k_flow.hip", "k_flow_support.hip", "k_frontend.hip", "k_resample_stream.hip", "k_vocoder.hip", "k_vocoder_amp.hip"]
 HEADERS = ["bvc_internal.h", "bvc_host.h", "weight_pack.h", "recurrence.h", "k_gemm.h", "k_flow_handoff.h", "k_flow_layers.h", "k_flow_gru.h", "k_vocoder.h", os.path.join("..", "..", "include", "bvcodec.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

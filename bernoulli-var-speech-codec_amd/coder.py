@@ -3,8 +3,8 @@ and ``BigVGAN`` (``model.vocoder(x, length)``, models.py:207-238), each on the e
 import numpy as np
 import torch
 
-from ._abi import BvcConfig, check as _abi_check, load as _abi_load, ptr
-from .engine import _OnDevice, _prep, _trimmed
+from ._abi import ptr
+from .engine import _OnDevice, _prep, _trimmed, grad_layout as _grad_layout
 from .vbr_args import _check_cap_q8, _check_ladder
 
 
@@ -101,22 +101,54 @@ class BVRNN(_OnDevice):
         return out[:2] + (dict(zip(extra, out[2:])),) if return_all else out
 
     def grad_parameters(self):
-        """The trainable tensors of ``BVRNN.forward`` as this model holds them: a dict of float32 CPU copies keyed by the reference's
-        state-dict names (36 tensors; not mean_mel / std_mel, which are buffers, nor log_sigma, which does not enter forward)."""
-        names = [n for n in self._tensors if n.split(".")[0] in ("phi_x", "phi_z", "enc", "prior", "dec", "rnn")]
-        return {n: self._tensors[n].detach().clone() for n in names}
+        """The trainable tensors of ``BVRNN.forward`` as this model holds them NOW - after ``load_parameters`` or an optimiser step, the
+        updated values: a dict of float32 CPU copies keyed by the reference's state-dict names (36 tensors; not mean_mel / std_mel,
+        which are buffers, nor log_sigma, which does not enter forward)."""
+        tensors = self._live_tensors()
+        names = [n for n in tensors if n.split(".")[0] in ("phi_x", "phi_z", "enc", "prior", "dec", "rnn")]
+        return {n: tensors[n].detach().clone() for n in names}
 
     def grad_layout(self):
         """``bvc_bvrnn_grad_layout``: ([(name, offset, numel)], total floats) of the flat gradient buffer of ``backward`` (needs no GPU)."""
-        import ctypes
-        lib = _abi_load()
-        cfg = BvcConfig()
-        cfg.num_mels, cfg.h_dim, cfg.z_dim, cfg.var_bit = self.x_dim, self.h_dim, self.z_dim, int(self.varBit)
-        n, total = ctypes.c_int32(0), ctypes.c_int64(0)
-        _abi_check(lib.bvc_bvrnn_grad_layout(ctypes.byref(cfg), None, None, None, 0, ctypes.byref(n), ctypes.byref(total)))
-        names, offs, nums = (ctypes.c_char_p * n.value)(), (ctypes.c_int64 * n.value)(), (ctypes.c_int64 * n.value)()
-        _abi_check(lib.bvc_bvrnn_grad_layout(ctypes.byref(cfg), names, offs, nums, n.value, None, None))
-        return [(names[i].decode(), int(offs[i]), int(nums[i])) for i in range(n.value)], int(total.value)
+        return _grad_layout(self.conf)
+
+    def _check_named(self, tensors, who):
+        """A dict of tensors keyed by some of the 36 trainable names, each of its state-dict shape."""
+        if not isinstance(tensors, dict):
+            raise ValueError(f"{who}: a dict keyed by state-dict names expected, got {type(tensors).__name__}")
+        known = {n for n, _, _ in self.grad_layout()[0]}
+        unknown = [n for n in tensors if n not in known]
+        if unknown:
+            raise ValueError(f"{who}: {unknown} are no trainable tensors of BVRNN.forward")
+        for n, t in tensors.items():
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != tuple(self._tensors[n].shape)):
+                raise ValueError(f"{who}: '{n}' must be a tensor {tuple(self._tensors[n].shape)}, got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+
+    @torch.no_grad()
+    def load_parameters(self, tensors):
+        """New values for some of the 36 trainable tensors (a dict keyed like ``grad_parameters()``), written into the LIVE model
+        (``bvc_bvrnn_params_get``, patch, ``bvc_bvrnn_params_set``): every form of the weights the kernels read is rewritten in
+        place on the device, stream-ordered on the current stream, and the next call - on any schedule, a captured graph included -
+        runs on them; the model is then bit for bit the one a checkpoint with these values loads.  It applies to the engine of the
+        model's device (engines on other devices keep their values); a call in flight on another stream is the caller's to
+        serialise."""
+        self._check_named(tensors, "load_parameters")
+        eng = self.engine()
+        layout, total = self.grad_layout()
+        flat = eng.params_get(total)
+        for name, off, numel in layout:
+            if tensors.get(name) is not None:
+                flat[off:off + numel].copy_(_prep(tensors[name], eng.device).reshape(-1))
+        eng.params_set(flat)
+        self._tensors.stale = eng
+
+    def optimizer(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=0.0):
+        """An AdamW optimiser of this model's trainable tensors (``bvcodec.optim.AdamW``; torch.optim.AdamW's defaults): its ``step``
+        takes what ``backward`` returns and updates the live model in place.  ``max_grad_norm > 0`` clips the gradients' 2-norm first
+        (torch.nn.utils.clip_grad_norm_)."""
+        from .optim import AdamW
+        return AdamW(self, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
 
     def _check_backward_args(self, y, greedy, varBitrate, grad_dec, grad_kld, r, noise):
         if not torch.is_tensor(y) or y.dim() != 3 or y.shape[2] != self.x_dim or y.shape[0] < 1 or y.shape[1] < 1:
@@ -140,15 +172,19 @@ class BVRNN(_OnDevice):
 
     @torch.no_grad()
     def backward(self, y, p_use_gen, greedy, varBitrate, grad_dec, grad_kld, *, r=None, noise=None, grad_input=False,
-                 return_forward=False):
+                 return_forward=False, flat=False):
         """The vector-Jacobian product of ``forward`` (``bvc_bvrnn_backward``): given ``grad_dec`` (B,T,x_dim), the gradient of a
         loss with respect to all_dec_mean, and the scalar ``grad_kld``, its gradient with respect to the returned kld, a dict of the
         loss's gradients keyed by the reference's state-dict names, each of its state-dict shape (``grad_parameters`` has the same
         keys); ``grad_input=True`` adds "y", the gradient with respect to the input mel.  The call runs its own forward, with the
         randomness of ``forward``: the same draws in the same order from the global CPU generator unless ``r`` / ``noise`` are
         given.  ``return_forward=True``: (grads, dict(dec, kld, kld_frames, z, prob, prior)), that forward's values - the bits
-        ``forward`` returns for the same inputs.  The model's weights are not touched: an optimiser step means a new model."""
+        ``forward`` returns for the same inputs.  ``flat=True``: instead of the dict, the flat device buffer the library wrote
+        (``grad_layout``), on the model's device - what ``optimizer().step`` takes as it is; not together with ``grad_input``.  The
+        call leaves the model's weights alone: ``optimizer()`` updates them in place."""
         B, T = self._check_backward_args(y, greedy, varBitrate, grad_dec, grad_kld, r, noise)
+        if flat and grad_input:
+            raise ValueError("backward: flat=True returns the parameters' gradients only (not together with grad_input)")
         eng, out_dev, y = self._enter(y)
         r, noise = _draw_randomness(B, T, self.z_dim, greedy, r, noise)
         use_gen = (torch.as_tensor(r).detach().cpu().float() < p_use_gen).to(torch.uint8).contiguous()
@@ -156,7 +192,7 @@ class BVRNN(_OnDevice):
         un = None if greedy else _prep(noise, eng.device)
         gdec = _prep(grad_dec, eng.device)
         layout, total = self.grad_layout()
-        flat = torch.empty(total, device=eng.device)
+        want_flat, flat = flat, torch.empty(total, device=eng.device)
         gy = torch.empty(B, T, self.x_dim, device=eng.device) if grad_input else None
         fwd = {}
         if return_forward:
@@ -165,7 +201,7 @@ class BVRNN(_OnDevice):
         eng.call("bvc_bvrnn_backward", eng.handle, ptr(y), ptr(bits), ptr(use_gen, torch.uint8), int(p_use_gen < 1), int(p_use_gen > 0),
                  ptr(un), B, T, ptr(gdec), float(grad_kld), ptr(flat), ptr(gy), ptr(fwd.get("dec")), ptr(fwd.get("kld_frames")),
                  ptr(fwd.get("z")), ptr(fwd.get("prob")), ptr(fwd.get("prior")), scratch=(B, T, "backward"))
-        grads = {name: flat[off:off + numel].view(self._tensors[name].shape).to(out_dev) for name, off, numel in layout}
+        grads = flat if want_flat else {name: flat[off:off + numel].view(self._tensors[name].shape).to(out_dev) for name, off, numel in layout}
         if grad_input:
             grads["y"] = gy.to(out_dev)
         if not return_forward:

@@ -1,5 +1,5 @@
 // Host side of libbvcodec_hip.so, shared by its sources model_build.hip, model.hip, recurrence.hip, step_plan.hip, flow_launch.hip,
-// generator.hip, stream_codec.hip and bvcodec_abi.hip (what only the three sources of the recurrence share is in recurrence.h; the
+// backward.hip, optimizer.hip, generator.hip, stream_codec.hip and bvcodec_abi.hip (what only the three sources of the recurrence share is in recurrence.h; the
 // arithmetic behind every uploaded weight is weight_pack.h, which model_build.hip alone includes): the model, the workspace layout, the GEMM parameter helpers, the drivers of the offline paths and the state that
 // crosses a file boundary.  Host only.  What more than one source uses lives in namespace bvc, next to the launchers of
 // bvc_internal.h; everything else is local to its file.
@@ -103,6 +103,11 @@ struct bvc_model {
     mutable bool bwd_ready = false;
     mutable bvc::Linear bwd_t[18];
     mutable std::vector<void *> bwd_allocs;
+    // The optimiser (optimizer.hip): the flat float32 master copy of the 36 trainable tensors in grad_layout order.  Made on the first
+    // bvc_bvrnn_params_set or bvc_optimizer_step, under bwd_mu, from the values the model holds; from then on bvc_bvrnn_params_set
+    // writes it and every form derived from it (a step updates it in place and ends in that rewrite).  A model that never calls them
+    // allocates nothing.
+    mutable float *master = nullptr;
 
     ~bvc_model() {
         for (auto &g : graphs) { (void)hipGraphExecDestroy(g.exec1); (void)hipGraphExecDestroy(g.execN); if (g.idle) (void)hipEventDestroy(g.idle); }
@@ -114,6 +119,7 @@ struct bvc_model {
         if (h_status) (void)hipHostFree(const_cast<unsigned *>(h_status));
         for (void *p : allocs) (void)hipFree(p);
         for (void *p : bwd_allocs) (void)hipFree(p);
+        if (master) (void)hipFree(master);
     }
 };
 

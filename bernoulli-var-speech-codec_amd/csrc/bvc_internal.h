@@ -227,6 +227,27 @@ int launch_gru_bwd(const float *dhn, const float *gi, const float *gh, const flo
 // out (N) = column sums of dY (M, N), rows in a fixed order
 int launch_col_sum(const float *dY, int M, int N, float *out, hipStream_t s);
 
+// ------------------------------------------------------------------ optimiser step and in-place weight rewrite (k_optimizer.hip)
+// up to COPY_SEGMENTS copies in one launch: n floats (a multiple of 4) from src to dst, both 16-byte aligned
+constexpr int COPY_SEGMENTS = 40;
+struct CopySegment { const float *src; float *dst; long long n; };
+struct CopySegments { CopySegment s[COPY_SEGMENTS]; int n; };
+int launch_copy_segments(const CopySegments &segs, hipStream_t s);
+// weight_pack.h's pack_gru_interleaved and fold_px0_dec3 on device tensors, the same bits; the fold writes W fragment-packed
+int launch_pack_gru_interleaved(const float *W, int H, int K, float *out, hipStream_t s);
+int launch_fold_px0_dec3(const float *wp0, const float *bp0, const float *wd6, const float *bd6, const float *mean, const float *stdv, int H,
+                         int X, float *wp_out, float *b_out, hipStream_t s);
+// The 2-norm of `total` floats (a multiple of 4) in two stages with float64 accumulators: chunks of NORM_CHUNK floats into partial
+// (norm_chunks(total) doubles), then one workgroup.  scal[0] = min(1, max_norm / (norm + 1e-6)) (1 where max_norm <= 0), scal[1] = the
+// norm, also to norm_out if given.
+constexpr int NORM_CHUNK = 8192;
+int norm_chunks(long long total);
+int launch_grad_norm(const float *g, long long total, float max_norm, double *partial, float *scal, float *norm_out, hipStream_t s);
+// One AdamW step over `total` floats, per element in f32 and in this order, every operation rounded on its own:
+//   p *= decay;  m = b1 m + one_b1 g;  v = b2 v + (one_b2 g) g;  p -= step_size (m / (sqrt(v) / bc2_sqrt + eps)),  g = scal[0] * the gradient
+struct AdamScalars { float decay, b1, one_b1, b2, one_b2, step_size, bc2_sqrt, eps; };
+int launch_adam(float *p, float *m, float *v, const float *g, const float *scal, long long total, const AdamScalars &a, hipStream_t s);
+
 // ------------------------------------------------------------------ persistent recurrence (k_flow.hip, k_flow_support.hip)
 // All frames of BVRNN.encode / BVRNN.decode in one launch; layers are chained by "poisoned buffer" dataflow
 // (see k_flow_handoff.h).  Activations live in the flow region of the workspace: FlowBuf id, frame parity ->

@@ -24,6 +24,26 @@ def _as_device(device):
     return device
 
 
+def grad_layout(conf):
+    """``bvc_bvrnn_grad_layout``: ([(name, offset, numel)], total floats) of the flat buffer of the coder's 36 trainable tensors - the
+    gradients of ``BVRNN.backward``, the parameters and the optimiser's moments (needs no GPU)."""
+    lib = _abi.load()
+    cfg = _abi.BvcConfig()
+    cfg.num_mels, cfg.h_dim, cfg.z_dim, cfg.var_bit = conf["num_mels"], conf["h_dim"], conf["z_dim"], int(bool(conf["var_bit"]))
+    n, total = ctypes.c_int32(0), ctypes.c_int64(0)
+    _abi.check(lib.bvc_bvrnn_grad_layout(ctypes.byref(cfg), None, None, None, 0, ctypes.byref(n), ctypes.byref(total)))
+    names, offs, nums = (ctypes.c_char_p * n.value)(), (ctypes.c_int64 * n.value)(), (ctypes.c_int64 * n.value)()
+    _abi.check(lib.bvc_bvrnn_grad_layout(ctypes.byref(cfg), names, offs, nums, n.value, None, None))
+    return [(names[i].decode(), int(offs[i]), int(nums[i])) for i in range(n.value)], int(total.value)
+
+
+class _Tensors(dict):
+    """The host tensors a model was loaded with, by name: what an engine is created from.  ``stale``: the engine whose coder weights
+    were updated in place (``load_parameters``, an optimiser step) since these copies were made, or None; ``_OnDevice._live_tensors``
+    fetches them when somebody reads the copies."""
+    stale = None
+
+
 class _Engine:
     """One device-resident copy of the weights (a bvc_model handle) + its workspace."""
 
@@ -98,6 +118,16 @@ class _Engine:
             self.poll_status()
         return res[0] if len(res) == 1 else res
 
+    def params_get(self, total):
+        """``bvc_bvrnn_params_get``: the coder's trainable tensors as this engine holds them, one flat device tensor (``grad_layout``)."""
+        flat = torch.empty(total, device=self.device)
+        self.call("bvc_bvrnn_params_get", self.handle, _abi.ptr(flat))
+        return flat
+
+    def params_set(self, flat):
+        """``bvc_bvrnn_params_set``: every form of the coder's weights rewritten in place from the flat device tensor ``flat``."""
+        self.call("bvc_bvrnn_params_set", self.handle, _abi.ptr(flat))
+
     def set_option(self, name, value):
         _abi.check(self.lib.bvc_model_set_option(self.handle, name.encode(), int(value)))
 
@@ -166,9 +196,20 @@ class _OnDevice(nn.Module):
     def __init__(self, conf, tensors, shared=None):
         super().__init__()
         self.conf = conf
-        self._tensors = tensors
+        self._tensors = tensors if isinstance(tensors, _Tensors) else _Tensors(tensors)
         self._engines = {} if shared is None else shared
         self._device = None
+
+    def _live_tensors(self):
+        """``self._tensors`` with the coder's trainable tensors as the model holds them NOW: after ``load_parameters`` or an
+        optimiser step the CPU copies are refreshed here, once, from the engine that was updated (``bvc_bvrnn_params_get``)."""
+        eng, self._tensors.stale = self._tensors.stale, None
+        if eng is not None:
+            layout, total = grad_layout(self.conf)
+            flat = eng.params_get(total).cpu()
+            for name, off, numel in layout:
+                self._tensors[name] = flat[off:off + numel].view(self._tensors[name].shape).clone()
+        return self._tensors
 
     def _apply(self, fn, *a, **k):              # follow .to('cuda:N') / .cuda(); there is no CPU residence
         # probe where a tensor that lives where this module lives would end up: a dtype-only conversion (.float(), .half(),
@@ -206,7 +247,7 @@ class _OnDevice(nn.Module):
             dev = like.device
         dev = _as_device(dev)
         if dev not in self._engines:
-            self._engines[dev] = _Engine(self.conf, self._tensors, dev)
+            self._engines[dev] = _Engine(self.conf, self._live_tensors(), dev)     # (a new engine starts from the updated weights)
             if getattr(self, "_recurrence", None) is not None:
                 self._engines[dev].set_option("recurrence", self._SCHEDULES[self._recurrence])
         return self._engines[dev]

@@ -267,8 +267,8 @@ int bvc_bvrnn_forward(const bvc_model *m, const float *d_mel, const float *d_bit
  * h_dim) floats.  The first call on a model uploads the transposed weights (or bvc_bvrnn_backward_prepare does, which synchronises the
  * stream; needed before a call is captured into a graph); a model that never calls either allocates nothing.  Refusals as
  * bvc_bvrnn_forward, with its messages: BVC_EMISSING without the prior.* tensors; BVC_EINVAL for z_dim > h_dim, var_bit without
- * d_bits, no state updated, a frame conditioned on a state that is never updated; BVC_ENOMEM for a short workspace.  The model's
- * packed weights are not updated in place: an optimiser step means a new model. */
+ * d_bits, no state updated, a frame conditioned on a state that is never updated; BVC_ENOMEM for a short workspace.  The call leaves
+ * the model's weights alone; bvc_optimizer_step (below) takes d_grads and updates them in place. */
 int bvc_bvrnn_backward(const bvc_model *m, const float *d_mel, const float *d_bits, const uint8_t *h_use_gen, int32_t update_h,
                        int32_t update_h2, const float *d_noise, int32_t B, int64_t T, const float *d_gdec, float g_kld,
                        float *d_grads, float *d_gmel, float *d_dec, float *d_kld, float *d_z, float *d_prob, float *d_prior,
@@ -280,6 +280,45 @@ int bvc_bvrnn_backward_prepare(const bvc_model *m, void *stream);
  * may be NULL (to ask for count and total); otherwise each has room for `capacity` entries, BVC_EINVAL if that is too few. */
 int bvc_bvrnn_grad_layout(const bvc_config *cfg, const char **names, int64_t *offsets, int64_t *numels, int32_t capacity, int32_t *count,
                           int64_t *total);
+
+/* The trainable tensors of a LIVE model as one flat device buffer in bvc_bvrnn_grad_layout order (`total` floats, 16-byte aligned).
+ * bvc_bvrnn_params_get gathers the values the model holds.  bvc_bvrnn_params_set rewrites, in place and stream-ordered, every form of
+ * the weights the model's kernels read - natural, fragment-packed and gate-interleaved copies, the float64 fold of dec.6 -> norm ->
+ * phi_x.0 (computed on the device with the host's operations, the same bits), and the transposed copies of the backward pass once they
+ * exist - at the addresses they already have: the next encode, decode, forward or backward on any schedule, a captured graph included,
+ * runs on the new values, and the model is then BIT FOR BIT the one bvc_model_create builds from them.  No host synchronisation, no host
+ * copy, no new model.  mean_mel / std_mel are read by the fold and never written.  The first bvc_bvrnn_params_set (or bvc_optimizer_step)
+ * on a model allocates the model's flat float32 master copy of the parameters (not inside a stream capture); a model that calls none of
+ * this allocates nothing.  Like the model options, a rewrite is ordered on ITS stream only: a call in flight on another stream while the
+ * weights change is the caller's to serialise.  BVC_EMISSING without the prior.* tensors. */
+int bvc_bvrnn_params_get(const bvc_model *m, float *d_params, void *stream);
+int bvc_bvrnn_params_set(bvc_model *m, const float *d_params, void *stream);
+
+/* AdamW (torch.optim.AdamW without amsgrad and maximize; weight_decay = 0: Adam) on a live model's parameters, everything on the device.
+ * The optimiser owns exp_avg and exp_avg_sq (`total` floats each, zero at creation) and the step count; the master copy of the
+ * parameters belongs to the model (above), so bvc_bvrnn_params_set followed by a step starts from the values that were set.  Destroy the
+ * optimiser before its model.
+ * bvc_optimizer_step: d_grads = the flat buffer bvc_bvrnn_backward writes (read, never written).  Per element, in f32, in this order and
+ * every operation rounded on its own, with t the count of this step, bc1 = 1 - beta1^t and bc2 = 1 - beta2^t computed in double:
+ *     p *= 1 - lr weight_decay;  m = beta1 m + (1 - beta1) g;  v = beta2 v + ((1 - beta2) g) g;
+ *     p -= (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps))
+ * max_grad_norm > 0: g is first scaled by min(1, max_grad_norm / (norm + 1e-6)), norm the 2-norm of ALL of d_grads
+ * (torch.nn.utils.clip_grad_norm_).  The norm is summed in float64 in two stages over fixed chunks, without atomics: two calls give the
+ * same bits; the update reads the factor from device memory (no host synchronisation).  d_grad_norm (optional, one device float)
+ * receives the unclipped norm.  The step ends with the rewrite of bvc_bvrnn_params_set from the new values.  The hyperparameters are
+ * passed with every step: a schedule is the caller's.  BVC_EINVAL for lr < 0, a beta outside [0, 1), eps <= 0, weight_decay < 0, a null
+ * argument or a stream that is being captured (the scalars change with every step). */
+typedef struct bvc_optimizer bvc_optimizer;
+typedef struct bvc_adamw_config { double lr, beta1, beta2, eps, weight_decay, max_grad_norm; } bvc_adamw_config;
+int bvc_optimizer_create(bvc_model *m, bvc_optimizer **out);
+void bvc_optimizer_destroy(bvc_optimizer *opt);
+int bvc_optimizer_step(bvc_optimizer *opt, const bvc_adamw_config *cfg, const float *d_grads, float *d_grad_norm, void *stream);
+/* The optimiser's state, for checkpoints: the step count and the two moments (`total` floats each, device memory; any of the three
+ * may be NULL). */
+int bvc_optimizer_state_get(const bvc_optimizer *opt, int64_t *step, float *d_exp_avg, float *d_exp_avg_sq, void *stream);
+int bvc_optimizer_state_set(bvc_optimizer *opt, const int64_t *step, const float *d_exp_avg, const float *d_exp_avg_sq, void *stream);
+/* tests: the folded hop px0_dec3 as the model holds it, d_w (h_dim, h_dim) unpacked to its natural layout and d_b (h_dim) */
+int bvc_test_folded_hop(const bvc_model *m, float *d_w, float *d_b, void *stream);
 
 /* BigVGAN.forward(x, length) (models.py:207-238) followed by `/ out_scale_div`
  * (bvrnn_codec_model.py:71: .squeeze(1) / SCALING).  d_mel is TIME-major (B,T,num_mels), i.e. what
