@@ -131,44 +131,165 @@ def _cases():
 
 CASES = _cases()
 
+# ---- the cases of tests/test_gpu_backward_shapes.py: the same tuple, with a z_dim behind it where that is not 64, and "uptoN" for
+# bits drawn from 0..N.  Which path of the pass each ROW_CASES entry is there for: paths() below, asserted in test_backward_shapes_cpu.py.
+ROW_CASES = (
+    (64, "default", True, 5, 48, 2, "random"),        # 240 rows: one chunk of two blocks, the second short; the carries cross 48 frames
+    (64, "default", True, 17, 16, 2, "random"),       # 272 rows, 544 stacked: enc.0 / dec.0 / weight_ih in chunks with ldo = 2 K
+    (64, "default", True, 17, 16, 0, "upto8"),        # only chain h ran: Mg = TB (greedy: every e is the rounded argument, so few bits)
+    (256, "default", True, 17, 16, 1, "random"),      # only chain h2 ran: Mg = TB from row TB on; full tiles of the batched GEMM
+    (1024, "default", True, 17, 16, 2, "random"),     # H x H in two chunks, 3H x H one chunk of three blocks
+    (1040, "default", True, 17, 16, 2, "random"),     # N K > 4096 x 256 in chunks: the reduce kernel loops
+    (1024, "default", True, 66, 16, 2, 8),            # TB H > 4096 x 256: the all-frame kernels loop
+)
+SIZES = ((16, 16), (48, 48), (112, 96), (128, 16), (256, 48), (512, 96), (1024, 128), (1024, 16), (192, 64), (384, 32), (1040, 64))
+REFUSED_SIZES = ((64, 128), (16, 64), (64, 144))      # z_dim > h_dim: the forward's refusal
+SIZE_SHAPES = {(1024, 128): ((80, 4),)}                # every other size: bvrnn_draws.SMALL
+SIZE_CASES = tuple((h, draw, True, B, T, 2, "random", z) for h, z in SIZES for B, T in SIZE_SHAPES.get((h, z), ((5, 12), (20, 12)))
+                   for draw in ("default", "wide"))
+SATURATED_CASES = ((64, "saturated", True, 3, 7, 2, "random"), (64, "saturated", True, 3, 7, 3, "random"),
+                   (64, "saturated", True, 17, 7, 1, "upto8"), (1024, "saturated", True, 3, 7, 2, "random"))
+TRAINING_ROWS = 32 * 344                               # profiles/backward_cost.md
+
+
+def z_of(case):
+    return case[7] if len(case) > 7 else 64
+
 
 def case_id(c):
-    return f"h{c[0]}-{c[1]}-{'var' if c[2] else 'fix'}-B{c[3]}-T{c[4]}-m{c[5]}-bits{c[6]}"
+    return f"h{c[0]}-{c[1]}-{'var' if c[2] else 'fix'}-B{c[3]}-T{c[4]}-m{c[5]}-bits{c[6]}" + (f"-z{c[7]}" if len(c) > 7 else "")
 
 
-def draw_inputs(case, seed):
-    """The inputs of a case at one seed: dict(y, bits, r, noise, gdec, gkld, p_use_gen, greedy)."""
+def draw_inputs(case, seed, z_dim=None):
+    """The inputs of a case at one seed: dict(y, bits, r, noise, gdec, gkld, p_use_gen, greedy).  z_dim: the case's own (z_of)."""
     import numpy as np
-    h_dim, draw, var_bit, B, T, mode, nbits = case
+    h_dim, draw, var_bit, B, T, mode, nbits = case[:7]
+    z_dim = z_of(case) if z_dim is None else z_dim
     p_use_gen, greedy = MODES[mode]
     rng = np.random.default_rng(seed)
     y = torch.from_numpy((-4.0 + 1.6 * rng.standard_normal((B, T, 80))).astype(np.float32))
-    bits = torch.from_numpy(rng.integers(0, 65, size=(B, T)).astype(np.float32))
-    if nbits != "random":
+    bits = torch.from_numpy(rng.integers(0, z_dim + 1, size=(B, T)).astype(np.float32))
+    if isinstance(nbits, str) and nbits.startswith("upto"):
+        bits = torch.remainder(bits, float(int(nbits[4:]) + 1))
+    elif nbits != "random":
         bits = torch.full((B, T), float(nbits))
     r = torch.from_numpy(rng.random(T).astype(np.float32))
-    noise = None if greedy else torch.from_numpy(rng.random((B, T, 64)).astype(np.float32))
+    noise = None if greedy else torch.from_numpy(rng.random((B, T, z_dim)).astype(np.float32))
     gdec = torch.from_numpy(rng.standard_normal((B, T, 80)).astype(np.float32))
     return dict(y=y, bits=bits, r=r, noise=noise, gdec=gdec, gkld=0.5 + float(rng.random()), p_use_gen=p_use_gen, greedy=greedy)
 
 
-_SELECTED = {}
+_FOUND, _SELECTED = {}, {}
+SEARCHED = {"forwards": 0, "gradients": 0}             # what the search has computed so far (test_backward_shapes_cpu.py)
 
 
-def select(case, sd):
-    """The first seed (from a base that depends on the case) at which the float64 oracle keeps the margins: dict(inputs.., seed, g64, f64,
-    margins).  Searched, never skipped: a case without such a seed among 200 is an error.  Cached."""
-    if case in _SELECTED:
-        return _SELECTED[case]
+def find_seed(case, sd, z_dim=None):
+    """The first seed (from a base that depends on the case) at which the float64 forward keeps the margins: dict(inputs.., seed, f64,
+    margins).  Searched, never skipped: a case without such a seed among 200 is an error.  No gradient is taken.  Cached."""
+    z_dim = z_of(case) if z_dim is None else z_dim
+    if (case, z_dim) in _FOUND:
+        return _FOUND[(case, z_dim)]
     import zlib
     var_bit = case[2]
+    assert sd["enc.4.weight"].shape[0] == z_dim, (case_id(case), sd["enc.4.weight"].shape[0], z_dim)
+    p64 = {k: torch.as_tensor(v).double() for k, v in sd.items() if k != "log_sigma"}
     base = zlib.crc32(case_id(case).encode()) % 100000
     for seed in range(base, base + 200):
-        inp = draw_inputs(case, seed)
-        g64, f64 = grads(sd, inp["y"], inp["bits"], inp["p_use_gen"], inp["greedy"], inp["r"], inp["noise"], inp["gdec"], inp["gkld"],
-                         torch.float64, var_bit=var_bit)
-        rm, cm = margins(f64, inp["bits"] if var_bit else None, 64)
+        inp = draw_inputs(case, seed, z_dim)
+        with torch.no_grad():
+            f64 = forward(p64, inp["y"].double(), inp["bits"], inp["p_use_gen"], inp["greedy"], inp["r"], inp["noise"], var_bit=var_bit)
+        SEARCHED["forwards"] += 1
+        rm, cm = margins(f64, inp["bits"] if var_bit else None, z_dim)
         if rm >= ROUND_MARGIN and cm >= CLIP_MARGIN:
-            _SELECTED[case] = dict(inp, seed=seed, g64=g64, f64=f64, margins=(rm, cm))
-            return _SELECTED[case]
+            _FOUND[(case, z_dim)] = dict(inp, seed=seed, tried=seed - base + 1, f64=f64, margins=(rm, cm))
+            return _FOUND[(case, z_dim)]
     raise AssertionError(f"{case_id(case)}: no seed in [{base}, {base + 200}) keeps the margins")
+
+
+def select(case, sd, z_dim=None):
+    """find_seed's case with the float64 gradients g64, taken once, at the seed found (f64: that run's forward, the same values).  Cached."""
+    z_dim = z_of(case) if z_dim is None else z_dim
+    if (case, z_dim) not in _SELECTED:
+        c = find_seed(case, sd, z_dim)
+        g64, f64 = grads(sd, c["y"], c["bits"], c["p_use_gen"], c["greedy"], c["r"], c["noise"], c["gdec"], c["gkld"], torch.float64, var_bit=case[2])
+        SEARCHED["gradients"] += 1
+        assert margins(f64, c["bits"] if case[2] else None, z_dim) == c["margins"]
+        _SELECTED[(case, z_dim)] = dict(c, g64=g64, f64=f64)
+    return _SELECTED[(case, z_dim)]
+
+
+# ---------------------------------------------------------------------------------------------- which code a case runs
+# Restated from csrc/k_backward.hip (weight_grad_cut, blocks_for), csrc/backward.hip (run_backward's launches, carve_backward's b.wg) and
+# csrc/k_gemm_batched.hip (the LDS path and its tile heights), so that a change of a rule is a change of this file too.
+TILE, BLOCK, MIN_CHUNK, TARGET = 64, 128, 256, 512
+GRID_ELEMENTS = 4096 * 256                             # what one trip of a grid-stride loop covers
+LDS_HEIGHTS = (144, 128, 112)
+
+
+def want_cut(M, N, K):
+    """(chunks, rows per chunk) of a weight gradient."""
+    tiles = -(-N // TILE) * -(-K // TILE)
+    want = max(1, min(-(-TARGET // tiles), -(-M // MIN_CHUNK)))
+    rows = -(-(-(-M // want)) // BLOCK) * BLOCK
+    return -(-M // rows), rows
+
+
+def ws_floats(M, N, K):
+    chunks, _ = want_cut(M, N, K)
+    return chunks * N * K if chunks > 1 else 0
+
+
+def wg_floats(H, X=80):
+    """The floats of the chunk-sum workspace b.wg."""
+    return 512 * 4096 + 6 * H * H + 3 * H * X
+
+
+def weight_grads(H, Z, B, T, mode, X=80):
+    """[(name, M, N, K, ldo)] of every launch_weight_grad of one call, and [(name, M, N)] of every launch_col_sum."""
+    p_use_gen = MODES[mode][0]
+    M1 = B * T
+    Mp = 2 * M1 if p_use_gen > 0 else M1
+    Mg = (M1 if p_use_gen < 1 else 0) + (M1 if p_use_gen > 0 else 0)
+    w = [("phi_x.0", Mp, H, X, X), ("phi_x.2", Mp, H, H, H), ("phi_x.4", Mp, H, H, H),
+         ("phi_z.0", M1, H, Z, Z), ("phi_z.2", M1, H, H, H), ("phi_z.4", M1, H, H, H),
+         ("enc.0[:, :H]", M1, H, H, 2 * H), ("enc.0[:, H:]", M1, H, H, 2 * H), ("enc.2", M1, H, H, H), ("enc.4", M1, Z, H, H),
+         ("prior.0", M1, H, H, H), ("prior.2", M1, H, H, H), ("prior.4", M1, Z, H, H),
+         ("dec.0[:, :H]", M1, H, H, 2 * H), ("dec.0[:, H:]", M1, H, H, 2 * H), ("dec.2", M1, H, H, H), ("dec.4", M1, H, H, H),
+         ("dec.6", M1, X, H, H),
+         ("weight_ih[:, :H]", Mg, 3 * H, H, 2 * H), ("weight_ih[:, H:]", Mg, 3 * H, H, 2 * H), ("weight_hh", Mg, 3 * H, H, H)]
+    b = [(n, Mp, H) for n in ("phi_x.0", "phi_x.2", "phi_x.4")] + [(n, M1, H) for n in ("phi_z.0", "phi_z.2", "phi_z.4", "enc.0", "enc.2",
+         "prior.0", "prior.2", "dec.0", "dec.2", "dec.4")] + [("enc.4", M1, Z), ("prior.4", M1, Z), ("dec.6", M1, X), ("bias_ih", Mg, 3 * H),
+                                                                ("bias_hh", Mg, 3 * H)]
+    return w, b
+
+
+PATHS = ("seam", "chunks ldo == K", "chunks ldo != K enc.0", "chunks ldo != K dec.0", "chunks ldo != K weight_ih[:, :H]",
+         "chunks ldo != K weight_ih[:, H:]", "short last chunk", "col_sum blocks", "batched GEMM full tile + tail", "all-frame loop",
+         "reduce loop")
+
+
+def paths(case):
+    """The subset of PATHS that one call of the case runs."""
+    H, B, T, mode = case[0], case[3], case[4], case[5]
+    TB = B * T
+    w, b = weight_grads(H, z_of(case), B, T, mode)
+    out = set()
+    for name, M, N, K, ldo in w:
+        chunks, rows = want_cut(M, N, K)
+        if chunks == 1 and M > BLOCK and M % BLOCK:
+            out.add("seam")                                     # tot += acc after 128 rows, then a short block
+        if chunks > 1:
+            half = name if name.startswith("weight_ih") else name.split("[")[0]
+            out.add("chunks ldo == K" if ldo == K else "chunks ldo != K " + half)
+            if M % rows:
+                out.add("short last chunk")
+            if N * K > GRID_ELEMENTS:
+                out.add("reduce loop")
+    if any(M > BLOCK for _, M, _ in b):
+        out.add("col_sum blocks")
+    # d phi_x through the transposed phi_x.4 / .2 (N = K = H) on the LDS kernels: a full tile at whichever height the cut takes, and rows left over
+    if H % 256 == 0 and TB > max(LDS_HEIGHTS) and all(TB % h for h in LDS_HEIGHTS):
+        out.add("batched GEMM full tile + tail")
+    if TB * H > GRID_ELEMENTS:
+        out.add("all-frame loop")                               # elu_bwd over dP, unpack_frames of the tape
+    return out

@@ -22,15 +22,7 @@ ROWS = (1, 3, 16, 17, 100, 1000, 11129)
 SHAPES = ((64, 64), (1024, 80), (80, 1024), (64, 1024), (1024, 2048), (3072, 1024))        # (N, K) of dW
 CANARY_ROWS, CANARY = 16, 777.0
 LEDGER = bd.Ledger("weight gradient")
-# restated from csrc/k_backward.hip (weight_grad_cut), so that a change of the rule is a change of this file too
-TILE, BLOCK, MIN_CHUNK, TARGET = 64, 128, 256, 512
-
-
-def want_cut(M, N, K):
-    tiles = -(-N // TILE) * -(-K // TILE)
-    want = max(1, min(-(-TARGET // tiles), -(-M // MIN_CHUNK)))
-    rows = -(-(-(-M // want)) // BLOCK) * BLOCK
-    return -(-M // rows), rows
+from backward_oracle import BLOCK, want_cut  # noqa: E402  (weight_grad_cut restated, shared with the CPU tests of the case tables)
 
 
 @pytest.fixture(scope="module")
@@ -145,12 +137,14 @@ def hip_backward(model, c, gdec=None, gkld=None, grad_input=True):
 
 
 def hold(got, g64, g32, what, ledger, names=None):
-    """Every tensor of ``names`` (default: all of g64) to the bar; all failures of the case are reported."""
+    """Every tensor of ``names`` (default: all of g64) to the bar; all failures of the case are reported.  ledger: a key of BWD_LEDGERS,
+    or a Ledger."""
+    ledger = BWD_LEDGERS[ledger] if isinstance(ledger, str) else ledger
     bad = []
     for k in (g64 if names is None else names):
         v = bd.compare(got[k].detach().cpu().double().reshape(1, -1).numpy(), g64[k].reshape(1, -1).numpy(), g32[k].double().reshape(1, -1).numpy(),
                        f"{what} {k}")
-        BWD_LEDGERS[ledger].add(family(k), v)
+        ledger.add(family(k), v)
         if not v.ok:
             bad.append(v.message)
     assert not bad, "\n".join(bad)
